@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MVF brute-force similarity-search path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+    A plain run sets up the `value` workload, warms it up, times exactly K steps and prints the line: `metric`, `value`,
+    `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the `roofline` read from the events of those K steps.  Every
+    other leg below (host API, recall against the oracle, CPU baselines, the other paths, configs and sizes, the vendor
+    GEMM reference) runs only with --full.  --dump-outputs DIR writes what the last timed step returned (scores.npy f32,
+    indices.npy and raw.npy as f64, each [queries, k]; a seeded sample of query rows when they pass 64 MB in all, their
+    numbers in query_rows.npy); the inputs come from fixed seeds, so two builds can be compared output for output.
     N > 1 from a plain shell: bench.py starts its N ranks itself (a child `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N ... bench.py --gpus N ...`, launched before this process touches the GPU; rank 0's JSON line and
     the child's exit code are passed through).  Already under torch.distributed.run (RANK / WORLD_SIZE set): runs as a
@@ -105,6 +111,10 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (recall, CPU baselines, other paths and configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy")
     ap.add_argument("--rows", type=int, default=10_000_000, help="rows per GPU")
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--dtype", type=int, default=0, help="schema DataType code (0 f32, 1 f16, 2 i8, 3 u8)")
@@ -126,7 +136,10 @@ def parse_args():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget per leg")
     ap.add_argument("--shardset-only", action="store_true",
                     help="internal: run ONLY the single-process shard-set leg over --gpus devices and print its JSON")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def host_description():
@@ -247,6 +260,30 @@ def timed_steps(step, warmup, steps, world, dist, torch):
         dist.barrier()
     torch.cuda.synchronize()
     return time.perf_counter() - t0, out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out):
+    """What the caller of the timed path receives from its last step: scores f32, indices (u64 bit pattern) and raw i32,
+    each [nq, k], written as float32 / float64 .npy files.  Above 64 MB in all, a fixed seeded sample of the query rows
+    is written, and which rows in query_rows.npy."""
+    scores = out[0].cpu().numpy()
+    indices = out[1].cpu().numpy().view(np.uint64)
+    raw = out[2].cpu().numpy()
+    nq, k = scores.shape
+    per_row = k * (4 + 8 + 8)
+    arrays = {}
+    if nq * per_row > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * nq) // per_row)
+        sel = np.sort(np.random.default_rng(SEED).choice(nq, size=keep, replace=False))
+        scores, indices, raw = scores[sel], indices[sel], raw[sel]
+        arrays["query_rows"] = sel.astype(np.float64)
+    arrays.update(scores=scores.astype(np.float32), indices=indices.astype(np.float64), raw=raw.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def max_over_ranks(x, world, dist, torch, device):
@@ -889,6 +926,8 @@ def main():
     local_ms, exch_ms = searcher.take_timings()
     searcher.timing = False
     elapsed = max_over_ranks(elapsed, world, dist, torch, dev if backend == "nccl" else "cpu")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
 
     result = None
     if rank == 0:
@@ -907,7 +946,7 @@ def main():
             "value_timed_region": "query already on the device -> kernels + on-device top-k (+ all-gather and merge at N > 1) -> "
                                   "results left on the device; the query's H2D copy and the results' D2H copy of SURVEY.md "
                                   "§8(d)'s region are NOT in `value` -- `host_api` is the same search including both (its ms_per_step is in the "
-                                  "line: within 0.5 % either way since the host call moves small queries / results through pinned memory in place)",
+                                  "--full line: within 0.5 % either way since the host call moves small queries / results through pinned memory in place)",
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -915,7 +954,7 @@ def main():
             "data": "synthetic",
             "config": {"workload": f"{args.rows // 1_000_000}M x {args.dim} {dtname} {mname}, {args.queries} query, "
                                    f"top-{args.k}, per GPU (BASELINE.json configs[1] at --gpus 1)",
-                       "second_workload": None if args.no_cfg5 else
+                       "second_workload": None if args.no_cfg5 or not args.full else
                        "cfg5_sharded: 12.5M x 1024 f16 L2 per GPU, 1024 batched queries, top-100 (BASELINE.json configs[4])",
                        "rows_per_gpu": args.rows, "dim": args.dim, "queries": args.queries, "k": args.k,
                        "metric": mname, "sharding": f"row-range x{world}" if world > 1 else "none"},
@@ -926,7 +965,7 @@ def main():
         if rehearsal:
             result["rehearsal"] = rehearsal
         if world > 1:
-            result["cpu_baseline_note"] = "cpu_baseline, recall of the headline and the N = 1 legs are reported by the --gpus 1 run only"
+            result["cpu_baseline_note"] = "cpu_baseline, recall of the headline and the N = 1 legs are reported by the --gpus 1 --full run only"
         # ---- roofline of the dominant kernel (rank 0's shard) ---------------------------
         alg_bytes = float(args.rows) * args.dim * es  # N*d*es per launch
         if tm.samples and tm.scan_ms_avg > 0 and tm.scan_kernel >= 2:
@@ -954,7 +993,7 @@ def main():
                     result["roofline"]["traffic_source"] = "profiles/" + name
         result["corpus_generation_s"] = gen_s
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from oracle import mvf_oracle as oracle
         oracle.build()
         q = dq.cpu().numpy()
@@ -1193,7 +1232,7 @@ def main():
     torch.cuda.empty_cache()
 
     # ---- second workload, every N: BASELINE.json configs[4] per rank ----------------------------------------------
-    if not args.no_cfg5:
+    if args.full and not args.no_cfg5:
         leg = cfg5_sharded_leg(args, rank, local_rank, world, backend, dist, torch, G, ShardedSearcher, _lib)
         if rank == 0:
             if rehearsal:
@@ -1201,7 +1240,7 @@ def main():
             result["cfg5_sharded"] = leg
 
     # ---- the same config as STRONG scaling, every N: ONE fixed 100M x 1024 f16 corpus split by row range over the ranks --
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         torch.cuda.empty_cache()
         try:
             leg = cfg5_sharded_leg(args, rank, local_rank, world, backend, dist, torch, G, ShardedSearcher, _lib,
@@ -1216,11 +1255,11 @@ def main():
             result["cfg5_strong"] = leg
 
     # ---- context for the MFMA fractions above: what the vendor GEMM library holds on THIS box (best case, 8192^3) --------
-    if rank == 0 and world == 1 and not args.no_batched:
+    if args.full and rank == 0 and world == 1 and not args.no_batched:
         result["vendor_gemm_reference"] = vendor_gemm_reference(torch, dev)
 
     # ---- N = 1: BASELINE.json configs[3] and configs[0] ------------------------------------------------------------------
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from oracle import mvf_oracle as oracle
         if not args.no_cfg4:
             torch.cuda.empty_cache()
@@ -1243,7 +1282,7 @@ def main():
         return
 
     # ---- third workload, every N: the single-process shard set over the same N devices (child process) ------------------
-    if not args.no_shardset:
+    if args.full and not args.no_shardset:
         result["shardset"] = shardset_leg(args, world)
 
     result["bench_wall_s"] = time.perf_counter() - T_START  # rank 0, from interpreter start to the line (all legs, oracle checks included)
