@@ -29,6 +29,10 @@ extern "C" {
     fn mvfgpu_search_fetch(corpus: *const MvfGpuCorpus, metric: u8, queries: *const c_void, query_dtype: u8,
                            query_dim: u32, nq: u32, k: u32, out_scores: *mut f32, out_indices: *mut u64,
                            out_raw: *mut i32, out_vectors: *mut c_void) -> c_int;
+    /// Every row within a radius of each query (include/mvf_gpu.h): exact counts, the best `max_per_query` entries.
+    fn mvfgpu_search_radius(corpus: *const MvfGpuCorpus, metric: u8, queries: *const c_void, query_dtype: u8,
+                            query_dim: u32, nq: u32, radii: *const f32, max_per_query: u64, out_counts: *mut u64,
+                            out_scores: *mut f32, out_indices: *mut u64, out_raw: *mut i32) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;
     /// `MVFGPU_ABI_VERSION` of the loaded library (include/mvf_gpu.h): struct layouts and signatures this file mirrors.
     fn mvfgpu_abi_version() -> u32;

@@ -316,6 +316,21 @@ public:
         }
         return out;
     }
+    // Every row within `radius` of the query, best first (mvfgpu_search_radius): L2 distance <= radius,
+    // InnerProduct / Cosine score >= radius, inclusive.  At most max_results hits (the best ones); the payload is not fetched.
+    std::vector<ScoredVector> find_within_radius(const std::vector<float>& query, float radius, size_t max_results) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "find_within_radius takes f32 queries: Float32 / Float16 spaces");
+        uint64_t count = 0;
+        std::vector<float> scores(max_results);
+        std::vector<uint64_t> idx(max_results);
+        detail::check_gpu(mvfgpu_search_radius(c_, (uint8_t)metric_, query.data(), MVF_DTYPE_FLOAT32, (uint32_t)query.size(), 1, &radius,
+                                               max_results, &count, max_results ? scores.data() : nullptr,
+                                               max_results ? idx.data() : nullptr, nullptr));
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < max_results && i < count; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
     mvfgpu_corpus* raw() const { return c_; }
 
 private:

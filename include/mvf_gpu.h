@@ -337,6 +337,51 @@ int mvfgpu_merge_topk_packed_device(const void* d_packed, uint32_t nlists,
                                     uint64_t* d_out_indices, int32_t* d_out_raw,
                                     int device, void* hip_stream);
 
+/* ---- radius search ------------------------------------------------------- */
+
+/*
+ * Every row within a score threshold of each query ("Radius search").
+ *   radii        : host [nq] f32, one bound per query.  Row r matches query q iff r is live (not deleted), its score is not
+ *                  NaN and its order key is <= that of radii[q]: L2 distance <= radius, InnerProduct / Cosine score >=
+ *                  radius; inclusive.  +inf (L2) / -inf (InnerProduct, Cosine) matches every live non-NaN row.  A NaN
+ *                  radius -> MVF_ERR_INVALID_ARGUMENT.  Int8 / UInt8 spaces with L2 / InnerProduct compare the EXACT i32:
+ *                  the radius becomes the largest R with sqrtf((float)R) <= radius (L2) / the smallest R with
+ *                  (float)R >= radius (InnerProduct), so the matches are bit-exact.
+ *   out_counts   : host [nq] u64, the EXACT number of matches of each query, also beyond max_per_query.
+ *   out_scores / out_indices / out_raw : host [nq][max_per_query] as mvfgpu_search's (out_raw nullable): the first
+ *                  min(count, max_per_query) entries of row q are the query's BEST matches, best first, ties by ascending
+ *                  position; the rest is mvfgpu_search's padding (index UINT64_MAX).  Vector ids and index_base as there.
+ *   max_per_query: 0 .. MVFGPU_MAX_K; 0 = counts only (the entry buffers may then be NULL).
+ * Argument checks and error codes are mvfgpu_search's.  Blocking.  A streaming kernel reads the rows once per 1 or 4
+ * queries (batches of 16 and more on Float32 corpora: one pass of the batched f32 MFMA selection kernel with the radius
+ * loosened by its proven bound, then exact re-scoring; mvfgpu_selftest_radius_route) and appends matches to device lists
+ * of MVFGPU_RADIUS_LIST_CAP entries per query; a query with more matches
+ * (and max_per_query > 0) is completed by one mvfgpu_search over such queries with k = max_per_query: when count >
+ * max_per_query the entries ARE the top-max_per_query result.
+ */
+#define MVFGPU_RADIUS_LIST_CAP 8192u
+int mvfgpu_search_radius(const mvfgpu_corpus* corpus, uint8_t metric,
+                         const void* queries, uint8_t query_dtype, uint32_t query_dim,
+                         uint32_t nq, const float* radii, uint64_t max_per_query,
+                         uint64_t* out_counts, float* out_scores,
+                         uint64_t* out_indices, int32_t* out_raw);
+
+/*
+ * Self-test of the radius conversion (no GPU needed): the largest order key (mvf_common.h) a row may have to match
+ * `radius` on a space of `data_type` under `metric`, and in *out_raw (nullable) the exact i32 bound R of Int8 / UInt8
+ * spaces under L2 / InnerProduct (0 otherwise; L2 -1 = nothing matches, InnerProduct INT32_MAX = nothing can match).
+ */
+int mvfgpu_selftest_radius_bound(uint8_t data_type, uint8_t metric, float radius, uint32_t* out_key, int32_t* out_raw);
+
+/*
+ * Self-test of the route a radius search takes (no GPU needed): *out_route = 0 when the streaming radius kernel serves `nq`
+ * queries on a corpus of `data_type` (one read of the rows per 1 or 4 queries), 1 when ONE thresholded pass of the batched
+ * f32 MFMA selection kernel (the radius loosened by its proven error bound) + exact re-scoring of its candidates does
+ * (Float32 corpora, nq >= 16; queries whose candidates overflow are redone by the streaming kernel).  scan_path as in
+ * mvfgpu_set_scan_path: 1 forces the streaming route, 2 / 3 / 5 the batched one on Float32 corpora, anything else is automatic.
+ */
+int mvfgpu_selftest_radius_route(uint8_t data_type, uint32_t nq, int scan_path, uint32_t* out_route);
+
 /* ---- several GPUs in one process ------------------------------------------ */
 
 /*
@@ -451,7 +496,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
 /*
  * ABI version of the library: bumped whenever a struct layout or a function signature of this header changes in a way
  * an older caller would misread (2: every out-struct starts with struct_size, round 3; 3: corpus_info.selection_state,
- * reload_tuning, k beyond 1024; the later lift of the k <= 16384 limit changed no layout and no signature).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * reload_tuning, k beyond 1024; the later lift of the k <= 16384 limit changed no layout and no signature, nor did the
+ * radius search, which only ADDS mvfgpu_search_radius and mvfgpu_selftest_radius_bound).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

@@ -1917,6 +1917,37 @@ int check_query_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries
 
 }  // namespace
 
+namespace mvf {
+CorpusView corpus_view(const mvfgpu_corpus* c) {
+    CorpusView v;
+    v.device = c->device, v.num_cus = c->num_cus, v.k1_g = c->tune.k1_g;
+    v.n = c->n, v.index_base = c->index_base;
+    v.dim = c->dim, v.pitch = c->pitch, v.V = c->V, v.dtype = c->dtype;
+    v.rows = c->d_rows;
+    v.tomb = static_cast<const uint32_t*>(c->tomb.p);
+    v.ids = static_cast<const uint64_t*>(c->ids.p);
+    v.stream = c->own_stream;
+    v.scan_path = c->scan_path;
+    return v;
+}
+int corpus_row_norms(const mvfgpu_corpus* c, void* stream, const float** xnorm, const float** xx2, const float** xxmax) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int rc = ensure_norms(c, static_cast<hipStream_t>(stream));
+    if (rc != MVF_OK) return rc;
+    const float* xn = static_cast<const float*>(c->xnorm.p);
+    *xnorm = xn;
+    *xx2 = xn + norm_stride(c->n);
+    *xxmax = xn + norm_max_at(c->n);
+    return MVF_OK;
+}
+std::mutex& corpus_host_mutex(const mvfgpu_corpus* c) { return c->host_mu; }
+void k1_group(uint32_t V, int nqv, int forced, int* G, uint32_t* J) { choose_group(V, nqv, G, J, forced); }
+int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
+                      uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices) {
+    return check_query_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
+}
+}  // namespace mvf
+
 extern "C" {
 
 int mvfgpu_device_count(int* out_count) {

@@ -5,7 +5,10 @@
 
 #include <cstdint>
 #include <cstring>
+#include <mutex>
 #include <string>
+
+typedef struct mvfgpu_corpus mvfgpu_corpus;
 
 namespace mvf {
 
@@ -59,5 +62,29 @@ struct Tuning {
     int large_k = 0;            // MVF_LARGE_K=1|2: k beyond one pass always by passes (1; k <= 16384) / always by the whole-shard sort (2); 0: the cheaper one
 };
 Tuning read_tuning();
+
+// What the radius search (radius.hip) reads of a handle: the resident rows and their masks, fixed for the handle's life
+// (set_tombstones / set_vector_ids must not race with searches), and the stream of the host-buffer calls.
+struct CorpusView {
+    int device = 0, num_cus = 256, k1_g = 0;
+    uint64_t n = 0, index_base = 0;
+    uint32_t dim = 0, pitch = 0, V = 0;
+    uint8_t dtype = 0;
+    const unsigned char* rows = nullptr;
+    const uint32_t* tomb = nullptr;  // NULL = no deletions
+    const uint64_t* ids = nullptr;   // NULL = index_base + row
+    void* stream = nullptr;          // hipStream_t of the host-buffer API (used under host_mutex)
+    int scan_path = 0;               // mvfgpu_set_scan_path
+};
+CorpusView corpus_view(const mvfgpu_corpus* c);
+std::mutex& corpus_host_mutex(const mvfgpu_corpus* c);  // serialises the host-buffer calls of a handle
+// Float32 / Float16 corpora: the row norms the batched kernels read (built on first use, on `stream`): xnorm[n] = |x|,
+// xx2[n] = sum x^2, xxmax[1] = max of xx2
+int corpus_row_norms(const mvfgpu_corpus* c, void* stream, const float** xnorm, const float** xx2, const float** xxmax);
+// K1's lane-group width for rows of V 16-byte vectors and nqv queries per pass (MVF_K1_G forces one: `forced`)
+void k1_group(uint32_t V, int nqv, int forced, int* G, uint32_t* J);
+// mvfgpu_search's argument checks (k = 1 .. MVFGPU_MAX_K, non-NULL query and output buffers)
+int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
+                      uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices);
 
 }  // namespace mvf

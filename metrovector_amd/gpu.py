@@ -43,6 +43,39 @@ class SearchResult:
     raw: np.ndarray      # i32 [nq, k] (exact integer score on Int8/UInt8 spaces)
 
 
+@dataclass
+class RadiusResult:
+    counts: np.ndarray   # u64 [nq]: exact number of matches per query (also beyond max_per_query)
+    scores: np.ndarray   # f32 [nq, max_per_query]: the best min(count, max_per_query) matches, best first, then padding
+    indices: np.ndarray  # u64 [nq, max_per_query] (UINT64_MAX = padding)
+    raw: np.ndarray      # i32 [nq, max_per_query] (exact integer score on Int8/UInt8 spaces)
+
+    @property
+    def overflowed(self) -> np.ndarray:
+        """Queries whose matches did not fit the device list (MVFGPU_RADIUS_LIST_CAP) and that the library completed
+        through the top-k search (only when max_per_query > 0)."""
+        return self.counts > RADIUS_LIST_CAP if self.scores.shape[1] > 0 else np.zeros(self.counts.shape, bool)
+
+
+RADIUS_LIST_CAP = 8192  # include/mvf_gpu.h MVFGPU_RADIUS_LIST_CAP
+
+
+def radius_bound(data_type: int, metric: int, radius: float) -> tuple[int, int]:
+    """(largest matching order key, exact i32 bound of Int8/UInt8 L2/InnerProduct spaces) of a radius --
+    `mvfgpu_selftest_radius_bound`; no GPU needed."""
+    key, raw = C.c_uint32(0), C.c_int32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_radius_bound(data_type, metric, float(radius), C.byref(key), C.byref(raw)))
+    return key.value, raw.value
+
+
+def radius_route(data_type: int, nq: int, scan_path: int = 0) -> int:
+    """0: the streaming radius kernel serves the batch, 1: one thresholded batched MFMA pass + exact re-scoring --
+    `mvfgpu_selftest_radius_route`; no GPU needed."""
+    out = C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_radius_route(data_type, nq, scan_path, C.byref(out)))
+    return out.value
+
+
 class GpuCorpus:
     """One shard of a vector space, resident in HBM on one MI355X."""
 
@@ -200,6 +233,31 @@ class GpuCorpus:
                                                       sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
                                                       raw.ctypes.data_as(C.c_void_p), vec.ctypes.data_as(C.c_void_p)))
         return SearchResult(sc, idx, raw), vec
+
+    def search_radius(self, queries: np.ndarray, radius, max_per_query: int, metric: int = L2) -> RadiusResult:
+        """Every row within `radius` of each query (`mvfgpu_search_radius`): L2 distance <= radius, InnerProduct /
+        Cosine score >= radius.  `radius` is a scalar or one value per query; `max_per_query` = 0 asks for counts only."""
+        q = np.asarray(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, qdim = q.shape
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (nq,)), np.float32)
+        m = int(max_per_query)
+        if m < 0:
+            raise InvalidArgument("max_per_query must be >= 0")
+        counts = np.zeros(nq, np.uint64)
+        sc = np.empty((nq, m), np.float32)
+        idx = np.empty((nq, m), np.uint64)
+        raw = np.empty((nq, m), np.int32)
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if m else (lambda a: None)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_radius(self._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
+                                                       r.ctypes.data_as(C.c_void_p), m, counts.ctypes.data_as(C.c_void_p),
+                                                       ptr(sc), ptr(idx), ptr(raw)))
+        return RadiusResult(counts, sc, idx, raw)
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
                       d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:

@@ -145,3 +145,40 @@ def find_top_k_similar_batch(space: VectorSpace, queries, k: int, metric: int | 
             hits.append(ScoredVector(int(idx), float(score), payload))
         out.append(hits)
     return out
+
+
+def find_within_radius(space: VectorSpace, query, radius: float, max_results: int | None = None, metric: int | None = None,
+                       corpus: GpuCorpus | None = None, device: int = 0, with_vectors: bool = True) -> list[ScoredVector]:
+    """Every row within `radius` of `query` (`mvfgpu_search_radius`), best first like `find_top_k_similar`: L2 distance
+    <= radius, InnerProduct / Cosine score >= radius (inclusive).  `max_results` keeps the best that many
+    (None: all of them).  Deleted rows never match; ids and the payload as in `find_top_k_similar`."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    if max_results is not None and max_results < 0:
+        raise BuildError("max_results must be >= 0")
+    dt = int(space.data_type())
+    q = np.asarray(query, dtype=_NP_OF[query_dtype_code(dt)])
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        want = max_results
+        if want is None:  # all matches: the count first (no lists), then one call for exactly that many
+            want = int(corpus.search_radius(q, radius, 0, metric).counts[0])
+        res = corpus.search_radius(q, radius, want, metric)
+        count = int(res.counts[0])
+        n = min(count, res.indices.shape[1])
+        idx, sc = res.indices[0][:n], res.scores[0][:n]
+        rows = corpus.gather_rows(idx) if (with_vectors and n) else None
+    finally:
+        if own:
+            corpus.close()
+    out = []
+    for i in range(n):
+        payload = None
+        if rows is not None:
+            payload = rows[i].astype(np.float32) if dt in (0, 1) else rows[i].copy()
+        out.append(ScoredVector(int(idx[i]), float(sc[i]), payload))
+    return out

@@ -21,7 +21,7 @@ from typing import Callable
 import numpy as np
 
 from . import _lib
-from .gpu import GpuCorpus, SearchResult, merge_topk_host, query_dtype_code
+from .gpu import GpuCorpus, RadiusResult, SearchResult, merge_topk_host, query_dtype_code
 
 
 def shard_range(total_rows: int, world_size: int, rank: int) -> tuple[int, int]:
@@ -156,3 +156,36 @@ def sharded_search_host(local_search: Callable[[], SearchResult], metric: int, d
     for w in (w1, w2, w3):
         w.wait()
     return merge_topk_host(gs.numpy(), gi.numpy().view(np.uint64), gr.numpy(), metric, data_type)
+
+
+def merge_radius(results: list[RadiusResult], metric: int, data_type: int, max_per_query: int) -> RadiusResult:
+    """Merge the radius results of row-range shards, given in ASCENDING ROW-RANGE ORDER (host only, no GPU): the counts
+    add up; each query's entries are the shards' entries concatenated and ordered best first, ties by shard order and
+    rank inside the shard (= ascending global position), cut at `max_per_query`.  Exact when every shard was searched
+    with at least `max_per_query` entries per query."""
+    if not results:
+        raise ValueError("merge_radius needs at least one shard result")
+    nq = results[0].counts.shape[0]
+    m = int(max_per_query)
+    counts = np.zeros(nq, np.uint64)
+    for r in results:
+        counts += r.counts.astype(np.uint64)
+    sc = np.empty((nq, m), np.float32)
+    idx = np.full((nq, m), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+    raw = np.zeros((nq, m), np.int32)
+    sc[:] = np.float32(np.inf) if metric == 0 else np.float32(-np.inf)
+    exact_int = data_type in (2, 3) and metric in (0, 1)
+    for q in range(nq):
+        parts = [(r.scores[q][:n], r.indices[q][:n], r.raw[q][:n])
+                 for r in results for n in [int(min(r.counts[q], r.scores.shape[1]))]]
+        s_all = np.concatenate([p[0] for p in parts]).astype(np.float32)
+        i_all = np.concatenate([p[1] for p in parts]).astype(np.uint64)
+        r_all = np.concatenate([p[2] for p in parts]).astype(np.int32)
+        if exact_int:
+            order_val = r_all.astype(np.int64) if metric == 0 else -r_all.astype(np.int64)
+        else:
+            order_val = s_all.astype(np.float64) if metric == 0 else -s_all.astype(np.float64)
+        order = np.argsort(order_val, kind="stable")[:m]  # stable: ties keep the (shard, rank) order
+        n = order.size
+        sc[q, :n], idx[q, :n], raw[q, :n] = s_all[order], i_all[order], r_all[order]
+    return RadiusResult(counts, sc, idx, raw)
