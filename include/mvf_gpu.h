@@ -448,10 +448,9 @@ int mvfgpu_last_timing(const mvfgpu_corpus* corpus, mvfgpu_timing* out);
  * STREAM THE F16 SHADOW instead of the stored rows (half the bytes, so about
  * half the time; same proven-margin selection and exact re-scoring as the
  * batched path: the same rows as path 1, scores within the 1e-5 tolerance --
- * the re-scoring kernel sums in another order than the streaming kernel;
- * also enabled by MVF_STREAM_SHADOW=1 in the environment).  Off by default:
- * the default single-query path reads the stored rows, whatever the handle
- * has served before.
+ * the re-scoring kernel sums in another order than the streaming kernel).
+ * Off by default: the default single-query path reads the stored rows,
+ * whatever the handle has served before.
  * 5 = K2 selecting on an INT8 SHADOW of a Float32 / Float16 corpus (per-row
  * scale; built on first use, `dimension` bytes per row; also enabled by
  * MVF_I8_SHADOW=1): the int8 MFMA runs at about twice the f16 kernel's rate
@@ -485,8 +484,8 @@ int mvfgpu_last_timing(const mvfgpu_corpus* corpus, mvfgpu_timing* out);
 int mvfgpu_set_scan_path(mvfgpu_corpus* corpus, int path);
 
 /*
- * The tuning switches of the environment (MVF_K1_G, MVF_K1_RANK_MERGE, MVF_K2_*, MVF_I8_SHADOW, MVF_F16_SHADOW, MVF_QS_REFINE,
- * MVF_STREAM_*, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
+ * The tuning switches of the environment (MVF_K1_G, MVF_K2_*, MVF_I8_SHADOW, MVF_F16_SHADOW, MVF_QS_REFINE,
+ * MVF_STREAM_I8, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
  * handle, when it is created: a search never calls getenv.  An A/B script that changes the environment of a live handle
  * calls this to have it read again.  A development aid: it waits for the handle's host-buffer searches, but
  * mvfgpu_search_device reads the switches unlocked -- do not call it beside device-pointer searches of the same handle.

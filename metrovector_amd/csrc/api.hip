@@ -111,16 +111,11 @@ Tuning read_tuning() {
     };
     const long g = num("MVF_K1_G", 0);
     t.k1_g = (g == 64 || g == 32 || g == 16 || g == 8 || g == 4 || g == 1) ? (int)g : 0;
-    t.k2_dma = flag("MVF_K2_DMA", true);
-    t.k2_sb = flag("MVF_K2_SB", true);
     t.k2_pp = getenv("MVF_K2_PP") ? (int)flag("MVF_K2_PP", false) : -1;
     t.k2_growth = (uint32_t)std::max(2l, num("MVF_K2_GROWTH", 4));
     t.k2_growth_small = (uint32_t)std::max(2l, num("MVF_K2_GROWTH_SMALL", getenv("MVF_K2_GROWTH") ? (long)t.k2_growth : 6));
-    t.k2_direct64 = (int)num("MVF_K2_DIRECT64", 1);
     t.qs_refine_phases = (uint32_t)std::max(0l, num("MVF_QS_REFINE_PHASES", 2));
     t.k2_bias = flag("MVF_K2_BIAS", true);
-    t.k2_persistent = getenv("MVF_K2_PERSISTENT") ? (int)flag("MVF_K2_PERSISTENT", false) : -1;
-    t.k2_persistent16 = getenv("MVF_K2_PERSISTENT16") ? (int)flag("MVF_K2_PERSISTENT16", true) : -1;
     const long tile = num("MVF_K2_TILE", 0);
     t.k2_tile = tile == 0 ? 0 : tile == 64 ? 64 : tile == 128 ? 128 : 256;
     t.f16_shadow = flag("MVF_F16_SHADOW", true);
@@ -132,13 +127,10 @@ Tuning read_tuning() {
     t.repair_window = (uint32_t)std::max(0l, num("MVF_REPAIR_WINDOW", 0));
     if (const char* e = getenv("MVF_K2_REGION_RECORDS")) t.region_records = strtoull(e, nullptr, 10);
     t.stream_i8 = flag("MVF_STREAM_I8", false);
-    t.stream_shadow = flag("MVF_STREAM_SHADOW", false);
     t.upload_threads = (unsigned)std::max(0l, num("MVF_UPLOAD_THREADS", 0));
-    t.k1_rank_merge = (uint32_t)std::min(256l, std::max(0l, num("MVF_K1_RANK_MERGE", 256)));
     t.host_zc_query = (size_t)std::max(0l, num("MVF_HOST_ZC_QUERY", 64l << 10));
     t.host_zc_results = (size_t)std::max(0l, num("MVF_HOST_ZC_RESULTS", 256l << 10));
     t.large_k = (int)std::min(2l, std::max(0l, num("MVF_LARGE_K", 0)));
-    t.k1_first_piece = flag("MVF_K1_FIRST_PIECE", true);
     t.host_flag_wait = flag("MVF_HOST_FLAG_WAIT", true);
     return t;
 }
@@ -298,6 +290,10 @@ int alloc_rows(mvfgpu_corpus* c) {
     if (c->rows_bytes) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rows), c->rows_bytes));
     return MVF_OK;
 }
+
+// K1: a piece's survivors up to this many join the running list by counting, more go through the sort network (<= 256;
+// 128 until the counting loops got eight reads in flight: profiles/r04_k1_merge_ab.txt)
+constexpr uint32_t kK1RankMerge = 256;
 
 hipError_t scan_launch(uint8_t dtype, const ScanParams& p, int metric, int G, int nqv, dim3 grid, size_t lds,
                        hipStream_t s) {
@@ -488,11 +484,10 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
                 const uint32_t step = 16u * 64u / (uint32_t)G, want = std::max(k, 64u);
                 // (not under the long chunks of short rows: a threshold from 128 rows lets too many of the next 4000 through --
                 // 4 GB of <= 128-byte rows at k = 100 lost 5-8 %, profiles/r04_k1_first_piece_ab.txt)
-                sp.first_piece = (c->tune.k1_first_piece && chunk_rows <= scan_chunk_safe(G)) ? std::min(sp.chunk_safe, (want + step - 1) / step * step)
-                                                                                             : sp.chunk_safe;
+                sp.first_piece = chunk_rows <= scan_chunk_safe(G) ? std::min(sp.chunk_safe, (want + step - 1) / step * step) : sp.chunk_safe;
             }
             sp.nchunks = nchunks;
-            sp.rank_merge_max = c->tune.k1_rank_merge;
+            sp.rank_merge_max = kK1RankMerge;
             sp.floor1 = floor1;
             sp.dump = rank ? rank->a : nullptr;
             if (ps && first) HIP_TRY(hipEventRecord(ps->e[0], s));
@@ -583,21 +578,14 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
 }
 
 
-// The f16/int8 MFMA kernel: scan_mfma16_dma.hip (LDS-DMA ring, 16x16 MFMA shape) by default; MVF_K2_DMA=0 selects the
-// register-staged scan_mfma16.hip (kept as the A/B reference: same results, ~7 % slower).
-bool k2_dma_enabled(const mvfgpu_corpus* c) { return c->tune.k2_dma; }
-
-// One tile of at most 64 queries: the streaming MFMA kernel (scan_mfma16_sb.hip) instead of the 64-query shape of the
-// LDS-DMA tile kernel; MVF_K2_SB=0 goes back (A/B runs).
-bool k2_sb_enabled(const mvfgpu_corpus* c) { return c->tune.k2_sb; }
-
-// 256-query tile: the ping-pong schedule (scan_mfma16_pp.hip) or the lockstep LDS-DMA kernel.  Measured (MI355X,
-// profiles/r02_k2_ab.txt): Float16 rows / the f16 shadow 5 % faster on the ping-pong kernel once a block walks several
-// tiles (cfg5 last phase 20.7 -> 19.7 ms), short phases and Int8 rows a few percent slower (its longer prologue; cfg4
-// 6.94 vs 7.02 ms).  MVF_K2_PP=0|1 forces one of them (A/B runs).
+// 256-query tile on Float16 rows / the f16 shadow: the ping-pong schedule (scan_mfma16_pp.hip) or the lockstep LDS-DMA
+// kernel.  Measured (MI355X, profiles/r02_k2_ab.txt): 5 % faster on the ping-pong kernel once a block walks several
+// tiles (cfg5 last phase 20.7 -> 19.7 ms), short phases a few percent slower (its longer prologue); Int8 rows were slower
+// on it as well (cfg4 6.94 vs 7.02 ms) and have no ping-pong kernel.  MVF_K2_PP=0|1 forces one of them on Float16 tiles.
 bool k2_pp_wanted(const mvfgpu_corpus* c, uint8_t kdtype, uint32_t ntiles, uint32_t mtiles, int num_cus) {
+    if (kdtype != MVF_DTYPE_FLOAT16) return false;
     if (c->tune.k2_pp >= 0) return c->tune.k2_pp != 0;
-    return kdtype == MVF_DTYPE_FLOAT16 && (uint64_t)ntiles * mtiles >= 8ull * (uint64_t)num_cus;
+    return (uint64_t)ntiles * mtiles >= 8ull * (uint64_t)num_cus;
 }
 
 // Largest phase-to-phase growth of the K2 scan (MVF_K2_GROWTH overrides, for A/B runs).  A phase lets through
@@ -644,10 +632,6 @@ std::vector<uint64_t> k2_phase_bounds(uint64_t nr, uint32_t cap, uint32_t g) {
 // The folded pre-filter of the LDS-DMA kernel's i32-accumulator flavours (scan_mfma16_bias.inc); MVF_K2_BIAS=0 keeps
 // round 2's epilogue (A/B runs).
 bool k2_bias_enabled(const mvfgpu_corpus* c) { return c->tune.k2_bias; }
-
-bool k2_dma_persistent(const mvfgpu_corpus* c) {  // measured: int8 15 % and f16 5 % faster with one persistent block per CU
-    return c->tune.k2_persistent16 < 0 ? true : c->tune.k2_persistent16 != 0;
-}
 
 // ---- scaled-f16 shadow of a Float32 corpus (selection only) -----------------------------------------------------
 uint32_t shadow_pitch(uint32_t dim) { return (dim * 2u + 15u) & ~15u; }
@@ -702,7 +686,6 @@ constexpr uint32_t kQsStreamMaxK = kBatchCap / 2 / 10;    // streamed (select_fi
 bool qs_possible(const mvfgpu_corpus* c, uint32_t k) {
     if (is_int_dtype(c->dtype) || c->n == 0) return false;
     if (k > kQsMaxK) return false;
-    if (!k2_dma_enabled(c)) return false;  // the register-staged A/B kernel (MVF_K2_DMA=0) has no int8-shadow flavour
     if ((size_t)((c->dim + 7u) & ~7u) * 4 + kBatchCapQS * 4 > 64 * 1024) return false;  // re-scoring: query + candidates in LDS
     if (c->scan_path == 5 || c->scan_path == 6) return true;
     if (c->scan_path != 0 && c->scan_path != 4) return false;
@@ -969,11 +952,10 @@ int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d
         sp.chunk_safe = std::min(scan_chunk_safe(G), chunk_rows);
         {
             const uint32_t step = 16u * 64u / (uint32_t)G, want = std::max(k, 64u);
-            sp.first_piece = (c->tune.k1_first_piece && chunk_rows <= scan_chunk_safe(G)) ? std::min(sp.chunk_safe, (want + step - 1) / step * step)
-                                                                                         : sp.chunk_safe;
+            sp.first_piece = chunk_rows <= scan_chunk_safe(G) ? std::min(sp.chunk_safe, (want + step - 1) / step * step) : sp.chunk_safe;
         }
         sp.nchunks = nchunks;
-        sp.rank_merge_max = c->tune.k1_rank_merge;
+        sp.rank_merge_max = kK1RankMerge;
         sp.redo_list = redo_list;
         sp.redo_cnt = redo_cnt;
         sp.redo_base = base;
@@ -1008,8 +990,8 @@ int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d
 }
 
 // K2 path: MFMA batched scan in geometric phases with per-query candidate
-// compaction between them (scan_mfma.hip for Float32 rows, scan_mfma16.hip for
-// Float16 / Int8 rows).  Asynchronous: queries whose candidate budget overflowed are
+// compaction between them (scan_mfma.hip for Float32 rows, scan_mfma16_dma.hip and its
+// siblings for Float16 / Int8 / UInt8 rows and the shadows).  Asynchronous: queries whose candidate budget overflowed are
 // redone exactly by K1 in repair launches that decide on the device whether to run.
 // One ROW RANGE [lo, hi) of the corpus (the whole of it, or one of the two ranges of a corpus whose int8 shadow covers a prefix
 // of the rows: search_batched_path below).  allow_qs: the range may select on the int8 shadow (it lies inside it).  defer: the
@@ -1043,12 +1025,11 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
                                  : use_shadow ? static_cast<const unsigned char*>(c->shadow.p)
                                               : c->d_rows;
     const uint32_t kpitch = use_qs ? shadow8_pitch(c->dim) : use_shadow ? shadow_pitch(c->dim) : c->pitch;
-    const bool dma = !wide && k2_dma_enabled(c);            // LDS-DMA kernel (default) or the register-staged one
-    const uint32_t qpb = wide ? 128u : dma ? scan_mfma16_dma_queries_per_block(nq, c->tune.k2_tile) : scan_mfma16_queries_per_block(kdtype);
-    const uint32_t tile_rows = wide ? 128u : dma ? scan_mfma16_dma_tile_rows(qpb) : 256u;
+    const uint32_t qpb = wide ? 128u : scan_mfma16_dma_queries_per_block(nq, c->tune.k2_tile);
+    const uint32_t tile_rows = wide ? 128u : scan_mfma16_dma_tile_rows(qpb);
     const uint32_t nq_pad = (nq + qpb - 1u) / qpb * qpb;
-    const uint32_t ktb = dma ? 64u : 128u;                  // k-tile bytes of the f16/int8 kernel in use
-    const uint32_t KT = wide ? (c->dim + 31u) / 32u : (c->dim * elem_size(kdtype) + ktb - 1u) / ktb;
+    const uint32_t ktb = wide ? 128u : 64u;                // k-tile bytes: 32 floats / 64 bytes of the f16/int8 kernels
+    const uint32_t KT = (c->dim * elem_size(kdtype) + ktb - 1u) / ktb;
     const uint32_t KPB = KT * ktb;                         // prepared query row, bytes
     const uint32_t planes = 1u;
     const uint32_t cap = use_qs ? kBatchCapQS : kBatchCap;
@@ -1143,7 +1124,7 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
     // all -- twice what the per-query lists can hold, at least the 128 MiB of round 2 -- split evenly over the blocks of
     // the launch; the LDS-DMA kernel's i32-accumulator flavours split a block's share once more per wave (raw records)
     uint64_t blk_records = 0;
-    if (dma) {
+    if (!wide) {
         blk_records = std::min<uint64_t>(std::max<uint64_t>((uint64_t)kBlkMaxBlocks * kBlkCap, 2ull * nq_pad * cap), 32ull << 20);
         if (c->tune.region_records)  // MVF_K2_REGION_RECORDS (tests: force the regions to overflow)
             blk_records = std::max<uint64_t>((uint64_t)kBlkMaxBlocks * kBlkWaves, c->tune.region_records);
@@ -1216,14 +1197,13 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
             bp.direct = hp.direct = (begin == 0 && end - begin <= cap) ? 1u : 0u;
             const bool regions = hp.blk_cand && !hp.direct;
             // which kernel takes the phase
-            const bool use_pp = !wide && dma && qpb == 256u && k2_pp_wanted(c, kdtype, hp.ntiles, hp.mtiles, c->num_cus) &&
+            const bool use_pp = !wide && qpb == 256u && k2_pp_wanted(c, kdtype, hp.ntiles, hp.mtiles, c->num_cus) &&
                                 scan_mfma16_pp_usable(hp.mtiles, c->num_cus, KT);
-            const bool use_sb = !wide && !use_pp && dma && qpb == 64u && k2_sb_enabled(c) && scan_mfma16_sb_usable(nq_pad, KT, nq);
-            const bool persistent = k2_dma_persistent(c);
+            const bool use_sb = !wide && !use_pp && qpb == 64u && scan_mfma16_sb_usable(nq_pad, KT, nq);
             // per-wave regions of raw records (scan_mfma16_bias.inc): the persistent LDS-DMA kernel on i32 accumulators
             // (per-wave regions: num_cus blocks x kBlkWaves counters in blk_cnt, which holds kBlkMaxBlocks * kBlkWaves -- a part
             // with more CUs than kBlkMaxBlocks keeps round 2's per-block regions instead of reading counters past the array)
-            const bool wave_regions = !wide && dma && !use_pp && !use_sb && persistent && !c->bias_disabled && k2_bias_enabled(c) &&
+            const bool wave_regions = !wide && !use_pp && !use_sb && !c->bias_disabled && k2_bias_enabled(c) &&
                                       (uint32_t)c->num_cus <= kBlkMaxBlocks &&
                                       scan_mfma16_dma_wave_regions(kdtype, qpb, hp.direct != 0, regions, c->dim);
             hp.wave_regions = wave_regions ? 1u : 0u;
@@ -1236,10 +1216,10 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
                 regions_armed = true;
             }
             if (ps && last) HIP_TRY(hipEventRecord(ps->e[0], s));
-            if (wide) HIP_TRY(launch_scan_mfma_f32(bp, metric, c->num_cus, c->tune.k2_persistent, s));
+            if (wide) HIP_TRY(launch_scan_mfma_f32(bp, metric, s));
             else if (use_pp) HIP_TRY(launch_scan_mfma16_pp(hp, kdtype, metric, c->num_cus, s));
             else if (use_sb) HIP_TRY(launch_scan_mfma16_sb(hp, kdtype, metric, c->num_cus, s));
-            else if (dma && hp.direct && qpb >= 128u && c->tune.k2_direct64) {
+            else if (hp.direct && qpb >= 128u) {
                 // The direct phase is a few thousand rows: 10 row tiles x 4 query tiles of 256 x 256 leave 216 CUs idle while 40 blocks
                 // multiply, key and store 65536 pairs each.  In 64-query tiles (64 x 512) the same pairs spread over twice the blocks
                 // at half the work each (the prepared queries and the slots by row offset do not depend on the tile shape).
@@ -1247,9 +1227,8 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
                 const uint32_t tr = scan_mfma16_dma_tile_rows(64u);
                 dp.mtiles = nq_pad / 64u;
                 dp.ntiles = (uint32_t)((end - begin + tr - 1) / tr);
-                HIP_TRY(launch_scan_mfma16_dma(dp, kdtype, metric, c->num_cus, 64u, persistent, s));
-            } else if (dma) HIP_TRY(launch_scan_mfma16_dma(hp, kdtype, metric, c->num_cus, qpb, persistent, s));
-            else HIP_TRY(launch_scan_mfma16(hp, kdtype, metric, c->num_cus, c->tune.k2_persistent16, s));
+                HIP_TRY(launch_scan_mfma16_dma(dp, kdtype, metric, c->num_cus, 64u, s));
+            } else HIP_TRY(launch_scan_mfma16_dma(hp, kdtype, metric, c->num_cus, qpb, s));
             if (ps && last) {
                 HIP_TRY(hipEventRecord(ps->e[1], s));
                 ps->scanned = true;
@@ -1564,7 +1543,7 @@ bool stream_qs_wanted(const mvfgpu_corpus* c, uint32_t nq, uint32_t k) {
 // Scan path 4 applies to one or two queries on a Float32 corpus whose shadow exists (or can be built now).
 bool stream_shadow_wanted(const mvfgpu_corpus* c, uint32_t nq) {
     if (c->dtype != MVF_DTYPE_FLOAT32 || nq > 2 || c->n == 0) return false;
-    if (c->scan_path != 4 && !(c->scan_path == 0 && c->tune.stream_shadow)) return false;
+    if (c->scan_path != 4) return false;
     return (size_t)((c->dim + 7u) & ~7u) * 4 + kBatchCap * 4 <= 64 * 1024;  // the re-scoring kernel keeps the query in LDS
 }
 

@@ -381,7 +381,7 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                 bp.mtiles = wpad / 128u;
                 bp.cap = kBatchCap;
                 bp.direct = 0;  // every candidate passes the threshold test
-                RAD_TRY(launch_scan_mfma_f32(bp, metric, v.num_cus, -1, s));
+                RAD_TRY(launch_scan_mfma_f32(bp, metric, s));
                 RadiusRescoreParams rr{};
                 rr.cand = static_cast<const uint64_t*>(dcand.p);
                 rr.ccnt = static_cast<const uint32_t*>(dccnt.p);

@@ -28,7 +28,7 @@ struct BatchParams {
     uint32_t direct;              // phase 0 (row_end - row_begin <= cap): candidate slot = row - row_begin, no counter
 };
 
-// K2 for 16-byte-operand MFMAs (Float16 / Int8 rows), scan_mfma16.hip
+// K2 for 16-byte-operand MFMAs (Float16 / Int8 / UInt8 rows): scan_mfma16_dma.hip, scan_mfma16_pp.hip, scan_mfma16_sb.hip
 struct Batch16Params {
     const unsigned char* qprep;  // [nq_pad][KPB]: f16: one plane f16(q 2^e); i8: int8; zero padded
     const float* qaux0;          // [nq_pad] f16: 2^-e (undo of the query scale); i8: bit pattern of i32 sum q^2
@@ -38,7 +38,7 @@ struct Batch16Params {
     const float* xx2;            // [n] f16 rows: sum x^2 (batched L2)
     const float* xxmax;          // [1] max over rows of sum x^2
     const float* xscale;         // [n] or NULL: rows are the scaled-f16 shadow of a Float32 corpus, row r times xscale[r]
-    const unsigned char* zeros;  // >= 16 zero bytes (LDS-DMA kernel: source of k beyond a row's pitch)
+    const unsigned char* zeros;  // >= 16 zero bytes (source of k beyond a row's pitch)
     const int32_t* xnorm_i;      // [n] int rows: sum x^2 (UInt8: of the shifted values x-128)
     const int32_t* xbias_i;      // [n] UInt8 rows: 128 * sum (x-128)
     uint32_t dim;
@@ -47,10 +47,10 @@ struct Batch16Params {
     uint64_t* cand;
     uint32_t* cnt;
     uint32_t pitch, V;
-    uint32_t KPB, KT;            // padded row bytes of qprep, k-tiles (128 bytes; 64 for the LDS-DMA kernel)
+    uint32_t KPB, KT;            // padded row bytes of qprep, k-tiles of 64 bytes
     uint32_t nq, nq_pad;
     uint32_t row_begin, row_end;
-    uint32_t ntiles, mtiles;     // ceil(rows/256), nq_pad / queries-per-block
+    uint32_t ntiles, mtiles;     // ceil(rows / tile rows), nq_pad / queries-per-block
     uint32_t cap;
     uint32_t direct;             // phase 0: candidate slot = row - row_begin, no counter
     // Candidate hand-off without global atomics (persistent grids of <= kBlkMaxBlocks blocks): a block appends
@@ -111,7 +111,7 @@ struct CompactParams {
 constexpr uint32_t kBatchCap = 4096;  // candidate slots per query between compactions (32 KiB of LDS to sort)
 
 size_t scan_mfma_lds_bytes();
-hipError_t launch_scan_mfma_f32(const BatchParams& p, int metric, int num_cus, int force_persistent /* -1: the default grid */, hipStream_t s);
+hipError_t launch_scan_mfma_f32(const BatchParams& p, int metric, hipStream_t s);
 hipError_t launch_prep_queries(const float* q, uint32_t nq, uint32_t nq_pad, uint32_t dim, uint32_t KP, float* qmat,
                                float* qnorm, hipStream_t s);
 hipError_t launch_row_norms_f32(const unsigned char* rows, uint32_t n, uint32_t pitch, float* xnorm, float* xx2,
@@ -150,17 +150,14 @@ hipError_t launch_rescore(const RescoreParams& p, int metric, uint32_t nq, hipSt
 hipError_t launch_refine_tau(const RescoreParams& p, int metric, uint32_t nq, const uint32_t* ntop, uint32_t* lkey,
                              const float* delta, hipStream_t s);
 
-uint32_t scan_mfma16_queries_per_block(int dtype);
-hipError_t launch_scan_mfma16(const Batch16Params& p, int dtype, int metric, int num_cus, int force_persistent /* -1: per type */, hipStream_t s);
 // small batches (one tile of <= 64 queries): streaming kernel with MFMA dots (scan_mfma16_sb.hip)
 bool scan_mfma16_sb_usable(uint32_t nq_pad, uint32_t KT, uint32_t nq);
 hipError_t launch_scan_mfma16_sb(const Batch16Params& p, int dtype, int metric, int num_cus, hipStream_t s);
 uint32_t scan_mfma16_dma_queries_per_block(uint32_t nq, int forced_tile = 0 /* MVF_K2_TILE */);
 uint32_t scan_mfma16_dma_tile_rows(uint32_t bmq);
 bool scan_mfma16_dma_wave_regions(int dtype, uint32_t bmq, bool direct, bool has_regions, uint32_t dim);
-hipError_t launch_scan_mfma16_dma(const Batch16Params& p, int dtype, int metric, int num_cus, uint32_t bmq, bool persistent,
-                                  hipStream_t s);
-// ping-pong schedule of the 256-query tile (scan_mfma16_pp.hip); same parameters as the LDS-DMA kernel with bmq = 256
+hipError_t launch_scan_mfma16_dma(const Batch16Params& p, int dtype, int metric, int num_cus, uint32_t bmq, hipStream_t s);
+// ping-pong schedule of the 256-query tile on Float16 rows (scan_mfma16_pp.hip); same parameters as the LDS-DMA kernel with bmq = 256
 bool scan_mfma16_pp_usable(uint32_t mtiles, int num_cus, uint32_t KT);
 hipError_t launch_scan_mfma16_pp(const Batch16Params& p, int dtype, int metric, int num_cus, hipStream_t s);
 // files the per-block candidate records of one K2 launch into the per-query lists (p.cand / p.cnt); RAW records (the

@@ -1,39 +1,22 @@
-// scan_mfma16_common.inc -- shared by the two K2 kernels for the narrow types (register-staged: scan_mfma16.hip;
-// LDS-DMA ring: scan_mfma16_dma.hip): traits, the per-query constants and the epilogue of one finished 256 x 256 tile.
+// scan_mfma16_common.inc -- shared by the K2 kernels for the narrow types (LDS-DMA tiles: scan_mfma16_dma.hip, ping-pong:
+// scan_mfma16_pp.hip, streaming: scan_mfma16_sb.hip): the per-query constants and the epilogue of one finished tile.
 // Included inside namespace mvf { namespace { ... } }.
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int AROWS = 256, BROWS = 256;     // LDS rows per operand tile
-
-template <int DT> struct T16;
-template <> struct T16<MVF_DTYPE_FLOAT16> {
-    static constexpr int PLANES = 1, IT = 4;  // i-tiles (32 queries) per wave
-    using Acc = f32x16;
-};
-template <> struct T16<MVF_DTYPE_INT8> {
-    static constexpr int PLANES = 1, IT = 4;
-    using Acc = i32x16;
-};
 // UInt8 rows ride the SIGNED int8 MFMA shifted by 128 (x_s = x_u - 128 = x_u ^ 0x80 as int8, same for q):
 //   dot_u = dot_s + 128 (Sq_s + Sx_s) + 16384 d,   L2_u = qq_s + xx_s - 2 dot_s (shift invariant),
 //   qq_u = qq_s + 256 Sq_s + 16384 d,  xx_u likewise -- all exact integers, so the results stay bit-identical to
 //   K1's v_dot4_u32_u8 path.  Per row K4 stores xx_s and bx = 128 Sx_s; per query qq_s and cqq = 128 Sq_s + 16384 d.
-template <> struct T16<MVF_DTYPE_UINT8> {
-    static constexpr int PLANES = 1, IT = 4;
-    using Acc = i32x16;
-};
 
-// Per-query constants of one M-tile (256 queries) into LDS: qa_s (f16: 2^-e / i8: qq as int), qb_s (f16: |q| / u8: cqq),
+// Per-query constants of one M-tile (BMQ queries) into LDS: qa_s (f16: 2^-e / i8: qq as int), qb_s (f16: |q| / u8: cqq),
 // tau_s (threshold key) and thr_s, the pre-filter threshold in ACCUMULATOR units.
 // FLT: scores are floats -- Float16 rows, or (QS) the INT8 SHADOW of a Float32 / Float16 corpus (shadow_i8.hip): int8 rows
 // with a per-row scale p.xscale and int8 queries with a per-query scale qaux0; the i32 sums are converted and then
 // treated exactly like the scaled-f16 shadow's (dot ~ acc * xscale[r] * qaux0[q]).
-template <int DT, int METRIC, int BMQ = AROWS, bool QS = false>
+template <int DT, int METRIC, int BMQ, bool QS>
 __device__ __forceinline__ void load_query_consts16(const Batch16Params& p, uint32_t q0, int tid, float* qa_s, float* qb_s,
                                                     uint32_t* tau_s, float* thr_s) {
     constexpr bool U8 = DT == MVF_DTYPE_UINT8;
@@ -96,8 +79,7 @@ __device__ __forceinline__ void load_query_consts16(const Batch16Params& p, uint
 // appended.  Per-row constants (norms, shadow scale, UInt8 bias) come from global memory, or -- RC_LDS, the ping-pong
 // kernel -- from an LDS copy its loader DMA'd beside the tile (rc0 / rc1, indexed by the row's offset in the tile): an
 // ordinary load there would make hipcc drain the whole LDS-DMA ring (s_waitcnt vmcnt(0)) once per tile.
-template <int DT, int METRIC, bool DIRECT, bool XS, int BMQ, int SH, int WQ, int WR, int TR = BROWS, bool RC_LDS = false,
-          typename AccT>
+template <int DT, int METRIC, bool DIRECT, bool XS, int BMQ, int SH, int WQ, int WR, int TR, bool RC_LDS, typename AccT>
 __device__ __forceinline__ void epilogue16(const Batch16Params& p, AccT (&acc)[WQ / SH][WR / SH], uint32_t nt, uint32_t mt,
                                            int wm, int wn, int lane, const float* qa_s, const float* qb_s,
                                            const uint32_t* tau_s, const float* thr_s, const uint32_t* rc0 = nullptr,

@@ -1,10 +1,26 @@
-// scan_mfma16_dma.hip — K2 for the narrow types with LDS-DMA staging.
+// scan_mfma16_dma.hip — K2 for the narrow types: Float16 rows on v_mfma_f32_16x16x32_f16, Int8 / UInt8 rows on
+// v_mfma_i32_16x16x64_i8, operands staged by LDS-DMA.
 //
-// Same role, persistent XCD-aware schedule and epilogue as scan_mfma16.hip (which stages through registers and is kept
-// as the A/B reference); what differs is how the operands reach LDS, the MFMA shape and a second, HBM-bound block shape
-// for small batches.  The register-staged kernel spends ~830 of ~3600 cycles per 128-B
-// k-tile on the VGPR->LDS store path alone (ds_write_b128 moves ~79 B/clk/CU) plus the waits in front of it.  Here
-// every operand byte goes global -> LDS directly (global_load_lds_dwordx4, no VGPRs, no ds_write):
+// Same role as scan_mfma.hip (the batched form of the reference loop, examples/similarity_search.rs:147-169), different
+// balance: these MFMAs are 16-32x faster than the f32 one, so the large tile is 256 corpus rows x 256 queries (8 waves as
+// 2 x 4, each 128 x 64 outputs) — smaller tiles would be bound by L2->LDS traffic, not by the matrix cores or HBM.
+//
+//   Int8    : exact i32 accumulation -> bit-exact dot / L2 (qq + xx - 2 dot) / cosine, identical to K1 and the CPU
+//             (UInt8 rides the same MFMA shifted by 128: scan_mfma16_common.inc).
+//   Float16 : the reference semantics are "f32 query x exactly-widened f16 row" (Vector::as_f32,
+//             src/vectors/vector.rs:81-89).  An f16 MFMA needs an f16 query: each query is scaled by a power of two
+//             (max |q| into [2^14, 2^15)) and ROUNDED to one f16 plane, q~ = f16(q 2^e) (scan_mfma16_prep.hip).  This
+//             kernel only SELECTS with it: |q~.x 2^-e - q.x| <= 2^-11 |q||x| (Cauchy-Schwarz over the per-element
+//             rounding), so the scores are approximate with a proven bound; compact_margin_kernel keeps every row
+//             within twice that bound of the k-th and rescore_kernel recomputes the kept rows from the f32 query
+//             (scan_mfma.hip).  An exact hi+lo two-plane split needs twice the MFMA, LDS and L2 traffic for precision
+//             that only ~k rows per query ever use.
+//
+// Blocks are PERSISTENT (one per CU: the LDS ring allows no more) and walk their tiles in an XCD-aware order with the
+// load pipeline running across tile boundaries: with one tile per block every prologue (two HBM round trips), epilogue
+// and dispatch gap would be exposed.  Every operand byte goes global -> LDS directly (global_load_lds_dwordx4, no
+// VGPRs, no ds_write): staging through registers spent ~830 of ~3600 cycles per 128-B k-tile on the VGPR->LDS store
+// path alone (ds_write_b128 moves ~79 B/clk/CU) plus the waits in front of it.
 //
 //   * k-tile = 64 bytes per row (64 int8 / 32 f16) = the k of one 16x16 MFMA; stage = BMQ query rows + 256 corpus rows x
 //     64 B; a RING of S stages (256-query shape: 4 x 32 KB; 64-query shape: 6 x 20 KB, see CfT).  During k-tile g the
@@ -20,7 +36,8 @@
 //   * UInt8's x ^ 0x80 happens on the B fragments after the LDS read.
 //
 // MFMA shape: v_mfma_f32_16x16x32_f16 / v_mfma_i32_16x16x64_i8 -- one MFMA consumes the whole 64-B k of a fragment
-// pair.  Same LDS bytes and matrix-pipe cycles per k-tile as the 32x32 shapes, but this loop is POWER-limited (the
+// pair; the exact k order inside it does not matter (A and B share the lane->k map).  Same LDS bytes and matrix-pipe
+// cycles per k-tile as the 32x32 shapes, but this loop is POWER-limited (the
 // matrix pipe is ~50 % busy at ~1.8 GHz whatever the staging: the clock falls as the MFMAs pack closer) and the chip
 // holds a higher clock on the 16x16 shape: +7 % wall.  Measured alternatives that did not pay are in DESIGN.md.
 //
@@ -157,7 +174,7 @@ __global__ void __launch_bounds__(512, 2) scan_mfma16_dma_kernel(Batch16Params p
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / Cf::WN, wn = wave % Cf::WN;
 
-    // persistent blocks, XCD-aware tile order (scan_mfma16.hip)
+    // persistent blocks, XCD-aware tile order (file header)
     const uint32_t xcd = blockIdx.x & 7u, ls = blockIdx.x >> 3, nls = gridDim.x >> 3;
     auto slot_tile = [&](uint32_t n, uint32_t& nt, uint32_t& mt) {
         const uint32_t slot = ls + n * nls;
@@ -687,12 +704,11 @@ bool scan_mfma16_dma_wave_regions(int dtype, uint32_t bmq, bool direct, bool has
 
 // p.KPB / p.KT are in 64-byte k-tiles here; p.zeros points at >= 16 zero bytes; p.mtiles = nq_pad / bmq;
 // p.ntiles = ceil(rows / scan_mfma16_dma_tile_rows(bmq)).
-hipError_t launch_scan_mfma16_dma(const Batch16Params& p, int dtype, int metric, int num_cus, uint32_t bmq, bool persistent,
-                                  hipStream_t s) {
+hipError_t launch_scan_mfma16_dma(const Batch16Params& p, int dtype, int metric, int num_cus, uint32_t bmq, hipStream_t s) {
     const uint32_t total = ((p.ntiles + 7) / 8) * p.mtiles * 8;
     uint32_t nls = std::max(1u, (uint32_t)num_cus / 8u);
     if (nls > p.mtiles) nls -= nls % p.mtiles;
-    const dim3 grid(persistent ? std::min(total, nls * 8u) : total);
+    const dim3 grid(std::min(total, nls * 8u));  // persistent: one block per CU (measured: int8 15 % and f16 5 % faster than one tile per block)
     Batch16Params q = p;
     if (grid.x > kBlkMaxBlocks || (q.wave_regions && grid.x > (uint32_t)num_cus))  // one candidate region per block: small grids only
         q.blk_cand = nullptr, q.blk_cnt = nullptr, q.wave_regions = 0;

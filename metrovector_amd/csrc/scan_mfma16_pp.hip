@@ -1,7 +1,9 @@
-// scan_mfma16_pp.hip — K2 for the narrow types, 256-query tile: PING-PONG schedule.
+// scan_mfma16_pp.hip — K2 for Float16 rows (stored, or the f16 shadow of a Float32 corpus), 256-query tile: PING-PONG
+// schedule.  Integer rows measured a few percent slower on it (its longer prologue: profiles/r02_k2_ab.txt) and stay on
+// the lockstep kernel.
 //
 // Same tile (256 queries x 256 corpus rows, 8 waves as 2 x 4, 128 x 64 outputs per wave), LDS-DMA staging, XOR-swizzled
-// 64-byte k-tiles, MFMA shape (v_mfma_f32_16x16x32_f16 / v_mfma_i32_16x16x64_i8) and epilogue as scan_mfma16_dma.hip;
+// 64-byte k-tiles, MFMA shape (v_mfma_f32_16x16x32_f16) and epilogue as scan_mfma16_dma.hip;
 // what differs is WHEN the waves do what.  That kernel runs all 8 waves in lockstep: one barrier per k-tile, and
 // behind it every wave first waits for its LDS fragment reads -- both waves of a SIMD stall together and the matrix pipe
 // idles (SQ_VALU_MFMA_BUSY 54 %, 36 % of wave cycles parked; profiles/r01_cfg5_f16_mfma16_dma_pmc.json).  Here:
@@ -66,16 +68,15 @@ __device__ __forceinline__ uint32_t slot_swz(uint32_t x) { return (0x78u >> (2u 
         __builtin_amdgcn_sched_barrier(0);      \
     } while (0)
 
+// XS = the rows are the scaled-f16 shadow of a Float32 corpus (p.xscale)
 template <int DT, int METRIC, bool DIRECT, bool XS>
 __global__ void __launch_bounds__(512, 2) scan_mfma16_pp_kernel(Batch16Params p) {
-    using AccT = typename std::conditional<DT == MVF_DTYPE_FLOAT16, f32x4, i32x4>::type;
+    static_assert(DT == MVF_DTYPE_FLOAT16, "Float16 rows only");
+    using AccT = f32x4;
     constexpr int NI = WQ / SH, NJ = WR / SH, NE = SH * SH / 64, HI = NI / 2;
-    constexpr bool U8 = DT == MVF_DTYPE_UINT8;
-    constexpr bool QS = DT == MVF_DTYPE_INT8 && XS;             // int8 shadow of a float corpus: float scores (common.inc)
-    constexpr bool F16 = DT == MVF_DTYPE_FLOAT16 || QS;         // ... so the per-row constants are the float ones
-    // per-row constants the epilogue needs (scan_mfma16_common.inc): array 0 = norms, array 1 = shadow scale / UInt8 bias
+    // per-row constants the epilogue needs (scan_mfma16_common.inc): array 0 = norms, array 1 = shadow scale
     constexpr bool NEED0 = METRIC != MVF_METRIC_INNER_PRODUCT;
-    constexpr bool NEED1 = F16 ? XS : (U8 && METRIC != MVF_METRIC_L2);
+    constexpr bool NEED1 = XS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* ringA = smem;
     unsigned char* ringB = smem + NSA * STG;
@@ -85,9 +86,8 @@ __global__ void __launch_bounds__(512, 2) scan_mfma16_pp_kernel(Batch16Params p)
     float* thr_s = qb_s + BMQ;
     uint32_t* rc_s = reinterpret_cast<uint32_t*>(thr_s + BMQ);  // [NRC][2][BR]
     uint32_t* bc_s = rc_s + NRC * 2 * BR;                       // records in the block's candidate region
-    const uint32_t* arr0 = F16 ? reinterpret_cast<const uint32_t*>(METRIC == MVF_METRIC_COSINE ? p.xnorm_f : p.xx2)
-                               : reinterpret_cast<const uint32_t*>(p.xnorm_i);
-    const uint32_t* arr1 = F16 ? reinterpret_cast<const uint32_t*>(p.xscale) : reinterpret_cast<const uint32_t*>(p.xbias_i);
+    const uint32_t* arr0 = reinterpret_cast<const uint32_t*>(METRIC == MVF_METRIC_COSINE ? p.xnorm_f : p.xx2);
+    const uint32_t* arr1 = reinterpret_cast<const uint32_t*>(p.xscale);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(512, 2) scan_mfma16_pp_kernel(Batch16Params p)
     };
     zero_acc();
 
-    load_query_consts16<DT, METRIC, BMQ, QS>(p, mt * BMQ, tid, qa_s, qb_s, tau_s, thr_s);
+    load_query_consts16<DT, METRIC, BMQ, false>(p, mt * BMQ, tid, qa_s, qb_s, tau_s, thr_s);
     if (tid == 0) *bc_s = 0;
     set_dma_tile(0);
     // prologue: A k-tiles 0, 1 (group 0) / B k-tiles 0 .. 3 (group 1)
@@ -182,20 +182,15 @@ __global__ void __launch_bounds__(512, 2) scan_mfma16_pp_kernel(Batch16Params p)
         return *reinterpret_cast<const u32x4*>(st + a_off + i * SH * DKB);
     };
     auto read_b = [&](const unsigned char* st, int j) __attribute__((always_inline)) -> u32x4 {
-        u32x4 x = *reinterpret_cast<const u32x4*>(st + b_off + j * SH * DKB);
-        if (U8) x ^= u32x4{0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
-        return x;
+        return *reinterpret_cast<const u32x4*>(st + b_off + j * SH * DKB);
     };
     auto mfma1 = [&](AccT& c, const u32x4& fa, const u32x4& fb) __attribute__((always_inline)) {
-        if constexpr (DT == MVF_DTYPE_FLOAT16) {
 #ifdef MVF_DIAG_BF16  // diagnostic build only (power / clock of the bf16 MFMA on the same operand bits; results are garbage)
-            typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb), c, 0, 0, 0);
+        typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb), c, 0, 0, 0);
 #else
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, fa), __builtin_bit_cast(half8, fb), c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, fa), __builtin_bit_cast(half8, fb), c, 0, 0, 0);
 #endif
-        } else
-            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, fa), __builtin_bit_cast(i32x4, fb), c, 0, 0, 0);
     };
 
     if (grp == 1) PP_BARRIER();  // the stagger: group 1 runs one barrier behind group 0
@@ -264,24 +259,15 @@ __global__ void __launch_bounds__(512, 2) scan_mfma16_pp_kernel(Batch16Params p)
 
 static_assert(PPW * (NSB - 2) < 16 && PPW * (NSA - 3) < 16, "vmcnt low field");
 
-template <int DT, int METRIC>
-hipError_t launch_dtm(const Batch16Params& p, dim3 grid, hipStream_t s) {
+template <int METRIC>
+hipError_t launch_m(const Batch16Params& p, dim3 grid, hipStream_t s) {
+    constexpr int DT = MVF_DTYPE_FLOAT16;
     void (*fn)(Batch16Params) = p.direct ? &scan_mfma16_pp_kernel<DT, METRIC, true, false> : &scan_mfma16_pp_kernel<DT, METRIC, false, false>;
-    if constexpr (DT == MVF_DTYPE_FLOAT16 || DT == MVF_DTYPE_INT8)  // rows are a scaled shadow (f16, or the int8 shadow: QS)
-        if (p.xscale) fn = p.direct ? &scan_mfma16_pp_kernel<DT, METRIC, true, true> : &scan_mfma16_pp_kernel<DT, METRIC, false, true>;
+    if (p.xscale) fn = p.direct ? &scan_mfma16_pp_kernel<DT, METRIC, true, true> : &scan_mfma16_pp_kernel<DT, METRIC, false, true>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fn, grid, dim3(512), PP_LDS, s, p);
     return hipGetLastError();
-}
-
-template <int DT>
-hipError_t launch_dt(const Batch16Params& p, int metric, dim3 grid, hipStream_t s) {
-    switch (metric) {
-    case MVF_METRIC_L2: return launch_dtm<DT, MVF_METRIC_L2>(p, grid, s);
-    case MVF_METRIC_INNER_PRODUCT: return launch_dtm<DT, MVF_METRIC_INNER_PRODUCT>(p, grid, s);
-    default: return launch_dtm<DT, MVF_METRIC_COSINE>(p, grid, s);
-    }
 }
 
 }  // namespace
@@ -293,15 +279,18 @@ bool scan_mfma16_pp_usable(uint32_t mtiles, int num_cus, uint32_t KT) {
     return KT >= 2 && mtiles >= 1 && mtiles <= std::max(1u, (uint32_t)num_cus / 8u);
 }
 
-// p as for launch_scan_mfma16_dma with the 256-query tile.
+// p as for launch_scan_mfma16_dma with the 256-query tile; Float16 rows only.
 hipError_t launch_scan_mfma16_pp(const Batch16Params& p, int dtype, int metric, int num_cus, hipStream_t s) {
+    if (dtype != MVF_DTYPE_FLOAT16) return hipErrorInvalidValue;
     const uint32_t total = ((p.ntiles + 7) / 8) * p.mtiles * 8;
     uint32_t nls = std::max(1u, (uint32_t)num_cus / 8u);
     nls -= nls % p.mtiles;  // >= mtiles by scan_mfma16_pp_usable
     const dim3 grid(std::min(total, nls * 8u));
-    if (dtype == MVF_DTYPE_FLOAT16) return launch_dt<MVF_DTYPE_FLOAT16>(p, metric, grid, s);
-    if (dtype == MVF_DTYPE_UINT8) return launch_dt<MVF_DTYPE_UINT8>(p, metric, grid, s);
-    return launch_dt<MVF_DTYPE_INT8>(p, metric, grid, s);
+    switch (metric) {
+    case MVF_METRIC_L2: return launch_m<MVF_METRIC_L2>(p, grid, s);
+    case MVF_METRIC_INNER_PRODUCT: return launch_m<MVF_METRIC_INNER_PRODUCT>(p, grid, s);
+    default: return launch_m<MVF_METRIC_COSINE>(p, grid, s);
+    }
 }
 
 }  // namespace mvf

@@ -2,7 +2,7 @@
 
 An LDS-DMA stage read before its data landed passes any single comparison whenever the DMA happens to win the
 race; it shows up as rare run-to-run differences.  For each config: N searches must return bit-identical
-(scores, indices, raw), and the register-staged reference kernel (MVF_K2_DMA=0) must return the same."""
+(scores, indices, raw)."""
 import hashlib, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -56,13 +56,9 @@ for (n, dim, dt, metric, nq) in CONFIGS:
     ds = set()
     for i in range(REPS):
         ds.add(digest(c.search(q, 100, metric)))
-    os.environ["MVF_K2_DMA"] = "0"
-    c.reload_tuning()
-    ref = digest(c.search(q, 100, metric))
-    del os.environ["MVF_K2_DMA"]
-    ok = len(ds) == 1 and ref in ds
+    ok = len(ds) == 1
     bad += not ok
-    print(f"n={n} dim={dim} dt={dt} metric={metric} nq={nq}: {REPS} runs -> {len(ds)} distinct digest(s); "
-          f"register-staged kernel {'agrees' if ref in ds else 'DIFFERS'}  [{time.time()-t0:.1f} s]  {'OK' if ok else 'FAIL'}", flush=True)
+    print(f"n={n} dim={dim} dt={dt} metric={metric} nq={nq}: {REPS} runs -> {len(ds)} distinct digest(s)  "
+          f"[{time.time()-t0:.1f} s]  {'OK' if ok else 'FAIL'}", flush=True)
     c.close()
 sys.exit(1 if bad else 0)

@@ -142,9 +142,8 @@ def test_every_combination_of_the_tuning_switches_returns_the_same_rows(oracle, 
     """The environment switches choose kernels, tiles, shadows and schedules -- never results."""
     import itertools
     import os
-    switches = {"MVF_K2_PP": ("0", "1"), "MVF_K2_DMA": ("0", "1"), "MVF_I8_SHADOW": ("0", "1"), "MVF_F16_SHADOW": ("0", "1"),
-                "MVF_K2_TILE": ("64", "256"), "MVF_K2_GROWTH": ("2", "8"), "MVF_QS_REFINE": ("0", "1"),
-                "MVF_K2_PERSISTENT16": ("0", "1"), "MVF_K2_SB": ("0", "1")}
+    switches = {"MVF_K2_PP": ("0", "1"), "MVF_I8_SHADOW": ("0", "1"), "MVF_F16_SHADOW": ("0", "1"),
+                "MVF_K2_TILE": ("64", "256"), "MVF_K2_GROWTH": ("2", "8"), "MVF_QS_REFINE": ("0", "1")}
     n, dim, nq, k = 90_000, 72, 140, 25
     metric = dtype % 3
     rows = oracle.synth_rows(SEED + dtype, 0, n, dim, dtype)

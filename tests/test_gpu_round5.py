@@ -192,8 +192,7 @@ def test_phase_schedule_switches_do_not_change_the_results(oracle, monkeypatch, 
         all_sc = oracle_scores_all_rows(oracle, SEED, 0, n, dim, dt, metric, q[sel], chunk=400_000)
         for j, qi in enumerate(sel):
             assert_float_topk(metric, base.scores[qi], base.indices[qi], all_sc[j], None, q[qi], k)
-        for var, values in (("MVF_K2_GROWTH_SMALL", ("4", "8")), ("MVF_K2_GROWTH", ("3", "6")), ("MVF_QS_REFINE_PHASES", ("0", "1", "3")),
-                            ("MVF_K2_DIRECT64", ("0",))):
+        for var, values in (("MVF_K2_GROWTH_SMALL", ("4", "8")), ("MVF_K2_GROWTH", ("3", "6")), ("MVF_QS_REFINE_PHASES", ("0", "1", "3"))):
             for v in values:
                 monkeypatch.setenv(var, v)
                 c.reload_tuning()
