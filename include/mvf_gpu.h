@@ -464,12 +464,17 @@ int mvfgpu_last_timing(const mvfgpu_corpus* corpus, mvfgpu_timing* out);
  * would not fit the candidate budget, such requests take the f16 shadow / the
  * stored rows.
  * 6 = as 5, and ONE TO FOUR queries STREAM THE INT8 SHADOW through K1
- * (`dimension` bytes per row instead of 4x / 2x that; same bound, same exact
- * re-scoring: 1.2-1.3 ms for one query instead of 4.5 on 10M x 768 f32).
- * MVF_STREAM_I8=1 makes path 0 do this for ONE query once the corpus holds an
- * int8 shadow anyway (round 2 did so unasked: the answer to the same query then
- * depended, within the tolerance, on what the handle had served before).  Two
- * to four queries are served as fast by the 64-query MFMA tile.
+ * (`dimension` bytes per row instead of 4x / 2x that; same bound, exact
+ * re-scoring: ~1.2 ms for one query instead of 4.5 on 10M x 768 f32).  On
+ * Float32 rows the re-scoring uses K1's own arithmetic, so a single query gets
+ * the bits of path 1.  Path 0 does the same BY DEFAULT for ONE query on a
+ * Float32 corpus of at least 512 MiB of rows (k <= 204), once its whole int8
+ * shadow is held or fits beside it (+25 % of the rows' HBM, built by the first
+ * such query, ~13 ms on 10M x 768) and its rows are finite; the answer does not
+ * depend on the route.  MVF_STREAM_I8=0 keeps path 0 on the stored rows;
+ * MVF_STREAM_I8=1 also takes the route below 512 MiB, and on Float16 corpora,
+ * once the corpus holds a whole int8 shadow.  Two to four queries are served
+ * as fast by the 64-query MFMA tile.
  *
  * Selection shadows: batched searches on a Float32 / Float16 corpus select
  * candidates on an INT8 copy of the rows (path 5's, the default: built by the
@@ -520,6 +525,15 @@ int mvfgpu_selftest_feedback(const uint32_t* samples, uint32_t n_samples, uint32
  */
 int mvfgpu_selftest_route(uint64_t rows, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq, uint32_t k,
                           uint32_t* out_route);
+
+/*
+ * Self-test of the rows a search on path 0 reads (no GPU needed; same arguments and tuning as mvfgpu_selftest_route, whose
+ * answer it refines for route 0): *out_rows = 1 where ONE query streams the int8 shadow of the Float32 rows (K1 over a
+ * quarter of the bytes, re-scored with K1's arithmetic: the same bits), 0 where K1 reads the stored rows.  The shape part of
+ * the rule only: at run time the shadow must also be whole, fit (or be held) and have finite bound maxima.
+ */
+int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq, uint32_t k,
+                                uint32_t* out_rows);
 
 /*
  * Self-test of a batched search's phase schedule (no GPU needed): the row boundaries R_1 .. R_last = rows of the geometric phases a

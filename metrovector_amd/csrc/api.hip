@@ -14,6 +14,7 @@
 #include "scan_stream.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <chrono>
@@ -126,7 +127,7 @@ Tuning read_tuning() {
     t.debug_repair = getenv("MVF_DEBUG_REPAIR") != nullptr;
     t.repair_window = (uint32_t)std::max(0l, num("MVF_REPAIR_WINDOW", 0));
     if (const char* e = getenv("MVF_K2_REGION_RECORDS")) t.region_records = strtoull(e, nullptr, 10);
-    t.stream_i8 = flag("MVF_STREAM_I8", false);
+    t.stream_i8 = getenv("MVF_STREAM_I8") ? (flag("MVF_STREAM_I8", false) ? 1 : 0) : -1;
     t.upload_threads = (unsigned)std::max(0l, num("MVF_UPLOAD_THREADS", 0));
     t.host_zc_query = (size_t)std::max(0l, num("MVF_HOST_ZC_QUERY", 64l << 10));
     t.host_zc_results = (size_t)std::max(0l, num("MVF_HOST_ZC_RESULTS", 256l << 10));
@@ -180,6 +181,7 @@ struct mvfgpu_corpus {
     mutable DevBuf shadow8, xscale8, qs_stats;  // Float32 / Float16 corpora: int8 shadow rows, s_r per row, the 4 bound maxima
     mutable int shadow8_state = 0;             // 0 not tried, 1 all rows, 2 a PREFIX of the rows (shadow8_rows; batched path only), -1 no room for all rows, -2 none for a useful prefix either
     mutable uint64_t shadow8_rows = 0;         // rows the int8 shadow covers
+    mutable int shadow8_finite = -1;           // the shadow's four bound maxima are finite: -1 not read back yet, 0 no (a row holds Inf / NaN), 1 yes
     mutable DevBuf split_out;                  // partial shadow: the two row ranges' result lists before their merge
     // feedback for the automatic choice: after a search that selected on the int8 shadow the number of queries the
     // repair launches had to redo is copied to pinned host memory (no wait); a later search that finds it large
@@ -312,6 +314,18 @@ const void* scan_kernel(uint8_t dtype, int metric, int G, int nqv, bool redo = f
     case MVF_DTYPE_INT8: return scan_stream_kernel_ptr_dt2(metric, G, nqv, redo, floor);
     default: return scan_stream_kernel_ptr_dt3(metric, G, nqv, redo, floor);
     }
+}
+
+// The lane-group width G, steps J and queries per pass K1 takes on the STORED rows for a search of nq <= 4 queries at k
+// (search_stream_path's rule: one query alone, two to four in one four-query pass unless its LDS does not fit).
+void k1_stored_group(const mvfgpu_corpus* c, uint32_t nq, uint32_t k, int* G, uint32_t* J, int* nqv_out) {
+    int nqv = nq >= 2 ? 4 : 1;
+    choose_group(c->V, nqv, G, J, c->tune.k1_g);
+    if (nqv == 4 && scan_lds_bytes(c->dtype, *G, *J, nqv, next_pow2(k + scan_chunk_safe(*G))) > 150 * 1024) {
+        nqv = 1;
+        choose_group(c->V, nqv, G, J, c->tune.k1_g);
+    }
+    *nqv_out = nqv;
 }
 
 // Streaming over the scaled-f16 shadow of a Float32 corpus (scan path 4): K1 reads the shadow rows instead of the stored
@@ -828,6 +842,7 @@ hipError_t ensure_shadow8(const mvfgpu_corpus* c, hipStream_t s, bool insist, bo
     if (e == hipSuccess) {
         c->shadow8_rows = rows;
         c->shadow8_state = rows == std::max<uint64_t>(c->n, 1) ? 1 : 2;
+        c->shadow8_finite = -1;
     }
     return e;
 }
@@ -891,18 +906,20 @@ int ensure_norms(const mvfgpu_corpus* c, hipStream_t s) {
 // when its window is empty.  The common case (nothing flagged) costs a few empty launches (~2.5 us each on the device,
 // hidden behind the scan on the host); an adversarial corpus is still answered exactly.  R (queries per pair) is what
 // 256 MiB of per-block lists hold.
+// nqv_want = 1: the repair passes take one query each, with the lane-group width K1 uses for ONE query (a single-query search
+// whose answer must carry the bits the stored-row route gives it: search_stream_qs_path).
 int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t nq_pad,
                            uint32_t k, uint32_t* overflow, float* d_scores, uint64_t* d_indices, int32_t* d_raw,
-                           hipStream_t s) {
+                           hipStream_t s, int nqv_want = 4) {
     (void)nq_pad;
     if (c->n == 0) return MVF_OK;
     const uint32_t kcap = next_pow2(k);
-    int nqv = 4, G;
+    int nqv = nqv_want == 1 ? 1 : 4, G;
     uint32_t J;
     choose_group(c->V, nqv, &G, &J, c->tune.k1_g);
     uint32_t chunk_rows = scan_chunk_rows(G, J, nqv), pmax = next_pow2(k + scan_chunk_safe(G));
     size_t lds = scan_lds_bytes(c->dtype, G, J, nqv, pmax);
-    if (lds > 150 * 1024) {
+    if (nqv == 4 && lds > 150 * 1024) {
         nqv = 1;
         choose_group(c->V, nqv, &G, &J, c->tune.k1_g);
         chunk_rows = scan_chunk_rows(G, J, nqv);
@@ -922,7 +939,8 @@ int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d
     // 10,000-query batch in three pairs at k = 10), and a 1024-query search enqueues 2 (empty) pairs instead of 16
     // (0.14 ms of launches on a 10-ms search; a 10,000-query search on 1M x 128 spent 0.36 of its 5.6 ms in 40 empty pairs
     // while the cap was 256).
-    const uint32_t nblocks = std::min<uint32_t>(nchunks, (uint32_t)std::min(occ, 2) * (uint32_t)c->num_cus);
+    // (a one-query repair -- nqv_want = 1, one search's single flagged query -- keeps K1's full grid: its lists are few)
+    const uint32_t nblocks = std::min<uint32_t>(nchunks, (uint32_t)(nqv_want == 1 ? occ : std::min(occ, 2)) * (uint32_t)c->num_cus);
     const size_t per_query = (size_t)nblocks * kcap * 8;
     uint32_t R = (uint32_t)std::min<size_t>(4096, std::max<size_t>(4, ((size_t)256 << 20) / per_query));
     if (c->tune.repair_window) R = std::min<uint32_t>(R, std::max<uint32_t>(4, c->tune.repair_window));  // tests: several windows on small batches
@@ -1517,27 +1535,53 @@ int search_stream_qs_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_
     rp.out_scores = d_scores;
     rp.out_indices = d_indices;
     rp.out_raw = d_raw;
-    HIP_TRY(launch_rescore(rp, metric, nq, s));
-    rc = repair_flagged_queries(c, metric, d_queries, nq, nq_pad, k, overflow, d_scores, d_indices, d_raw, s);
+    // Float32 rows: re-scored in K1's arithmetic at the width K1 takes for these queries on the stored rows, and a flagged
+    // query redone by K1 at that width too -- the answer carries the bits the stored-row route gives it (Float16 rows: the
+    // wave kernel's order; out of that promise)
+    int G, nqv;
+    uint32_t J;
+    k1_stored_group(c, nq, k, &G, &J, &nqv);
+    if (c->dtype == MVF_DTYPE_FLOAT32) HIP_TRY(launch_rescore_k1(rp, metric, nq, G, J, s));
+    else HIP_TRY(launch_rescore(rp, metric, nq, s));
+    rc = repair_flagged_queries(c, metric, d_queries, nq, nq_pad, k, overflow, d_scores, d_indices, d_raw, s, nqv);
     if (rc == MVF_OK && c->scan_path != 6) rc = qs_feedback_post(c, nq, s);
     return rc;
 }
 
-// One to four queries stream the int8 shadow on request (scan path 6; MVF_STREAM_I8=1: one query on scan path 0, once the
-// corpus HOLDS an int8 shadow anyway): 1.24 instead of 4.5 ms on 10M x 768, same rows, scores within the tolerance (the
-// re-scoring kernel sums in another order than K1).  By default one query reads the stored rows, whatever the handle
-// has served before (the bench's headline: no extra memory, no build).  Two to four queries are served as fast by the 64-query MFMA tile on the same
-// shadow (1.55-1.65 ms against 1.53-1.72: profiles/r02_stream_int8_shadow_1to4_queries.txt).  MVF_STREAM_I8=0 opts
-// out; a corpus whose queries keep needing the repair pass switches itself back (qs_disabled).
+// ONE query on a Float32 corpus of at least this many bytes of rows streams its int8 shadow by default (scan path 0): a quarter
+// of the bytes, re-scored in K1's arithmetic -- the same bits as K1 on the stored rows.  Below it the fixed cost of the route
+// (query preparation, the margin select, the re-scoring, the repair check: ~58 us of kernels) outweighs the bytes it spares.
+// Measured, 768-dim f32 cosine, top-100, device time per search (profiles/r06_stream_i8_crossover.txt): 256 MiB 0.084 ms
+// against K1's 0.081; 512 MiB 0.084 against 0.123; 1 GiB 0.112 / 0.200; 4 GiB 0.234 / 0.673.
+constexpr uint64_t kStreamI8MinBytes = 512ull << 20;
+
+// The shape part of that rule, a pure function (mvfgpu_selftest_stream_rows pins it without a GPU): Float32 rows, one query,
+// k <= kQsStreamMaxK, rows the int8 selection's re-scoring takes (qs_possible), at least kStreamI8MinBytes of rows.
+bool stream_i8_shape(uint64_t rows, uint32_t dim, uint8_t dtype, uint32_t nq, uint32_t k) {
+    if (dtype != MVF_DTYPE_FLOAT32 || nq != 1 || k == 0 || k > kQsStreamMaxK || rows == 0 || dim == 0) return false;
+    if ((size_t)((dim + 7u) & ~7u) * 4 + kBatchCapQS * 4 > 64 * 1024) return false;
+    return rows * (uint64_t)dim * 4u >= kStreamI8MinBytes;
+}
+
+// One to four queries stream the int8 shadow on request (scan path 6), and ONE query on scan path 0 does by default where
+// stream_i8_shape holds: 10M x 768 f32, one query, 4.47 -> ~1.2 ms.  The re-scoring (launch_rescore_k1) and the repair of a
+// flagged query (K1 at the one-query width) both give K1's bits, so the answer does not depend on the route -- nor on the
+// handle's history (round 2 made this route automatic with the re-scoring kernel's own summation order, and the same query
+// then scored differently depending on whether an earlier batched search had built the shadow; it was reverted).
+// Scan path 0 takes the route only with a WHOLE shadow, held or buildable now under ensure_shadow8's free-memory rule (a
+// prefix, or no room: the stored rows), and not over a shadow whose bound maxima are non-finite (search_device: every query
+// would be flagged and repaired).  MVF_STREAM_I8=0 opts out; MVF_STREAM_I8=1 also takes any size once the shadow exists.
+// A corpus whose queries keep needing the repair pass switches itself back (qs_disabled).  Two to four queries are served as
+// fast by the 64-query MFMA tile on the same shadow (1.55-1.65 ms against 1.53-1.72:
+// profiles/r02_stream_int8_shadow_1to4_queries.txt).
 bool stream_qs_wanted(const mvfgpu_corpus* c, uint32_t nq, uint32_t k) {
     if (nq < 1 || nq > 4 || k > kQsStreamMaxK || !qs_wanted(c, k)) return false;
     if (c->scan_path == 6) return true;
-    // scan path 0: only with MVF_STREAM_I8=1 and once the corpus holds an int8 shadow anyway.  (Round 2 did this by itself:
-    // the same query on the same handle then gave scores in a different summation order -- K1's against the re-scoring
-    // kernel's -- depending on whether an earlier batched search had built the shadow.  An automatic path must not
-    // depend on the handle's history.)
-    if (c->scan_path != 0 || nq != 1 || c->shadow8_state != 1) return false;
-    return c->tune.stream_i8;
+    if (c->scan_path != 0 || nq != 1 || c->tune.stream_i8 == 0) return false;
+    if (c->shadow8_state != 0 && c->shadow8_state != 1) return false;
+    if (c->shadow8_state == 1 && c->shadow8_finite == 0) return false;
+    if (c->tune.stream_i8 == 1 && c->shadow8_state == 1) return true;
+    return stream_i8_shape(c->n, c->dim, c->dtype, nq, k);
 }
 
 // Scan path 4 applies to one or two queries on a Float32 corpus whose shadow exists (or can be built now).
@@ -1547,6 +1591,9 @@ bool stream_shadow_wanted(const mvfgpu_corpus* c, uint32_t nq) {
     return (size_t)((c->dim + 7u) & ~7u) * 4 + kBatchCap * 4 <= 64 * 1024;  // the re-scoring kernel keeps the query in LDS
 }
 
+// Batched MFMA route or K1.  Where it answers K1 for ONE Float32 query, search_device first asks stream_qs_wanted: from
+// kStreamI8MinBytes of rows K1 then streams the int8 shadow instead of the stored rows (same kernel, a quarter of the bytes,
+// the same bits) -- mvfgpu_selftest_route still reports route 0 there, mvfgpu_selftest_stream_rows which rows K1 reads.
 bool use_batched_path(const mvfgpu_corpus* c, uint8_t metric, uint32_t nq) {
     if (c->scan_path == 1) return false;
     // Float32 / Float16: every metric (L2 = GEMM-form selection with an error margin + exact re-scoring);
@@ -1768,6 +1815,7 @@ int upload_rows(mvfgpu_corpus* c, const void* rows, uint64_t stride, const mvfgp
     if (want_norms) c->xnorm_ready = true;
     c->shadow_state = want_shadow ? 1 : c->shadow_state;
     c->shadow8_state = want_shadow8 ? 1 : c->shadow8_state;
+    if (want_shadow8) c->shadow8_finite = -1;
     return MVF_OK;
 }
 
@@ -2343,6 +2391,13 @@ int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
         hipError_t e = ensure_shadow8(c, s, c->scan_path == 6);
         if (e != hipSuccess) return fail(MVF_ERR_DEVICE, std::string("int8 shadow build: ") + hipGetErrorString(e));
         qs_stream = c->shadow8_state == 1;
+        if (qs_stream && c->scan_path == 0 && c->shadow8_finite < 0) {  // once per shadow: its bound maxima (one small wait)
+            float st[4] = {0.f, 0.f, 0.f, 0.f};
+            HIP_TRY(hipMemcpyAsync(st, c->qs_stats.p, sizeof(st), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            c->shadow8_finite = std::isfinite(st[0]) && std::isfinite(st[1]) && std::isfinite(st[2]) && std::isfinite(st[3]) ? 1 : 0;
+        }
+        if (qs_stream && c->scan_path == 0 && c->shadow8_finite == 0) qs_stream = false;  // a row holds Inf / NaN: the stored rows
     }
     if (!qs_stream && stream_shadow_wanted(c, nq)) {
         hipError_t e = ensure_shadow(c, s, c->scan_path == 4);
@@ -2795,6 +2850,17 @@ int mvfgpu_selftest_route(uint64_t rows, uint32_t dimension, uint8_t data_type, 
     c->tune = Tuning{};
     if (k > MVFGPU_K_PER_PASS) *out_route = large_k_by_sort(c.get(), nq, k) ? 3u : 2u;
     else *out_route = use_batched_path(c.get(), metric, nq) ? 1u : 0u;
+    return MVF_OK;
+}
+
+int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq, uint32_t k,
+                                uint32_t* out_rows) {
+    if (!out_rows) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (elem_size(data_type) == 0 || dimension == 0 || nq == 0 || k == 0 || k > MVFGPU_MAX_K)
+        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported type or empty dimension / batch / k");
+    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
+        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code");
+    *out_rows = stream_i8_shape(rows, dimension, data_type, nq, k) ? 1u : 0u;
     return MVF_OK;
 }
 

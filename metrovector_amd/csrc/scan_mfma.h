@@ -142,6 +142,9 @@ struct RescoreParams {
 };
 hipError_t launch_compact_margin(const CompactParams& p, uint32_t nq, hipStream_t s);
 hipError_t launch_rescore(const RescoreParams& p, int metric, uint32_t nq, hipStream_t s);
+// The same final re-scoring + select on Float32 rows in K1's arithmetic (k1_rowscore.h) for K1's lane-group width G and
+// steps J on the stored rows: the scores carry the bits scan_stream_kernel gives the same queries (the int8-shadow stream)
+hipError_t launch_rescore_k1(const RescoreParams& p, int metric, uint32_t nq, int G, uint32_t J, hipStream_t s);
 // Threshold refinement between two phases of an int8-shadow selection: the ntop[q] >= k best approximate candidates of
 // every query are scored EXACTLY (rescore's arithmetic; L2 as the squared distance the selection works on); the worst of
 // those exact scores, L, is a lower bound of the final k-th best score, so a row of the final top-k has an approximate

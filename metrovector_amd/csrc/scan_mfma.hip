@@ -31,6 +31,7 @@
 #include "scan_mfma.h"
 
 #include "bitonic.h"
+#include "k1_rowscore.h"
 #include "mvf_common.h"
 #include "scan_mfma16_key.h"
 
@@ -934,6 +935,111 @@ bool launch_rescore_wave(const RescoreParams& p, uint32_t nq, uint32_t slices, c
     return true;
 }
 
+// ---- the same scoring in K1's ARITHMETIC, one query's candidates over the chip (the int8-shadow stream, Float32 rows) ------
+// rescore_wave_kernel's items and ballot, but a candidate is scored as K1 scores it for one query on the stored rows
+// (k1_rowscore.h): G lanes per row, lane `sub` owning the vectors j G + sub, the xor butterfly over G lanes, the query's sum
+// of squares in K1's staging order -- so the streamed shadow returns K1's bits, and the route a query takes does not change
+// its answer.  A round scores U = 4 row groups of 64 / G rows (the live candidates of the slice, compacted by the ballot:
+// the one in rank `n` sits in the lane of the n-th set bit), all J x 4 row loads of a lane in flight together.  The
+// query is read from global memory (a few KiB: cache-resident), zero beyond the dimension as K1's LDS copy.
+__device__ __forceinline__ int nth_set_bit(unsigned long long mask, uint32_t n) {  // n < popcount(mask)
+    int pos = 0;
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) {
+        const uint32_t lo = (uint32_t)__builtin_popcountll(mask & ((1ull << w) - 1ull));
+        if (n >= lo) {
+            n -= lo;
+            mask >>= w;
+            pos += w;
+        }
+    }
+    return pos;
+}
+
+template <int METRIC, int G>
+__global__ void __launch_bounds__(256) rescore_k1_kernel(RescoreParams p, uint32_t nq, uint32_t slices, uint32_t split, uint32_t J) {
+    constexpr int RPG = 64 / G, U = 4;
+    constexpr uint32_t PER_ROUND = (uint32_t)(RPG * U);
+    constexpr bool NEED_XX = METRIC == MVF_METRIC_COSINE;
+    const int lane = threadIdx.x & 63, sub = lane % G, rsel = lane / G;
+    const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = (gridDim.x * 256u) >> 6;
+    const uint32_t keep_cap = p.cap / 2;
+    const uint32_t V = p.pitch / 16;
+    for (uint32_t item = wave; item < nq * slices * split; item += nwaves) {
+        const uint32_t q = item % nq, sl0 = (item / nq) % slices, part = item / (nq * slices);
+        const uint32_t m = min(p.cnt[q], keep_cap);
+        if (sl0 * 64u >= m) continue;  // wave-uniform
+        const float* qp = p.queries + (size_t)q * p.dim;
+        const float qq = NEED_XX ? k1::query_qq_wave(qp, p.dim, lane) : 0.0f;
+        const uint32_t tau_q = p.tau[q];
+        uint64_t* c = p.cand + (size_t)q * p.cap;
+        for (uint32_t sl = sl0; sl * 64u < m; sl += slices) {
+            const uint32_t ci = sl * 64u + (uint32_t)lane;
+            const uint64_t ce = ci < m ? c[ci] : kPadComposite;
+            const bool live = ci < m && (tau_q == kNanKey || (uint32_t)(ce >> 32) <= tau_q);
+            if (part == 0 && ci < m && !live) c[keep_cap + ci] = kPadComposite;  // outside the threshold: not scored
+            const unsigned long long mask = __builtin_amdgcn_ballot_w64(live);
+            const uint32_t nlive = (uint32_t)__builtin_popcountll(mask);
+            for (uint32_t rnd = part; rnd * PER_ROUND < nlive; rnd += split) {  // wave-uniform
+                int src[U];
+                bool ok[U];
+                uint32_t row[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t rank = rnd * PER_ROUND + (uint32_t)(u * RPG + rsel);
+                    ok[u] = rank < nlive;
+                    src[u] = ok[u] ? nth_set_bit(mask, rank) : 0;
+                    row[u] = (uint32_t)__shfl((int)(uint32_t)ce, src[u], 64);
+                }
+                float acc[U], xx[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) acc[u] = 0.0f, xx[u] = 0.0f;
+                for (uint32_t j = 0; j < J; j++) {
+                    const uint32_t v = j * G + (uint32_t)sub;
+                    const bool vv = v < V;
+                    k1::u32x4 x[U];
+#pragma unroll
+                    for (int u = 0; u < U; u++)
+                        x[u] = (vv && ok[u]) ? *reinterpret_cast<const k1::u32x4*>(p.rows + (size_t)row[u] * p.pitch + (size_t)v * 16)
+                                             : k1::u32x4{0, 0, 0, 0};
+                    float qe[4];
+#pragma unroll
+                    for (int w = 0; w < 4; w++) {
+                        const uint32_t e = v * 4u + (uint32_t)w;
+                        qe[w] = e < p.dim ? qp[e] : 0.0f;
+                    }
+                    const float4 qv = make_float4(qe[0], qe[1], qe[2], qe[3]);
+#pragma unroll
+                    for (int u = 0; u < U; u++) {
+                        acc[u] = k1::acc4<METRIC>(acc[u], qv, x[u]);
+                        if constexpr (NEED_XX) xx[u] = k1::xx4(xx[u], x[u]);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const float s = k1::group_sum<G>(acc[u]);
+                    const float xxs = NEED_XX ? k1::group_sum<G>(xx[u]) : 0.0f;
+                    const uint32_t key = k1::key<METRIC>(s, xxs, qq);
+                    if (sub == 0 && ok[u]) c[keep_cap + sl * 64u + (uint32_t)src[u]] = ((uint64_t)key << 32) | row[u];
+                }
+            }
+        }
+    }
+}
+
+template <int METRIC>
+const void* pick_rescore_k1(int G) {
+    switch (G) {
+    case 1: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 1>);
+    case 4: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 4>);
+    case 8: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 8>);
+    case 16: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 16>);
+    case 32: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 32>);
+    case 64: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 64>);
+    default: return nullptr;
+    }
+}
+
 // One thread per query: tau[q] = the tighter of itself and ord(L -/+ delta), L = the worst exact score of its k best
 // approximate candidates (rescore_score_kernel<., true>); re-arms lkey.  The 2 % on delta covers the f32 rounding of the
 // exact scores themselves (the final ranking is by those f32 values).
@@ -1086,6 +1192,29 @@ hipError_t launch_rescore(const RescoreParams& p, int metric, uint32_t nq, hipSt
     else if (metric == MVF_METRIC_COSINE) hipLaunchKernelGGL(rescore_score_kernel<MVF_METRIC_COSINE>, grid, dim3(256), lds, s, p);
     else hipLaunchKernelGGL(rescore_score_kernel<MVF_METRIC_INNER_PRODUCT>, grid, dim3(256), lds, s, p);
     hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rescore_select_kernel, dim3(nq), dim3(1024), (size_t)(p.cap / 2) * 8, s, p, metric);
+    return hipGetLastError();
+}
+
+hipError_t launch_rescore_k1(const RescoreParams& p, int metric, uint32_t nq, int G, uint32_t J, hipStream_t s) {
+    if (nq == 0) return hipSuccess;
+    if (p.dtype != MVF_DTYPE_FLOAT32) return hipErrorInvalidValue;
+    const void* fn = metric == MVF_METRIC_L2               ? pick_rescore_k1<MVF_METRIC_L2>(G)
+                     : metric == MVF_METRIC_INNER_PRODUCT ? pick_rescore_k1<MVF_METRIC_INNER_PRODUCT>(G)
+                     : metric == MVF_METRIC_COSINE        ? pick_rescore_k1<MVF_METRIC_COSINE>(G)
+                                                          : nullptr;
+    if (!fn) return hipErrorInvalidValue;
+    // items as the final pass of launch_rescore_wave: a query's 64-candidate slices, `split` waves sharing a slice so that
+    // ONE query's ~1000 candidates spread over the chip (nq = 1: 32 slices x 16 waves, 128 blocks)
+    const uint32_t slices = (p.cap / 2 + 63u) / 64u;
+    const uint32_t split = std::max(1u, std::min(16u, 8192u / std::max(1u, nq * slices)));
+    const uint32_t items = nq * slices * split;
+    const dim3 grid(std::max(1u, std::min((items + 3u) / 4u, 2048u)));
+    RescoreParams arg = p;
+    uint32_t a_nq = nq, a_slices = slices, a_split = split, a_j = J;
+    void* args[] = {&arg, &a_nq, &a_slices, &a_split, &a_j};
+    hipError_t e = hipLaunchKernel(fn, grid, dim3(256), args, 0, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rescore_select_kernel, dim3(nq), dim3(1024), (size_t)(p.cap / 2) * 8, s, p, metric);
     return hipGetLastError();

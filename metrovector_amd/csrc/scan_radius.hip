@@ -13,6 +13,7 @@
 
 #include "scan_radius.h"
 #include "bitonic.h"
+#include "k1_rowscore.h"
 #include "mvf_common.h"
 
 #include <hip/hip_fp16.h>
@@ -348,7 +349,8 @@ __global__ void __launch_bounds__(1024) radius_pack_kernel(RadiusPackParams p) {
     }
 }
 
-// R3: grid (nq), block 256, dynamic LDS radius_scan_lds_bytes(Float32, G, J, 1)
+// R3: grid (nq), block 256, dynamic LDS radius_scan_lds_bytes(Float32, G, J, 1).  The per-row arithmetic is K1's, from
+// k1_rowscore.h (shared with the int8-shadow stream's re-scoring); the query's sum of squares is staged in K1's order below.
 template <int METRIC, int G>
 __global__ void __launch_bounds__(256) radius_rescore_kernel(RadiusRescoreParams p) {
     constexpr int RPG = 64 / G;
@@ -384,39 +386,15 @@ __global__ void __launch_bounds__(256) radius_rescore_kernel(RadiusRescoreParams
         float acc = 0.0f, xx = 0.0f;
         for (uint32_t j = 0; j < p.J; j++) {
             const uint32_t v = j * G + sub;
-            u32x4 x = u32x4{0, 0, 0, 0};
-            if (ok && v < p.V) x = *reinterpret_cast<const u32x4*>(rp + (size_t)v * 16);
+            k1::u32x4 x = k1::u32x4{0, 0, 0, 0};
+            if (ok && v < p.V) x = *reinterpret_cast<const k1::u32x4*>(rp + (size_t)v * 16);
             const float4 qv = *reinterpret_cast<const float4*>(qs + v * 4);
-            const float x0 = __uint_as_float(x.x), x1 = __uint_as_float(x.y), x2 = __uint_as_float(x.z), x3 = __uint_as_float(x.w);
-            if constexpr (METRIC == MVF_METRIC_L2) {
-                float t0 = qv.x - x0, t1 = qv.y - x1, t2 = qv.z - x2, t3 = qv.w - x3;
-                acc = fmaf(t0, t0, acc);
-                acc = fmaf(t1, t1, acc);
-                acc = fmaf(t2, t2, acc);
-                acc = fmaf(t3, t3, acc);
-            } else {
-                acc = fmaf(qv.x, x0, acc);
-                acc = fmaf(qv.y, x1, acc);
-                acc = fmaf(qv.z, x2, acc);
-                acc = fmaf(qv.w, x3, acc);
-            }
-            if constexpr (NEED_XX) {
-                xx = fmaf(x0, x0, xx);
-                xx = fmaf(x1, x1, xx);
-                xx = fmaf(x2, x2, xx);
-                xx = fmaf(x3, x3, xx);
-            }
+            acc = k1::acc4<METRIC>(acc, qv, x);
+            if constexpr (NEED_XX) xx = k1::xx4(xx, x);
         }
-        const float s = rgroup_sum<G>(acc);
-        float sc;
-        if constexpr (METRIC == MVF_METRIC_L2) sc = sqrtf(s);
-        else if constexpr (METRIC == MVF_METRIC_INNER_PRODUCT) sc = s;
-        else {
-            const float xxs = rgroup_sum<G>(xx);
-            const float den = sqrtf(qq) * sqrtf(xxs);
-            sc = den > 0.0f ? s / den : 0.0f;
-        }
-        const uint32_t key = key_from_score(sc, METRIC);
+        const float s = k1::group_sum<G>(acc);
+        const float xxs = NEED_XX ? k1::group_sum<G>(xx) : 0.0f;
+        const uint32_t key = k1::key<METRIC>(s, xxs, qq);
         const bool hit = sub == 0 && ok && key <= bnd;
         radius_append(hit, ((uint64_t)key << 32) | row, p.counts + q, list, p.cap, lane);
     }

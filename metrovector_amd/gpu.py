@@ -76,6 +76,15 @@ def radius_route(data_type: int, nq: int, scan_path: int = 0) -> int:
     return out.value
 
 
+def stream_rows(rows: int, dim: int, data_type: int, metric: int, nq: int, k: int) -> int:
+    """1: on scan path 0 the search streams the int8 shadow of the Float32 rows (re-scored with K1's arithmetic: the
+    same bits as the stored rows), 0: K1 reads the stored rows -- the shape part of the rule, default tuning;
+    `mvfgpu_selftest_stream_rows`; no GPU needed."""
+    out = C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_stream_rows(rows, dim, data_type, metric, nq, k, C.byref(out)))
+    return out.value
+
+
 class GpuCorpus:
     """One shard of a vector space, resident in HBM on one MI355X."""
 
