@@ -33,6 +33,11 @@ extern "C" {
     fn mvfgpu_search_radius(corpus: *const MvfGpuCorpus, metric: u8, queries: *const c_void, query_dtype: u8,
                             query_dim: u32, nq: u32, radii: *const f32, max_per_query: u64, out_counts: *mut u64,
                             out_scores: *mut f32, out_indices: *mut u64, out_raw: *mut i32) -> c_int;
+    /// The exact top-k over each query's own list of rows (include/mvf_gpu.h): positions or vector ids, skipped entries
+    /// and duplicates as there; `out_counts` (nullable) receives the distinct live candidates per query.
+    fn mvfgpu_search_candidates(corpus: *const MvfGpuCorpus, metric: u8, queries: *const c_void, query_dtype: u8,
+                                query_dim: u32, nq: u32, candidates: *const u64, m: u32, k: u32, out_scores: *mut f32,
+                                out_indices: *mut u64, out_raw: *mut i32, out_counts: *mut u64) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;
     /// `MVFGPU_ABI_VERSION` of the loaded library (include/mvf_gpu.h): struct layouts and signatures this file mirrors.
     fn mvfgpu_abi_version() -> u32;
@@ -167,6 +172,23 @@ impl GpuCorpus {
         }
         let _ = self.dimension;
         Ok(indices.into_iter().zip(scores).take_while(|(i, _)| *i != u64::MAX).collect())
+    }
+
+    /// Exact re-ranking of one f32 query's candidate rows (global positions, or vector ids when the space carries them),
+    /// best first: (index, score).  Entries the shard does not hold and deleted rows are skipped, duplicates count once.
+    pub fn rerank(&self, metric: DistanceMetric, query: &[f32], candidates: &[u64], k: usize) -> Result<Vec<(u64, f32)>> {
+        let mut scores = vec![0f32; k];
+        let mut indices = vec![0u64; k];
+        let mut count = 0u64;
+        let rc = unsafe {
+            mvfgpu_search_candidates(self.handle, metric.0, query.as_ptr() as *const c_void, DataType::Float32.0,
+                                     query.len() as u32, 1, candidates.as_ptr(), candidates.len() as u32, k as u32,
+                                     scores.as_mut_ptr(), indices.as_mut_ptr(), std::ptr::null_mut(), &mut count)
+        };
+        if rc != 0 {
+            return Err(status_to_error(rc));
+        }
+        Ok(indices.into_iter().zip(scores).take(count.min(k as u64) as usize).collect())
     }
 
     /// The k best rows WITH their payload -- the reference's `ScoredVector { index, score, vector }`

@@ -331,6 +331,23 @@ public:
         for (size_t i = 0; i < max_results && i < count; i++) out.push_back({idx[i], scores[i], {}});
         return out;
     }
+    // Exact re-ranking (mvfgpu_search_candidates): the k best of the rows `candidates` names -- global
+    // positions, or vector ids when the space carries them -- scored as find_top_k_similar scores them.  Entries the space
+    // does not hold and deleted rows are skipped, a row listed twice counts once; fewer than k candidates give fewer hits.
+    std::vector<ScoredVector> rerank_top_k(const std::vector<float>& query, const std::vector<uint64_t>& candidates, size_t k) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "rerank_top_k takes f32 queries: Float32 / Float16 spaces");
+        if (k == 0) return {};
+        uint64_t count = 0;
+        std::vector<float> scores(k);
+        std::vector<uint64_t> idx(k);
+        detail::check_gpu(mvfgpu_search_candidates(c_, (uint8_t)metric_, query.data(), MVF_DTYPE_FLOAT32, (uint32_t)query.size(), 1,
+                                                   candidates.empty() ? nullptr : candidates.data(), (uint32_t)candidates.size(),
+                                                   (uint32_t)k, scores.data(), idx.data(), nullptr, &count));
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < k && i < count; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
     mvfgpu_corpus* raw() const { return c_; }
 
 private:

@@ -366,6 +366,38 @@ int mvfgpu_search_radius(const mvfgpu_corpus* corpus, uint8_t metric,
                          uint64_t* out_counts, float* out_scores,
                          uint64_t* out_indices, int32_t* out_raw);
 
+/* ---- candidate search (re-ranking) ---------------------------------------- */
+
+/*
+ * The exact top-k over a given list of rows per query ("Candidate search"): the rows an index, a
+ * filter or several retrievers proposed, scored exactly and ranked.
+ *   candidates   : [nq][m] u64, one list per query (shorter lists padded with UINT64_MAX).  An entry is what a search on
+ *                  this handle reports: a global position (index_base + local row), or a vector id when ids are attached
+ *                  (mapped back as mvfgpu_corpus_gather_rows maps them; duplicate ids: the first position holding the id).
+ *                  The device call always takes positions.  UINT64_MAX, positions outside the shard, ids the shard does not
+ *                  hold and deleted rows are skipped, not refused: every row-range shard can take the same global lists,
+ *                  and mvfgpu_merge_topk_* of their results is the global answer.  A row listed twice counts once.
+ *   out_scores / out_indices / out_raw : [nq][k] as mvfgpu_search's (out_raw nullable): the k best of the query's distinct,
+ *                  live, in-shard candidates, best first, ties by ascending position, NaN last, then padding.  Every score
+ *                  is the one a one-query mvfgpu_search on the stored rows reports for that (query, row): re-ranking rows a
+ *                  search returned reproduces its scores, and a list of every row reproduces the search.
+ *   out_counts   : [nq] u64 (nullable): the number of such candidates; the first min(count, k) entries are real.  Across
+ *                  row-range shards the counts add up.
+ *   k            : 1 .. MVFGPU_MAX_K (k > m pads).  m = 0 is allowed (every result is padding; candidates may be NULL).
+ * Argument checks and error codes are mvfgpu_search's; candidates NULL while nq * m > 0 -> MVF_ERR_INVALID_ARGUMENT.
+ * mvfgpu_search_candidates is blocking (host buffers); mvfgpu_search_candidates_device takes device buffers and is
+ * asynchronous on hip_stream (NULL = the null stream), ordered like mvfgpu_search_device.
+ */
+int mvfgpu_search_candidates(const mvfgpu_corpus* corpus, uint8_t metric,
+                             const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                             const uint64_t* candidates, uint32_t m, uint32_t k,
+                             float* out_scores, uint64_t* out_indices, int32_t* out_raw, uint64_t* out_counts);
+int mvfgpu_search_candidates_device(const mvfgpu_corpus* corpus, uint8_t metric,
+                                    const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                                    const uint64_t* d_candidates, uint32_t m, uint32_t k,
+                                    float* d_scores, uint64_t* d_indices, int32_t* d_raw, uint64_t* d_counts,
+                                    void* hip_stream);
+
 /*
  * Self-test of the radius conversion (no GPU needed): the largest order key (mvf_common.h) a row may have to match
  * `radius` on a space of `data_type` under `metric`, and in *out_raw (nullable) the exact i32 bound R of Int8 / UInt8
@@ -501,7 +533,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * ABI version of the library: bumped whenever a struct layout or a function signature of this header changes in a way
  * an older caller would misread (2: every out-struct starts with struct_size, round 3; 3: corpus_info.selection_state,
  * reload_tuning, k beyond 1024; the later lift of the k <= 16384 limit changed no layout and no signature, nor did the
- * radius search, which only ADDS mvfgpu_search_radius and mvfgpu_selftest_radius_bound).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * radius search, which only ADDS mvfgpu_search_radius and mvfgpu_selftest_radius_bound, nor did the candidate search, which
+ * only adds mvfgpu_search_candidates and mvfgpu_search_candidates_device).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

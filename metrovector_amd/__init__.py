@@ -10,10 +10,10 @@ from .errors import (BuildError, CorruptedData, DeviceError, DimensionMismatch, 
 
 from .reader import MvfReader, Vector, VectorSlice, VectorSpace  # noqa: F401,E402  (reference: src/reader.rs, src/vectors/*)
 from .builder import BuiltMvf, MvfBuilder  # noqa: F401,E402                      (reference: src/builder.rs)
-from .gpu import GpuCorpus, RadiusResult, SearchResult  # noqa: F401,E402
+from .gpu import CandidateResult, GpuCorpus, RadiusResult, SearchResult  # noqa: F401,E402
 from .search import (ScoredVector, find_top_k_similar, find_top_k_similar_batch, find_within_radius,  # noqa: F401,E402
-                     upload_space)  # examples/similarity_search.rs:140-176; find_within_radius: DESIGN.md §3
+                     rerank_top_k, upload_space)  # examples/similarity_search.rs:140-176; find_within_radius, rerank_top_k: DESIGN.md §3
 
 __all__ = ["MvfError", "MvfReader", "VectorSpace", "Vector", "VectorSlice", "MvfBuilder", "BuiltMvf", "GpuCorpus",
-           "SearchResult", "RadiusResult", "ScoredVector", "find_top_k_similar", "find_top_k_similar_batch",
-           "find_within_radius", "upload_space"]
+           "SearchResult", "RadiusResult", "CandidateResult", "ScoredVector", "find_top_k_similar", "find_top_k_similar_batch",
+           "find_within_radius", "rerank_top_k", "upload_space"]

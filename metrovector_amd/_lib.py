@@ -143,6 +143,10 @@ def gpu() -> C.CDLL:
         getattr(lib, name).restype = C.c_int
     lib.mvfgpu_search_radius.argtypes = [vp, u8, vp, u8, u32, u32, vp, u64, vp, vp, vp, vp]
     lib.mvfgpu_search_radius.restype = C.c_int
+    lib.mvfgpu_search_candidates.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_search_candidates.restype = C.c_int
+    lib.mvfgpu_search_candidates_device.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp]
+    lib.mvfgpu_search_candidates_device.restype = C.c_int
     lib.mvfgpu_selftest_radius_bound.argtypes = [u8, u8, C.c_float, vp, vp]
     lib.mvfgpu_selftest_radius_bound.restype = C.c_int
     lib.mvfgpu_selftest_radius_route.argtypes = [u8, u32, C.c_int, vp]

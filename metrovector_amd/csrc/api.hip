@@ -1969,6 +1969,50 @@ int corpus_row_norms(const mvfgpu_corpus* c, void* stream, const float** xnorm, 
 }
 std::mutex& corpus_host_mutex(const mvfgpu_corpus* c) { return c->host_mu; }
 void k1_group(uint32_t V, int nqv, int forced, int* G, uint32_t* J) { choose_group(V, nqv, G, J, forced); }
+bool corpus_ids_to_positions(const mvfgpu_corpus* c, const uint64_t* ids, uint64_t count, uint64_t* out) {
+    if (c->h_ids.empty()) return false;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->id_index.empty()) {
+        c->id_index.reserve(c->h_ids.size());
+        for (size_t r = 0; r < c->h_ids.size(); r++) c->id_index.emplace_back(c->h_ids[r], (uint32_t)r);
+        std::sort(c->id_index.begin(), c->id_index.end());
+    }
+    for (uint64_t i = 0; i < count; i++) {
+        out[i] = ~0ull;
+        if (ids[i] == ~0ull) continue;
+        auto it = std::lower_bound(c->id_index.begin(), c->id_index.end(), std::make_pair(ids[i], 0u));
+        if (it != c->id_index.end() && it->first == ids[i]) out[i] = c->index_base + it->second;  // duplicates: the first position holding the id
+    }
+    return true;
+}
+int corpus_pinned_mirrors(const mvfgpu_corpus* c, size_t in_bytes, size_t out_bytes, void** pin_in, void** pin_out) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->has_done && c->confirmed_gen != c->work_gen) HIP_TRY(hipEventSynchronize(c->ev_done));
+    HIP_TRY(c->pin_q.reserve(in_bytes));
+    HIP_TRY(c->pin_out.reserve(out_bytes));
+    *pin_in = c->pin_q.p;
+    *pin_out = c->pin_out.p;
+    return MVF_OK;
+}
+int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function<int()>& body) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->work_gen++;
+    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done, 0));
+    struct DoneGuard {  // as search_device's: work may already sit on the stream whatever `body` returns
+        const mvfgpu_corpus* c;
+        hipStream_t s;
+        ~DoneGuard() {
+            if (hipEventRecord(c->ev_done, s) == hipSuccess) {
+                c->has_done = true;
+                c->last_stream = s;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    } done_guard{c, s};
+    return body();
+}
 int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                       uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices) {
     return check_query_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
@@ -2181,24 +2225,13 @@ namespace {
 int gather_rows_host_locked(const mvfgpu_corpus* c, const uint64_t* indices, uint64_t count, void* out_rows) {
     std::vector<uint64_t> mapped;  // with vector ids a search reports ids: translate them back to positions
     if (!c->h_ids.empty()) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (c->id_index.empty()) {
-            c->id_index.reserve(c->h_ids.size());
-            for (size_t r = 0; r < c->h_ids.size(); r++) c->id_index.emplace_back(c->h_ids[r], (uint32_t)r);
-            std::sort(c->id_index.begin(), c->id_index.end());
-        }
         mapped.resize(count);
+        corpus_ids_to_positions(c, indices, count, mapped.data());
         for (uint64_t i = 0; i < count; i++) {
-            if (indices[i] == ~0ull) {
-                mapped[i] = ~0ull;
-                continue;
-            }
-            auto it = std::lower_bound(c->id_index.begin(), c->id_index.end(), std::make_pair(indices[i], 0u));
-            if (it == c->id_index.end() || it->first != indices[i]) {
+            if (indices[i] != ~0ull && mapped[i] == ~0ull) {
                 g_last_error = "Index out of bounds: vector id " + std::to_string(indices[i]) + " is not in this shard";
                 return MVF_ERR_INDEX_OUT_OF_BOUNDS;
             }
-            mapped[i] = c->index_base + it->second;  // duplicates: the first position holding the id
         }
         indices = mapped.data();
     }

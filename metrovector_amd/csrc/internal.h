@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 
@@ -55,8 +56,9 @@ struct Tuning {
 };
 Tuning read_tuning();
 
-// What the radius search (radius.hip) reads of a handle: the resident rows and their masks, fixed for the handle's life
-// (set_tombstones / set_vector_ids must not race with searches), and the stream of the host-buffer calls.
+// What the radius and candidate searches (radius.hip, candidates.hip) read of a handle: the resident rows and their masks,
+// fixed for the handle's life (set_tombstones / set_vector_ids must not race with searches), and the stream of the
+// host-buffer calls.
 struct CorpusView {
     int device = 0, num_cus = 256, k1_g = 0;
     uint64_t n = 0, index_base = 0;
@@ -78,5 +80,15 @@ void k1_group(uint32_t V, int nqv, int forced, int* G, uint32_t* J);
 // mvfgpu_search's argument checks (k = 1 .. MVFGPU_MAX_K, non-NULL query and output buffers)
 int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                       uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices);
+// With vector ids attached (mvfgpu_corpus_set_vector_ids): out[i] = the global position (index_base + row) of the FIRST row
+// holding ids[i], through the sorted (id, row) table the first call builds; UINT64_MAX and ids the shard does not hold give
+// UINT64_MAX.  Returns false, out untouched, when the handle has no ids (entries are positions then).
+bool corpus_ids_to_positions(const mvfgpu_corpus* c, const uint64_t* ids, uint64_t count, uint64_t* out);
+// The handle's pinned host mirrors of the host-buffer calls (search_host's), at least in_bytes / out_bytes; the caller holds
+// corpus_host_mutex.  Waits for the handle's newest work first: a search may still write the old ones in place.
+int corpus_pinned_mirrors(const mvfgpu_corpus* c, size_t in_bytes, size_t out_bytes, void** pin_in, void** pin_out);
+// mvfgpu_search_device's stream discipline around `body`, which enqueues work on `stream`: under the handle's lock, ordered
+// behind the handle's newest work on another stream (ev_done), and ev_done recorded on `stream` on every way out.
+int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function<int()>& body);
 
 }  // namespace mvf

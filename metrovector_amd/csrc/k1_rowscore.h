@@ -1,6 +1,7 @@
-// k1_rowscore.h — K1's per-row Float32 arithmetic (scan_stream.inc), for the kernels that re-score rows and must return
-// K1's bits: R3 (scan_radius.hip: radius_rescore_kernel) and the one-query re-scoring of the int8-shadow stream
-// (scan_mfma.hip: rescore_k1_kernel).  Every piece is the order of operations K1 uses on one query:
+// k1_rowscore.h — K1's per-row arithmetic (scan_stream.inc), for the kernels that re-score rows and must return K1's bits:
+// R3 (scan_radius.hip: radius_rescore_kernel) and the one-query re-scoring of the int8-shadow stream (scan_mfma.hip:
+// rescore_k1_kernel) on Float32 rows, and C1 of the candidate search (scan_candidates.hip) on all four types.  Every
+// piece is the order of operations K1 uses on one query:
 //   * lane `sub` of a G-lane group owns the 16-B vectors v = j G + sub, j = 0 .. J-1 (J G >= V: the steps past the row's
 //     last vector read zeros from the row and the zero-padded query, as K1's do), and accumulates one fmaf per element
 //     in x, y, z, w order (L2: the squared difference; IP / Cosine: the product; Cosine also the row's sum of squares);
@@ -9,10 +10,11 @@
 //   * the query's sum of squares in K1's staging order: thread t of the 256-thread block sums elements t, t + 256, ..
 //     by fmaf, each wave's 64 partials meet in the butterfly, the four wave sums are added as ((w0 + w1) + w2) + w3;
 //   * the key: L2 sqrt(s), IP s, Cosine s / (sqrt(qq) sqrt(xx)) (0 when the denominator is 0), then key_from_score.
-// K1 itself keeps its own copy of these lines (it is the yardstick); tests/test_gpu_stream_i8_default.py and
-// tests/test_gpu_radius.py hold the kernels that include this header to K1's bits.
+// K1 itself keeps its own copy of these lines (it is the yardstick); tests/test_gpu_stream_i8_default.py,
+// tests/test_gpu_radius.py and tests/test_gpu_candidates.py hold the kernels that include this header to K1's bits.
 #pragma once
 
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -80,6 +82,75 @@ __device__ __forceinline__ float query_qq_wave(const float* q, uint32_t dim, int
         part[w] = group_sum<64>(part[w]);
     }
     return part[0] + part[1] + part[2] + part[3];
+}
+
+// ---- Float16 / Int8 / UInt8 rows (the candidate search C1, scan_candidates.hip): K1's per-row arithmetic of those types, as
+// R1 (scan_radius.hip: radius_scan_kernel) restates it.  Float16: every element is widened exactly, the f32 query holds 8
+// elements per 16-B vector (32 bytes in LDS) and the fmaf order is element 0 .. 7; the key is key() above.  Int8 / UInt8:
+// sdot4 / udot4 in x, y, z, w order -- exact i32, so any order gives the same sums.
+
+__device__ __forceinline__ void widen_f16(u32x4 x, float xf[8]) {
+    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        xf[2 * i] = __half2float(__ushort_as_half((unsigned short)(w[i] & 0xFFFFu)));
+        xf[2 * i + 1] = __half2float(__ushort_as_half((unsigned short)(w[i] >> 16)));
+    }
+}
+
+template <int METRIC>
+__device__ __forceinline__ float acc8_f16(float acc, float4 qa, float4 qb, const float xf[8]) {
+    const float qf[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        if constexpr (METRIC == MVF_METRIC_L2) {
+            float t = qf[i] - xf[i];
+            acc = fmaf(t, t, acc);
+        } else {
+            acc = fmaf(qf[i], xf[i], acc);
+        }
+    }
+    return acc;
+}
+
+__device__ __forceinline__ float xx8_f16(float xx, const float xf[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) xx = fmaf(xf[i], xf[i], xx);
+    return xx;
+}
+
+template <bool SIGNED>
+__device__ __forceinline__ int32_t dot16_int(int32_t acc, uint4 a, u32x4 b) {
+    if constexpr (SIGNED) {
+        acc = __builtin_amdgcn_sdot4((int)a.x, (int)b.x, acc, false);
+        acc = __builtin_amdgcn_sdot4((int)a.y, (int)b.y, acc, false);
+        acc = __builtin_amdgcn_sdot4((int)a.z, (int)b.z, acc, false);
+        acc = __builtin_amdgcn_sdot4((int)a.w, (int)b.w, acc, false);
+    } else {
+        acc = (int32_t)__builtin_amdgcn_udot4(a.x, b.x, (uint32_t)acc, false);
+        acc = (int32_t)__builtin_amdgcn_udot4(a.y, b.y, (uint32_t)acc, false);
+        acc = (int32_t)__builtin_amdgcn_udot4(a.z, b.z, (uint32_t)acc, false);
+        acc = (int32_t)__builtin_amdgcn_udot4(a.w, b.w, (uint32_t)acc, false);
+    }
+    return acc;
+}
+
+template <int G>
+__device__ __forceinline__ int32_t group_sum_i32(int32_t v) {
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// K1's key of exact integer sums: L2 and InnerProduct on the i32 itself, Cosine on the float score
+template <int METRIC>
+__device__ __forceinline__ uint32_t key_int(int32_t s, int32_t xxs, int32_t qq) {
+    if constexpr (METRIC == MVF_METRIC_L2) return key_from_raw(qq + xxs - 2 * s, METRIC);
+    else if constexpr (METRIC == MVF_METRIC_INNER_PRODUCT) return key_from_raw(s, METRIC);
+    else {
+        const float den = sqrtf((float)qq) * sqrtf((float)xxs);
+        return key_from_score(den > 0.0f ? (float)s / den : 0.0f, METRIC);
+    }
 }
 
 }  // namespace k1

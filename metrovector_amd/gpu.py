@@ -60,6 +60,11 @@ class RadiusResult:
 RADIUS_LIST_CAP = 8192  # include/mvf_gpu.h MVFGPU_RADIUS_LIST_CAP
 
 
+@dataclass
+class CandidateResult(SearchResult):
+    counts: np.ndarray   # u64 [nq]: distinct live in-shard candidates per query; the first min(count, k) entries are real
+
+
 def radius_bound(data_type: int, metric: int, radius: float) -> tuple[int, int]:
     """(largest matching order key, exact i32 bound of Int8/UInt8 L2/InnerProduct spaces) of a radius --
     `mvfgpu_selftest_radius_bound`; no GPU needed."""
@@ -267,6 +272,47 @@ class GpuCorpus:
                                                        r.ctypes.data_as(C.c_void_p), m, counts.ctypes.data_as(C.c_void_p),
                                                        ptr(sc), ptr(idx), ptr(raw)))
         return RadiusResult(counts, sc, idx, raw)
+
+    def search_candidates(self, queries: np.ndarray, candidates: np.ndarray, k: int, metric: int = L2) -> CandidateResult:
+        """The exact top-k of each query over its own list of rows (`mvfgpu_search_candidates`): `candidates` is a 2-D
+        [nq, m] uint64 array of global positions, or vector ids when ids are attached; UINT64_MAX pads a short list.
+        Entries this shard does not hold and deleted rows are skipped, a row listed twice counts once."""
+        q = np.asarray(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, qdim = q.shape
+        cand = candidates if isinstance(candidates, np.ndarray) else np.asarray(candidates)
+        if cand.ndim != 2 or cand.dtype != np.uint64:
+            raise InvalidArgument(f"candidates must be a 2-D uint64 array [nq, m], got {cand.dtype} of shape {cand.shape}")
+        if cand.shape[0] != nq:
+            raise InvalidArgument(f"candidates holds {cand.shape[0]} lists for {nq} queries")
+        if cand.shape[1] > 0xFFFFFFFF:
+            raise InvalidArgument("at most 2^32 - 1 candidates per query")
+        cand = np.ascontiguousarray(cand)
+        m = cand.shape[1]
+        sc = np.empty((nq, k), np.float32)
+        idx = np.empty((nq, k), np.uint64)
+        raw = np.empty((nq, k), np.int32)
+        counts = np.zeros(nq, np.uint64)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_candidates(self._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
+                                                           cand.ctypes.data_as(C.c_void_p) if m else None, m, k,
+                                                           sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                           raw.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+        return CandidateResult(sc, idx, raw, counts)
+
+    def search_candidates_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, d_candidates: int, m: int,
+                                 k: int, metric: int, d_scores: int, d_indices: int, d_raw: int = 0, d_counts: int = 0,
+                                 stream: int = 0) -> None:
+        """Device-pointer candidate search (`mvfgpu_search_candidates_device`), asynchronous on `stream`; the lists are
+        global positions."""
+        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_candidates_device(self._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
+                                                                  nq, opt(d_candidates), m, k, C.c_void_p(d_scores),
+                                                                  C.c_void_p(d_indices), opt(d_raw), opt(d_counts), opt(stream)))
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
                       d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:

@@ -147,6 +147,46 @@ def find_top_k_similar_batch(space: VectorSpace, queries, k: int, metric: int | 
     return out
 
 
+def rerank_top_k(space: VectorSpace, queries, candidates, k: int, metric: int | None = None, corpus: GpuCorpus | None = None,
+                 device: int = 0, with_vectors: bool = False) -> list[list[ScoredVector]]:
+    """Exact re-ranking (`mvfgpu_search_candidates`; DESIGN.md §3 "Candidate search"): for each query ([nq, dimension]) the
+    k best of ITS candidate rows -- `candidates` [nq, m] uint64, the positions (or vector ids) an index, a filter or several
+    retrievers proposed, UINT64_MAX padding a short list.  Rows the space does not hold and deleted rows are skipped, a row
+    listed twice counts once; each query's list holds min(k, distinct live candidates) results, shaped and scored like
+    `find_top_k_similar_batch`'s.  The row payloads are fetched only when `with_vectors` is set."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    dt = int(space.data_type())
+    q = np.asarray(queries, dtype=_NP_OF[query_dtype_code(dt)])
+    if q.ndim != 2:
+        raise BuildError("queries must be a 2-D array [nq, dimension]")
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        res = corpus.search_candidates(q, candidates, k, metric)
+        n = np.minimum(res.counts, np.uint64(k)).astype(np.int64)
+        rows = None
+        if with_vectors and int(n.sum()):
+            rows = corpus.gather_rows(np.concatenate([res.indices[i][:n[i]] for i in range(q.shape[0])]))
+    finally:
+        if own:
+            corpus.close()
+    out, r = [], 0
+    for i in range(q.shape[0]):
+        hits = []
+        for j in range(int(n[i])):
+            payload = None
+            if rows is not None:
+                payload = rows[r].astype(np.float32) if dt in (0, 1) else rows[r].copy()
+                r += 1
+            hits.append(ScoredVector(int(res.indices[i][j]), float(res.scores[i][j]), payload))
+        out.append(hits)
+    return out
+
+
 def find_within_radius(space: VectorSpace, query, radius: float, max_results: int | None = None, metric: int | None = None,
                        corpus: GpuCorpus | None = None, device: int = 0, with_vectors: bool = True) -> list[ScoredVector]:
     """Every row within `radius` of `query` (`mvfgpu_search_radius`), best first like `find_top_k_similar`: L2 distance
