@@ -1584,6 +1584,8 @@ bool stream_qs_wanted(const mvfgpu_corpus* c, uint32_t nq, uint32_t k) {
     return stream_i8_shape(c->n, c->dim, c->dtype, nq, k);
 }
 
+constexpr uint32_t kWideFinalMaxDim = 16384;  // widest Float32 row whose InnerProduct / Cosine keys the f32 MFMA kernel may finalise (use_batched_path)
+
 // Scan path 4 applies to one or two queries on a Float32 corpus whose shadow exists (or can be built now).
 bool stream_shadow_wanted(const mvfgpu_corpus* c, uint32_t nq) {
     if (c->dtype != MVF_DTYPE_FLOAT32 || nq > 2 || c->n == 0) return false;
@@ -1602,6 +1604,12 @@ bool use_batched_path(const mvfgpu_corpus* c, uint8_t metric, uint32_t nq) {
     if ((metric == MVF_METRIC_L2 || c->dtype == MVF_DTYPE_FLOAT16) && !is_int_dtype(c->dtype) &&
         (size_t)((c->dim + 7u) & ~7u) * 4 + kBatchCap * 4 > 64 * 1024)
         supported = false;  // the re-scoring kernel keeps the query in LDS
+    // Float32 InnerProduct / Cosine beyond the shadows' reach (dimension > 12288) are left to the exact f32 MFMA kernel, whose
+    // keys are FINAL: nothing re-scores them.  Each of its sums is one long chain of accumulations over the row, and on rows whose
+    // products share a sign its rounding grows with the row: 0.51-0.55 of DESIGN section 3's tolerance at 12296-16000
+    // dimensions, 0.61 at 20000, 0.75 at 28000, 0.90-1.006 at 38656 (worst entry of 130 queries x 100 results on 3000 rows;
+    // K1's 64 short chains stay at 0.02: tests/test_gpu_wide_rows.py group D caught it).  Wider rows go to K1.
+    if (c->dtype == MVF_DTYPE_FLOAT32 && metric != MVF_METRIC_L2 && c->dim > kWideFinalMaxDim) supported = false;
     if (!supported) return false;
     if (c->scan_path == 2 || c->scan_path == 3 || (c->scan_path == 5 && !is_int_dtype(c->dtype))) return true;
     if (c->scan_path == 6 && !is_int_dtype(c->dtype)) return nq > 4;

@@ -39,10 +39,28 @@ def score_tolerance(metric, oracle_scores, rows_f32, q_f32, idx):
     return TOL * np.maximum(xn * qn, 1e-30)
 
 
+def boundary_band(metric, all_scores, rows_f32, q_f32, kk):
+    """(key, kth, btol): every row's score as an ascending "best first" f64 key (NaN last), the kk-th best key and the
+    width of the band around it inside which a row may fall on either side of the top-k (the tolerance at the k-th, 2x)."""
+    sign = 1.0 if metric == 0 else -1.0
+    key = sign * all_scores.astype(np.float64)
+    key = np.where(np.isnan(key), np.inf, key)
+    kth = np.partition(key, kk - 1)[kk - 1] if kk else np.inf
+    if metric == 0:
+        btol = TOL * max(abs(kth), 1e-30)
+    elif metric == 2:
+        btol = TOL
+    else:
+        xn, qn = norms(rows_f32, q_f32)
+        xfin = xn[np.isfinite(xn)]           # rows holding Inf / NaN have no meaningful norm
+        btol = TOL * float((xfin.max() if xfin.size else 0.0) * qn)
+    return key, kth, 2 * btol
+
+
 def assert_float_topk(metric, got_scores, got_idx, all_scores, rows_f32, q_f32, k, index_base=0):
     """GPU top-k of ONE query vs the oracle's score of every row.
 
-    all_scores: oracle f32 score per local row.  Checks: padding, uniqueness,
+    all_scores: the reference's score per local row (the oracle's f32, or float64: tests/_wide.py).  Checks: padding, uniqueness,
     per-entry score within tolerance, best-first order, and set equality up to
     rows whose oracle score is within tolerance of the k-th best."""
     n = len(all_scores)
@@ -64,18 +82,7 @@ def assert_float_topk(metric, got_scores, got_idx, all_scores, rows_f32, q_f32, 
     finite_order = order[np.isfinite(order)]
     assert (np.diff(finite_order) >= 0).all(), "not sorted best-first"
     # set equality modulo near-ties at the boundary
-    key = sign * all_scores.astype(np.float64)
-    key = np.where(np.isnan(key), np.inf, key)
-    kth = np.partition(key, kk - 1)[kk - 1] if kk else np.inf
-    if metric == 0:
-        btol = TOL * max(abs(kth), 1e-30)
-    elif metric == 2:
-        btol = TOL
-    else:
-        xn, qn = norms(rows_f32, q_f32)
-        xfin = xn[np.isfinite(xn)]           # rows holding Inf / NaN have no meaningful norm
-        btol = TOL * float((xfin.max() if xfin.size else 0.0) * qn)
-    btol *= 2
+    key, kth, btol = boundary_band(metric, all_scores, rows_f32, q_f32, kk)
     must = set(np.nonzero(key < kth - btol)[0].tolist())
     may = set(np.nonzero(key <= kth + btol)[0].tolist())
     got = set(li.tolist())
