@@ -38,6 +38,13 @@ extern "C" {
     fn mvfgpu_search_candidates(corpus: *const MvfGpuCorpus, metric: u8, queries: *const c_void, query_dtype: u8,
                                 query_dim: u32, nq: u32, candidates: *const u64, m: u32, k: u32, out_scores: *mut f32,
                                 out_indices: *mut u64, out_raw: *mut i32, out_counts: *mut u64) -> c_int;
+    /// The k-NN join (include/mvf_gpu.h, DESIGN.md section 3 "Join"): the exact top-k of rows `first .. first + count` of
+    /// `query_corpus` (NULL: `corpus` itself, the k-NN graph) among the rows of `corpus`; `flags`: 1 = MVFGPU_JOIN_EXCLUDE_SELF.
+    fn mvfgpu_knn_join(corpus: *const MvfGpuCorpus, query_corpus: *const MvfGpuCorpus, metric: u8, first: u64, count: u64,
+                       k: u32, flags: u32, out_scores: *mut f32, out_indices: *mut u64, out_raw: *mut i32) -> c_int;
+    fn mvfgpu_knn_join_device(corpus: *const MvfGpuCorpus, query_corpus: *const MvfGpuCorpus, metric: u8, first: u64,
+                              count: u64, k: u32, flags: u32, d_scores: *mut f32, d_indices: *mut u64, d_raw: *mut i32,
+                              hip_stream: *mut c_void) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;
     /// `MVFGPU_ABI_VERSION` of the loaded library (include/mvf_gpu.h): struct layouts and signatures this file mirrors.
     fn mvfgpu_abi_version() -> u32;

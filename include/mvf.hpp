@@ -348,6 +348,27 @@ public:
         for (size_t i = 0; i < k && i < count; i++) out.push_back({idx[i], scores[i], {}});
         return out;
     }
+    // The k-NN graph (mvfgpu_knn_join; DESIGN.md section 3, "Join"): for each of the rows [first, first + count) -- count
+    // UINT64_MAX: to the end of the space -- its k nearest OTHER rows under the space's metric, best first.  A row is never its
+    // own neighbour (decided by position: its exact duplicates are); a deleted row gets an empty list; fewer than k live
+    // others give fewer hits.  The rows never leave the device.
+    std::vector<std::vector<ScoredVector>> knn_graph(size_t k, uint64_t first = 0, uint64_t count = UINT64_MAX) const {
+        if (count == UINT64_MAX) {
+            mvfgpu_corpus_info inf;
+            MVFGPU_INIT(inf);
+            detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+            count = inf.rows > first ? inf.rows - first : 0;
+        }
+        std::vector<std::vector<ScoredVector>> out((size_t)count);
+        if (k == 0 || count == 0) return out;
+        std::vector<float> scores((size_t)count * k);
+        std::vector<uint64_t> idx((size_t)count * k);
+        detail::check_gpu(mvfgpu_knn_join(c_, nullptr, (uint8_t)metric_, first, count, (uint32_t)k, MVFGPU_JOIN_EXCLUDE_SELF, scores.data(),
+                                          idx.data(), nullptr));
+        for (size_t i = 0; i < (size_t)count; i++)
+            for (size_t j = 0; j < k && idx[i * k + j] != UINT64_MAX; j++) out[i].push_back({idx[i * k + j], scores[i * k + j], {}});
+        return out;
+    }
     mvfgpu_corpus* raw() const { return c_; }
 
 private:

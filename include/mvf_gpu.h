@@ -398,6 +398,48 @@ int mvfgpu_search_candidates_device(const mvfgpu_corpus* corpus, uint8_t metric,
                                     float* d_scores, uint64_t* d_indices, int32_t* d_raw, uint64_t* d_counts,
                                     void* hip_stream);
 
+/* ---- k-NN join (queries taken from resident rows) -------------------------- */
+
+#define MVFGPU_JOIN_WINDOW 1024u        /* query rows per search of a join, counted from `first` */
+#define MVFGPU_JOIN_EXCLUDE_SELF 1u     /* a query row is never among its own results (decided on positions) */
+
+/*
+ * The exact top-k of rows [first, first + count) of `query_corpus` (NULL = `corpus`: the self-join, the k-NN graph) among
+ * the live rows of `corpus` ("Join").  Nothing leaves the device but the results: the query rows are
+ * staged on the device from the stored rows (Float32 as stored, Float16 widened exactly, Int8 / UInt8 as stored), searched
+ * with the metric and arithmetic of mvfgpu_search, and reported in its order and padding ([count][k]; out_raw nullable;
+ * entries are corpus' index_base + row, or corpus' vector ids where attached).
+ *   flags        : MVFGPU_JOIN_EXCLUDE_SELF: the row of `corpus` whose GLOBAL POSITION equals the query row's global position
+ *                  (query_corpus' index_base + row) is not reported for that query.  Positions decide, never ids (duplicate
+ *                  ids are legal) and never scores (exact duplicates of a row are its neighbours and are reported).  Where
+ *                  the two handles' row ranges do not overlap the flag changes nothing.  Unknown bits are refused.
+ *   k            : 1 .. MVFGPU_MAX_K, with the flag 1 .. MVFGPU_MAX_K - 1.
+ *   first, count : local rows of query_corpus, first + count <= its rows; count = 0 is allowed (nothing is written).
+ * A deleted (tombstoned) query row gets a result row of padding; deleted rows of `corpus` are never reported.
+ * The range is processed in windows of MVFGPU_JOIN_WINDOW query rows counted from `first` (the last may be short), and the
+ * entries of a query row are exactly -- indices, score bits, raw -- what mvfgpu_search_device on `corpus` returns for its
+ * window's staged queries with k' = k + 1 (k' = k without the flag or where the row ranges do not overlap), with the query
+ * row's own entry removed if it is among the k', else the last entry dropped.  So dimension limits, refusals, scan_path and
+ * tuning are those of mvfgpu_search on `corpus` with that batch size and k'; k = MVFGPU_K_PER_PASS with the flag gives
+ * k' = 1025 and takes the large-k route.  The searches ARE searches of `corpus`: its repair feedback sees them, and its rule
+ * "at most two int8-selected batched searches in flight" paces the join's windows too.
+ * The two handles must agree in dimension (MVF_ERR_DIMENSION_MISMATCH) and data type (MVF_ERR_BUILD) and live on one device
+ * (MVF_ERR_INVALID_ARGUMENT); unknown flag bits, NULL outputs while count > 0 and a range outside query_corpus are
+ * MVF_ERR_INVALID_ARGUMENT; every check comes before the first device call.
+ * mvfgpu_knn_join is blocking (host buffers): window w's results leave through pinned memory on a copy stream while window
+ * w + 1 is searched.  mvfgpu_knn_join_device takes device buffers and enqueues every window on hip_stream (NULL = the null
+ * stream) without a host wait, ordered like mvfgpu_search_device behind both handles' newest work.  Device scratch is one
+ * window's queries and lists, 1024 x (4 dimension + 16 k') bytes at most (the host call: + 2 x 1024 x 16 k bytes of
+ * results); it does not grow with count.  Row-range shards: join every shard as query_corpus against every shard as
+ * corpus with the flag set and merge the lists in ascending row-range order with mvfgpu_merge_topk_*.
+ */
+int mvfgpu_knn_join(const mvfgpu_corpus* corpus, const mvfgpu_corpus* query_corpus /* NULL = corpus */,
+                    uint8_t metric, uint64_t first, uint64_t count, uint32_t k, uint32_t flags,
+                    float* out_scores, uint64_t* out_indices, int32_t* out_raw /* nullable */);
+int mvfgpu_knn_join_device(const mvfgpu_corpus* corpus, const mvfgpu_corpus* query_corpus /* NULL = corpus */,
+                           uint8_t metric, uint64_t first, uint64_t count, uint32_t k, uint32_t flags,
+                           float* d_scores, uint64_t* d_indices, int32_t* d_raw /* nullable */, void* hip_stream);
+
 /*
  * Self-test of the radius conversion (no GPU needed): the largest order key (mvf_common.h) a row may have to match
  * `radius` on a space of `data_type` under `metric`, and in *out_raw (nullable) the exact i32 bound R of Int8 / UInt8
@@ -534,7 +576,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * an older caller would misread (2: every out-struct starts with struct_size, round 3; 3: corpus_info.selection_state,
  * reload_tuning, k beyond 1024; the later lift of the k <= 16384 limit changed no layout and no signature, nor did the
  * radius search, which only ADDS mvfgpu_search_radius and mvfgpu_selftest_radius_bound, nor did the candidate search, which
- * only adds mvfgpu_search_candidates and mvfgpu_search_candidates_device).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * only adds mvfgpu_search_candidates and mvfgpu_search_candidates_device, nor did the k-NN join, which only adds mvfgpu_knn_join and
+ * mvfgpu_knn_join_device).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

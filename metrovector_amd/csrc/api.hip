@@ -214,6 +214,7 @@ struct mvfgpu_corpus {
     mutable DevBuf done_ticket;
     mutable uint32_t flag_seq = 0;
     mutable HostFlagReq* flag_req = nullptr;  // the host-buffer call's request to the search being enqueued (set and read under mu)
+    mutable bool positions_only = false;      // the search being enqueued reports index_base + row even where ids are attached (the join's: set and read under mu)
     mutable uint64_t work_gen = 0, confirmed_gen = ~0ull;  // searches enqueued on the handle / the newest one seen complete through the flag
     mutable PinBuf pin_q, pin_out, pin_vec;  // ... and its pinned host mirrors (small queries / results / payload rows: no copy engine at all)
     mutable DevBuf h_v;                   // payload rows of mvfgpu_search_fetch too large for that
@@ -296,6 +297,9 @@ int alloc_rows(mvfgpu_corpus* c) {
 // K1: a piece's survivors up to this many join the running list by counting, more go through the sort network (<= 256;
 // 128 until the counting loops got eight reads in flight: profiles/r04_k1_merge_ab.txt)
 constexpr uint32_t kK1RankMerge = 256;
+
+// the id table the final kernels of a search map local rows through (NULL = index_base + row)
+const uint64_t* result_ids(const mvfgpu_corpus* c) { return c->positions_only ? nullptr : static_cast<const uint64_t*>(c->ids.p); }
 
 hipError_t scan_launch(uint8_t dtype, const ScanParams& p, int metric, int G, int nqv, dim3 grid, size_t lds,
                        hipStream_t s) {
@@ -523,7 +527,7 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
             fp.metric = metric;
             fp.dtype = c->dtype;
             fp.index_base = c->index_base;
-            fp.ids = static_cast<const uint64_t*>(c->ids.p);
+            fp.ids = result_ids(c);
             fp.out_scores = d_scores;
             fp.out_indices = d_indices;
             fp.out_raw = d_raw;
@@ -545,7 +549,7 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
             fp.metric = metric;
             fp.dtype = c->dtype;
             fp.index_base = c->index_base;
-            fp.ids = static_cast<const uint64_t*>(c->ids.p);
+            fp.ids = result_ids(c);
             if (alt) {
                 fp.out_cand = alt->cand + (size_t)q0 * alt->cand_cap;
                 fp.out_cnt = alt->cnt + q0;
@@ -989,7 +993,7 @@ int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d
         fp.metric = metric;
         fp.dtype = c->dtype;
         fp.index_base = c->index_base;
-        fp.ids = static_cast<const uint64_t*>(c->ids.p);
+        fp.ids = result_ids(c);
         fp.out_scores = d_scores;
         fp.out_indices = d_indices;
         fp.out_raw = d_raw;
@@ -1167,7 +1171,7 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
     cp.metric = metric;
     cp.dtype = c->dtype;
     cp.index_base = c->index_base;
-    cp.ids = static_cast<const uint64_t*>(c->ids.p);
+    cp.ids = result_ids(c);
     cp.out_scores = d_scores;
     cp.out_indices = d_indices;
     cp.out_raw = d_raw;
@@ -1311,7 +1315,7 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
         rp.dim = c->dim;
         rp.dtype = c->dtype;
         rp.index_base = c->index_base;
-        rp.ids = static_cast<const uint64_t*>(c->ids.p);
+        rp.ids = result_ids(c);
         rp.out_scores = d_scores;
         rp.out_indices = d_indices;
         rp.out_raw = d_raw;
@@ -1431,7 +1435,7 @@ int search_stream_shadow_path(const mvfgpu_corpus* c, uint8_t metric, const void
     cp.metric = metric;
     cp.dtype = c->dtype;
     cp.index_base = c->index_base;
-    cp.ids = static_cast<const uint64_t*>(c->ids.p);
+    cp.ids = result_ids(c);
     cp.qnorm = qaux1;
     cp.xxmax = static_cast<const float*>(c->xnorm.p) + norm_max_at(n);
     // per-element relative rounding of the shadow rows (2^-11) and f32 accumulation of `dim` terms ((dim + 16) 2^-23
@@ -1455,7 +1459,7 @@ int search_stream_shadow_path(const mvfgpu_corpus* c, uint8_t metric, const void
     rp.dim = c->dim;
     rp.dtype = c->dtype;
     rp.index_base = c->index_base;
-    rp.ids = static_cast<const uint64_t*>(c->ids.p);
+    rp.ids = result_ids(c);
     rp.out_scores = d_scores;
     rp.out_indices = d_indices;
     rp.out_raw = d_raw;
@@ -1531,7 +1535,7 @@ int search_stream_qs_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_
     rp.dim = c->dim;
     rp.dtype = c->dtype;
     rp.index_base = c->index_base;
-    rp.ids = static_cast<const uint64_t*>(c->ids.p);
+    rp.ids = result_ids(c);
     rp.out_scores = d_scores;
     rp.out_indices = d_indices;
     rp.out_raw = d_raw;
@@ -2361,24 +2365,11 @@ int mvfgpu_search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
 }
 
 namespace {
-// mvfgpu_search_device, and -- with `req` -- the enqueue step of the host-buffer calls (search_host)
-int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
-                  uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, void* hip_stream, HostFlagReq* req) {
-    int rc = check_query_args(c, metric, d_queries, query_dtype, query_dim, nq, k, d_scores, d_indices);
-    if (rc != MVF_OK) return rc;
-    DeviceGuard guard(c->device);
-    if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->work_gen++;
-    struct ReqGuard {  // the request belongs to this call only
-        const mvfgpu_corpus* c;
-        ~ReqGuard() { c->flag_req = nullptr; }
-    } req_guard{c};
-    c->flag_req = req;
-    if (req) req->gen = c->work_gen;
-    // the scratch buffers are stream-ordered: a call on another stream waits for the previous one
-    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done, 0));
+// The search itself: profiling events, the route, its kernels on `s`.  The caller holds c->mu, has ordered `s` behind the
+// handle's newest work and records ev_done on every way out (search_device below; the join through corpus_device_call).
+int search_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
+                  uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
+    int rc = MVF_OK;
     mvfgpu_corpus::ProfSlot* wps = nullptr;  // whole-search events: every kernel of this call on the stream
     const uint64_t prof_before = c->prof_next;
     if (c->profiling) {
@@ -2388,20 +2379,6 @@ int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
         wps->whole = false;
         HIP_TRY(hipEventRecord(wps->e[3], s));
     }
-    // Whatever happens below, work may already sit on the stream (norms, a shadow build, scratch): the next call on
-    // ANOTHER stream orders itself behind ev_done, so it is recorded on every way out.
-    struct DoneGuard {
-        const mvfgpu_corpus* c;
-        hipStream_t s;
-        ~DoneGuard() {
-            if (hipEventRecord(c->ev_done, s) == hipSuccess) {
-                c->has_done = true;
-                c->last_stream = s;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-    } done_guard{c, s};
     if (k > MVFGPU_K_PER_PASS) {  // more results than one pass selects: the whole shard ranked by a sort, or passes of the exact streaming kernel
         uint32_t scans = 1;
         bool sorted = false;
@@ -2455,7 +2432,42 @@ int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
         wps->whole = true;
         c->timing.search_flops = 2ull * nq * c->n * c->dim;
     }
-    return MVF_OK;  // ev_done: DoneGuard
+    return MVF_OK;
+}
+
+// mvfgpu_search_device, and -- with `req` -- the enqueue step of the host-buffer calls (search_host)
+int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                  uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, void* hip_stream, HostFlagReq* req) {
+    int rc = check_query_args(c, metric, d_queries, query_dtype, query_dim, nq, k, d_scores, d_indices);
+    if (rc != MVF_OK) return rc;
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->work_gen++;
+    struct ReqGuard {  // the request belongs to this call only
+        const mvfgpu_corpus* c;
+        ~ReqGuard() { c->flag_req = nullptr; }
+    } req_guard{c};
+    c->flag_req = req;
+    if (req) req->gen = c->work_gen;
+    // the scratch buffers are stream-ordered: a call on another stream waits for the previous one
+    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done, 0));
+    // Whatever happens below, work may already sit on the stream (norms, a shadow build, scratch): the next call on
+    // ANOTHER stream orders itself behind ev_done, so it is recorded on every way out.
+    struct DoneGuard {
+        const mvfgpu_corpus* c;
+        hipStream_t s;
+        ~DoneGuard() {
+            if (hipEventRecord(c->ev_done, s) == hipSuccess) {
+                c->has_done = true;
+                c->last_stream = s;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    } done_guard{c, s};
+    return search_locked(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s);  // ev_done: DoneGuard
 }
 }  // namespace
 
@@ -2906,3 +2918,16 @@ int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_
 }
 
 }  // extern "C"
+
+namespace mvf {
+int search_positions_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
+                            uint64_t* d_indices, int32_t* d_raw, void* stream) {
+    struct Guard {  // the switch belongs to this search only
+        const mvfgpu_corpus* c;
+        ~Guard() { c->positions_only = false; }
+    } guard{c};
+    c->positions_only = true;
+    c->flag_req = nullptr;
+    return search_locked(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, static_cast<hipStream_t>(stream));
+}
+}  // namespace mvf

@@ -90,5 +90,11 @@ int corpus_pinned_mirrors(const mvfgpu_corpus* c, size_t in_bytes, size_t out_by
 // mvfgpu_search_device's stream discipline around `body`, which enqueues work on `stream`: under the handle's lock, ordered
 // behind the handle's newest work on another stream (ev_done), and ev_done recorded on `stream` on every way out.
 int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function<int()>& body);
+// mvfgpu_search_device's search -- its routes, kernels, repair feedback and timing -- for a caller that already runs under
+// corpus_device_call(c, stream, ...): no argument checks, the handle's lock is not taken again, and the id mapping of the final
+// kernels is switched off: every entry is a global position (index_base + row) even where vector ids are attached (the join
+// excludes by position and maps ids itself).
+int search_positions_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
+                            uint64_t* d_indices, int32_t* d_raw, void* stream);
 
 }  // namespace mvf

@@ -58,6 +58,8 @@ class RadiusResult:
 
 
 RADIUS_LIST_CAP = 8192  # include/mvf_gpu.h MVFGPU_RADIUS_LIST_CAP
+JOIN_WINDOW = 1024      # include/mvf_gpu.h MVFGPU_JOIN_WINDOW
+JOIN_EXCLUDE_SELF = 1   # include/mvf_gpu.h MVFGPU_JOIN_EXCLUDE_SELF
 
 
 @dataclass
@@ -313,6 +315,33 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_search_candidates_device(self._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                   nq, opt(d_candidates), m, k, C.c_void_p(d_scores),
                                                                   C.c_void_p(d_indices), opt(d_raw), opt(d_counts), opt(stream)))
+
+    def knn_join(self, k: int, metric: int = L2, first: int = 0, count: int | None = None,
+                 queries_from: "GpuCorpus | None" = None, exclude_self: bool = True) -> SearchResult:
+        """The exact top-k of rows [first, first + count) of `queries_from` (None: this corpus, the k-NN graph) among this
+        corpus' rows (`mvfgpu_knn_join`): the queries are staged on the device from the stored rows, `exclude_self` leaves
+        the row at the query row's own global position out.  `count` None = to the end of the query corpus."""
+        src = self if queries_from is None else queries_from
+        if count is None:
+            count = src.rows - first
+        if first < 0 or count < 0:
+            raise InvalidArgument("first and count must be >= 0")
+        sc = np.empty((count, k), np.float32)
+        idx = np.empty((count, k), np.uint64)
+        raw = np.empty((count, k), np.int32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_knn_join(self._h, None if queries_from is None else queries_from._h, metric, first, count, k,
+                                                  JOIN_EXCLUDE_SELF if exclude_self else 0, sc.ctypes.data_as(C.c_void_p),
+                                                  idx.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p)))
+        return SearchResult(sc, idx, raw)
+
+    def knn_join_device(self, k: int, metric: int, first: int, count: int, d_scores: int, d_indices: int, d_raw: int = 0,
+                        queries_from: "GpuCorpus | None" = None, exclude_self: bool = True, stream: int = 0) -> None:
+        """Device-pointer join (`mvfgpu_knn_join_device`): [count, k] results in device memory, every window enqueued on
+        `stream` without a host wait."""
+        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        _lib.gpu_check(_lib.gpu().mvfgpu_knn_join_device(self._h, None if queries_from is None else queries_from._h, metric, first,
+                                                         count, k, JOIN_EXCLUDE_SELF if exclude_self else 0, opt(d_scores),
+                                                         opt(d_indices), opt(d_raw), opt(stream)))
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
                       d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:

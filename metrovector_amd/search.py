@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .errors import BuildError, InvalidVectorType
-from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, query_dtype_code
+from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, SearchResult, query_dtype_code
 from .reader import VectorSpace
 
 _NP_OF = {0: np.float32, 1: np.float16, 2: np.int8, 3: np.uint8}
@@ -185,6 +185,27 @@ def rerank_top_k(space: VectorSpace, queries, candidates, k: int, metric: int | 
             hits.append(ScoredVector(int(res.indices[i][j]), float(res.scores[i][j]), payload))
         out.append(hits)
     return out
+
+
+def build_knn_graph(space: VectorSpace, k: int, metric: int | None = None, corpus: GpuCorpus | None = None, first: int = 0,
+                    count: int | None = None, device: int = 0) -> SearchResult:
+    """The k-NN graph of a space (`mvfgpu_knn_join`; DESIGN.md §3 "Join"): for rows [first, first + count) (local rows of
+    the corpus; None: to its end) the k nearest OTHER rows -- a row is never its own neighbour (decided by position; its exact
+    duplicates are), deleted rows neither appear nor get neighbours (their result rows are padding).  The rows never leave the
+    device.  Returns [count, k] arrays like a search: indices (positions, or vector ids where the space has them; UINT64_MAX
+    pads), scores, raw.  `first` / `count` let a caller stream a graph that does not fit in host memory."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        return corpus.knn_join(k, metric, first=first, count=count, exclude_self=True)
+    finally:
+        if own:
+            corpus.close()
 
 
 def find_within_radius(space: VectorSpace, query, radius: float, max_results: int | None = None, metric: int | None = None,
