@@ -95,10 +95,14 @@ typedef struct mvfgpu_corpus_info {
 typedef struct mvfgpu_timing {
     uint32_t struct_size; /* in: sizeof(mvfgpu_timing); out: bytes filled */
     uint32_t samples;    /* searches averaged */
-    /* HIP-event times of searches on the handle, milliseconds.  Events are
-     * recorded (never waited for) on the search's own stream while
-     * mvfgpu_set_profiling(corpus, 1) is in effect; mvfgpu_last_timing waits
-     * for the newest and reads them back. */
+    /* Device times of searches on the handle, milliseconds, taken (never waited for) while
+     * mvfgpu_set_profiling(corpus, 1) is in effect; mvfgpu_last_timing waits for the newest search and reads them back.
+     * The streaming routes (scan_kernel 1, 5, 7) time themselves: block 0 of the scan stores the device's wall clock
+     * (hipDeviceAttributeWallClockRate) at its start and every block folds it at its end into a per-handle ring, the select behind it adds its own
+     * end, and -- scan_kernel 1 and 7 -- the search's last kernel the end of the search.  scan_ms is then block 0
+     * started (the first block dispatched, by the dispatcher's habit, not by guarantee) -> last block finished, without the dispatch latency an event pair around the launch includes, and
+     * search_ms starts with the first kernel of the search.  The batched routes (and the whole-search time of
+     * scan_kernel 5 and 8) are HIP events recorded on the search's own stream. */
     float scan_ms;     /* newest search: the dominant kernel (streaming or MFMA scan) */
     float select_ms;   /* newest search: candidate select / top-k kernels */
     float total_ms;    /* newest search: scan_ms + select_ms */
@@ -121,7 +125,11 @@ typedef struct mvfgpu_timing {
     uint32_t repaired_queries; /* newest BATCHED search (whether profiled or not): queries whose candidate budget or region
                                   overflowed and that the streaming kernel re-did exactly (0 on sane data; a corpus that
                                   keeps producing them goes back to the slower selection paths by itself) */
-    uint32_t reserved;
+    uint32_t search_launches; /* newest search (whether profiled or not): kernel launches it enqueued, counted on the host,
+                                 on the routes that count them -- the streaming kernel on the stored rows (2: scan + select)
+                                 or on the int8 shadow (scan_kernel 7: scan, margin select, re-scoring, final select,
+                                 the repair pair); 0 = the route does not count (batched searches, scan path 4,
+                                 k > MVFGPU_K_PER_PASS).  (`reserved` until round 7.) */
 } mvfgpu_timing;
 
 /* ---- library / device ---------------------------------------------------- */

@@ -190,8 +190,14 @@ struct mvfgpu_corpus {
     // Two slots, used alternately: a search first CONSUMES the count the search two before it posted into its slot
     // (waiting for that copy if need be: it is two searches old), then posts its own -- so which path a search takes
     // depends on the sequence of searches alone, never on how fast the host runs ahead of the device.
+    // (the count is waited for through the end-of-call event of the search that posted it: ev_done below)
     mutable uint32_t* qs_redo_host = nullptr;  // [2] pinned
-    mutable hipEvent_t qs_redo_ev[2] = {nullptr, nullptr};
+    mutable uint32_t qs_redo_done[2] = {0, 0};  // which of the two ev_done covers the slot's count ...
+    // ... unless the search that posted it shared its call with others (the windows of a join: corpus_device_call runs them all
+    // under ONE end-of-call event, recorded when the last has been enqueued): such a search records an event of its own
+    mutable hipEvent_t qs_redo_ev[2] = {nullptr, nullptr};  // created by the first search that needs one
+    mutable bool qs_redo_own[2] = {false, false};
+    mutable bool one_search_call = false;  // the call being enqueued holds exactly one search (search_device; set and read under mu)
     mutable bool qs_redo_pending[2] = {false, false};
     mutable bool qs_disabled = false;
     mutable uint32_t qs_redo_nq[2] = {0, 0};
@@ -220,9 +226,21 @@ struct mvfgpu_corpus {
     mutable DevBuf h_v;                   // payload rows of mvfgpu_search_fetch too large for that
     mutable hipStream_t own_stream = nullptr;
     hipStream_t up_stream = nullptr;      // upload pipeline: re-pitch / norms / shadow of chunk i beside the copy of chunk i+1
-    mutable hipEvent_t ev_done = nullptr;
+    // End of the newest call on the handle: ONE event per call, recorded on the call's stream on every way out (record_done).
+    // It orders the next call on another stream behind this one, it is what mvfgpu_last_timing and the host-buffer calls wait
+    // for, and -- two events used alternately, done_idx the newest -- the repair feedback waits on the same event for the count
+    // the search two back posted (until round 7 that search recorded a second event of its own right in front of this one).
+    // Where OTHER calls on the handle (a K1 search, a gather) sit between two posting searches, the event a slot remembers has
+    // been recorded again by a later call: the poll then waits for that newer call -- the count is still the right one (a later
+    // event implies the earlier work), but the host may run one call ahead instead of two searches.
+    mutable hipEvent_t ev_done[2] = {nullptr, nullptr};
+    mutable uint32_t done_idx = 0;
     mutable hipStream_t last_stream = nullptr;
     mutable bool has_done = false;
+    // kernel launches the search being enqueued has made so far (mvfgpu_timing::search_launches), counted by the routes that
+    // know their launches: K1 on the stored rows or a shadow, the margin select, the K1-order re-scoring, the repair
+    mutable uint32_t launches = 0, search_launches = 0;
+    mutable bool launches_known = false;
 
     bool profiling = false;
     int scan_path = 0;
@@ -230,7 +248,14 @@ struct mvfgpu_corpus {
     struct ProfSlot {
         hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // [0,1] the timed scan launch, [2] end of its select; [3,4] the whole search
         bool scanned = false, whole = false;
+        // The K1 routes record no events: five markers in the stream cost a one-query search 18 us (profiles/r07_stream_fixed_cost.txt).
+        // Their kernels read the device's wall clock themselves (ScanParams::ts, SelectParams::ts_*) into entry `slot` of prof_ts:
+        // [0] first block of the scan to start, [1] last to finish, [2] end of the select behind it, [3] end of the search's last kernel
+        bool ts_scan = false, ts_whole = false;
     };
+    mutable DevBuf prof_ts;              // [kProfSlots][4] published times, then the pair the scan writes (block 0's start; the maximum of the blocks' ends, 0 when armed)
+    mutable bool whole_by_clock = false;  // the search being enqueued takes its whole-search time from prof_ts (set and read under mu)
+    double wall_khz = 100000.0;           // ticks of the device's wall clock per millisecond
     static constexpr int kProfSlots = 64;
     mutable ProfSlot prof[kProfSlots];
     mutable uint64_t prof_next = 0;  // searches profiled since profiling was switched on
@@ -269,7 +294,10 @@ int init_common(mvfgpu_corpus* c) {
     HIP_TRY(hipGetDeviceProperties(&prop, c->device));
     c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
+    for (auto& e : c->ev_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0) c->wall_khz = (double)khz;
+    else (void)hipGetLastError();
     return MVF_OK;
 }
 
@@ -346,13 +374,13 @@ struct RankAll {
 struct ShadowStream {
     const unsigned char* rows;
     const float* xscale;
-    // int8 shadow (dt2x unit) only: prepared int8 queries `qstride` bytes apart, their scale / norm, the rows' norm array
+    // int8 shadow (dt2x unit) only: K1's prologue quantises the f32 queries itself and leaves their scale / norm / bound in
+    // qaux0 / qaux1 / delta (qstats, xxmax: what the bound is made of); xrow: the rows' norm array
     bool i8;
-    const unsigned char* qprep;
-    const float *qaux0, *qaux1, *xrow;
-    uint32_t qstride;
+    float *qaux0, *qaux1;
+    const float *qstats, *xxmax, *xrow;
     // ... and select_final's margin mode instead of the k best: every row within 2 delta[q] of the rank_k-th best
-    const float* delta;
+    float* delta;
     uint32_t *tau, *overflow;
     uint32_t rank_k;
     uint32_t pitch, V, J;
@@ -383,6 +411,20 @@ int scan_occupancy(const mvfgpu_corpus* c, const void* kfn, size_t lds, int* occ
 }
 
 
+// The clock entries of the profiled K1 routes (ProfSlot): allocated and armed by the first profiled search.
+int prof_ts_ensure(const mvfgpu_corpus* c, hipStream_t s) {
+    if (c->prof_ts.p) return MVF_OK;
+    const size_t words = (size_t)mvfgpu_corpus::kProfSlots * 4 + 2;
+    HIP_TRY(c->prof_ts.reserve(words * 8));
+    HIP_TRY(hipMemsetAsync(c->prof_ts.p, 0, words * 8, s));
+    HIP_TRY(hipMemsetAsync(static_cast<uint64_t*>(c->prof_ts.p) + words - 2, 0xFF, 8, s));
+    return MVF_OK;
+}
+uint64_t* prof_ts_entry(const mvfgpu_corpus* c, uint64_t search) {
+    return static_cast<uint64_t*>(c->prof_ts.p) + (search % mvfgpu_corpus::kProfSlots) * 4;
+}
+uint64_t* prof_ts_work(const mvfgpu_corpus* c) { return static_cast<uint64_t*>(c->prof_ts.p) + (size_t)mvfgpu_corpus::kProfSlots * 4; }
+
 int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
                        float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s, bool profile = true,
                        const ShadowStream* alt = nullptr, const uint64_t* floor1 = nullptr, uint64_t* out_floor1 = nullptr,
@@ -401,11 +443,19 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
     tm.scan_kernel = alt8 ? 7u : alt ? 5u : 1u;
     bool first = true;
     mvfgpu_corpus::ProfSlot* ps = nullptr;
+    uint64_t *ts_work = nullptr, *ts_entry = nullptr;
     if (c->profiling && profile) {
         ps = &c->prof[c->prof_next % mvfgpu_corpus::kProfSlots];
         for (auto& e : ps->e)
             if (!e) HIP_TRY(hipEventCreate(&e));
         ps->scanned = false;
+        ps->ts_scan = false;
+        if (!rank) {  // a select_final follows the scan: the pair times itself
+            const int trc = prof_ts_ensure(c, s);
+            if (trc != MVF_OK) return trc;
+            ts_work = prof_ts_work(c);
+            ts_entry = prof_ts_entry(c, c->prof_next);
+        }
     }
 
     for (uint32_t q0 = 0; q0 < nq;) {
@@ -477,12 +527,14 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
             ScanParams sp{};
             sp.rows = alt ? alt->rows : c->d_rows;
             sp.xscale = alt ? alt->xscale : nullptr;
-            sp.queries = alt8 ? static_cast<const void*>(alt->qprep) : d_queries;
+            sp.queries = d_queries;
             if (alt8) {
                 sp.qaux0 = alt->qaux0;
                 sp.qaux1 = alt->qaux1;
+                sp.qdelta = alt->delta;
+                sp.qstats = alt->qstats;
+                sp.xxmax = alt->xxmax;
                 sp.xrow = alt->xrow;
-                sp.qstride = alt->qstride;
             }
             sp.tomb = static_cast<const uint32_t*>(c->tomb.p);
             sp.cand = static_cast<uint64_t*>(c->cand.p);
@@ -508,18 +560,21 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
             sp.rank_merge_max = kK1RankMerge;
             sp.floor1 = floor1;
             sp.dump = rank ? rank->a : nullptr;
-            if (ps && first) HIP_TRY(hipEventRecord(ps->e[0], s));
+            if (ps && first && ts_work) sp.ts = ts_work;
+            else if (ps && first) HIP_TRY(hipEventRecord(ps->e[0], s));
             if (alt8) HIP_TRY(scan_stream_launch_dt2x(sp, metric, G, nqv, dim3(nblocks), lds, s));
             else if (alt) HIP_TRY(scan_stream_launch_dt1x(sp, metric, G, nqv, dim3(nblocks), lds, s));
             else HIP_TRY(scan_launch(c->dtype, sp, metric, G, nqv, dim3(nblocks, npass), lds, s));
             if (ps && first) {
-                HIP_TRY(hipEventRecord(ps->e[1], s));
+                if (!ts_work) HIP_TRY(hipEventRecord(ps->e[1], s));
                 ps->scanned = true;
+                ps->ts_scan = ts_work != nullptr;
                 tm.scan_bytes = (uint64_t)c->n * c->dim * elem_size(kdtype);
                 tm.scan_flops = 2ull * nq_here * c->n * c->dim;
                 if (npass > 1) tm.scan_bytes *= npass;
             }
             tm.scan_launches++;
+            c->launches++;
         }
         if (rank) {  // every row of these queries is ranked: sort each query's n composites, format the first k_out
             SelectParams fp{};
@@ -538,6 +593,7 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
             }
             for (uint32_t q = 0; q < nq_here; q++)
                 HIP_TRY(launch_write_sorted(fp, sorted + (size_t)q * c->n, (uint32_t)c->n, (size_t)(q0 + q) * rank->k_out, s));
+            c->launches_known = false;  // (the device-wide sort's launches are its own business)
         } else {
             SelectParams fp{};
             fp.lists = static_cast<const uint64_t*>(c->cand.p);
@@ -582,9 +638,15 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
                     c->flag_req->armed = true;
                 }
             }
+            if (ps && first && ps->ts_scan) {
+                fp.ts_work = ts_work;
+                fp.ts_out = ts_entry;
+            }
+            if (ps && ts_entry && c->whole_by_clock && !alt && q0 + nq_here == nq) fp.ts_end = ts_entry + 3;  // the search's last kernel
             HIP_TRY(launch_select_final(fp, nq_here, s));
+            c->launches++;
         }
-        if (ps && first) HIP_TRY(hipEventRecord(ps->e[2], s));
+        if (ps && first && !ps->ts_scan) HIP_TRY(hipEventRecord(ps->e[2], s));
         first = false;
         q0 += nq_here;
     }
@@ -747,12 +809,24 @@ void feedback_consume(uint32_t& seen, uint32_t& redone, bool& bias_disabled, boo
     }
 }
 
+// The end-of-call event (mvfgpu_corpus::ev_done): the older of the two is recorded and becomes the newest.
+void record_done(const mvfgpu_corpus* c, hipStream_t s) {
+    const uint32_t i = c->done_idx ^ 1u;
+    if (hipEventRecord(c->ev_done[i], s) == hipSuccess) {
+        c->done_idx = i;
+        c->has_done = true;
+        c->last_stream = s;
+    } else {
+        (void)hipGetLastError();
+    }
+}
+
 // What the search before the previous one had to repair (its count was copied to pinned memory behind it; waited for
 // here -- by now it is two searches old -- so the decision does not depend on timing).
 void qs_feedback_poll(const mvfgpu_corpus* c) {
     const uint32_t sl = c->qs_slot;
     if (!c->qs_redo_pending[sl]) return;
-    if (hipEventSynchronize(c->qs_redo_ev[sl]) != hipSuccess) {
+    if (hipEventSynchronize(c->qs_redo_own[sl] ? c->qs_redo_ev[sl] : c->ev_done[c->qs_redo_done[sl]]) != hipSuccess) {
         (void)hipGetLastError();
         return;
     }
@@ -768,8 +842,6 @@ void qs_feedback_poll(const mvfgpu_corpus* c) {
 int feedback_slots(const mvfgpu_corpus* c) {
     if (c->qs_redo_host) return MVF_OK;
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->qs_redo_host), 64, hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&c->qs_redo_ev[0], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->qs_redo_ev[1], hipEventDisableTiming));
     return MVF_OK;
 }
 
@@ -783,7 +855,9 @@ uint32_t* feedback_mirror(const mvfgpu_corpus* c) {
     return c->qs_redo_host + c->qs_slot;
 }
 
-// ... and the request for it: the repair count of the search just enqueued, in pinned memory behind an event.
+// ... and the request for it: the repair count of the search just enqueued, in pinned memory behind the event its call
+// records on the way out (record_done) where the call holds this search alone (search_device), behind an event of the
+// search's own otherwise (the windows of a join).
 int qs_feedback_post(const mvfgpu_corpus* c, uint32_t nq, hipStream_t s, bool used_bias = false, bool used_qs = true) {
     const uint32_t sl = c->qs_slot;
     if (c->qs_redo_pending[sl] || !c->repair.p) return MVF_OK;  // (pending: this search did not poll -- it took another path first)
@@ -796,7 +870,13 @@ int qs_feedback_post(const mvfgpu_corpus* c, uint32_t nq, hipStream_t s, bool us
     if (c->fb_mirrored != c->qs_redo_host + sl)  // (the repair pass could not store it there itself)
         HIP_TRY(hipMemcpyAsync(c->qs_redo_host + sl, c->last_redo_cnt, 4, hipMemcpyDeviceToHost, s));
     c->fb_mirrored = nullptr;
-    HIP_TRY(hipEventRecord(c->qs_redo_ev[sl], s));
+    c->qs_redo_own[sl] = !c->one_search_call;
+    if (c->qs_redo_own[sl]) {  // more searches follow in this call: the end-of-call event comes too late for their polls
+        if (!c->qs_redo_ev[sl]) HIP_TRY(hipEventCreateWithFlags(&c->qs_redo_ev[sl], hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->qs_redo_ev[sl], s));
+    } else {
+        c->qs_redo_done[sl] = c->done_idx ^ 1u;
+    }
     c->qs_redo_pending[sl] = true;
     c->qs_redo_nq[sl] = nq;
     c->qs_slot = sl ^ 1u;
@@ -907,15 +987,24 @@ int ensure_norms(const mvfgpu_corpus* c, hipStream_t s) {
 // synchronised the stream): flag_compact_kernel turns the flags into a dense list + count; then ceil(nq / R) pairs of
 // REPAIR launches follow unconditionally -- K1's repair variant (every block walks its window of the list in groups of
 // four queries, one pass over the rows per group) and select_final's -- each of which reads the count and exits at once
-// when its window is empty.  The common case (nothing flagged) costs a few empty launches (~2.5 us each on the device,
+// when its window is empty.  The common case (nothing flagged) costs a few empty launches (4-5 us each on the device,
 // hidden behind the scan on the host); an adversarial corpus is still answered exactly.  R (queries per pair) is what
 // 256 MiB of per-block lists hold.
 // nqv_want = 1: the repair passes take one query each, with the lane-group width K1 uses for ONE query (a single-query search
 // whose answer must carry the bits the stored-row route gives it: search_stream_qs_path).
-int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t nq_pad,
-                           uint32_t k, uint32_t* overflow, float* d_scores, uint64_t* d_indices, int32_t* d_raw,
-                           hipStream_t s, int nqv_want = 4) {
-    (void)nq_pad;
+// The shape of the repair launches and their buffers, fixed before anything is launched: a search of one to four streamed
+// queries hands the list and the count to its final select, whose block 0 compacts the flags (RescoreParams::flags) -- the
+// launch of flag_compact_kernel spared.
+struct RepairPlan {
+    bool any = false;  // an empty corpus has nothing to repair
+    int nqv = 4, G = 64;
+    uint32_t J = 0, kcap = 0, chunk_rows = 0, pmax = 0, nchunks = 0, nblocks = 0, R = 0;
+    size_t lds = 0;
+    uint64_t* lists = nullptr;
+    uint32_t *redo_cnt = nullptr, *redo_list = nullptr;
+};
+int plan_repair(const mvfgpu_corpus* c, uint8_t metric, uint32_t nq, uint32_t k, int nqv_want, RepairPlan* rp) {
+    *rp = RepairPlan{};
     if (c->n == 0) return MVF_OK;
     const uint32_t kcap = next_pow2(k);
     int nqv = nqv_want == 1 ? 1 : 4, G;
@@ -949,10 +1038,45 @@ int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d
     uint32_t R = (uint32_t)std::min<size_t>(4096, std::max<size_t>(4, ((size_t)256 << 20) / per_query));
     if (c->tune.repair_window) R = std::min<uint32_t>(R, std::max<uint32_t>(4, c->tune.repair_window));  // tests: several windows on small batches
     HIP_TRY(c->repair.reserve((size_t)R * per_query + (size_t)nq * 4 + 16));
-    uint64_t* lists = static_cast<uint64_t*>(c->repair.p);
-    uint32_t* redo_cnt = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(c->repair.p) + (size_t)R * per_query);
-    uint32_t* redo_list = redo_cnt + 4;
-    HIP_TRY(launch_flag_compact(overflow, nq, redo_list, redo_cnt, feedback_mirror(c), s));
+    rp->any = true;
+    rp->nqv = nqv;
+    rp->G = G;
+    rp->J = J;
+    rp->kcap = kcap;
+    rp->chunk_rows = chunk_rows;
+    rp->pmax = pmax;
+    rp->nchunks = nchunks;
+    rp->nblocks = nblocks;
+    rp->R = R;
+    rp->lds = lds;
+    rp->lists = static_cast<uint64_t*>(c->repair.p);
+    rp->redo_cnt = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(c->repair.p) + (size_t)R * per_query);
+    rp->redo_list = rp->redo_cnt + 4;
+    return MVF_OK;
+}
+
+// compacted != NULL: the caller's last kernel has compacted the flags into that plan's list already
+int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t nq_pad,
+                           uint32_t k, uint32_t* overflow, float* d_scores, uint64_t* d_indices, int32_t* d_raw,
+                           hipStream_t s, int nqv_want = 4, const RepairPlan* compacted = nullptr, uint64_t* ts_end = nullptr) {
+    // ts_end: the last select of the last window is the last kernel of a profiled search on the streamed-shadow route
+    (void)nq_pad;
+    RepairPlan own;
+    if (!compacted) {
+        const int prc = plan_repair(c, metric, nq, k, nqv_want, &own);
+        if (prc != MVF_OK) return prc;
+    }
+    const RepairPlan& pl = compacted ? *compacted : own;
+    if (!pl.any) return MVF_OK;
+    const int nqv = pl.nqv, G = pl.G;
+    const uint32_t J = pl.J, kcap = pl.kcap, chunk_rows = pl.chunk_rows, pmax = pl.pmax, nchunks = pl.nchunks, nblocks = pl.nblocks, R = pl.R;
+    const size_t lds = pl.lds;
+    uint64_t* lists = pl.lists;
+    uint32_t *redo_cnt = pl.redo_cnt, *redo_list = pl.redo_list;
+    if (!compacted) {
+        HIP_TRY(launch_flag_compact(overflow, nq, redo_list, redo_cnt, feedback_mirror(c), s));
+        c->launches++;
+    }
     c->last_redo_cnt = redo_cnt;
     for (uint32_t base = 0; base < nq; base += R) {
         ScanParams sp{};
@@ -1000,7 +1124,9 @@ int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d
         fp.redo_list = redo_list;
         fp.redo_cnt = redo_cnt;
         fp.redo_base = base;
+        if (base + R >= nq) fp.ts_end = ts_end;
         HIP_TRY(launch_select_final(fp, std::min(R, nq - base), s));
+        c->launches += 2;
     }
     if (c->tune.debug_repair) {  // diagnostics only: how many queries took the repair path (synchronises)
         uint32_t n = 0;
@@ -1490,27 +1616,25 @@ int search_stream_qs_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_
     uint32_t* overflow = cnt + c->bstate_slots;
     HIP_TRY(c->bcand.reserve((size_t)nq_pad * cap * 8));
     const uint32_t KPB = shadow8_pitch(c->dim);
-    HIP_TRY(c->bq.reserve((size_t)nq_pad * KPB + (size_t)nq_pad * 12 + 64));
+    // the queries' scale, norm and bound: K1's prologue over the shadow prepares the queries itself and stores them here
+    // (block 0 of the scan; an empty corpus, which launches no scan, never gets here: qs_possible refuses n == 0)
+    HIP_TRY(c->bq.reserve((size_t)nq_pad * 12 + 64));
     c->bq_zeros = nullptr;  // another layout of the buffer: the batched path's zero bytes may be overwritten
-    unsigned char* qprep = static_cast<unsigned char*>(c->bq.p);
-    float* qaux0 = reinterpret_cast<float*>(qprep + (size_t)nq_pad * KPB);
+    float* qaux0 = static_cast<float*>(c->bq.p);
     float* qaux1 = qaux0 + nq_pad;
     float* qdelta = qaux1 + nq_pad;
     const size_t nn = norm_stride(n);
     const float* xn = static_cast<const float*>(c->xnorm.p);
-    const float* xxmax = xn + norm_max_at(n);
-    HIP_TRY(launch_prep_queries_i8s(static_cast<const float*>(d_queries), nq, nq, c->dim, KPB, metric,
-                                    static_cast<const float*>(c->qs_stats.p), xxmax, qprep, qaux0, qaux1, qdelta, s));
 
     ShadowStream alt{};
     alt.i8 = true;
     alt.rows = static_cast<const unsigned char*>(c->shadow8.p);
     alt.xscale = static_cast<const float*>(c->xscale8.p);
-    alt.qprep = qprep;
     alt.qaux0 = qaux0;
     alt.qaux1 = qaux1;
+    alt.qstats = static_cast<const float*>(c->qs_stats.p);
+    alt.xxmax = xn + norm_max_at(n);
     alt.xrow = metric == MVF_METRIC_L2 ? xn + nn : xn;  // sum x^2 | |x| of the stored rows
-    alt.qstride = KPB;
     alt.pitch = KPB;
     alt.V = KPB / 16;
     alt.cand = static_cast<uint64_t*>(c->bcand.p);
@@ -1520,6 +1644,7 @@ int search_stream_qs_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_
     alt.tau = tau;
     alt.overflow = overflow;
     alt.rank_k = k;
+    uint64_t* ts_end = c->whole_by_clock ? prof_ts_entry(c, c->prof_next) + 3 : nullptr;  // (this search's entry: prof_next moves below)
     rc = search_stream_path(c, metric, d_queries, nq, stream_qs_klist(k), nullptr, nullptr, nullptr, s, /*profile=*/true, &alt);
     if (rc != MVF_OK) return rc;
 
@@ -1539,22 +1664,34 @@ int search_stream_qs_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_
     rp.out_scores = d_scores;
     rp.out_indices = d_indices;
     rp.out_raw = d_raw;
-    // Float32 rows: re-scored in K1's arithmetic at the width K1 takes for these queries on the stored rows, and a flagged
-    // query redone by K1 at that width too -- the answer carries the bits the stored-row route gives it (Float16 rows: the
-    // wave kernel's order; out of that promise)
+    // Re-scored in K1's arithmetic at the width K1 takes for these queries on the stored rows, and a flagged query redone by
+    // K1 at that width too -- the answer carries the bits the stored-row route gives it (Float16 rows too since round 7; they
+    // went through the wave kernel's summation order before)
     int G, nqv;
     uint32_t J;
     k1_stored_group(c, nq, k, &G, &J, &nqv);
-    if (c->dtype == MVF_DTYPE_FLOAT32) HIP_TRY(launch_rescore_k1(rp, metric, nq, G, J, s));
-    else HIP_TRY(launch_rescore(rp, metric, nq, s));
-    rc = repair_flagged_queries(c, metric, d_queries, nq, nq_pad, k, overflow, d_scores, d_indices, d_raw, s, nqv);
+    // the flags are final since the margin select: block 0 of the final select turns them into the repair launches' list
+    RepairPlan plan;
+    rc = plan_repair(c, metric, nq, k, nqv, &plan);
+    if (rc != MVF_OK) return rc;
+    if (plan.any) {
+        rp.flags = overflow;
+        rp.flags_nq = nq;
+        rp.redo_list = plan.redo_list;
+        rp.redo_cnt = plan.redo_cnt;
+        rp.redo_mirror = feedback_mirror(c);
+    }
+    HIP_TRY(launch_rescore_k1(rp, metric, nq, G, J, s));
+    c->launches += 2;
+    rc = repair_flagged_queries(c, metric, d_queries, nq, nq_pad, k, overflow, d_scores, d_indices, d_raw, s, nqv, &plan, ts_end);
     if (rc == MVF_OK && c->scan_path != 6) rc = qs_feedback_post(c, nq, s);
     return rc;
 }
 
 // ONE query on a Float32 corpus of at least this many bytes of rows streams its int8 shadow by default (scan path 0): a quarter
 // of the bytes, re-scored in K1's arithmetic -- the same bits as K1 on the stored rows.  Below it the fixed cost of the route
-// (query preparation, the margin select, the re-scoring, the repair check: ~58 us of kernels) outweighs the bytes it spares.
+// (the margin select, the re-scoring, the repair check: ~48 us of kernels in five launches since round 7, 58 us in
+// seven before; the crossover below is round 6's and was not moved: profiles/r07_stream_fixed_cost.txt) outweighs the bytes it spares.
 // Measured, 768-dim f32 cosine, top-100, device time per search (profiles/r06_stream_i8_crossover.txt): 256 MiB 0.084 ms
 // against K1's 0.081; 512 MiB 0.084 against 0.123; 1 GiB 0.112 / 0.200; 4 GiB 0.234 / 0.673.
 constexpr uint64_t kStreamI8MinBytes = 512ull << 20;
@@ -1999,7 +2136,7 @@ bool corpus_ids_to_positions(const mvfgpu_corpus* c, const uint64_t* ids, uint64
 }
 int corpus_pinned_mirrors(const mvfgpu_corpus* c, size_t in_bytes, size_t out_bytes, void** pin_in, void** pin_out) {
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->has_done && c->confirmed_gen != c->work_gen) HIP_TRY(hipEventSynchronize(c->ev_done));
+    if (c->has_done && c->confirmed_gen != c->work_gen) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
     HIP_TRY(c->pin_q.reserve(in_bytes));
     HIP_TRY(c->pin_out.reserve(out_bytes));
     *pin_in = c->pin_q.p;
@@ -2010,18 +2147,12 @@ int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lk(c->mu);
     c->work_gen++;
-    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done, 0));
+    c->one_search_call = false;  // `body` may run any number of searches
+    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done[c->done_idx], 0));
     struct DoneGuard {  // as search_device's: work may already sit on the stream whatever `body` returns
         const mvfgpu_corpus* c;
         hipStream_t s;
-        ~DoneGuard() {
-            if (hipEventRecord(c->ev_done, s) == hipSuccess) {
-                c->has_done = true;
-                c->last_stream = s;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
+        ~DoneGuard() { record_done(c, s); }
     } done_guard{c, s};
     return body();
 }
@@ -2182,13 +2313,15 @@ void mvfgpu_corpus_destroy(mvfgpu_corpus* c) {
         c->done_ticket.release();
         c->pin_out.release();
         c->pin_vec.release();
+        c->prof_ts.release();
         c->h_v.release();
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
         if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
+        for (auto e : c->ev_done)
+            if (e) (void)hipEventDestroy(e);
         for (auto e : c->qs_redo_ev)
             if (e) (void)hipEventDestroy(e);
         if (c->qs_redo_host) (void)hipHostFree(c->qs_redo_host);
-        if (c->ev_done) (void)hipEventDestroy(c->ev_done);
         for (auto& ps : c->prof)
             for (auto& e : ps.e)
                 if (e) (void)hipEventDestroy(e);
@@ -2264,7 +2397,7 @@ int gather_rows_host_locked(const mvfgpu_corpus* c, const uint64_t* indices, uin
     void *di, *dout;
     {
         std::lock_guard<std::mutex> lk(c->mu);
-        if (c->has_done) HIP_TRY(hipEventSynchronize(c->ev_done));
+        if (c->has_done) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
         if (zc_i) {
             HIP_TRY(c->pin_q.reserve(ibytes));
             memcpy(c->pin_q.p, indices, ibytes);
@@ -2370,24 +2503,29 @@ namespace {
 int search_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
                   uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
     int rc = MVF_OK;
+    c->launches = c->search_launches = 0;
+    c->launches_known = true;
     mvfgpu_corpus::ProfSlot* wps = nullptr;  // whole-search events: every kernel of this call on the stream
     const uint64_t prof_before = c->prof_next;
     if (c->profiling) {
         wps = &c->prof[c->prof_next % mvfgpu_corpus::kProfSlots];
         for (auto& e : wps->e)
             if (!e) HIP_TRY(hipEventCreate(&e));
-        wps->whole = false;
-        HIP_TRY(hipEventRecord(wps->e[3], s));
+        wps->whole = wps->ts_whole = false;
     }
+    c->whole_by_clock = false;
+    bool e3_recorded = false;
     if (k > MVFGPU_K_PER_PASS) {  // more results than one pass selects: the whole shard ranked by a sort, or passes of the exact streaming kernel
         uint32_t scans = 1;
         bool sorted = false;
+        if (wps) HIP_TRY(hipEventRecord(wps->e[3], s));
         if (large_k_by_sort(c, nq, k)) {
             bool no_room = false;
             rc = search_sorted_k(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s, &no_room);
             sorted = rc == MVF_OK;
             if (!sorted && !(no_room && k <= MVFGPU_K_BY_PASSES)) return rc;
         }
+        c->launches_known = false;
         if (!sorted) {
             rc = search_large_k(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s);
             if (rc != MVF_OK) return rc;
@@ -2403,6 +2541,14 @@ int search_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
     }
     bool shadow_stream = false, qs_stream = false;
     if (stream_qs_wanted(c, nq, k)) qs_feedback_poll(c);  // may switch the int8 selection off
+    // K1 on the stored rows and the streamed int8 shadow time themselves (ProfSlot::ts_whole: from the search's first kernel, so
+    // not the norms / the shadow a handle's first search builds in front of it); every other route keeps the event pair around the
+    // whole call, in front of whatever it builds first.  The route is only known behind those builds: where it was expected to time
+    // itself and cannot (no room for the shadow, non-finite maxima) and the batched route answers, e[3] is recorded behind them too
+    if (wps && !(stream_qs_wanted(c, nq, k) || (!stream_shadow_wanted(c, nq) && !use_batched_path(c, metric, nq)))) {
+        HIP_TRY(hipEventRecord(wps->e[3], s));
+        e3_recorded = true;
+    }
     if (stream_qs_wanted(c, nq, k)) {
         rc = ensure_norms(c, s);
         if (rc != MVF_OK) return rc;
@@ -2422,14 +2568,27 @@ int search_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
         if (e != hipSuccess) return fail(MVF_ERR_DEVICE, std::string("shadow build: ") + hipGetErrorString(e));
         shadow_stream = c->shadow_state == 1;
     }
+    const bool by_clock = wps && (qs_stream || (!shadow_stream && !use_batched_path(c, metric, nq)));
+    if (by_clock) {
+        rc = prof_ts_ensure(c, s);
+        if (rc != MVF_OK) return rc;
+        c->whole_by_clock = true;
+    } else if (wps && !e3_recorded) {
+        HIP_TRY(hipEventRecord(wps->e[3], s));
+    }
     rc = qs_stream                           ? search_stream_qs_path(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s)
          : shadow_stream                     ? search_stream_shadow_path(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s)
          : use_batched_path(c, metric, nq) ? search_batched_path(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s)
                                            : search_stream_path(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s);
     if (rc != MVF_OK) return rc;
+    if (c->launches_known && (qs_stream || !(shadow_stream || use_batched_path(c, metric, nq)))) c->search_launches = c->launches;
     if (wps && c->prof_next == prof_before + 1) {  // the path filled this slot
-        HIP_TRY(hipEventRecord(wps->e[4], s));
-        wps->whole = true;
+        if (by_clock) {
+            wps->ts_whole = wps->ts_scan;  // (an empty corpus launches no scan: nothing to time)
+        } else {
+            HIP_TRY(hipEventRecord(wps->e[4], s));
+            wps->whole = true;
+        }
         c->timing.search_flops = 2ull * nq * c->n * c->dim;
     }
     return MVF_OK;
@@ -2450,22 +2609,16 @@ int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
         ~ReqGuard() { c->flag_req = nullptr; }
     } req_guard{c};
     c->flag_req = req;
+    c->one_search_call = true;
     if (req) req->gen = c->work_gen;
     // the scratch buffers are stream-ordered: a call on another stream waits for the previous one
-    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done, 0));
+    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done[c->done_idx], 0));
     // Whatever happens below, work may already sit on the stream (norms, a shadow build, scratch): the next call on
     // ANOTHER stream orders itself behind ev_done, so it is recorded on every way out.
     struct DoneGuard {
         const mvfgpu_corpus* c;
         hipStream_t s;
-        ~DoneGuard() {
-            if (hipEventRecord(c->ev_done, s) == hipSuccess) {
-                c->has_done = true;
-                c->last_stream = s;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
+        ~DoneGuard() { record_done(c, s); }
     } done_guard{c, s};
     return search_locked(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s);  // ev_done: DoneGuard
 }
@@ -2511,7 +2664,7 @@ int search_host(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uin
         std::lock_guard<std::mutex> lk(c->mu);
         // wait for any in-flight user of the mirrors before (re)allocating them (nothing is in flight when the newest work
         // was seen complete through the flag: its event would only be signalled a few microseconds from now)
-        if (c->has_done && c->confirmed_gen != c->work_gen) HIP_TRY(hipEventSynchronize(c->ev_done));
+        if (c->has_done && c->confirmed_gen != c->work_gen) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
         fused_fetch = out_vectors && c->h_ids.empty();
         if (zc_q) {
             HIP_TRY(c->pin_q.reserve(qbytes));
@@ -2791,26 +2944,46 @@ int mvfgpu_last_timing(const mvfgpu_corpus* c, mvfgpu_timing* out) {
     mvfgpu_timing tm = c->timing;
     if (c->last_redo_cnt) {  // the newest batched search's repair count (waits for the handle's last search)
         DeviceGuard guard(c->device);
-        if (c->has_done) HIP_TRY(hipEventSynchronize(c->ev_done));
+        if (c->has_done) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
         uint32_t n = 0;
         HIP_TRY(hipMemcpy(&n, c->last_redo_cnt, 4, hipMemcpyDeviceToHost));
         tm.repaired_queries = n;
     }
+    tm.search_launches = c->search_launches;
     if (c->prof_next > 0) {
         DeviceGuard guard(c->device);
         const uint64_t newest = c->prof_next - 1;
         const uint64_t oldest = c->prof_next > mvfgpu_corpus::kProfSlots ? c->prof_next - mvfgpu_corpus::kProfSlots : 0;
         double ssum = 0, lsum = 0, wsum = 0;
         uint32_t cnt = 0, wcnt = 0;
+        std::vector<uint64_t> clk;  // the clock entries of the searches that timed themselves, behind the handle's newest call
+        for (uint64_t i = oldest; i <= newest && clk.empty(); i++)
+            if (c->prof[i % mvfgpu_corpus::kProfSlots].ts_scan && c->prof_ts.p) {
+                if (c->has_done) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+                clk.resize((size_t)mvfgpu_corpus::kProfSlots * 4);
+                HIP_TRY(hipMemcpy(clk.data(), c->prof_ts.p, clk.size() * 8, hipMemcpyDeviceToHost));
+            }
         for (uint64_t i = newest + 1; i-- > oldest;) {
             const auto& ps = c->prof[i % mvfgpu_corpus::kProfSlots];
-            HIP_TRY(hipEventSynchronize(ps.whole ? ps.e[4] : ps.e[2]));
             float a = 0, b = 0, w = 0;
-            if (ps.scanned) {
+            if (ps.ts_scan && !clk.empty()) {
+                const uint64_t* t = clk.data() + (i % mvfgpu_corpus::kProfSlots) * 4;
+                if (t[1] >= t[0]) a = (float)((double)(t[1] - t[0]) / c->wall_khz);
+                if (t[2] >= t[1]) b = (float)((double)(t[2] - t[1]) / c->wall_khz);
+                if (ps.ts_whole && t[3] >= t[0]) {
+                    w = (float)((double)(t[3] - t[0]) / c->wall_khz);
+                    wsum += w;
+                    wcnt++;
+                }
+            } else {
+                HIP_TRY(hipEventSynchronize(ps.whole ? ps.e[4] : ps.e[2]));
+            }
+            if (ps.scanned && !ps.ts_scan) {
                 HIP_TRY(hipEventElapsedTime(&a, ps.e[0], ps.e[1]));
                 HIP_TRY(hipEventElapsedTime(&b, ps.e[1], ps.e[2]));
             }
             if (ps.whole) {
+                if (ps.ts_scan) HIP_TRY(hipEventSynchronize(ps.e[4]));
                 HIP_TRY(hipEventElapsedTime(&w, ps.e[3], ps.e[4]));
                 wsum += w;
                 wcnt++;

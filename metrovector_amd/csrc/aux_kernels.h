@@ -56,6 +56,13 @@ struct SelectParams {
     const unsigned char* gather_rows;
     unsigned char* gather_out;
     uint32_t gather_pitch, gather_row_bytes;
+    // Profiled searches on the K1 routes take their times from the wall clock the kernels read themselves (api.hip): block 0
+    // publishes the scan's start / end (ts_work[0..1], folded by the scan's blocks: ScanParams::ts) and its own end as
+    // ts_out[0..2] and re-arms ts_work; the LAST select of a search also stores its end to *ts_end -- even where it exits at
+    // once (an empty repair launch).  NULL = none.
+    uint64_t* ts_work;
+    uint64_t* ts_out;
+    uint64_t* ts_end;
 };
 
 // queries flagged by the K2 compactions -> a dense list + its length, flags cleared (one block)

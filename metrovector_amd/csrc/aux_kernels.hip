@@ -8,6 +8,7 @@
 #include "aux_kernels.h"
 #include "bitonic.h"
 #include "mvf_common.h"
+#include "repair_flags.h"
 
 #include <hip/hip_fp16.h>
 
@@ -58,8 +59,24 @@ __global__ void __launch_bounds__(1024) select_final_kernel(SelectParams p) {
     const int tid = threadIdx.x;
     const uint32_t q = blockIdx.x;
     uint32_t qout = q;  // the query whose result row this block writes
+    // the block's end on the device's wall clock, for profiled searches (block 0; the other blocks run beside it)
+    auto stamp = [&]() __attribute__((always_inline)) {
+        if (q != 0 || tid != 0) return;
+        const uint64_t now = (uint64_t)wall_clock64();
+        if (p.ts_out) {
+            p.ts_out[0] = p.ts_work[0];
+            p.ts_out[1] = p.ts_work[1];
+            p.ts_out[2] = now;
+            p.ts_work[0] = ~0ull;  // (the next profiled scan's block 0 overwrites it: "no start" until then, never a stale one)
+            p.ts_work[1] = 0;
+        }
+        if (p.ts_end) *p.ts_end = now;
+    };
     if (p.redo_list) {
-        if (p.redo_base + q >= *p.redo_cnt) return;  // block-uniform: nothing (more) to repair
+        if (p.redo_base + q >= *p.redo_cnt) {  // block-uniform: nothing (more) to repair
+            stamp();
+            return;
+        }
         qout = p.redo_list[p.redo_base + q];
     }
     const uint64_t* lists = p.lists + (size_t)q * p.nlists * p.kcap;
@@ -199,12 +216,14 @@ __global__ void __launch_bounds__(1024) select_final_kernel(SelectParams p) {
             p.out_cnt[q] = inside < p.keep_cap ? inside : p.keep_cap;
             p.out_tau[q] = tkey;
         }
+        stamp();
         return;
     }
     if (p.out_cand) {
         const uint32_t keep = m < p.k ? m : p.k;
         for (uint32_t i = tid; i < keep; i += 1024) p.out_cand[(size_t)q * p.cand_cap + i] = buf[i];
         if (tid == 0) p.out_cnt[q] = keep;
+        stamp();
         return;
     }
     const uint32_t stride = p.out_stride ? p.out_stride : p.k;
@@ -226,6 +245,7 @@ __global__ void __launch_bounds__(1024) select_final_kernel(SelectParams p) {
             }
         }
     }
+    stamp();
     if (p.done_flag) {  // block-uniform: tell the waiting host call (results in pinned host memory) that everything is there
         __threadfence_system();
         __syncthreads();
@@ -255,19 +275,7 @@ __global__ void __launch_bounds__(256) write_sorted_kernel(SelectParams p, const
 __global__ void __launch_bounds__(1024) flag_compact_kernel(uint32_t* overflow, uint32_t nq, uint32_t* redo_list, uint32_t* redo_cnt,
                                                              uint32_t* host_mirror) {
     __shared__ uint32_t n_s;
-    if (threadIdx.x == 0) n_s = 0;
-    __syncthreads();
-    for (uint32_t q = threadIdx.x; q < nq; q += 1024) {
-        if (overflow[q]) {
-            redo_list[atomicAdd(&n_s, 1u)] = q;
-            overflow[q] = 0;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        *redo_cnt = n_s;
-        if (host_mirror) *host_mirror = n_s;  // pinned host memory: the repair feedback reads it two searches later, behind an event
-    }
+    compact_flags(overflow, nq, redo_list, redo_cnt, host_mirror, &n_s);
 }
 
 // Cross-shard merge of formatted results.  An entry is the u64 composite (order key << 32 | slot), slot = list * k +

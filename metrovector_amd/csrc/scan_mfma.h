@@ -139,11 +139,19 @@ struct RescoreParams {
     // refinement's ntop[]) neither fetches nor writes those entries again.  A third fewer random row fetches in the final pass.
     uint32_t write_head;
     const uint32_t* head_done;
+    // One to four streamed queries (api.hip: search_stream_qs_path): block 0 of the final select also turns the queries'
+    // overflow flags -- final since the margin select -- into the repair launches' list (repair_flags.h), which spares the
+    // search the launch of flag_compact_kernel.  NULL = the caller compacts the flags itself.
+    uint32_t* flags;        // [flags_nq], cleared
+    uint32_t flags_nq;
+    uint32_t* redo_list;
+    uint32_t* redo_cnt;
+    uint32_t* redo_mirror;  // pinned host memory, or NULL
 };
 hipError_t launch_compact_margin(const CompactParams& p, uint32_t nq, hipStream_t s);
 hipError_t launch_rescore(const RescoreParams& p, int metric, uint32_t nq, hipStream_t s);
-// The same final re-scoring + select on Float32 rows in K1's arithmetic (k1_rowscore.h) for K1's lane-group width G and
-// steps J on the stored rows: the scores carry the bits scan_stream_kernel gives the same queries (the int8-shadow stream)
+// The same final re-scoring + select on Float32 / Float16 rows in K1's arithmetic (k1_rowscore.h) for K1's lane-group width G
+// and steps J on the stored rows: the scores carry the bits scan_stream_kernel gives the same queries (the int8-shadow stream)
 hipError_t launch_rescore_k1(const RescoreParams& p, int metric, uint32_t nq, int G, uint32_t J, hipStream_t s);
 // Threshold refinement between two phases of an int8-shadow selection: the ntop[q] >= k best approximate candidates of
 // every query are scored EXACTLY (rescore's arithmetic; L2 as the squared distance the selection works on); the worst of

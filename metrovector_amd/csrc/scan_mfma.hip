@@ -33,6 +33,7 @@
 #include "bitonic.h"
 #include "k1_rowscore.h"
 #include "mvf_common.h"
+#include "repair_flags.h"
 #include "scan_mfma16_key.h"
 
 #include <hip/hip_fp16.h>
@@ -956,7 +957,8 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long mask, uint32_t n) 
     return pos;
 }
 
-template <int METRIC, int G>
+// F16: Float16 rows -- eight elements per 16-B vector, widened exactly, K1's fmaf order over them (k1_rowscore.h).
+template <int METRIC, int G, bool F16 = false>
 __global__ void __launch_bounds__(256) rescore_k1_kernel(RescoreParams p, uint32_t nq, uint32_t slices, uint32_t split, uint32_t J) {
     constexpr int RPG = 64 / G, U = 4;
     constexpr uint32_t PER_ROUND = (uint32_t)(RPG * U);
@@ -1002,17 +1004,29 @@ __global__ void __launch_bounds__(256) rescore_k1_kernel(RescoreParams p, uint32
                     for (int u = 0; u < U; u++)
                         x[u] = (vv && ok[u]) ? *reinterpret_cast<const k1::u32x4*>(p.rows + (size_t)row[u] * p.pitch + (size_t)v * 16)
                                              : k1::u32x4{0, 0, 0, 0};
-                    float qe[4];
+                    constexpr int EPV = F16 ? 8 : 4;
+                    float qe[EPV];
 #pragma unroll
-                    for (int w = 0; w < 4; w++) {
-                        const uint32_t e = v * 4u + (uint32_t)w;
+                    for (int w = 0; w < EPV; w++) {
+                        const uint32_t e = v * (uint32_t)EPV + (uint32_t)w;
                         qe[w] = e < p.dim ? qp[e] : 0.0f;
                     }
-                    const float4 qv = make_float4(qe[0], qe[1], qe[2], qe[3]);
+                    if constexpr (F16) {
+                        const float4 qa = make_float4(qe[0], qe[1], qe[2], qe[3]), qb = make_float4(qe[4], qe[5], qe[6], qe[7]);
 #pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        acc[u] = k1::acc4<METRIC>(acc[u], qv, x[u]);
-                        if constexpr (NEED_XX) xx[u] = k1::xx4(xx[u], x[u]);
+                        for (int u = 0; u < U; u++) {
+                            float xf[8];
+                            k1::widen_f16(x[u], xf);
+                            acc[u] = k1::acc8_f16<METRIC>(acc[u], qa, qb, xf);
+                            if constexpr (NEED_XX) xx[u] = k1::xx8_f16(xx[u], xf);
+                        }
+                    } else {
+                        const float4 qv = make_float4(qe[0], qe[1], qe[2], qe[3]);
+#pragma unroll
+                        for (int u = 0; u < U; u++) {
+                            acc[u] = k1::acc4<METRIC>(acc[u], qv, x[u]);
+                            if constexpr (NEED_XX) xx[u] = k1::xx4(xx[u], x[u]);
+                        }
                     }
                 }
 #pragma unroll
@@ -1027,18 +1041,20 @@ __global__ void __launch_bounds__(256) rescore_k1_kernel(RescoreParams p, uint32
     }
 }
 
-template <int METRIC>
+template <int METRIC, bool F16>
 const void* pick_rescore_k1(int G) {
     switch (G) {
-    case 1: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 1>);
-    case 4: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 4>);
-    case 8: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 8>);
-    case 16: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 16>);
-    case 32: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 32>);
-    case 64: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 64>);
+    case 1: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 1, F16>);
+    case 4: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 4, F16>);
+    case 8: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 8, F16>);
+    case 16: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 16, F16>);
+    case 32: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 32, F16>);
+    case 64: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 64, F16>);
     default: return nullptr;
     }
 }
+template <int METRIC>
+const void* pick_rescore_k1(int G, bool f16) { return f16 ? pick_rescore_k1<METRIC, true>(G) : pick_rescore_k1<METRIC, false>(G); }
 
 // One thread per query: tau[q] = the tighter of itself and ord(L -/+ delta), L = the worst exact score of its k best
 // approximate candidates (rescore_score_kernel<., true>); re-arms lkey.  The 2 % on delta covers the f32 rounding of the
@@ -1094,6 +1110,10 @@ __global__ void __launch_bounds__(1024) rescore_select_kernel(RescoreParams p, i
     if (tid == 0) {
         p.cnt[q] = 0;
         p.tau[q] = kNanKey;
+    }
+    if (p.flags && q == 0) {  // block-uniform
+        __shared__ uint32_t flagged_s;
+        compact_flags(p.flags, p.flags_nq, p.redo_list, p.redo_cnt, p.redo_mirror, &flagged_s);
     }
 }
 
@@ -1199,10 +1219,11 @@ hipError_t launch_rescore(const RescoreParams& p, int metric, uint32_t nq, hipSt
 
 hipError_t launch_rescore_k1(const RescoreParams& p, int metric, uint32_t nq, int G, uint32_t J, hipStream_t s) {
     if (nq == 0) return hipSuccess;
-    if (p.dtype != MVF_DTYPE_FLOAT32) return hipErrorInvalidValue;
-    const void* fn = metric == MVF_METRIC_L2               ? pick_rescore_k1<MVF_METRIC_L2>(G)
-                     : metric == MVF_METRIC_INNER_PRODUCT ? pick_rescore_k1<MVF_METRIC_INNER_PRODUCT>(G)
-                     : metric == MVF_METRIC_COSINE        ? pick_rescore_k1<MVF_METRIC_COSINE>(G)
+    if (p.dtype != MVF_DTYPE_FLOAT32 && p.dtype != MVF_DTYPE_FLOAT16) return hipErrorInvalidValue;
+    const bool f16 = p.dtype == MVF_DTYPE_FLOAT16;
+    const void* fn = metric == MVF_METRIC_L2               ? pick_rescore_k1<MVF_METRIC_L2>(G, f16)
+                     : metric == MVF_METRIC_INNER_PRODUCT ? pick_rescore_k1<MVF_METRIC_INNER_PRODUCT>(G, f16)
+                     : metric == MVF_METRIC_COSINE        ? pick_rescore_k1<MVF_METRIC_COSINE>(G, f16)
                                                           : nullptr;
     if (!fn) return hipErrorInvalidValue;
     // items as the final pass of launch_rescore_wave: a query's 64-candidate slices, `split` waves sharing a slice so that

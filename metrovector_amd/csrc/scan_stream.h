@@ -10,12 +10,17 @@ struct ScanParams {
     const unsigned char* rows;  // device rows, `pitch` bytes apart, 16-B aligned
     const void* queries;        // device [nq_total][dim]: f32, or the space's int type
     const float* xscale;        // dt1x / dt2x: the rows are a scaled shadow (f16 of a Float32 corpus / int8 of a float corpus), row r times xscale[r]
-    // dt2x (int8 shadow, float scores): the queries are the int8 rows the query preparation wrote, `qstride` bytes apart,
-    // with their scale qaux0[q] and norm qaux1[q] = |q|; xrow[r] = |x_r| (cosine) / sum x_r^2 (L2) of the STORED row
+    // dt2x (int8 shadow, float scores): the queries are the caller's f32 rows; every block's prologue quantises them to int8
+    // while it stages them in LDS (query_i8s.h: the batched route's query preparation, the same device function) and block 0
+    // of the launch stores the scale qaux0[q], the norm qaux1[q] = |q| and the proven bound qdelta[q] for the margin select
+    // behind it (qstats: the shadow's four bound maxima, xxmax: the largest sum x^2 of a stored row).
+    // xrow[r] = |x_r| (cosine) / sum x_r^2 (L2) of the STORED row
     const float* xrow;
-    const float* qaux0;
-    const float* qaux1;
-    uint32_t qstride;
+    float* qaux0;
+    float* qaux1;
+    float* qdelta;
+    const float* qstats;
+    const float* xxmax;
     const uint32_t* tomb;       // deletion bitmap, bit (r & 31) of word (r >> 5) = local row r is deleted; NULL = none
     uint64_t* cand;             // out: [launch queries][gridDim.x][kcap] sorted composites, ~0-padded
     uint32_t n;                 // rows in the shard
@@ -48,6 +53,10 @@ struct ScanParams {
     // candidates; the rank entry (mvf_common.h) of every row of query q0 + q goes to dump[q * n + row] (a deleted row marked
     // dead) and a device-wide sort of the n entries ranks the whole shard.  NULL = none.
     uint64_t* dump;
+    // Profiled searches (api.hip: mvfgpu_set_profiling): the launch times itself -- block 0, the first to be dispatched, stores the
+    // wall clock at its start to ts[0], thread 0 of every block folds it at its end into ts[1] (a vector atomic maximum); the select behind the
+    // launch publishes and re-arms the pair (SelectParams::ts_work).  NULL = not profiled: one scalar compare.
+    uint64_t* ts;
 };
 
 // nqv: queries per pass, 1 or 4; p.redo_list != NULL selects the repair variant of the kernel, p.floor1 != NULL the

@@ -25,6 +25,7 @@
 #include "mvf_common.h"
 #include "scan_stream.h"
 #include "bitonic.h"
+#include "query_i8s.h"
 
 #include <hip/hip_fp16.h>
 
@@ -61,8 +62,8 @@ __device__ __forceinline__ int32_t dot4_u8(uint32_t a, uint32_t b, int32_t c) {
 // XS: this translation unit scans the scaled-f16 SHADOW of a Float32 corpus (api.hip, scan path 4): every widened
 // element is multiplied by the row's xscale[r] = 2^-s_r, so all three metrics see x~ = x (1 + e), |e| <= 2^-11.
 constexpr bool XS = MVF_SCAN_XS != 0;
-// QSK: the XS unit over INT8 rows = the int8 shadow of a Float32 / Float16 corpus (shadow_i8.hip): int8 queries from the
-// query preparation, exact i32 dot products, FLOAT keys dot * xscale[r] * qaux0[q] (cosine: / (|q| |x_r|); L2: the
+// QSK: the XS unit over INT8 rows = the int8 shadow of a Float32 / Float16 corpus (shadow_i8.hip): the f32 queries are
+// quantised to int8 in the prologue (query_i8s.h), exact i32 dot products, FLOAT keys dot * xscale[r] * qaux0[q] (cosine: / (|q| |x_r|); L2: the
 // GEMM-form squared distance qq + xx - 2 dot) for the margin compaction + exact re-scoring that follow.
 constexpr bool QSK = XS && MVF_SCAN_DT == MVF_DTYPE_INT8;
 
@@ -98,6 +99,8 @@ scan_stream_kernel(ScanParams p) {
     const uint32_t VP = p.J * G;  // padded vectors per row held in LDS
     unsigned char* qs = smem;     // [NQ][VP*QB]
     const uint32_t qstride = VP * QB;
+    // (QSK: the first 24 floats of bufs are the scratch of the prologue's reductions -- bufs is first written in the row loop,
+    // behind the barrier that ends the staging, and pmax >= 512 entries)
     uint64_t* bufs = reinterpret_cast<uint64_t*>(smem + ((NQ * qstride + 15u) & ~15u));  // [NQ][p.pmax]
     uint32_t* cnt = reinterpret_cast<uint32_t*>(bufs + (size_t)NQ * p.pmax);              // [NQ]
     uint32_t* kprev = cnt + NQ;                                                            // [NQ]
@@ -115,6 +118,9 @@ scan_stream_kernel(ScanParams p) {
         if (avail == 0) return;  // the common case: nothing overflowed
         ngroups = (avail + NQ - 1) / NQ;
     }
+    // (profiled searches: block 0 is dispatched first -- a plain store.  Every block folding a minimum into one word at the
+    // same moment held its first row loads back behind the atomic: profiles/r07_stream_fixed_cost.txt)
+    if (p.ts && tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) p.ts[0] = (uint64_t)wall_clock64();
     for (uint32_t grp = 0; grp < ngroups; grp++) {
     if (REDO && grp) __syncthreads();  // the previous group's lists have left LDS
     // ---- stage the queries in LDS (f32 / packed int8, zero padded) -----------
@@ -126,7 +132,26 @@ scan_stream_kernel(ScanParams p) {
     [[maybe_unused]] uint64_t fl1[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; q++) qq_part[q] = 0, qsf[q] = 1.f, qnf[q] = 0.f, fl1[q] = 0;
-    {
+    if constexpr (QSK) {
+        // the caller's f32 queries are quantised here, by every block for itself (3 KiB of L2 hits per query against the
+        // launch the stand-alone preparation cost in front of every search of one to four queries); block 0 leaves what
+        // the margin select behind this launch reads.  The reductions' scratch is the head of the (still empty) candidate
+        // buffers: a static array would count against the 160 KiB the dynamic LDS of the short-row shapes is raised to.
+        float* prep_red = reinterpret_cast<float*>(bufs);
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const uint32_t qi = min(q0 + q, p.nq_total - 1u);  // padding lanes repeat the last query
+            const bool owner = blockIdx.x == 0 && blockIdx.y == 0 && q0 + q < p.nq_total;
+            float d = 0.f;
+            prep_query_i8s(reinterpret_cast<const float*>(p.queries) + (size_t)qi * p.dim, p.dim, VP * EPV, METRIC, p.qstats, p.xxmax,
+                           reinterpret_cast<int8_t*>(qs + q * qstride), prep_red + (q & 1) * 12, owner, &qsf[q], &qnf[q], &d);
+            if (owner && tid == 0) {
+                p.qaux0[qi] = qsf[q];
+                p.qaux1[qi] = qnf[q];
+                p.qdelta[qi] = d;
+            }
+        }
+    } else {
         const uint32_t nelem = VP * EPV;
         using QT = typename std::conditional<Tr::INT, typename Tr::Q, float>::type;
         const QT* src[NQ];
@@ -137,11 +162,7 @@ scan_stream_kernel(ScanParams p) {
             if (qi >= p.nq_total) qi = p.nq_total - 1;  // padding lanes repeat the last query
             if constexpr (REDO) qi = p.redo_list[p.redo_base + min(grp * NQ + q, avail - 1u)];
             if constexpr (FLOOR) fl1[q] = p.floor1 ? p.floor1[qi] : 0;
-            if constexpr (QSK) {
-                qsf[q] = p.qaux0[qi];
-                qnf[q] = p.qaux1[qi];
-            }
-            src[q] = reinterpret_cast<const QT*>(p.queries) + (size_t)qi * ((Tr::INT && QSK) ? p.qstride : p.dim);
+            src[q] = reinterpret_cast<const QT*>(p.queries) + (size_t)qi * p.dim;
             dst[q] = reinterpret_cast<QT*>(qs + q * qstride);
         }
         // the NQ queries' elements are fetched together (NQ loads in flight per step, not one query after the other: on a
@@ -646,6 +667,10 @@ scan_stream_kernel(ScanParams p) {
     }
 
     }  // groups
+    if (p.ts) {  // launch-uniform
+        __syncthreads();
+        if (tid == 0) atomicMax(reinterpret_cast<unsigned long long*>(p.ts) + 1, (unsigned long long)wall_clock64());
+    }
 }
 
 template <int DT, int METRIC, int G>

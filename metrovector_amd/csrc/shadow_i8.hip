@@ -22,6 +22,7 @@
 #include "scan_mfma.h"
 
 #include "mvf_common.h"
+#include "query_i8s.h"
 
 #include <hip/hip_fp16.h>
 
@@ -133,78 +134,18 @@ __global__ void __launch_bounds__(256) shadow_i8_kernel(const unsigned char* row
     }
 }
 
-// Queries for the int8 shadow: q8 = rint(q / s_q), s_q = max|q| / 127, zero padded to KPB bytes per row.
-//   qaux0 = s_q (the scale the epilogue undoes), qaux1 = |q| (f32 norm of the ORIGINAL query),
-//   delta[q] = the proven bound of |approximate score - exact score| for this query over ALL rows of the corpus:
-//     InnerProduct  s_q (|eq| A + |q8| B) + 4e-7 |q| max|x|
-//     Cosine        s_q (|eq| Ac + |q8| Bc) / |q| + 4e-7
-//     L2 (on the GEMM-form squared distance qq + xx - 2 q.x)   2 x the InnerProduct bound + 4e-7 (qq + max xx)
-//   (A, B, Ac, Bc = stats[0..3]; the 4e-7 terms cover the f32 evaluation of acc * s_r * s_q and of the norms.)
-// A non-finite query gets delta = +inf: every row is kept, the query overflows its budget and K1 repairs it.
+// Queries for the int8 shadow, one block per (padded) query row: query_i8s.h does the arithmetic -- the int8 values, zero
+// padded to KPB bytes per row, qaux0 = s_q (the scale the epilogue undoes), qaux1 = |q|, delta[q] = the proven bound.
+// The batched route's preparation; one to four streamed queries are prepared by K1's own prologue (scan_stream.inc).
 __global__ void __launch_bounds__(256) prep_queries_i8s_kernel(const float* q, uint32_t nq, uint32_t dim, uint32_t KPB, int metric,
                                                                 const float* stats, const float* xxmax, unsigned char* qprep,
                                                                 float* qaux0, float* qaux1, float* delta) {
     const uint32_t row = blockIdx.x;
     __shared__ float red[12];
-    float mx = 0.f, ss = 0.f;
-    bool bad = false;
-    if (row < nq)
-        for (uint32_t c = threadIdx.x; c < dim; c += 256) {
-            const float v = q[(size_t)row * dim + c];
-            bad |= !(fabsf(v) < 3.0e38f);
-            mx = fmaxf(mx, fabsf(v));
-            ss = fmaf(v, v, ss);
-        }
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        ss += __shfl_xor(ss, off, 64);
-    }
-    const bool wbad = __builtin_amdgcn_ballot_w64(bad) != 0;
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6] = mx;
-        red[4 + (threadIdx.x >> 6)] = ss;
-        red[8 + (threadIdx.x >> 6)] = wbad ? 1.f : 0.f;
-    }
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    ss = red[4] + red[5] + red[6] + red[7];
-    bad = (red[8] + red[9] + red[10] + red[11]) > 0.f || !(ss < 3.0e38f);
-    __syncthreads();
-    const float sq = (bad || !(mx > 0.f)) ? 0.f : mx / 127.0f;
-    float q2 = 0.f, e2 = 0.f;
-    for (uint32_t c = threadIdx.x; c < KPB; c += 256) {
-        const float v = (row < nq && c < dim) ? q[(size_t)row * dim + c] : 0.f;
-        const float t = sq > 0.f ? v / sq : 0.f;
-        float r8 = rintf(t);
-        r8 = fminf(fmaxf(r8, -127.f), 127.f);
-        const float e = t - r8;
-        q2 = fmaf(r8, r8, q2);
-        e2 = fmaf(e, e, e2);
-        reinterpret_cast<int8_t*>(qprep)[(size_t)row * KPB + c] = (int8_t)(int)r8;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        q2 += __shfl_xor(q2, off, 64);
-        e2 += __shfl_xor(e2, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6] = q2;
-        red[4 + (threadIdx.x >> 6)] = e2;
-    }
-    __syncthreads();
+    float sq, qn, d = 0.f;
+    prep_query_i8s(row < nq ? q + (size_t)row * dim : nullptr, dim, KPB, metric, stats, xxmax,
+                   reinterpret_cast<int8_t*>(qprep) + (size_t)row * KPB, red, true, &sq, &qn, &d);
     if (threadIdx.x == 0) {
-        q2 = red[0] + red[1] + red[2] + red[3];
-        e2 = red[4] + red[5] + red[6] + red[7];
-        const float qn = sqrtf(ss), inf = __uint_as_float(0x7F800000u);
-        const float eq = sqrtf(e2) * 1.0005f + 1e-3f, q8n = sqrtf(q2) * 1.0005f;
-        float d;
-        if (row >= nq) d = 0.f;
-        else if (bad) d = inf;
-        else if (metric == MVF_METRIC_COSINE) d = qn > 0.f ? sq * (eq * stats[2] + q8n * stats[3]) / qn * 1.0001f + 4e-7f : 0.f;
-        else {
-            const float xm = sqrtf(xxmax[0]);
-            d = sq * (eq * stats[0] + q8n * stats[1]) * 1.0001f + 4e-7f * qn * xm;
-            if (metric == MVF_METRIC_L2) d = 2.0f * d + 4e-7f * (ss + xxmax[0]);
-        }
         qaux0[row] = sq;
         qaux1[row] = qn;
         delta[row] = d;

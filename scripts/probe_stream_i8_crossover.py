@@ -1,6 +1,6 @@
 """One Float32 query, top-100 cosine: the int8-shadow stream (scan path 0's default above the threshold; path 6 below it)
 against K1 on the stored rows (path 1), by corpus size -- the crossover behind api.hip kStreamI8MinBytes.  Device time of
-the whole search (HIP events, first to last kernel) and the host call's wall time, medians.  Development aid."""
+the whole search (mvfgpu_timing.search_ms: first to last kernel) and the host call's wall time, medians.  Development aid."""
 import os
 import sys
 import time

@@ -2,6 +2,10 @@
 
   stats    <dir> <out.csv> <comment>             per-kernel calls / total / average duration (us) from the kernel trace
   launches <dir> <out.csv> <name filter> <comment>  one line per matching dispatch: id, kernel, grid, duration (us)
+  persearch <dir> <out.txt> <first-kernel name filter> <comment>
+           the trace cut into searches at every dispatch of the search's first kernel: per position in the search the kernel,
+           its mean / min / max duration, the mean gap in front of it; the mean gap from the last kernel of a search to the
+           first of the next (one-time set-up kernels in front of the first search and the first search itself are left out)
   traffic  <fetch dir> <write dir> <out.json> rows dim dtype metric queries k <comment>
            per-kernel FETCH_SIZE / WRITE_SIZE per launch (KiB) and, for the streaming scan kernel, the corrected HBM
            bytes per launch (gfx950: FETCH_SIZE reports half of a wide coalesced streaming read -> x2; WRITE_SIZE exact;
@@ -51,6 +55,38 @@ def launches(d, out, flt, comment):
             w.writerow([r["Dispatch_Id"], r["Kernel_Name"], grid, wg,
                         r.get("VGPR_Count", ""), r.get("LDS_Block_Size", ""), round((int(r["Start_Timestamp"]) - t0) / 1e3, 3),
                         round((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3, 3)])
+
+
+def persearch(d, out, first, comment):
+    rows = sorted(_trace(d), key=lambda r: int(r["Start_Timestamp"]))
+    searches, cur = [], None
+    for r in rows:
+        if first in r["Kernel_Name"]:
+            cur = []
+            searches.append(cur)
+        if cur is not None:
+            cur.append((r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
+    searches = searches[1:]  # the first search builds norms and shadow between its kernels
+    shape = max(set(tuple(k for k, _, _ in s) for s in searches), key=lambda sh: sum(1 for s in searches if tuple(k for k, _, _ in s) == sh))
+    same = [s for s in searches if tuple(k for k, _, _ in s) == shape]
+    with open(out, "w") as fh:
+        fh.write(f"# {comment}\n# {len(same)} searches of {len(shape)} kernels (of {len(searches)} cut at '{first}'); us\n")
+        fh.write("  pos   mean_us    min_us    max_us  gap_in_front_us  kernel\n")
+        ksum = gsum = 0.0
+        for i, name in enumerate(shape):
+            du = [(s[i][2] - s[i][1]) / 1e3 for s in same]
+            gap = [(s[i][1] - s[i - 1][2]) / 1e3 for s in same] if i else [0.0]
+            ksum += sum(du) / len(du)
+            gsum += sum(gap) / len(gap)
+            short = name.split("(")[0].replace("mvf::", "")
+            fh.write(f"  {i:3d}  {sum(du) / len(du):8.2f}  {min(du):8.2f}  {max(du):8.2f}  {sum(gap) / len(gap):15.2f}  {short}\n")
+        between = [(b[0][1] - a[-1][2]) / 1e3 for a, b in zip(searches, searches[1:]) if tuple(k for k, _, _ in a) == shape and tuple(k for k, _, _ in b) == shape]
+        span = [(s[-1][2] - s[0][1]) / 1e3 for s in same]
+        period = [(b[0][1] - a[0][1]) / 1e3 for a, b in zip(searches, searches[1:]) if tuple(k for k, _, _ in a) == shape and tuple(k for k, _, _ in b) == shape]
+        fh.write(f"  sum of kernel durations {ksum:.2f}; sum of gaps inside a search {gsum:.2f}; first start to last end {sum(span) / len(span):.2f}\n")
+        if between:
+            fh.write(f"  gap from the last kernel of a search to the first of the next: mean {sum(between) / len(between):.2f} "
+                     f"(min {min(between):.2f}, max {max(between):.2f}); start-to-start period {sum(period) / len(period):.2f}\n")
 
 
 def _counter(d, name):
@@ -183,6 +219,8 @@ if __name__ == "__main__":
         stats(sys.argv[2], sys.argv[3], sys.argv[4])
     elif mode == "launches":
         launches(sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5])
+    elif mode == "persearch":
+        persearch(sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5])
     elif mode == "calibrate":
         calibrate(sys.argv[2], sys.argv[3], sys.argv[4])
     elif mode == "k2traffic":
