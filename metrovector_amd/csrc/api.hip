@@ -35,25 +35,6 @@ int fail(int status, const std::string& msg) {
     return status;
 }
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess)                                                                 \
-            return fail(MVF_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));   \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -139,7 +120,7 @@ Tuning read_tuning() {
 
 // search_host's request to the search it is about to enqueue: "store `seq` to `flag` behind your results if your last kernel
 // can" (the streaming path's final select); `armed` comes back true if it will.  Handed to search_device (below) explicitly and
-// kept in the handle (flag_req) while that call holds the handle's lock.
+// on to the routes in the search's SearchCall.
 struct HostFlagReq {
     uint32_t* flag;
     uint32_t* ticket;
@@ -197,7 +178,6 @@ struct mvfgpu_corpus {
     // under ONE end-of-call event, recorded when the last has been enqueued): such a search records an event of its own
     mutable hipEvent_t qs_redo_ev[2] = {nullptr, nullptr};  // created by the first search that needs one
     mutable bool qs_redo_own[2] = {false, false};
-    mutable bool one_search_call = false;  // the call being enqueued holds exactly one search (search_device; set and read under mu)
     mutable bool qs_redo_pending[2] = {false, false};
     mutable bool qs_disabled = false;
     mutable uint32_t qs_redo_nq[2] = {0, 0};
@@ -219,8 +199,6 @@ struct mvfgpu_corpus {
     mutable PinBuf pin_flag;
     mutable DevBuf done_ticket;
     mutable uint32_t flag_seq = 0;
-    mutable HostFlagReq* flag_req = nullptr;  // the host-buffer call's request to the search being enqueued (set and read under mu)
-    mutable bool positions_only = false;      // the search being enqueued reports index_base + row even where ids are attached (the join's: set and read under mu)
     mutable uint64_t work_gen = 0, confirmed_gen = ~0ull;  // searches enqueued on the handle / the newest one seen complete through the flag
     mutable PinBuf pin_q, pin_out, pin_vec;  // ... and its pinned host mirrors (small queries / results / payload rows: no copy engine at all)
     mutable DevBuf h_v;                   // payload rows of mvfgpu_search_fetch too large for that
@@ -237,10 +215,7 @@ struct mvfgpu_corpus {
     mutable uint32_t done_idx = 0;
     mutable hipStream_t last_stream = nullptr;
     mutable bool has_done = false;
-    // kernel launches the search being enqueued has made so far (mvfgpu_timing::search_launches), counted by the routes that
-    // know their launches: K1 on the stored rows or a shadow, the margin select, the K1-order re-scoring, the repair
-    mutable uint32_t launches = 0, search_launches = 0;
-    mutable bool launches_known = false;
+    mutable uint32_t search_launches = 0;  // kernel launches of the newest search (mvfgpu_timing::search_launches; SearchCall counts them)
 
     bool profiling = false;
     int scan_path = 0;
@@ -254,7 +229,6 @@ struct mvfgpu_corpus {
         bool ts_scan = false, ts_whole = false;
     };
     mutable DevBuf prof_ts;              // [kProfSlots][4] published times, then the pair the scan writes (block 0's start; the maximum of the blocks' ends, 0 when armed)
-    mutable bool whole_by_clock = false;  // the search being enqueued takes its whole-search time from prof_ts (set and read under mu)
     double wall_khz = 100000.0;           // ticks of the device's wall clock per millisecond
     static constexpr int kProfSlots = 64;
     mutable ProfSlot prof[kProfSlots];
@@ -291,10 +265,10 @@ void choose_group(uint32_t V, int nqv, int* G_out, uint32_t* J_out, int forced =
 int init_common(mvfgpu_corpus* c) {
     c->tune = mvf::read_tuning();
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, c->device));
+    MVF_HIP_TRY(hipGetDeviceProperties(&prop, c->device));
     c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    for (auto& e : c->ev_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    MVF_HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    for (auto& e : c->ev_done) MVF_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0) c->wall_khz = (double)khz;
     else (void)hipGetLastError();
@@ -318,7 +292,7 @@ int alloc_rows(mvfgpu_corpus* c) {
     c->V = c->pitch / 16;
     choose_group(c->V, 1, &c->G, &c->J, c->tune.k1_g);
     c->rows_bytes = (size_t)c->n * c->pitch;
-    if (c->rows_bytes) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rows), c->rows_bytes));
+    if (c->rows_bytes) MVF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rows), c->rows_bytes));
     return MVF_OK;
 }
 
@@ -326,8 +300,59 @@ int alloc_rows(mvfgpu_corpus* c) {
 // 128 until the counting loops got eight reads in flight: profiles/r04_k1_merge_ab.txt)
 constexpr uint32_t kK1RankMerge = 256;
 
+// One search: what was asked, how, and what it has launched so far.  Lives on the stack of search_device /
+// search_positions_locked and travels down the routes by reference; nothing of it outlasts the search.
+struct SearchCall {
+    // the request
+    uint8_t metric;
+    const void* d_queries;
+    uint32_t nq, k;
+    float* d_scores;
+    uint64_t* d_indices;
+    int32_t* d_raw;
+    hipStream_t stream;
+    // how
+    HostFlagReq* flag_req = nullptr;  // the host-buffer call's request to this search (NULL = none)
+    bool positions_only = false;      // report index_base + row even where vector ids are attached (the join's searches)
+    bool shared_call = false;         // the enclosing call may hold more searches than this one (the windows of a join)
+    bool whole_by_clock = false;      // a profiled search that takes its whole-search time from prof_ts, not from events
+    // kernel launches made so far (mvfgpu_timing::search_launches), counted by the routes that know their launches: K1 on the
+    // stored rows or a shadow, the margin select, the K1-order re-scoring, the repair
+    uint32_t launches = 0;
+    bool launches_known = true;
+};
+
+// A search inside `sc` for another k into other buffers (a shadow route's selection, a pass of a large k, one of two row
+// ranges): `route` runs on a copy changed so, and what it launches counts for `sc`.
+template <class Route>
+int inner_search(SearchCall& sc, uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, Route route) {
+    SearchCall in = sc;
+    in.k = k;
+    in.d_scores = d_scores;
+    in.d_indices = d_indices;
+    in.d_raw = d_raw;
+    const int rc = route(in);
+    sc.launches = in.launches;
+    sc.launches_known = in.launches_known;
+    return rc;
+}
+
 // the id table the final kernels of a search map local rows through (NULL = index_base + row)
-const uint64_t* result_ids(const mvfgpu_corpus* c) { return c->positions_only ? nullptr : static_cast<const uint64_t*>(c->ids.p); }
+const uint64_t* result_ids(const mvfgpu_corpus* c, const SearchCall& sc) {
+    return sc.positions_only ? nullptr : static_cast<const uint64_t*>(c->ids.p);
+}
+
+// Where a search's results go and in what form: the fields SelectParams, CompactParams and RescoreParams share.
+template <class P>
+void set_result_format(P& p, const mvfgpu_corpus* c, const SearchCall& sc) {
+    p.k = sc.k;
+    p.dtype = c->dtype;
+    p.index_base = c->index_base;
+    p.ids = result_ids(c, sc);
+    p.out_scores = sc.d_scores;
+    p.out_indices = sc.d_indices;
+    p.out_raw = sc.d_raw;
+}
 
 hipError_t scan_launch(uint8_t dtype, const ScanParams& p, int metric, int G, int nqv, dim3 grid, size_t lds,
                        hipStream_t s) {
@@ -348,16 +373,59 @@ const void* scan_kernel(uint8_t dtype, int metric, int G, int nqv, bool redo = f
     }
 }
 
-// The lane-group width G, steps J and queries per pass K1 takes on the STORED rows for a search of nq <= 4 queries at k
-// (search_stream_path's rule: one query alone, two to four in one four-query pass unless its LDS does not fit).
-void k1_stored_group(const mvfgpu_corpus* c, uint32_t nq, uint32_t k, int* G, uint32_t* J, int* nqv_out) {
-    int nqv = nq >= 2 ? 4 : 1;
-    choose_group(c->V, nqv, G, J, c->tune.k1_g);
-    if (nqv == 4 && scan_lds_bytes(c->dtype, *G, *J, nqv, next_pow2(k + scan_chunk_safe(*G))) > 150 * 1024) {
-        nqv = 1;
-        choose_group(c->V, nqv, G, J, c->tune.k1_g);
+// The shape of a pass of K1 (k1_pass_shape, internal.h) with `queries` queries left at list length k over rows of V vectors
+// of type `dtype`: the STORED rows unless the caller names a shadow's.
+K1Shape k1_shape(const mvfgpu_corpus* c, uint32_t queries, uint32_t k, uint32_t V, uint8_t dtype) {
+    return k1_pass_shape(V, queries, k, c->tune.k1_g,
+                         [dtype](int G, uint32_t J, int nqv, uint32_t pmax) { return scan_lds_bytes(dtype, G, J, nqv, pmax); });
+}
+K1Shape k1_shape(const mvfgpu_corpus* c, uint32_t queries, uint32_t k) { return k1_shape(c, queries, k, c->V, c->dtype); }
+int k1_shape_fits(const K1Shape& sh) {
+    if (sh.lds > 160 * 1024) return fail(MVF_ERR_BUILD, "dimension too large for the streaming kernel's LDS query tile");
+    return MVF_OK;
+}
+
+// K1's parameters for a pass of shape `sh` over the STORED rows (a shadow route overrides the rows), `nchunks` chunks of
+// sh.chunk_rows rows, the blocks' lists going to `cand`.
+ScanParams stored_scan_params(const mvfgpu_corpus* c, const SearchCall& sc, const K1Shape& sh, uint32_t nchunks, uint64_t* cand) {
+    ScanParams sp{};
+    sp.rows = c->d_rows;
+    sp.queries = sc.d_queries;
+    sp.tomb = static_cast<const uint32_t*>(c->tomb.p);
+    sp.cand = cand;
+    sp.n = (uint32_t)c->n;
+    sp.pitch = c->pitch;
+    sp.dim = c->dim;
+    sp.V = c->V;
+    sp.J = sh.J;
+    sp.nq_total = sc.nq;
+    sp.k = sc.k;
+    sp.kcap = next_pow2(sc.k);
+    sp.pmax = sh.pmax;
+    sp.chunk_rows = sh.chunk_rows;
+    sp.chunk_safe = std::min(scan_chunk_safe(sh.G), sh.chunk_rows);
+    {
+        const uint32_t step = 16u * 64u / (uint32_t)sh.G, want = std::max(sc.k, 64u);
+        // (not under the long chunks of short rows: a threshold from 128 rows lets too many of the next 4000 through --
+        // 4 GB of <= 128-byte rows at k = 100 lost 5-8 %, profiles/r04_k1_first_piece_ab.txt)
+        sp.first_piece = sh.chunk_rows <= scan_chunk_safe(sh.G) ? std::min(sp.chunk_safe, (want + step - 1) / step * step) : sp.chunk_safe;
     }
-    *nqv_out = nqv;
+    sp.nchunks = nchunks;
+    sp.rank_merge_max = kK1RankMerge;
+    return sp;
+}
+
+// select_final's parameters behind such a pass: `nlists` lists per query at `lists`, merged and formatted as the search asks
+SelectParams final_select_params(const mvfgpu_corpus* c, const SearchCall& sc, const uint64_t* lists, uint32_t nlists) {
+    SelectParams fp{};
+    fp.lists = lists;
+    fp.nlists = nlists;
+    fp.kcap = next_pow2(sc.k);
+    fp.heads = nlists ? (sc.k + nlists - 1) / nlists : 1;
+    fp.P = 4096;  // 32 KiB of LDS: >= k + kcap (fold path) and >= nlists*heads (nlists <= 2048)
+    fp.metric = sc.metric;
+    set_result_format(fp, c, sc);
+    return fp;
 }
 
 // Streaming over the scaled-f16 shadow of a Float32 corpus (scan path 4): K1 reads the shadow rows instead of the stored
@@ -401,9 +469,9 @@ int scan_occupancy(const mvfgpu_corpus* c, const void* kfn, size_t lds, int* occ
         }
     // the attribute is only ever RAISED: to the part's ceiling, once per kernel and handle (set to this miss's size, a later hit at a
     // larger size the cache already knew would launch above it -- a runtime that enforces the attribute would refuse the launch)
-    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (lds > 48 * 1024) MVF_HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     int occ = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, 256, lds));
+    MVF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, 256, lds));
     if (occ < 1) occ = 1;
     if (c->occ_cache.size() < 64) c->occ_cache.emplace_back(key, occ);
     *occ_out = occ;
@@ -415,9 +483,9 @@ int scan_occupancy(const mvfgpu_corpus* c, const void* kfn, size_t lds, int* occ
 int prof_ts_ensure(const mvfgpu_corpus* c, hipStream_t s) {
     if (c->prof_ts.p) return MVF_OK;
     const size_t words = (size_t)mvfgpu_corpus::kProfSlots * 4 + 2;
-    HIP_TRY(c->prof_ts.reserve(words * 8));
-    HIP_TRY(hipMemsetAsync(c->prof_ts.p, 0, words * 8, s));
-    HIP_TRY(hipMemsetAsync(static_cast<uint64_t*>(c->prof_ts.p) + words - 2, 0xFF, 8, s));
+    MVF_HIP_TRY(c->prof_ts.reserve(words * 8));
+    MVF_HIP_TRY(hipMemsetAsync(c->prof_ts.p, 0, words * 8, s));
+    MVF_HIP_TRY(hipMemsetAsync(static_cast<uint64_t*>(c->prof_ts.p) + words - 2, 0xFF, 8, s));
     return MVF_OK;
 }
 uint64_t* prof_ts_entry(const mvfgpu_corpus* c, uint64_t search) {
@@ -425,14 +493,16 @@ uint64_t* prof_ts_entry(const mvfgpu_corpus* c, uint64_t search) {
 }
 uint64_t* prof_ts_work(const mvfgpu_corpus* c) { return static_cast<uint64_t*>(c->prof_ts.p) + (size_t)mvfgpu_corpus::kProfSlots * 4; }
 
-int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
-                       float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s, bool profile = true,
-                       const ShadowStream* alt = nullptr, const uint64_t* floor1 = nullptr, uint64_t* out_floor1 = nullptr,
-                       uint32_t out_stride = 0, uint32_t out_offset = 0, const RankAll* rank = nullptr) {
+int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = true, const ShadowStream* alt = nullptr,
+                       const uint64_t* floor1 = nullptr, uint64_t* out_floor1 = nullptr, uint32_t out_stride = 0,
+                       uint32_t out_offset = 0, const RankAll* rank = nullptr) {
     // floor1 / out_floor1 / out_stride / out_offset: one pass of a k > MVFGPU_K_PER_PASS search (search_large_k)
     // rank: the whole-shard sort (search_sorted_k) -- the scan DUMPS every row's composite, the selection kernel is replaced
     // by a device-wide sort of each query's n composites + the formatting of its first k_out; `k` is then only the (small)
     // list length the kernel's LDS layout is sized for
+    const uint8_t metric = sc.metric;
+    const uint32_t nq = sc.nq, k = sc.k;
+    hipStream_t s = sc.stream;
     const uint32_t kcap = next_pow2(k);
     const uint32_t ostride = out_stride ? out_stride : k;
     const bool alt8 = alt && alt->i8;
@@ -447,7 +517,7 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
     if (c->profiling && profile) {
         ps = &c->prof[c->prof_next % mvfgpu_corpus::kProfSlots];
         for (auto& e : ps->e)
-            if (!e) HIP_TRY(hipEventCreate(&e));
+            if (!e) MVF_HIP_TRY(hipEventCreate(&e));
         ps->scanned = false;
         ps->ts_scan = false;
         if (!rank) {  // a select_final follows the scan: the pair times itself
@@ -459,21 +529,13 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
     }
 
     for (uint32_t q0 = 0; q0 < nq;) {
-        int nqv = (nq - q0) >= 2 && (!alt || alt8) && !(rank && rank->nqv == 1) ? 4 : 1;
-        int G;
-        uint32_t J;
-        choose_group(kV, nqv, &G, &J, c->tune.k1_g);  // the lane-group width depends on the queries per pass
-        uint32_t chunk_rows = scan_chunk_rows(G, J, nqv), pmax = next_pow2(k + scan_chunk_safe(G));
-        size_t lds = scan_lds_bytes(kdtype, G, J, nqv, pmax);
-        if (nqv == 4 && lds > 150 * 1024) {
-            nqv = 1;
-            choose_group(kV, nqv, &G, &J, c->tune.k1_g);
-            chunk_rows = scan_chunk_rows(G, J, nqv);
-            pmax = next_pow2(k + scan_chunk_safe(G));
-            lds = scan_lds_bytes(kdtype, G, J, nqv, pmax);
-        }
+        // (the f16 shadow's unit and a one-query dump take one query per pass)
+        K1Shape sh = k1_shape(c, (!alt || alt8) && !(rank && rank->nqv == 1) ? nq - q0 : 1u, k, kV, kdtype);
+        const int G = sh.G, nqv = sh.nqv;
+        const size_t lds = sh.lds;
+        uint32_t& chunk_rows = sh.chunk_rows;  // (the small-corpus rule below may shorten it)
         uint32_t nchunks = (uint32_t)((c->n + chunk_rows - 1) / chunk_rows);
-        if (lds > 160 * 1024) return fail(MVF_ERR_BUILD, "dimension too large for the streaming kernel's LDS query tile");
+        if (const int frc = k1_shape_fits(sh)) return frc;
         uint32_t nq_here = std::min<uint32_t>(nqv, nq - q0);
         uint32_t npass = 1;  // passes of nqv queries in this launch (grid.y)
 
@@ -522,12 +584,15 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
                 npass = std::min<uint32_t>(8u, (nq - q0 + 3u) / 4u);
                 nq_here = std::min<uint32_t>(npass * 4u, nq - q0);
             }
-            HIP_TRY(c->cand.reserve((size_t)npass * nqv * nblocks * kcap * 8));
+            MVF_HIP_TRY(c->cand.reserve((size_t)npass * nqv * nblocks * kcap * 8));
 
-            ScanParams sp{};
-            sp.rows = alt ? alt->rows : c->d_rows;
-            sp.xscale = alt ? alt->xscale : nullptr;
-            sp.queries = d_queries;
+            ScanParams sp = stored_scan_params(c, sc, sh, nchunks, static_cast<uint64_t*>(c->cand.p));
+            if (alt) {  // the shadow's rows instead
+                sp.rows = alt->rows;
+                sp.xscale = alt->xscale;
+                sp.pitch = alt->pitch;
+                sp.V = alt->V;
+            }
             if (alt8) {
                 sp.qaux0 = alt->qaux0;
                 sp.qaux1 = alt->qaux1;
@@ -536,37 +601,16 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
                 sp.xxmax = alt->xxmax;
                 sp.xrow = alt->xrow;
             }
-            sp.tomb = static_cast<const uint32_t*>(c->tomb.p);
-            sp.cand = static_cast<uint64_t*>(c->cand.p);
-            sp.n = (uint32_t)c->n;
-            sp.pitch = alt ? alt->pitch : c->pitch;
-            sp.dim = c->dim;
-            sp.V = alt ? alt->V : c->V;
-            sp.J = J;
             sp.q0 = q0;
-            sp.nq_total = nq;
-            sp.k = k;
-            sp.kcap = kcap;
-            sp.pmax = pmax;
-            sp.chunk_rows = chunk_rows;
-            sp.chunk_safe = std::min(scan_chunk_safe(G), chunk_rows);
-            {
-                const uint32_t step = 16u * 64u / (uint32_t)G, want = std::max(k, 64u);
-                // (not under the long chunks of short rows: a threshold from 128 rows lets too many of the next 4000 through --
-                // 4 GB of <= 128-byte rows at k = 100 lost 5-8 %, profiles/r04_k1_first_piece_ab.txt)
-                sp.first_piece = chunk_rows <= scan_chunk_safe(G) ? std::min(sp.chunk_safe, (want + step - 1) / step * step) : sp.chunk_safe;
-            }
-            sp.nchunks = nchunks;
-            sp.rank_merge_max = kK1RankMerge;
             sp.floor1 = floor1;
             sp.dump = rank ? rank->a : nullptr;
             if (ps && first && ts_work) sp.ts = ts_work;
-            else if (ps && first) HIP_TRY(hipEventRecord(ps->e[0], s));
-            if (alt8) HIP_TRY(scan_stream_launch_dt2x(sp, metric, G, nqv, dim3(nblocks), lds, s));
-            else if (alt) HIP_TRY(scan_stream_launch_dt1x(sp, metric, G, nqv, dim3(nblocks), lds, s));
-            else HIP_TRY(scan_launch(c->dtype, sp, metric, G, nqv, dim3(nblocks, npass), lds, s));
+            else if (ps && first) MVF_HIP_TRY(hipEventRecord(ps->e[0], s));
+            if (alt8) MVF_HIP_TRY(scan_stream_launch_dt2x(sp, metric, G, nqv, dim3(nblocks), lds, s));
+            else if (alt) MVF_HIP_TRY(scan_stream_launch_dt1x(sp, metric, G, nqv, dim3(nblocks), lds, s));
+            else MVF_HIP_TRY(scan_launch(c->dtype, sp, metric, G, nqv, dim3(nblocks, npass), lds, s));
             if (ps && first) {
-                if (!ts_work) HIP_TRY(hipEventRecord(ps->e[1], s));
+                if (!ts_work) MVF_HIP_TRY(hipEventRecord(ps->e[1], s));
                 ps->scanned = true;
                 ps->ts_scan = ts_work != nullptr;
                 tm.scan_bytes = (uint64_t)c->n * c->dim * elem_size(kdtype);
@@ -574,38 +618,23 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
                 if (npass > 1) tm.scan_bytes *= npass;
             }
             tm.scan_launches++;
-            c->launches++;
+            sc.launches++;
         }
         if (rank) {  // every row of these queries is ranked: sort each query's n composites, format the first k_out
             SelectParams fp{};
-            fp.k = rank->k_out;
             fp.metric = metric;
-            fp.dtype = c->dtype;
-            fp.index_base = c->index_base;
-            fp.ids = result_ids(c);
-            fp.out_scores = d_scores;
-            fp.out_indices = d_indices;
-            fp.out_raw = d_raw;
+            set_result_format(fp, c, sc);
+            fp.k = rank->k_out;
             uint64_t* sorted = rank->a;
             if (c->n > 0) {  // the pass's queries in one set of launches
                 size_t tb = rank->tmp_bytes;
-                HIP_TRY(sort_composites(rank->tmp, &tb, rank->a, rank->b, (size_t)c->n, (size_t)rank->k_out, &sorted, s, nq_here, (size_t)c->n));
+                MVF_HIP_TRY(sort_composites(rank->tmp, &tb, rank->a, rank->b, (size_t)c->n, (size_t)rank->k_out, &sorted, s, nq_here, (size_t)c->n));
             }
             for (uint32_t q = 0; q < nq_here; q++)
-                HIP_TRY(launch_write_sorted(fp, sorted + (size_t)q * c->n, (uint32_t)c->n, (size_t)(q0 + q) * rank->k_out, s));
-            c->launches_known = false;  // (the device-wide sort's launches are its own business)
+                MVF_HIP_TRY(launch_write_sorted(fp, sorted + (size_t)q * c->n, (uint32_t)c->n, (size_t)(q0 + q) * rank->k_out, s));
+            sc.launches_known = false;  // (the device-wide sort's launches are its own business)
         } else {
-            SelectParams fp{};
-            fp.lists = static_cast<const uint64_t*>(c->cand.p);
-            fp.nlists = nblocks;
-            fp.kcap = kcap;
-            fp.heads = nblocks ? (k + nblocks - 1) / nblocks : 1;
-            fp.P = 4096;  // 32 KiB of LDS: >= k + kcap (fold path) and >= nlists*heads (nlists <= 2048)
-            fp.k = k;
-            fp.metric = metric;
-            fp.dtype = c->dtype;
-            fp.index_base = c->index_base;
-            fp.ids = result_ids(c);
+            SelectParams fp = final_select_params(c, sc, static_cast<const uint64_t*>(c->cand.p), nblocks);
             if (alt) {
                 fp.out_cand = alt->cand + (size_t)q0 * alt->cand_cap;
                 fp.out_cnt = alt->cnt + q0;
@@ -618,35 +647,36 @@ int search_stream_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_que
                     fp.margin_rank = alt->rank_k;
                 }
             } else {
-                fp.out_scores = d_scores + (size_t)q0 * ostride;
-                fp.out_indices = d_indices + (size_t)q0 * ostride;
-                fp.out_raw = d_raw ? d_raw + (size_t)q0 * ostride : nullptr;
+                fp.out_scores = sc.d_scores + (size_t)q0 * ostride;
+                fp.out_indices = sc.d_indices + (size_t)q0 * ostride;
+                fp.out_raw = sc.d_raw ? sc.d_raw + (size_t)q0 * ostride : nullptr;
                 fp.out_stride = out_stride;
                 fp.out_offset = out_offset;
                 fp.out_floor1 = out_floor1 ? out_floor1 + q0 : nullptr;
-                if (c->flag_req && !out_floor1 && c->flag_req->gather_out && !c->ids.p) {  // payload rows behind the results, by the same block
+                HostFlagReq* req = out_floor1 ? nullptr : sc.flag_req;
+                if (req && req->gather_out && !c->ids.p) {  // payload rows behind the results, by the same block
                     fp.gather_rows = c->d_rows;
-                    fp.gather_out = c->flag_req->gather_out + (size_t)q0 * ostride * (c->dim * elem_size(c->dtype));
+                    fp.gather_out = req->gather_out + (size_t)q0 * ostride * (c->dim * elem_size(c->dtype));
                     fp.gather_pitch = c->pitch;
                     fp.gather_row_bytes = c->dim * elem_size(c->dtype);
-                    if (q0 + nq_here == nq) c->flag_req->gathered = true;
+                    if (q0 + nq_here == nq) req->gathered = true;
                 }
-                if (c->flag_req && !out_floor1 && q0 + nq_here == nq) {  // the search's last kernel
-                    fp.done_flag = c->flag_req->flag;
-                    fp.done_ticket = c->flag_req->ticket;
-                    fp.done_seq = c->flag_req->seq;
-                    c->flag_req->armed = true;
+                if (req && q0 + nq_here == nq) {  // the search's last kernel
+                    fp.done_flag = req->flag;
+                    fp.done_ticket = req->ticket;
+                    fp.done_seq = req->seq;
+                    req->armed = true;
                 }
             }
             if (ps && first && ps->ts_scan) {
                 fp.ts_work = ts_work;
                 fp.ts_out = ts_entry;
             }
-            if (ps && ts_entry && c->whole_by_clock && !alt && q0 + nq_here == nq) fp.ts_end = ts_entry + 3;  // the search's last kernel
-            HIP_TRY(launch_select_final(fp, nq_here, s));
-            c->launches++;
+            if (ps && ts_entry && sc.whole_by_clock && !alt && q0 + nq_here == nq) fp.ts_end = ts_entry + 3;  // the search's last kernel
+            MVF_HIP_TRY(launch_select_final(fp, nq_here, s));
+            sc.launches++;
         }
-        if (ps && first && !ps->ts_scan) HIP_TRY(hipEventRecord(ps->e[2], s));
+        if (ps && first && !ps->ts_scan) MVF_HIP_TRY(hipEventRecord(ps->e[2], s));
         first = false;
         q0 += nq_here;
     }
@@ -821,6 +851,23 @@ void record_done(const mvfgpu_corpus* c, hipStream_t s) {
     }
 }
 
+// The discipline of every call that enqueues work of a handle on a caller's stream: under the handle's lock, `s` ordered
+// behind the handle's newest work on another stream (the scratch buffers are stream-ordered), and -- whatever `body` returns,
+// work may already sit on the stream (norms, a shadow build, scratch) -- ev_done recorded on `s` on every way out, for the
+// next call on ANOTHER stream to order itself behind.
+template <class Body>
+int device_call(const mvfgpu_corpus* c, hipStream_t s, Body&& body) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->work_gen++;
+    if (c->has_done && c->last_stream != s) MVF_HIP_TRY(hipStreamWaitEvent(s, c->ev_done[c->done_idx], 0));
+    struct DoneGuard {
+        const mvfgpu_corpus* c;
+        hipStream_t s;
+        ~DoneGuard() { record_done(c, s); }
+    } done_guard{c, s};
+    return body();
+}
+
 // What the search before the previous one had to repair (its count was copied to pinned memory behind it; waited for
 // here -- by now it is two searches old -- so the decision does not depend on timing).
 void qs_feedback_poll(const mvfgpu_corpus* c) {
@@ -841,7 +888,7 @@ void qs_feedback_poll(const mvfgpu_corpus* c) {
 
 int feedback_slots(const mvfgpu_corpus* c) {
     if (c->qs_redo_host) return MVF_OK;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->qs_redo_host), 64, hipHostMallocDefault));
+    MVF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->qs_redo_host), 64, hipHostMallocDefault));
     return MVF_OK;
 }
 
@@ -858,7 +905,8 @@ uint32_t* feedback_mirror(const mvfgpu_corpus* c) {
 // ... and the request for it: the repair count of the search just enqueued, in pinned memory behind the event its call
 // records on the way out (record_done) where the call holds this search alone (search_device), behind an event of the
 // search's own otherwise (the windows of a join).
-int qs_feedback_post(const mvfgpu_corpus* c, uint32_t nq, hipStream_t s, bool used_bias = false, bool used_qs = true) {
+int qs_feedback_post(const mvfgpu_corpus* c, const SearchCall& sc, bool used_bias = false, bool used_qs = true) {
+    hipStream_t s = sc.stream;
     const uint32_t sl = c->qs_slot;
     if (c->qs_redo_pending[sl] || !c->repair.p) return MVF_OK;  // (pending: this search did not poll -- it took another path first)
     {
@@ -868,17 +916,17 @@ int qs_feedback_post(const mvfgpu_corpus* c, uint32_t nq, hipStream_t s, bool us
     c->fb_bias[sl] = used_bias;
     c->fb_qs[sl] = used_qs;
     if (c->fb_mirrored != c->qs_redo_host + sl)  // (the repair pass could not store it there itself)
-        HIP_TRY(hipMemcpyAsync(c->qs_redo_host + sl, c->last_redo_cnt, 4, hipMemcpyDeviceToHost, s));
+        MVF_HIP_TRY(hipMemcpyAsync(c->qs_redo_host + sl, c->last_redo_cnt, 4, hipMemcpyDeviceToHost, s));
     c->fb_mirrored = nullptr;
-    c->qs_redo_own[sl] = !c->one_search_call;
+    c->qs_redo_own[sl] = sc.shared_call;
     if (c->qs_redo_own[sl]) {  // more searches follow in this call: the end-of-call event comes too late for their polls
-        if (!c->qs_redo_ev[sl]) HIP_TRY(hipEventCreateWithFlags(&c->qs_redo_ev[sl], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->qs_redo_ev[sl], s));
+        if (!c->qs_redo_ev[sl]) MVF_HIP_TRY(hipEventCreateWithFlags(&c->qs_redo_ev[sl], hipEventDisableTiming));
+        MVF_HIP_TRY(hipEventRecord(c->qs_redo_ev[sl], s));
     } else {
         c->qs_redo_done[sl] = c->done_idx ^ 1u;
     }
     c->qs_redo_pending[sl] = true;
-    c->qs_redo_nq[sl] = nq;
+    c->qs_redo_nq[sl] = sc.nq;
     c->qs_slot = sl ^ 1u;
     return MVF_OK;
 }
@@ -952,11 +1000,38 @@ bool qs_refine_enabled(const mvfgpu_corpus* c) { return c->tune.qs_refine; }
 // at the head of the list and the worst exact key among them), armed once and re-armed by the kernels that end a search.
 int ensure_bstate(const mvfgpu_corpus* c, uint32_t nq_pad, hipStream_t s) {
     if (c->bstate_slots >= nq_pad) return MVF_OK;
-    HIP_TRY(c->bstate.reserve((size_t)nq_pad * 20));
-    HIP_TRY(hipMemsetAsync(c->bstate.p, 0xFF, (size_t)nq_pad * 4, s));                                                     // tau
-    HIP_TRY(hipMemsetAsync(static_cast<unsigned char*>(c->bstate.p) + (size_t)nq_pad * 4, 0, (size_t)nq_pad * 16, s));  // cnt, overflow, ntop, lkey
+    MVF_HIP_TRY(c->bstate.reserve((size_t)nq_pad * 20));
+    MVF_HIP_TRY(hipMemsetAsync(c->bstate.p, 0xFF, (size_t)nq_pad * 4, s));                                                     // tau
+    MVF_HIP_TRY(hipMemsetAsync(static_cast<unsigned char*>(c->bstate.p) + (size_t)nq_pad * 4, 0, (size_t)nq_pad * 16, s));  // cnt, overflow, ntop, lkey
     c->bstate_slots = nq_pad;
     return MVF_OK;
+}
+
+struct BState {
+    uint32_t *tau, *cnt, *overflow, *ntop, *lkey;  // [bstate_slots] each
+};
+BState bstate_view(const mvfgpu_corpus* c) {
+    uint32_t* tau = static_cast<uint32_t*>(c->bstate.p);
+    const uint32_t n = c->bstate_slots;
+    return BState{tau, tau + n, tau + 2 * n, tau + 3 * n, tau + 4 * n};
+}
+
+// The re-scoring kernels' view of a search: the candidate lists (`cap` slots per query at `cand`) and their state, the
+// caller's f32 queries, the stored rows; `final`: the pass that formats the results as well.
+RescoreParams rescore_params(const mvfgpu_corpus* c, const SearchCall& sc, uint64_t* cand, uint32_t cap, const BState& bs, bool final) {
+    RescoreParams rp{};
+    if (final) set_result_format(rp, c, sc);
+    rp.cand = cand;
+    rp.cnt = bs.cnt;
+    rp.tau = bs.tau;
+    rp.cap = cap;
+    rp.k = sc.k;
+    rp.queries = static_cast<const float*>(sc.d_queries);
+    rp.rows = c->d_rows;
+    rp.pitch = c->pitch;
+    rp.dim = c->dim;
+    rp.dtype = c->dtype;
+    return rp;
 }
 
 // K4: per-row norms of the STORED rows, once per resident corpus (a shadow only feeds the dot products).
@@ -972,12 +1047,12 @@ int ensure_norms(const mvfgpu_corpus* c, hipStream_t s) {
     if (c->xnorm_ready) return MVF_OK;
     const uint32_t n = (uint32_t)c->n;
     const size_t nn = norm_stride(n);
-    HIP_TRY(c->xnorm.reserve((norm_max_at(n) + 1) * 4));
+    MVF_HIP_TRY(c->xnorm.reserve((norm_max_at(n) + 1) * 4));
     float* xn = static_cast<float*>(c->xnorm.p);
     float* xmax = xn + norm_max_at(n);
-    if (!is_int_dtype(c->dtype)) HIP_TRY(hipMemsetAsync(xmax, 0, 4, s));
-    if (c->dtype == MVF_DTYPE_FLOAT32) HIP_TRY(launch_row_norms_f32(c->d_rows, n, c->pitch, xn, xn + nn, xmax, s));
-    else HIP_TRY(launch_row_norms16(c->d_rows, c->dtype, n, c->pitch, c->dim, c->xnorm.p, xn + nn, xmax, s));
+    if (!is_int_dtype(c->dtype)) MVF_HIP_TRY(hipMemsetAsync(xmax, 0, 4, s));
+    if (c->dtype == MVF_DTYPE_FLOAT32) MVF_HIP_TRY(launch_row_norms_f32(c->d_rows, n, c->pitch, xn, xn + nn, xmax, s));
+    else MVF_HIP_TRY(launch_row_norms16(c->d_rows, c->dtype, n, c->pitch, c->dim, c->xnorm.p, xn + nn, xmax, s));
     c->xnorm_ready = true;
     return MVF_OK;
 }
@@ -997,34 +1072,21 @@ int ensure_norms(const mvfgpu_corpus* c, hipStream_t s) {
 // launch of flag_compact_kernel spared.
 struct RepairPlan {
     bool any = false;  // an empty corpus has nothing to repair
-    int nqv = 4, G = 64;
-    uint32_t J = 0, kcap = 0, chunk_rows = 0, pmax = 0, nchunks = 0, nblocks = 0, R = 0;
-    size_t lds = 0;
+    K1Shape sh;        // of the repair passes over the stored rows
+    uint32_t nchunks = 0, nblocks = 0, R = 0;
     uint64_t* lists = nullptr;
     uint32_t *redo_cnt = nullptr, *redo_list = nullptr;
 };
-int plan_repair(const mvfgpu_corpus* c, uint8_t metric, uint32_t nq, uint32_t k, int nqv_want, RepairPlan* rp) {
+int plan_repair(const mvfgpu_corpus* c, const SearchCall& sc, int nqv_want, RepairPlan* rp) {
     *rp = RepairPlan{};
     if (c->n == 0) return MVF_OK;
-    const uint32_t kcap = next_pow2(k);
-    int nqv = nqv_want == 1 ? 1 : 4, G;
-    uint32_t J;
-    choose_group(c->V, nqv, &G, &J, c->tune.k1_g);
-    uint32_t chunk_rows = scan_chunk_rows(G, J, nqv), pmax = next_pow2(k + scan_chunk_safe(G));
-    size_t lds = scan_lds_bytes(c->dtype, G, J, nqv, pmax);
-    if (nqv == 4 && lds > 150 * 1024) {
-        nqv = 1;
-        choose_group(c->V, nqv, &G, &J, c->tune.k1_g);
-        chunk_rows = scan_chunk_rows(G, J, nqv);
-        pmax = next_pow2(k + scan_chunk_safe(G));
-        lds = scan_lds_bytes(c->dtype, G, J, nqv, pmax);
-    }
-    const uint32_t nchunks = (uint32_t)((c->n + chunk_rows - 1) / chunk_rows);
-    if (lds > 160 * 1024) return fail(MVF_ERR_BUILD, "dimension too large for the streaming kernel's LDS query tile");
-    const void* kfn = scan_kernel(c->dtype, metric, G, nqv, /*redo=*/true);
+    const K1Shape sh = k1_shape(c, nqv_want == 1 ? 1u : 4u, sc.k);
+    const uint32_t nchunks = (uint32_t)((c->n + sh.chunk_rows - 1) / sh.chunk_rows);
+    if (const int frc = k1_shape_fits(sh)) return frc;
+    const void* kfn = scan_kernel(c->dtype, sc.metric, sh.G, sh.nqv, /*redo=*/true);
     int occ = 1;
     {
-        const int orc = scan_occupancy(c, kfn, lds, &occ);
+        const int orc = scan_occupancy(c, kfn, sh.lds, &occ);
         if (orc != MVF_OK) return orc;
     }
     // Two blocks per CU at most: the repair is rare, and every block's list costs scratch for EVERY query a launch pair may
@@ -1034,21 +1096,15 @@ int plan_repair(const mvfgpu_corpus* c, uint8_t metric, uint32_t nq, uint32_t k,
     // while the cap was 256).
     // (a one-query repair -- nqv_want = 1, one search's single flagged query -- keeps K1's full grid: its lists are few)
     const uint32_t nblocks = std::min<uint32_t>(nchunks, (uint32_t)(nqv_want == 1 ? occ : std::min(occ, 2)) * (uint32_t)c->num_cus);
-    const size_t per_query = (size_t)nblocks * kcap * 8;
+    const size_t per_query = (size_t)nblocks * next_pow2(sc.k) * 8;
     uint32_t R = (uint32_t)std::min<size_t>(4096, std::max<size_t>(4, ((size_t)256 << 20) / per_query));
     if (c->tune.repair_window) R = std::min<uint32_t>(R, std::max<uint32_t>(4, c->tune.repair_window));  // tests: several windows on small batches
-    HIP_TRY(c->repair.reserve((size_t)R * per_query + (size_t)nq * 4 + 16));
+    MVF_HIP_TRY(c->repair.reserve((size_t)R * per_query + (size_t)sc.nq * 4 + 16));
     rp->any = true;
-    rp->nqv = nqv;
-    rp->G = G;
-    rp->J = J;
-    rp->kcap = kcap;
-    rp->chunk_rows = chunk_rows;
-    rp->pmax = pmax;
+    rp->sh = sh;
     rp->nchunks = nchunks;
     rp->nblocks = nblocks;
     rp->R = R;
-    rp->lds = lds;
     rp->lists = static_cast<uint64_t*>(c->repair.p);
     rp->redo_cnt = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(c->repair.p) + (size_t)R * per_query);
     rp->redo_list = rp->redo_cnt + 4;
@@ -1056,83 +1112,42 @@ int plan_repair(const mvfgpu_corpus* c, uint8_t metric, uint32_t nq, uint32_t k,
 }
 
 // compacted != NULL: the caller's last kernel has compacted the flags into that plan's list already
-int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t nq_pad,
-                           uint32_t k, uint32_t* overflow, float* d_scores, uint64_t* d_indices, int32_t* d_raw,
-                           hipStream_t s, int nqv_want = 4, const RepairPlan* compacted = nullptr, uint64_t* ts_end = nullptr) {
+int repair_flagged_queries(const mvfgpu_corpus* c, SearchCall& sc, uint32_t* overflow, int nqv_want = 4,
+                           const RepairPlan* compacted = nullptr, uint64_t* ts_end = nullptr) {
     // ts_end: the last select of the last window is the last kernel of a profiled search on the streamed-shadow route
-    (void)nq_pad;
     RepairPlan own;
     if (!compacted) {
-        const int prc = plan_repair(c, metric, nq, k, nqv_want, &own);
+        const int prc = plan_repair(c, sc, nqv_want, &own);
         if (prc != MVF_OK) return prc;
     }
     const RepairPlan& pl = compacted ? *compacted : own;
     if (!pl.any) return MVF_OK;
-    const int nqv = pl.nqv, G = pl.G;
-    const uint32_t J = pl.J, kcap = pl.kcap, chunk_rows = pl.chunk_rows, pmax = pl.pmax, nchunks = pl.nchunks, nblocks = pl.nblocks, R = pl.R;
-    const size_t lds = pl.lds;
-    uint64_t* lists = pl.lists;
-    uint32_t *redo_cnt = pl.redo_cnt, *redo_list = pl.redo_list;
+    hipStream_t s = sc.stream;
     if (!compacted) {
-        HIP_TRY(launch_flag_compact(overflow, nq, redo_list, redo_cnt, feedback_mirror(c), s));
-        c->launches++;
+        MVF_HIP_TRY(launch_flag_compact(overflow, sc.nq, pl.redo_list, pl.redo_cnt, feedback_mirror(c), s));
+        sc.launches++;
     }
-    c->last_redo_cnt = redo_cnt;
-    for (uint32_t base = 0; base < nq; base += R) {
-        ScanParams sp{};
-        sp.rows = c->d_rows;
-        sp.queries = d_queries;
-        sp.tomb = static_cast<const uint32_t*>(c->tomb.p);
-        sp.cand = lists;
-        sp.n = (uint32_t)c->n;
-        sp.pitch = c->pitch;
-        sp.dim = c->dim;
-        sp.V = c->V;
-        sp.J = J;
-        sp.q0 = 0;
-        sp.nq_total = nq;
-        sp.k = k;
-        sp.kcap = kcap;
-        sp.pmax = pmax;
-        sp.chunk_rows = chunk_rows;
-        sp.chunk_safe = std::min(scan_chunk_safe(G), chunk_rows);
-        {
-            const uint32_t step = 16u * 64u / (uint32_t)G, want = std::max(k, 64u);
-            sp.first_piece = chunk_rows <= scan_chunk_safe(G) ? std::min(sp.chunk_safe, (want + step - 1) / step * step) : sp.chunk_safe;
-        }
-        sp.nchunks = nchunks;
-        sp.rank_merge_max = kK1RankMerge;
-        sp.redo_list = redo_list;
-        sp.redo_cnt = redo_cnt;
+    c->last_redo_cnt = pl.redo_cnt;
+    for (uint32_t base = 0; base < sc.nq; base += pl.R) {
+        ScanParams sp = stored_scan_params(c, sc, pl.sh, pl.nchunks, pl.lists);
+        sp.redo_list = pl.redo_list;
+        sp.redo_cnt = pl.redo_cnt;
         sp.redo_base = base;
-        sp.redo_max = R;
-        HIP_TRY(scan_launch(c->dtype, sp, metric, G, nqv, dim3(nblocks), lds, s));
-        SelectParams fp{};
-        fp.lists = lists;
-        fp.nlists = nblocks;
-        fp.kcap = kcap;
-        fp.heads = (k + nblocks - 1) / nblocks;
-        fp.P = 4096;
-        fp.k = k;
-        fp.metric = metric;
-        fp.dtype = c->dtype;
-        fp.index_base = c->index_base;
-        fp.ids = result_ids(c);
-        fp.out_scores = d_scores;
-        fp.out_indices = d_indices;
-        fp.out_raw = d_raw;
-        fp.redo_list = redo_list;
-        fp.redo_cnt = redo_cnt;
+        sp.redo_max = pl.R;
+        MVF_HIP_TRY(scan_launch(c->dtype, sp, sc.metric, pl.sh.G, pl.sh.nqv, dim3(pl.nblocks), pl.sh.lds, s));
+        SelectParams fp = final_select_params(c, sc, pl.lists, pl.nblocks);
+        fp.redo_list = pl.redo_list;
+        fp.redo_cnt = pl.redo_cnt;
         fp.redo_base = base;
-        if (base + R >= nq) fp.ts_end = ts_end;
-        HIP_TRY(launch_select_final(fp, std::min(R, nq - base), s));
-        c->launches += 2;
+        if (base + pl.R >= sc.nq) fp.ts_end = ts_end;
+        MVF_HIP_TRY(launch_select_final(fp, std::min(pl.R, sc.nq - base), s));
+        sc.launches += 2;
     }
     if (c->tune.debug_repair) {  // diagnostics only: how many queries took the repair path (synchronises)
         uint32_t n = 0;
-        HIP_TRY(hipMemcpyAsync(&n, redo_cnt, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (n) fprintf(stderr, "[mvfgpu] overflow repair: %u of %u queries redone by K1\n", n, nq);
+        MVF_HIP_TRY(hipMemcpyAsync(&n, pl.redo_cnt, 4, hipMemcpyDeviceToHost, s));
+        MVF_HIP_TRY(hipStreamSynchronize(s));
+        if (n) fprintf(stderr, "[mvfgpu] overflow repair: %u of %u queries redone by K1\n", n, sc.nq);
     }
     return MVF_OK;
 }
@@ -1147,12 +1162,14 @@ int repair_flagged_queries(const mvfgpu_corpus* c, uint8_t metric, const void* d
 // what it needs for that comes back in *dr.  profile: this range's last phase is the one the handle's timing reports.
 struct BatchedDeferred {
     uint32_t* overflow = nullptr;
-    uint32_t nq_pad = 0;
     bool used_bias = false, used_qs = false;
 };
-int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
-                         float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s, uint64_t lo, uint64_t hi, bool allow_qs,
-                         bool defer, bool profile, BatchedDeferred* dr) {
+int search_batched_range(const mvfgpu_corpus* c, SearchCall& sc, uint64_t lo, uint64_t hi, bool allow_qs, bool defer, bool profile,
+                         BatchedDeferred* dr) {
+    const uint8_t metric = sc.metric;
+    const void* d_queries = sc.d_queries;
+    const uint32_t nq = sc.nq, k = sc.k;
+    hipStream_t s = sc.stream;
     // Float32 rows: either the exact f32 MFMA kernel on the rows themselves, or -- 4x faster -- the f16 kernel on a
     // scaled-f16 SHADOW copy that only selects candidates (error bound below); the kept rows are re-scored from the
     // f32 rows and the f32 query either way, so results do not depend on which one ran.
@@ -1164,7 +1181,7 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
         use_qs = c->shadow8_state == 1 || (c->shadow8_state == 2 && hi <= c->shadow8_rows);  // built by the caller
     }
     if (!use_qs && c->dtype == MVF_DTYPE_FLOAT32 && c->scan_path != 2 && (c->scan_path == 3 || shadow_enabled(c)) && rescore_fits) {
-        HIP_TRY(ensure_shadow(c, s, c->scan_path == 3));
+        MVF_HIP_TRY(ensure_shadow(c, s, c->scan_path == 3));
         use_shadow = c->shadow_state == 1;
     }
     const bool wide = c->dtype == MVF_DTYPE_FLOAT32 && !use_shadow && !use_qs;  // f32 rows: 128x128x32-float tiles
@@ -1184,14 +1201,14 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
     const uint32_t n = (uint32_t)c->n;          // the corpus: layout of the norm arrays
     const uint64_t nr = hi - lo;                // the range: what the phases cover
 
-    HIP_TRY(c->bq.reserve((size_t)planes * nq_pad * KPB + (size_t)nq_pad * 12 + 64));
+    MVF_HIP_TRY(c->bq.reserve((size_t)planes * nq_pad * KPB + (size_t)nq_pad * 12 + 64));
     unsigned char* qprep = static_cast<unsigned char*>(c->bq.p);
     float* qaux0 = reinterpret_cast<float*>(qprep + (size_t)planes * nq_pad * KPB);
     float* qaux1 = qaux0 + nq_pad;
     unsigned char* zeros = reinterpret_cast<unsigned char*>(qaux1 + nq_pad);  // 64 zero bytes
     float* qdelta = reinterpret_cast<float*>(zeros + 64);                       // [nq_pad] int8-shadow selection: bound per query
     if (c->bq_zeros != zeros || c->bq_zero_bytes != c->bq.bytes) {  // nothing in this path writes them: set once per allocation and layout, not
-        HIP_TRY(hipMemsetAsync(zeros, 0, 64, s));                      // once per search (a fill kernel is 4.8 us); the streaming paths, which lay
+        MVF_HIP_TRY(hipMemsetAsync(zeros, 0, 64, s));                      // once per search (a fill kernel is 4.8 us); the streaming paths, which lay
         c->bq_zeros = zeros;                                            // the buffer out differently, forget the mark
         c->bq_zero_bytes = c->bq.bytes;
     }
@@ -1199,10 +1216,9 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
         int rc = ensure_bstate(c, nq_pad, s);
         if (rc != MVF_OK) return rc;
     }
-    uint32_t* tau = static_cast<uint32_t*>(c->bstate.p);
-    uint32_t* cnt = tau + c->bstate_slots;
-    uint32_t* overflow = cnt + c->bstate_slots;
-    HIP_TRY(c->bcand.reserve((size_t)nq_pad * cap * 8));
+    const BState bs = bstate_view(c);
+    uint32_t *const tau = bs.tau, *const cnt = bs.cnt, *const overflow = bs.overflow;
+    MVF_HIP_TRY(c->bcand.reserve((size_t)nq_pad * cap * 8));
     const bool is_float = !is_int_dtype(c->dtype);
     // approximate selection + exact re-scoring: float L2 (GEMM-form distances) and every metric on Float16 rows
     // (single f16 query plane); the other combinations carry final keys through the phases
@@ -1216,13 +1232,13 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
     const float* xx2 = is_float && c->xnorm.p ? static_cast<const float*>(c->xnorm.p) + nn : nullptr;
     const float* xxmax = is_float && c->xnorm.p ? static_cast<const float*>(c->xnorm.p) + norm_max_at(n) : nullptr;
     if (use_qs)
-        HIP_TRY(launch_prep_queries_i8s(static_cast<const float*>(d_queries), nq, nq_pad, c->dim, KPB, metric,
+        MVF_HIP_TRY(launch_prep_queries_i8s(static_cast<const float*>(d_queries), nq, nq_pad, c->dim, KPB, metric,
                                         static_cast<const float*>(c->qs_stats.p), xxmax, qprep, qaux0, qaux1, qdelta, s));
     else if (wide)
-        HIP_TRY(launch_prep_queries(static_cast<const float*>(d_queries), nq, nq_pad, c->dim, KPB / 4,
+        MVF_HIP_TRY(launch_prep_queries(static_cast<const float*>(d_queries), nq, nq_pad, c->dim, KPB / 4,
                                     reinterpret_cast<float*>(qprep), qaux0, s));
     else
-        HIP_TRY(launch_prep_queries16(d_queries, kdtype, nq, nq_pad, c->dim, KPB, qprep, qaux0, qaux1, s));
+        MVF_HIP_TRY(launch_prep_queries16(d_queries, kdtype, nq, nq_pad, c->dim, KPB, qprep, qaux0, qaux1, s));
 
     BatchParams bp{};
     bp.qmat = reinterpret_cast<const float*>(qprep);
@@ -1279,7 +1295,7 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
         blk_records -= blk_records % ((uint64_t)kBlkMaxBlocks * kBlkWaves);
         {
             const void* before = c->blk.p;
-            HIP_TRY(c->blk.reserve((size_t)blk_records * 16 + (size_t)kBlkMaxBlocks * kBlkWaves * 4));
+            MVF_HIP_TRY(c->blk.reserve((size_t)blk_records * 16 + (size_t)kBlkMaxBlocks * kBlkWaves * 4));
             if (c->blk.p != before) c->blk_armed_cnt = nullptr;  // fresh memory
         }
         hp.blk_cand = static_cast<uint4*>(c->blk.p);
@@ -1293,14 +1309,8 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
     cp.tau = tau;
     cp.overflow = overflow;
     cp.cap = cap;
-    cp.k = k;
     cp.metric = metric;
-    cp.dtype = c->dtype;
-    cp.index_base = c->index_base;
-    cp.ids = result_ids(c);
-    cp.out_scores = d_scores;
-    cp.out_indices = d_indices;
-    cp.out_raw = d_raw;
+    set_result_format(cp, c, sc);
     cp.qnorm = wide ? qaux0 : qaux1;  // |q| (f32 path: qnorm; f16 path: second aux array)
     cp.xxmax = xxmax;
     // bound of the approximate score's error in units of (qq + xx) [L2], 1 [cosine], |q||x| [inner product]:
@@ -1311,8 +1321,7 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
     if (use_shadow) cp.eps += 4.8828125e-4f * 1.001f;  // the shadow rows' own rounding (same bound, per element of x)
     cp.delta = use_qs ? qdelta : nullptr;               // int8 selection: the per-query bound from the query preparation
     // int8 selection: between the large phases the threshold is refined with exact scores of the k best (scan_mfma.h)
-    uint32_t* ntop = overflow + c->bstate_slots;
-    uint32_t* lkey = ntop + c->bstate_slots;
+    uint32_t *const ntop = bs.ntop, *const lkey = bs.lkey;
     const bool refine = use_qs && qs_refine_enabled(c);
     cp.ntop = refine ? ntop : nullptr;
 
@@ -1322,7 +1331,7 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
     if (c->profiling && profile) {
         ps = &c->prof[c->prof_next % mvfgpu_corpus::kProfSlots];
         for (auto& e : ps->e)
-            if (!e) HIP_TRY(hipEventCreate(&e));
+            if (!e) MVF_HIP_TRY(hipEventCreate(&e));
         ps->scanned = false;
     }
 
@@ -1360,13 +1369,13 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
             if (regions) hp.blk_cap = (uint32_t)(blk_records / region_blocks) & ~(kBlkWaves - 1u);
             // the region counters: zeroed once, re-armed by every scatter after it has read them
             if (regions && (!regions_armed || nq_pad > scatter_rearm_max_queries())) {
-                HIP_TRY(hipMemsetAsync(hp.blk_cnt, 0, (size_t)kBlkMaxBlocks * kBlkWaves * 4, s));
+                MVF_HIP_TRY(hipMemsetAsync(hp.blk_cnt, 0, (size_t)kBlkMaxBlocks * kBlkWaves * 4, s));
                 regions_armed = true;
             }
-            if (ps && last) HIP_TRY(hipEventRecord(ps->e[0], s));
-            if (wide) HIP_TRY(launch_scan_mfma_f32(bp, metric, s));
-            else if (use_pp) HIP_TRY(launch_scan_mfma16_pp(hp, kdtype, metric, c->num_cus, s));
-            else if (use_sb) HIP_TRY(launch_scan_mfma16_sb(hp, kdtype, metric, c->num_cus, s));
+            if (ps && last) MVF_HIP_TRY(hipEventRecord(ps->e[0], s));
+            if (wide) MVF_HIP_TRY(launch_scan_mfma_f32(bp, metric, s));
+            else if (use_pp) MVF_HIP_TRY(launch_scan_mfma16_pp(hp, kdtype, metric, c->num_cus, s));
+            else if (use_sb) MVF_HIP_TRY(launch_scan_mfma16_sb(hp, kdtype, metric, c->num_cus, s));
             else if (hp.direct && qpb >= 128u) {
                 // The direct phase is a few thousand rows: 10 row tiles x 4 query tiles of 256 x 256 leave 216 CUs idle while 40 blocks
                 // multiply, key and store 65536 pairs each.  In 64-query tiles (64 x 512) the same pairs spread over twice the blocks
@@ -1375,10 +1384,10 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
                 const uint32_t tr = scan_mfma16_dma_tile_rows(64u);
                 dp.mtiles = nq_pad / 64u;
                 dp.ntiles = (uint32_t)((end - begin + tr - 1) / tr);
-                HIP_TRY(launch_scan_mfma16_dma(dp, kdtype, metric, c->num_cus, 64u, s));
-            } else HIP_TRY(launch_scan_mfma16_dma(hp, kdtype, metric, c->num_cus, qpb, s));
+                MVF_HIP_TRY(launch_scan_mfma16_dma(dp, kdtype, metric, c->num_cus, 64u, s));
+            } else MVF_HIP_TRY(launch_scan_mfma16_dma(hp, kdtype, metric, c->num_cus, qpb, s));
             if (ps && last) {
-                HIP_TRY(hipEventRecord(ps->e[1], s));
+                MVF_HIP_TRY(hipEventRecord(ps->e[1], s));
                 ps->scanned = true;
                 tm.scan_bytes = (end - begin) * c->dim * elem_size(kdtype);
                 tm.scan_flops = 2ull * nq * (end - begin) * c->dim;
@@ -1387,26 +1396,16 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
             if (regions) {
                 Batch16Params sp = hp;  // the scatter pass sees a wave's slice as a region of its own
                 if (wave_regions) sp.blk_cap = hp.blk_cap / kBlkWaves;
-                HIP_TRY(launch_scatter_cand(sp, wave_regions ? region_blocks * kBlkWaves : region_blocks, metric, kdtype, s));
+                MVF_HIP_TRY(launch_scatter_cand(sp, wave_regions ? region_blocks * kBlkWaves : region_blocks, metric, kdtype, s));
             }
         }
         cp.direct_cnt = (begin == 0 && end > begin && end - begin <= cap) ? (uint32_t)(end - begin) : 0u;
-        if (approx) HIP_TRY(launch_compact_margin(cp, nq, s));
-        else HIP_TRY(launch_compact(cp, nq, last, s));
+        if (approx) MVF_HIP_TRY(launch_compact_margin(cp, nq, s));
+        else MVF_HIP_TRY(launch_compact(cp, nq, last, s));
         if (last) break;
         if (refine && k2_refine_before(c->tune, bounds, bi, nq)) {  // worth its ~0.07 ms in front of the last (largest) phases
-            RescoreParams rp{};
-            rp.cand = bp.cand;
-            rp.cnt = cnt;
-            rp.tau = tau;
-            rp.cap = cap;
-            rp.k = k;
-            rp.queries = static_cast<const float*>(d_queries);
-            rp.rows = c->d_rows;
-            rp.pitch = c->pitch;
-            rp.dim = c->dim;
-            rp.dtype = c->dtype;
-            HIP_TRY(launch_refine_tau(rp, metric, nq, ntop, lkey, qdelta, s));
+            const RescoreParams rp = rescore_params(c, sc, bp.cand, cap, bs, /*final=*/false);
+            MVF_HIP_TRY(launch_refine_tau(rp, metric, nq, ntop, lkey, qdelta, s));
         }
         begin = end;
         end = bounds[++bi];
@@ -1414,55 +1413,29 @@ int search_batched_range(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
     if (hp.blk_cnt && nq_pad <= scatter_rearm_max_queries()) c->blk_armed_cnt = hp.blk_cnt;  // every phase's scatter has been enqueued
     if (approx) {  // exact scores of the kept candidates from the caller's f32 queries, final top-k
         if (refine && nr >= kRefineMinRows) {  // once more on the final lists: the re-scoring skips what falls outside
-            RescoreParams fp{};
-            fp.cand = bp.cand;
-            fp.cnt = cnt;
-            fp.tau = tau;
-            fp.cap = cap;
-            fp.k = k;
-            fp.queries = static_cast<const float*>(d_queries);
-            fp.rows = c->d_rows;
-            fp.pitch = c->pitch;
-            fp.dim = c->dim;
-            fp.dtype = c->dtype;
+            RescoreParams fp = rescore_params(c, sc, bp.cand, cap, bs, /*final=*/false);
             fp.write_head = 1u;  // the exact composites of the head stay where the final pass would write them
-            HIP_TRY(launch_refine_tau(fp, metric, nq, ntop, lkey, qdelta, s));
+            MVF_HIP_TRY(launch_refine_tau(fp, metric, nq, ntop, lkey, qdelta, s));
         }
-        RescoreParams rp{};
+        RescoreParams rp = rescore_params(c, sc, bp.cand, cap, bs, /*final=*/true);
         rp.head_done = (refine && nr >= kRefineMinRows) ? ntop : nullptr;
-        rp.cand = bp.cand;
-        rp.cnt = cnt;
-        rp.tau = tau;
-        rp.cap = cap;
-        rp.k = k;
-        rp.queries = static_cast<const float*>(d_queries);
-        rp.rows = c->d_rows;
-        rp.pitch = c->pitch;
-        rp.dim = c->dim;
-        rp.dtype = c->dtype;
-        rp.index_base = c->index_base;
-        rp.ids = result_ids(c);
-        rp.out_scores = d_scores;
-        rp.out_indices = d_indices;
-        rp.out_raw = d_raw;
-        HIP_TRY(launch_rescore(rp, metric, nq, s));
+        MVF_HIP_TRY(launch_rescore(rp, metric, nq, s));
     }
     if (ps) {
-        HIP_TRY(hipEventRecord(ps->e[2], s));
+        MVF_HIP_TRY(hipEventRecord(ps->e[2], s));
         c->timing = tm;
         c->prof_next++;
     }
 
     if (dr) {
         dr->overflow = overflow;
-        dr->nq_pad = std::max(dr->nq_pad, nq_pad);
         dr->used_bias |= used_bias;
         dr->used_qs |= use_qs && c->scan_path != 5 && c->scan_path != 6;
     }
     if (defer) return MVF_OK;
-    int rc = repair_flagged_queries(c, metric, d_queries, nq, nq_pad, k, overflow, d_scores, d_indices, d_raw, s);
+    int rc = repair_flagged_queries(c, sc, overflow);
     if (rc == MVF_OK && ((use_qs && c->scan_path != 5 && c->scan_path != 6) || used_bias))
-        rc = qs_feedback_post(c, nq, s, used_bias, use_qs && c->scan_path != 5 && c->scan_path != 6);
+        rc = qs_feedback_post(c, sc, used_bias, use_qs && c->scan_path != 5 && c->scan_path != 6);
     return rc;
 }
 
@@ -1476,36 +1449,38 @@ int merge_topk_device_impl(const float* d_scores, const uint64_t* d_indices, con
 // prefix by the int8 selection, the rest by the f16 kernels on the stored rows -- whose exact top-k lists are merged like two
 // shards' (the same device merge: ties by ascending position); the repair of flagged queries runs once, behind the merge, over
 // the whole corpus.  100M x 1024 f16, 1024 queries: 181-184 ms -> 95.5 (profiles/r05_partial_shadow.json).
-int search_batched_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
-                        float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
+int search_batched_path(const mvfgpu_corpus* c, SearchCall& sc) {
+    const uint32_t nq = sc.nq, k = sc.k;
+    hipStream_t s = sc.stream;
     qs_feedback_poll(c);
     if (qs_wanted_batched(c, k)) {
         int rc = ensure_norms(c, s);
         if (rc != MVF_OK) return rc;
-        HIP_TRY(ensure_shadow8(c, s, c->scan_path == 5 || c->scan_path == 6, /*allow_partial=*/true));
+        MVF_HIP_TRY(ensure_shadow8(c, s, c->scan_path == 5 || c->scan_path == 6, /*allow_partial=*/true));
     }
     if (!(c->shadow8_state == 2 && qs_wanted(c, k) && c->shadow8_rows < c->n))
-        return search_batched_range(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s, 0, c->n, true, false, true, nullptr);
+        return search_batched_range(c, sc, 0, c->n, true, false, true, nullptr);
     {   // the per-query state (thresholds, counts, overflow flags) must not be re-allocated between the two ranges -- the second
         // would lose the first's overflow flags: sized here for the widest query tile either range may take
         const int brc = ensure_bstate(c, (nq + 255u) & ~255u, s);
         if (brc != MVF_OK) return brc;
     }
     const size_t ls = (size_t)nq * k;
-    HIP_TRY(c->split_out.reserve(2 * ls * 16));
+    MVF_HIP_TRY(c->split_out.reserve(2 * ls * 16));
     unsigned char* t = static_cast<unsigned char*>(c->split_out.p);
     uint64_t* ti = reinterpret_cast<uint64_t*>(t);                 // [2][nq k]
     float* ts = reinterpret_cast<float*>(t + 2 * ls * 8);          // [2][nq k]
     int32_t* tr = reinterpret_cast<int32_t*>(t + 2 * ls * 12);     // [2][nq k]
     BatchedDeferred dr{};
-    int rc = search_batched_range(c, metric, d_queries, nq, k, ts, ti, tr, s, 0, c->shadow8_rows, true, true, true, &dr);
+    int rc = inner_search(sc, k, ts, ti, tr, [&](SearchCall& in) { return search_batched_range(c, in, 0, c->shadow8_rows, true, true, true, &dr); });
     if (rc != MVF_OK) return rc;
-    rc = search_batched_range(c, metric, d_queries, nq, k, ts + ls, ti + ls, tr + ls, s, c->shadow8_rows, c->n, false, true, false, &dr);
+    rc = inner_search(sc, k, ts + ls, ti + ls, tr + ls,
+                      [&](SearchCall& in) { return search_batched_range(c, in, c->shadow8_rows, c->n, false, true, false, &dr); });
     if (rc != MVF_OK) return rc;
-    rc = merge_topk_device_impl(ts, ti, tr, ls, ls, ls, 2, nq, k, metric, c->dtype, d_scores, d_indices, d_raw, c->device, s);
+    rc = merge_topk_device_impl(ts, ti, tr, ls, ls, ls, 2, nq, k, sc.metric, c->dtype, sc.d_scores, sc.d_indices, sc.d_raw, c->device, s);
     if (rc != MVF_OK) return rc;
-    rc = repair_flagged_queries(c, metric, d_queries, nq, dr.nq_pad, k, dr.overflow, d_scores, d_indices, d_raw, s);
-    if (rc == MVF_OK && (dr.used_qs || dr.used_bias)) rc = qs_feedback_post(c, nq, s, dr.used_bias, dr.used_qs);
+    rc = repair_flagged_queries(c, sc, dr.overflow);
+    if (rc == MVF_OK && (dr.used_qs || dr.used_bias)) rc = qs_feedback_post(c, sc, dr.used_bias, dr.used_qs);
     return rc;
 }
 
@@ -1517,26 +1492,26 @@ int search_batched_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_qu
 // repair launches, like the batched path: asynchronous).
 //   x~ = x (1 + e), |e| <= 2^-11 per element:  |q.x~ - q.x| <= 2^-11 |q||x|;  | |q - x~| - |q - x| | <= 2^-11 |x|;
 //   cosine (numerator and denominator both from x~) <= 2 * 2^-11; plus the f32 accumulation, (dim + 16) 2^-23.
-int search_stream_shadow_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
-                              float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
+int search_stream_shadow_path(const mvfgpu_corpus* c, SearchCall& sc) {
+    const uint8_t metric = sc.metric;
+    const uint32_t nq = sc.nq, k = sc.k;
+    hipStream_t s = sc.stream;
     const uint32_t cap = kBatchCap;
     const uint32_t nq_pad = (nq + 255u) & ~255u;
     const uint32_t n = (uint32_t)c->n;
     int rc = ensure_bstate(c, nq_pad, s);
     if (rc == MVF_OK) rc = ensure_norms(c, s);
     if (rc != MVF_OK) return rc;
-    uint32_t* tau = static_cast<uint32_t*>(c->bstate.p);
-    uint32_t* cnt = tau + c->bstate_slots;
-    uint32_t* overflow = cnt + c->bstate_slots;
-    HIP_TRY(c->bcand.reserve((size_t)nq_pad * cap * 8));
+    const BState bs = bstate_view(c);
+    MVF_HIP_TRY(c->bcand.reserve((size_t)nq_pad * cap * 8));
     // |q| per query for the margins: the f16 query preparation computes it (its planes are not used here)
     const uint32_t KPB = ((c->dim * 2u + 63u) / 64u) * 64u;
-    HIP_TRY(c->bq.reserve((size_t)nq_pad * KPB + (size_t)nq_pad * 8 + 64));
+    MVF_HIP_TRY(c->bq.reserve((size_t)nq_pad * KPB + (size_t)nq_pad * 8 + 64));
     c->bq_zeros = nullptr;  // another layout of the buffer: the batched path's zero bytes may be overwritten
     unsigned char* qprep = static_cast<unsigned char*>(c->bq.p);
     float* qaux0 = reinterpret_cast<float*>(qprep + (size_t)nq_pad * KPB);
     float* qaux1 = qaux0 + nq_pad;
-    HIP_TRY(launch_prep_queries16(d_queries, MVF_DTYPE_FLOAT16, nq, nq_pad, c->dim, KPB, qprep, qaux0, qaux1, s));
+    MVF_HIP_TRY(launch_prep_queries16(sc.d_queries, MVF_DTYPE_FLOAT16, nq, nq_pad, c->dim, KPB, qprep, qaux0, qaux1, s));
 
     const uint32_t ksel = std::min<uint32_t>(MVFGPU_K_PER_PASS, std::max(2u * k, k + 64u));  // k' candidates per query
     ShadowStream alt{};
@@ -1546,22 +1521,22 @@ int search_stream_shadow_path(const mvfgpu_corpus* c, uint8_t metric, const void
     alt.V = alt.pitch / 16;
     choose_group(alt.V, 1, &alt.G, &alt.J, c->tune.k1_g);
     alt.cand = static_cast<uint64_t*>(c->bcand.p);
-    alt.cnt = cnt;
+    alt.cnt = bs.cnt;
     alt.cand_cap = cap;
-    rc = search_stream_path(c, metric, d_queries, nq, ksel, nullptr, nullptr, nullptr, s, /*profile=*/true, &alt);
+    rc = inner_search(sc, ksel, nullptr, nullptr, nullptr, [&](SearchCall& in) { return search_stream_path(c, in, /*profile=*/true, &alt); });
     if (rc != MVF_OK) return rc;
 
     CompactParams cp{};
     cp.cand = alt.cand;
-    cp.cnt = cnt;
-    cp.tau = tau;
-    cp.overflow = overflow;
+    cp.cnt = bs.cnt;
+    cp.tau = bs.tau;
+    cp.overflow = bs.overflow;
     cp.cap = cap;
     cp.k = k;
     cp.metric = metric;
     cp.dtype = c->dtype;
     cp.index_base = c->index_base;
-    cp.ids = result_ids(c);
+    cp.ids = result_ids(c, sc);
     cp.qnorm = qaux1;
     cp.xxmax = static_cast<const float*>(c->xnorm.p) + norm_max_at(n);
     // per-element relative rounding of the shadow rows (2^-11) and f32 accumulation of `dim` terms ((dim + 16) 2^-23
@@ -1571,26 +1546,11 @@ int search_stream_shadow_path(const mvfgpu_corpus* c, uint8_t metric, const void
     cp.eps_acc = 0.5f * eacc;
     cp.l2_is_distance = 1;
     cp.truncated_at = n > ksel ? ksel : 0u;
-    HIP_TRY(launch_compact_margin(cp, nq, s));
+    MVF_HIP_TRY(launch_compact_margin(cp, nq, s));
 
-    RescoreParams rp{};
-    rp.cand = alt.cand;
-    rp.cnt = cnt;
-    rp.tau = tau;
-    rp.cap = cap;
-    rp.k = k;
-    rp.queries = static_cast<const float*>(d_queries);
-    rp.rows = c->d_rows;
-    rp.pitch = c->pitch;
-    rp.dim = c->dim;
-    rp.dtype = c->dtype;
-    rp.index_base = c->index_base;
-    rp.ids = result_ids(c);
-    rp.out_scores = d_scores;
-    rp.out_indices = d_indices;
-    rp.out_raw = d_raw;
-    HIP_TRY(launch_rescore(rp, metric, nq, s));
-    return repair_flagged_queries(c, metric, d_queries, nq, nq_pad, k, overflow, d_scores, d_indices, d_raw, s);
+    const RescoreParams rp = rescore_params(c, sc, alt.cand, cap, bs, /*final=*/true);
+    MVF_HIP_TRY(launch_rescore(rp, metric, nq, s));
+    return repair_flagged_queries(c, sc, bs.overflow);
 }
 
 // One to four queries on a Float32 / Float16 corpus STREAM ITS INT8 SHADOW (dim bytes per row: a quarter / half of the
@@ -1603,22 +1563,22 @@ int search_stream_shadow_path(const mvfgpu_corpus* c, uint8_t metric, const void
 // rescore_kernel re-scores what was gathered from the stored rows and the f32 query.
 uint32_t stream_qs_klist(uint32_t k) { return std::max(k, 32u); }
 
-int search_stream_qs_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
-                          float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
+int search_stream_qs_path(const mvfgpu_corpus* c, SearchCall& sc) {
+    const uint8_t metric = sc.metric;
+    const uint32_t nq = sc.nq, k = sc.k;
+    hipStream_t s = sc.stream;
     const uint32_t cap = kBatchCap;
     const uint32_t nq_pad = (nq + 255u) & ~255u;
     const uint32_t n = (uint32_t)c->n;
     int rc = ensure_bstate(c, nq_pad, s);
     if (rc == MVF_OK) rc = ensure_norms(c, s);
     if (rc != MVF_OK) return rc;
-    uint32_t* tau = static_cast<uint32_t*>(c->bstate.p);
-    uint32_t* cnt = tau + c->bstate_slots;
-    uint32_t* overflow = cnt + c->bstate_slots;
-    HIP_TRY(c->bcand.reserve((size_t)nq_pad * cap * 8));
+    const BState bs = bstate_view(c);
+    MVF_HIP_TRY(c->bcand.reserve((size_t)nq_pad * cap * 8));
     const uint32_t KPB = shadow8_pitch(c->dim);
     // the queries' scale, norm and bound: K1's prologue over the shadow prepares the queries itself and stores them here
     // (block 0 of the scan; an empty corpus, which launches no scan, never gets here: qs_possible refuses n == 0)
-    HIP_TRY(c->bq.reserve((size_t)nq_pad * 12 + 64));
+    MVF_HIP_TRY(c->bq.reserve((size_t)nq_pad * 12 + 64));
     c->bq_zeros = nullptr;  // another layout of the buffer: the batched path's zero bytes may be overwritten
     float* qaux0 = static_cast<float*>(c->bq.p);
     float* qaux1 = qaux0 + nq_pad;
@@ -1638,53 +1598,37 @@ int search_stream_qs_path(const mvfgpu_corpus* c, uint8_t metric, const void* d_
     alt.pitch = KPB;
     alt.V = KPB / 16;
     alt.cand = static_cast<uint64_t*>(c->bcand.p);
-    alt.cnt = cnt;
+    alt.cnt = bs.cnt;
     alt.cand_cap = cap;
     alt.delta = qdelta;
-    alt.tau = tau;
-    alt.overflow = overflow;
+    alt.tau = bs.tau;
+    alt.overflow = bs.overflow;
     alt.rank_k = k;
-    uint64_t* ts_end = c->whole_by_clock ? prof_ts_entry(c, c->prof_next) + 3 : nullptr;  // (this search's entry: prof_next moves below)
-    rc = search_stream_path(c, metric, d_queries, nq, stream_qs_klist(k), nullptr, nullptr, nullptr, s, /*profile=*/true, &alt);
+    uint64_t* ts_end = sc.whole_by_clock ? prof_ts_entry(c, c->prof_next) + 3 : nullptr;  // (this search's entry: prof_next moves below)
+    rc = inner_search(sc, stream_qs_klist(k), nullptr, nullptr, nullptr,
+                      [&](SearchCall& in) { return search_stream_path(c, in, /*profile=*/true, &alt); });
     if (rc != MVF_OK) return rc;
 
-    RescoreParams rp{};
-    rp.cand = alt.cand;
-    rp.cnt = cnt;
-    rp.tau = tau;
-    rp.cap = cap;
-    rp.k = k;
-    rp.queries = static_cast<const float*>(d_queries);
-    rp.rows = c->d_rows;
-    rp.pitch = c->pitch;
-    rp.dim = c->dim;
-    rp.dtype = c->dtype;
-    rp.index_base = c->index_base;
-    rp.ids = result_ids(c);
-    rp.out_scores = d_scores;
-    rp.out_indices = d_indices;
-    rp.out_raw = d_raw;
+    RescoreParams rp = rescore_params(c, sc, alt.cand, cap, bs, /*final=*/true);
     // Re-scored in K1's arithmetic at the width K1 takes for these queries on the stored rows, and a flagged query redone by
     // K1 at that width too -- the answer carries the bits the stored-row route gives it (Float16 rows too since round 7; they
     // went through the wave kernel's summation order before)
-    int G, nqv;
-    uint32_t J;
-    k1_stored_group(c, nq, k, &G, &J, &nqv);
+    const K1Shape sh = k1_shape(c, nq, k);
     // the flags are final since the margin select: block 0 of the final select turns them into the repair launches' list
     RepairPlan plan;
-    rc = plan_repair(c, metric, nq, k, nqv, &plan);
+    rc = plan_repair(c, sc, sh.nqv, &plan);
     if (rc != MVF_OK) return rc;
     if (plan.any) {
-        rp.flags = overflow;
+        rp.flags = bs.overflow;
         rp.flags_nq = nq;
         rp.redo_list = plan.redo_list;
         rp.redo_cnt = plan.redo_cnt;
         rp.redo_mirror = feedback_mirror(c);
     }
-    HIP_TRY(launch_rescore_k1(rp, metric, nq, G, J, s));
-    c->launches += 2;
-    rc = repair_flagged_queries(c, metric, d_queries, nq, nq_pad, k, overflow, d_scores, d_indices, d_raw, s, nqv, &plan, ts_end);
-    if (rc == MVF_OK && c->scan_path != 6) rc = qs_feedback_post(c, nq, s);
+    MVF_HIP_TRY(launch_rescore_k1(rp, metric, nq, sh.G, sh.J, s));
+    sc.launches += 2;
+    rc = repair_flagged_queries(c, sc, bs.overflow, sh.nqv, &plan, ts_end);
+    if (rc == MVF_OK && c->scan_path != 6) rc = qs_feedback_post(c, sc);
     return rc;
 }
 
@@ -1859,7 +1803,7 @@ int upload_rows(mvfgpu_corpus* c, const void* rows, uint64_t stride, const mvfgp
     const uint64_t chunk_bytes = (uint64_t)(o.chunk_mib ? o.chunk_mib : (pinned ? 64u : 256u)) << 20;
     const uint64_t chunk_rows = std::max<uint64_t>(1, chunk_bytes / stride);
     const unsigned char* src = static_cast<const unsigned char*>(rows);
-    HIP_TRY(hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
+    MVF_HIP_TRY(hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
     hipStream_t s_copy = c->own_stream, s_comp = c->up_stream;
 
     // what the compute stream prepares per chunk
@@ -1871,9 +1815,9 @@ int upload_rows(mvfgpu_corpus* c, const void* rows, uint64_t stride, const mvfgp
     float* xn = nullptr;
     const size_t nn = norm_stride(n);
     if (want_norms) {
-        HIP_TRY(c->xnorm.reserve((norm_max_at(n) + 1) * 4));
+        MVF_HIP_TRY(c->xnorm.reserve((norm_max_at(n) + 1) * 4));
         xn = static_cast<float*>(c->xnorm.p);
-        if (!is_int_dtype(c->dtype)) HIP_TRY(hipMemsetAsync(xn + norm_max_at(n), 0, 4, s_comp));
+        if (!is_int_dtype(c->dtype)) MVF_HIP_TRY(hipMemsetAsync(xn + norm_max_at(n), 0, 4, s_comp));
     }
     if (want_shadow) {
         const size_t need = (size_t)n * shadow_pitch(c->dim);
@@ -1898,20 +1842,20 @@ int upload_rows(mvfgpu_corpus* c, const void* rows, uint64_t stride, const mvfgp
             c->xscale8.release();
             want_shadow8 = false;
         } else {
-            HIP_TRY(hipMemsetAsync(c->qs_stats.p, 0, 16, s_comp));  // the four bound maxima accumulate over the chunks
+            MVF_HIP_TRY(hipMemsetAsync(c->qs_stats.p, 0, 16, s_comp));  // the four bound maxima accumulate over the chunks
         }
     }
 
     StagePair stage;
     PinnedPair pin;
     EventSet ev;  // [0,1] copy of buffer b landed, [2,3] compute on buffer b done, [4,5] H2D out of pinned buffer b done
-    for (auto& e : ev.e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : ev.e) MVF_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const uint64_t span_max = (std::min(chunk_rows, n) - 1) * stride + row_bytes;  // bytes of one chunk as it lies
     if (!direct && !sparse)
-        for (auto& q : stage.p) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q), span_max));
+        for (auto& q : stage.p) MVF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q), span_max));
     if (pinned)
-        for (auto& q : pin.p) HIP_TRY(hipHostMalloc(&q, span_max, hipHostMallocDefault));
-    if (sparse && c->pitch != row_bytes) HIP_TRY(hipMemsetAsync(c->d_rows, 0, c->rows_bytes, s_copy));  // the 16-B padding
+        for (auto& q : pin.p) MVF_HIP_TRY(hipHostMalloc(&q, span_max, hipHostMallocDefault));
+    if (sparse && c->pitch != row_bytes) MVF_HIP_TRY(hipMemsetAsync(c->d_rows, 0, c->rows_bytes, s_copy));  // the 16-B padding
     unsigned threads = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
     if (c->tune.upload_threads) threads = c->tune.upload_threads;
 
@@ -1924,43 +1868,43 @@ int upload_rows(mvfgpu_corpus* c, const void* rows, uint64_t stride, const mvfgp
         const uint64_t h = std::min(chunk_rows, n - r0);
         const uint64_t span = (h - 1) * stride + row_bytes;
         unsigned char* place = c->d_rows + r0 * c->pitch;
-        if (!direct && !sparse && i >= 2) HIP_TRY(hipEventSynchronize(ev.e[2 + b]));  // stage b: its re-pitch is done
+        if (!direct && !sparse && i >= 2) MVF_HIP_TRY(hipEventSynchronize(ev.e[2 + b]));  // stage b: its re-pitch is done
         if (sparse) {
-            HIP_TRY(hipMemcpy2DAsync(place, c->pitch, src + r0 * stride, stride, row_bytes, h, hipMemcpyHostToDevice, s_copy));
+            MVF_HIP_TRY(hipMemcpy2DAsync(place, c->pitch, src + r0 * stride, stride, row_bytes, h, hipMemcpyHostToDevice, s_copy));
         } else {
             unsigned char* dst = direct ? place : stage.p[b];
             if (pinned) {
-                if (i >= 2) HIP_TRY(hipEventSynchronize(ev.e[4 + b]));  // pinned buffer b: its H2D is done
+                if (i >= 2) MVF_HIP_TRY(hipEventSynchronize(ev.e[4 + b]));  // pinned buffer b: its H2D is done
                 parallel_memcpy(pin.p[b], src + r0 * stride, span, threads);
-                HIP_TRY(hipMemcpyAsync(dst, pin.p[b], span, hipMemcpyHostToDevice, s_copy));
-                HIP_TRY(hipEventRecord(ev.e[4 + b], s_copy));
+                MVF_HIP_TRY(hipMemcpyAsync(dst, pin.p[b], span, hipMemcpyHostToDevice, s_copy));
+                MVF_HIP_TRY(hipEventRecord(ev.e[4 + b], s_copy));
             } else {
-                HIP_TRY(hipMemcpyAsync(dst, src + r0 * stride, span, hipMemcpyHostToDevice, s_copy));
+                MVF_HIP_TRY(hipMemcpyAsync(dst, src + r0 * stride, span, hipMemcpyHostToDevice, s_copy));
             }
         }
-        HIP_TRY(hipEventRecord(ev.e[b], s_copy));
-        HIP_TRY(hipStreamWaitEvent(s_comp, ev.e[b], 0));
+        MVF_HIP_TRY(hipEventRecord(ev.e[b], s_copy));
+        MVF_HIP_TRY(hipStreamWaitEvent(s_comp, ev.e[b], 0));
         if (!direct && !sparse)
-            HIP_TRY(launch_repack_rows(stage.p[b], place, h, (uint32_t)row_bytes, stride, c->pitch, s_comp));
+            MVF_HIP_TRY(launch_repack_rows(stage.p[b], place, h, (uint32_t)row_bytes, stride, c->pitch, s_comp));
         if (want_norms) {
             if (c->dtype == MVF_DTYPE_FLOAT32)
-                HIP_TRY(launch_row_norms_f32(place, (uint32_t)h, c->pitch, xn + r0, xn + nn + r0, xn + norm_max_at(n), s_comp));
+                MVF_HIP_TRY(launch_row_norms_f32(place, (uint32_t)h, c->pitch, xn + r0, xn + nn + r0, xn + norm_max_at(n), s_comp));
             else
-                HIP_TRY(launch_row_norms16(place, c->dtype, (uint32_t)h, c->pitch, c->dim, xn + r0, xn + nn + r0,
+                MVF_HIP_TRY(launch_row_norms16(place, c->dtype, (uint32_t)h, c->pitch, c->dim, xn + r0, xn + nn + r0,
                                            xn + norm_max_at(n), s_comp));
         }
         if (want_shadow8)
-            HIP_TRY(launch_shadow_i8(place, c->dtype, (uint32_t)h, c->pitch, c->dim,
+            MVF_HIP_TRY(launch_shadow_i8(place, c->dtype, (uint32_t)h, c->pitch, c->dim,
                                      static_cast<unsigned char*>(c->shadow8.p) + r0 * shadow8_pitch(c->dim), shadow8_pitch(c->dim),
                                      static_cast<float*>(c->xscale8.p) + r0, static_cast<float*>(c->qs_stats.p), s_comp));
         if (want_shadow)
-            HIP_TRY(launch_shadow_f16(place, (uint32_t)h, c->pitch, c->dim,
+            MVF_HIP_TRY(launch_shadow_f16(place, (uint32_t)h, c->pitch, c->dim,
                                       static_cast<unsigned char*>(c->shadow.p) + r0 * shadow_pitch(c->dim), shadow_pitch(c->dim),
                                       static_cast<float*>(c->xscale.p) + r0, s_comp));
-        HIP_TRY(hipEventRecord(ev.e[2 + b], s_comp));
+        MVF_HIP_TRY(hipEventRecord(ev.e[2 + b], s_comp));
     }
-    HIP_TRY(hipStreamSynchronize(s_copy));
-    HIP_TRY(hipStreamSynchronize(s_comp));
+    MVF_HIP_TRY(hipStreamSynchronize(s_copy));
+    MVF_HIP_TRY(hipStreamSynchronize(s_comp));
     if (want_norms) c->xnorm_ready = true;
     c->shadow_state = want_shadow ? 1 : c->shadow_state;
     c->shadow8_state = want_shadow8 ? 1 : c->shadow8_state;
@@ -1973,14 +1917,15 @@ int upload_rows(mvfgpu_corpus* c, const void* rows, uint64_t stride, const mvfgp
 // so "behind the floor" is exactly the set of rows not yet returned.  The floor travels on the device (select_final writes
 // it, the next pass's scan reads it): no host wait.  The reference takes any k: usize (examples/similarity_search.rs:143,
 // :166-168); its heap holds k + 1 entries whatever k is.
-int search_large_k(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
-                   uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
-    HIP_TRY(c->floor1.reserve((size_t)nq * 8));
+int search_large_k(const mvfgpu_corpus* c, SearchCall& sc) {
+    const uint32_t k = sc.k;
+    MVF_HIP_TRY(c->floor1.reserve((size_t)sc.nq * 8));
     uint64_t* fl = static_cast<uint64_t*>(c->floor1.p);
     for (uint32_t off = 0; off < k; off += MVFGPU_K_PER_PASS) {
         const uint32_t kk = std::min<uint32_t>(MVFGPU_K_PER_PASS, k - off);
-        int rc = search_stream_path(c, metric, d_queries, nq, kk, d_scores, d_indices, d_raw, s, /*profile=*/off == 0, nullptr,
-                                    off ? fl : nullptr, fl, k, off);
+        int rc = inner_search(sc, kk, sc.d_scores, sc.d_indices, sc.d_raw, [&](SearchCall& in) {
+            return search_stream_path(c, in, /*profile=*/off == 0, nullptr, off ? fl : nullptr, fl, k, off);
+        });
         if (rc != MVF_OK) return rc;
     }
     return MVF_OK;
@@ -1991,14 +1936,21 @@ int search_large_k(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries
 // (sort_topk.hip) and the formatting of the first k.  Exact, no host wait, any k (entries beyond the live rows pad); costs
 // the scan + ~130 bytes of sort traffic per row, i.e. less than a second pass whenever rows are longer than that.
 // Returns MVF_ERR_DEVICE with *no_room set when the buffers (16 bytes per row and query of a pass + scratch) do not fit.
-int search_sorted_k(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
-                    uint64_t* d_indices, int32_t* d_raw, hipStream_t s, bool* no_room) {
+int search_sorted_k(const mvfgpu_corpus* c, SearchCall& sc, bool* no_room) {
+    const uint32_t nq = sc.nq, k = sc.k;
+    hipStream_t s = sc.stream;
     *no_room = false;
     size_t tmp_bytes = 0;
-    if (c->n > 0) HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)c->n, (size_t)k, nullptr, s, 4, (size_t)c->n));
+    if (c->n > 0) MVF_HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)c->n, (size_t)k, nullptr, s, 4, (size_t)c->n));
     tmp_bytes = std::max<size_t>(tmp_bytes, 256);
     RankAll ra{};
     ra.k_out = k;
+    // the dumping scan: nothing is selected, so the kernel's own list length is the smallest its LDS layout takes
+    auto dump_scan = [&]() {
+        return inner_search(sc, 16, sc.d_scores, sc.d_indices, sc.d_raw, [&](SearchCall& in) {
+            return search_stream_path(c, in, /*profile=*/true, nullptr, nullptr, nullptr, 0, 0, &ra);
+        });
+    };
     // Up to 1 GiB the buffers stay with the handle; beyond it (50M rows x four queries: 3.2 GB) they come from the stream-ordered
     // allocator for this search only -- memory a later shadow build or upload may need, and no host wait either way.
     constexpr size_t kKeep = 1ull << 30;
@@ -2012,11 +1964,10 @@ int search_sorted_k(const mvfgpu_corpus* c, uint8_t metric, const void* d_querie
                 ra.b = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(scratch) + bytes);
                 ra.tmp = static_cast<unsigned char*>(scratch) + 2 * bytes;
                 ra.tmp_bytes = tmp_bytes;
-                const int rc = search_stream_path(c, metric, d_queries, nq, 16, d_scores, d_indices, d_raw, s, /*profile=*/true, nullptr,
-                                                  nullptr, nullptr, 0, 0, &ra);
+                const int rc = dump_scan();
                 const hipError_t ef = hipFreeAsync(scratch, s);
                 if (rc != MVF_OK) return rc;
-                HIP_TRY(ef);
+                MVF_HIP_TRY(ef);
                 return MVF_OK;
             }
             (void)hipGetLastError();
@@ -2032,7 +1983,7 @@ int search_sorted_k(const mvfgpu_corpus* c, uint8_t metric, const void* d_querie
         }
         if (nqv == 1) {
             if (c->shadow8_state == 2) {  // a shadow of what fitted took the room: the search the caller asked for comes first
-                HIP_TRY(hipStreamSynchronize(s));  // nothing may still read it
+                MVF_HIP_TRY(hipStreamSynchronize(s));  // nothing may still read it
                 c->shadow8.release();
                 c->xscale8.release();
                 c->shadow8_state = -2;
@@ -2047,9 +1998,7 @@ int search_sorted_k(const mvfgpu_corpus* c, uint8_t metric, const void* d_querie
     ra.b = static_cast<uint64_t*>(c->rank_b.p);
     ra.tmp = c->rank_tmp.p;
     ra.tmp_bytes = c->rank_tmp.bytes;
-    // the kernel's own list length: nothing is selected, so the smallest the LDS layout takes
-    return search_stream_path(c, metric, d_queries, nq, 16, d_scores, d_indices, d_raw, s, /*profile=*/true, nullptr, nullptr, nullptr, 0,
-                              0, &ra);
+    return dump_scan();
 }
 
 // Passes or the select + sort?  Measured in one process on every benchmark shape (profiles/r05_any_k.txt; round 4's library
@@ -2076,8 +2025,7 @@ bool large_k_by_sort(const mvfgpu_corpus* c, uint32_t nq, uint32_t k) {
 int check_query_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype,
                      uint32_t query_dim, uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices) {
     if (!c) return fail(MVF_ERR_INVALID_ARGUMENT, "corpus is NULL");
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code " + std::to_string(metric));
+    if (const int mrc = check_metric(metric)) return mrc;
     if (nq == 0) return fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
     if (k == 0 || k > MVFGPU_MAX_K) return fail(MVF_ERR_INVALID_ARGUMENT, "k must be in 1..2^31");
     if (!queries || !out_scores || !out_indices) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
@@ -2136,25 +2084,15 @@ bool corpus_ids_to_positions(const mvfgpu_corpus* c, const uint64_t* ids, uint64
 }
 int corpus_pinned_mirrors(const mvfgpu_corpus* c, size_t in_bytes, size_t out_bytes, void** pin_in, void** pin_out) {
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->has_done && c->confirmed_gen != c->work_gen) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
-    HIP_TRY(c->pin_q.reserve(in_bytes));
-    HIP_TRY(c->pin_out.reserve(out_bytes));
+    if (c->has_done && c->confirmed_gen != c->work_gen) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+    MVF_HIP_TRY(c->pin_q.reserve(in_bytes));
+    MVF_HIP_TRY(c->pin_out.reserve(out_bytes));
     *pin_in = c->pin_q.p;
     *pin_out = c->pin_out.p;
     return MVF_OK;
 }
 int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function<int()>& body) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->work_gen++;
-    c->one_search_call = false;  // `body` may run any number of searches
-    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done[c->done_idx], 0));
-    struct DoneGuard {  // as search_device's: work may already sit on the stream whatever `body` returns
-        const mvfgpu_corpus* c;
-        hipStream_t s;
-        ~DoneGuard() { record_done(c, s); }
-    } done_guard{c, s};
-    return body();
+    return device_call(c, static_cast<hipStream_t>(stream), body);
 }
 int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                       uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices) {
@@ -2218,7 +2156,7 @@ int mvfgpu_corpus_create_ex(const void* rows, uint64_t n, uint32_t dimension, ui
         return fail(MVF_ERR_DEVICE, "no HIP device available (libmvf_gpu has no CPU fallback)");
     }
     if (device < 0 || device >= ndev) return fail(MVF_ERR_INVALID_ARGUMENT, "device index out of range");
-    DeviceGuard guard(device);
+    DevScope guard(device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
 
     auto* c = new mvfgpu_corpus();
@@ -2255,7 +2193,7 @@ int mvfgpu_corpus_create_synthetic(uint64_t n, uint32_t dimension, uint8_t data_
         return fail(MVF_ERR_DEVICE, "no HIP device available (libmvf_gpu has no CPU fallback)");
     }
     if (device < 0 || device >= ndev) return fail(MVF_ERR_INVALID_ARGUMENT, "device index out of range");
-    DeviceGuard guard(device);
+    DevScope guard(device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     auto* c = new mvfgpu_corpus();
     c->device = device;
@@ -2281,7 +2219,7 @@ int mvfgpu_corpus_create_synthetic(uint64_t n, uint32_t dimension, uint8_t data_
 void mvfgpu_corpus_destroy(mvfgpu_corpus* c) {
     if (!c) return;
     {
-        DeviceGuard guard(c->device);
+        DevScope guard(c->device);
         (void)hipDeviceSynchronize();
         if (c->d_rows) (void)hipFree(c->d_rows);
         c->cand.release();
@@ -2358,9 +2296,9 @@ int mvfgpu_corpus_read_rows(const mvfgpu_corpus* c, uint64_t first, uint64_t cou
         return MVF_ERR_INDEX_OUT_OF_BOUNDS;  // reference src/vectors/vector_space.rs:156-161
     }
     if (count == 0) return MVF_OK;
-    DeviceGuard guard(c->device);
+    DevScope guard(c->device);
     const uint64_t row_bytes = (uint64_t)c->dim * elem_size(c->dtype);
-    HIP_TRY(hipMemcpy2D(out_rows, row_bytes, c->d_rows + first * c->pitch, c->pitch, row_bytes, count,
+    MVF_HIP_TRY(hipMemcpy2D(out_rows, row_bytes, c->d_rows + first * c->pitch, c->pitch, row_bytes, count,
                         hipMemcpyDeviceToHost));
     return MVF_OK;
 }
@@ -2388,7 +2326,7 @@ int gather_rows_host_locked(const mvfgpu_corpus* c, const uint64_t* indices, uin
             return MVF_ERR_INDEX_OUT_OF_BOUNDS;  // reference src/vectors/vector_space.rs:102-107
         }
     }
-    DeviceGuard guard(c->device);
+    DevScope guard(c->device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     const uint32_t row_bytes = c->dim * elem_size(c->dtype);
     // small fetches (the payload rows of one result list) go through pinned host memory in place, like mvfgpu_search's
@@ -2397,28 +2335,28 @@ int gather_rows_host_locked(const mvfgpu_corpus* c, const uint64_t* indices, uin
     void *di, *dout;
     {
         std::lock_guard<std::mutex> lk(c->mu);
-        if (c->has_done) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+        if (c->has_done) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
         if (zc_i) {
-            HIP_TRY(c->pin_q.reserve(ibytes));
+            MVF_HIP_TRY(c->pin_q.reserve(ibytes));
             memcpy(c->pin_q.p, indices, ibytes);
             di = c->pin_q.p;
         } else {
-            HIP_TRY(c->h_i.reserve(ibytes));
+            MVF_HIP_TRY(c->h_i.reserve(ibytes));
             di = c->h_i.p;
         }
         if (zc_o) {
-            HIP_TRY(c->pin_out.reserve(obytes));
+            MVF_HIP_TRY(c->pin_out.reserve(obytes));
             dout = c->pin_out.p;
         } else {
-            HIP_TRY(c->h_q.reserve(obytes));
+            MVF_HIP_TRY(c->h_q.reserve(obytes));
             dout = c->h_q.p;
         }
     }
-    if (!zc_i) HIP_TRY(hipMemcpyAsync(di, indices, ibytes, hipMemcpyHostToDevice, c->own_stream));
-    HIP_TRY(launch_gather_rows(c->d_rows, c->n, c->pitch, row_bytes, c->index_base, static_cast<const uint64_t*>(di),
+    if (!zc_i) MVF_HIP_TRY(hipMemcpyAsync(di, indices, ibytes, hipMemcpyHostToDevice, c->own_stream));
+    MVF_HIP_TRY(launch_gather_rows(c->d_rows, c->n, c->pitch, row_bytes, c->index_base, static_cast<const uint64_t*>(di),
                                (uint32_t)count, static_cast<unsigned char*>(dout), c->own_stream));
-    if (!zc_o) HIP_TRY(hipMemcpyAsync(out_rows, dout, obytes, hipMemcpyDeviceToHost, c->own_stream));
-    HIP_TRY(hipStreamSynchronize(c->own_stream));
+    if (!zc_o) MVF_HIP_TRY(hipMemcpyAsync(out_rows, dout, obytes, hipMemcpyDeviceToHost, c->own_stream));
+    MVF_HIP_TRY(hipStreamSynchronize(c->own_stream));
     if (zc_o) memcpy(out_rows, dout, obytes);
     return MVF_OK;
 }
@@ -2434,10 +2372,10 @@ int mvfgpu_corpus_gather_rows(const mvfgpu_corpus* c, const uint64_t* indices, u
 
 int mvfgpu_corpus_set_tombstones(mvfgpu_corpus* c, const uint8_t* bitmap, uint64_t first_bit, uint64_t nbits) {
     if (!c) return fail(MVF_ERR_INVALID_ARGUMENT, "corpus is NULL");
-    DeviceGuard guard(c->device);
+    DevScope guard(c->device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipDeviceSynchronize());  // searches in flight still read the old bitmap
+    MVF_HIP_TRY(hipDeviceSynchronize());  // searches in flight still read the old bitmap
     if (!bitmap || nbits == 0) {
         c->tomb.release();
         c->deleted = 0;
@@ -2460,18 +2398,18 @@ int mvfgpu_corpus_set_tombstones(mvfgpu_corpus* c, const uint8_t* bitmap, uint64
         c->deleted = 0;
         return MVF_OK;
     }
-    HIP_TRY(c->tomb.reserve((words + 1) * 4));
-    HIP_TRY(hipMemcpy(c->tomb.p, w.data(), (words + 1) * 4, hipMemcpyHostToDevice));
+    MVF_HIP_TRY(c->tomb.reserve((words + 1) * 4));
+    MVF_HIP_TRY(hipMemcpy(c->tomb.p, w.data(), (words + 1) * 4, hipMemcpyHostToDevice));
     c->deleted = dead;
     return MVF_OK;
 }
 
 int mvfgpu_corpus_set_vector_ids(mvfgpu_corpus* c, const void* ids_le, uint64_t n) {
     if (!c) return fail(MVF_ERR_INVALID_ARGUMENT, "corpus is NULL");
-    DeviceGuard guard(c->device);
+    DevScope guard(c->device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipDeviceSynchronize());
+    MVF_HIP_TRY(hipDeviceSynchronize());
     c->id_index.clear();
     if (!ids_le || n == 0) {
         c->ids.release();
@@ -2481,8 +2419,8 @@ int mvfgpu_corpus_set_vector_ids(mvfgpu_corpus* c, const void* ids_le, uint64_t 
     if (n != c->n) return fail(MVF_ERR_INVALID_ARGUMENT, "vector id count differs from the shard's row count");
     c->h_ids.resize(n);
     std::memcpy(c->h_ids.data(), ids_le, (size_t)n * 8);  // the block may sit at any alignment in the mapping
-    HIP_TRY(c->ids.reserve((size_t)n * 8));
-    HIP_TRY(hipMemcpy(c->ids.p, c->h_ids.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    MVF_HIP_TRY(c->ids.reserve((size_t)n * 8));
+    MVF_HIP_TRY(hipMemcpy(c->ids.p, c->h_ids.data(), (size_t)n * 8, hipMemcpyHostToDevice));
     return MVF_OK;
 }
 
@@ -2500,39 +2438,39 @@ int mvfgpu_search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_q
 namespace {
 // The search itself: profiling events, the route, its kernels on `s`.  The caller holds c->mu, has ordered `s` behind the
 // handle's newest work and records ev_done on every way out (search_device below; the join through corpus_device_call).
-int search_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
-                  uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
+int search_locked(const mvfgpu_corpus* c, SearchCall& sc) {
+    const uint8_t metric = sc.metric;
+    const uint32_t nq = sc.nq, k = sc.k;
+    hipStream_t s = sc.stream;
     int rc = MVF_OK;
-    c->launches = c->search_launches = 0;
-    c->launches_known = true;
+    c->search_launches = 0;
     mvfgpu_corpus::ProfSlot* wps = nullptr;  // whole-search events: every kernel of this call on the stream
     const uint64_t prof_before = c->prof_next;
     if (c->profiling) {
         wps = &c->prof[c->prof_next % mvfgpu_corpus::kProfSlots];
         for (auto& e : wps->e)
-            if (!e) HIP_TRY(hipEventCreate(&e));
+            if (!e) MVF_HIP_TRY(hipEventCreate(&e));
         wps->whole = wps->ts_whole = false;
     }
-    c->whole_by_clock = false;
     bool e3_recorded = false;
     if (k > MVFGPU_K_PER_PASS) {  // more results than one pass selects: the whole shard ranked by a sort, or passes of the exact streaming kernel
         uint32_t scans = 1;
         bool sorted = false;
-        if (wps) HIP_TRY(hipEventRecord(wps->e[3], s));
+        if (wps) MVF_HIP_TRY(hipEventRecord(wps->e[3], s));
         if (large_k_by_sort(c, nq, k)) {
             bool no_room = false;
-            rc = search_sorted_k(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s, &no_room);
+            rc = search_sorted_k(c, sc, &no_room);
             sorted = rc == MVF_OK;
             if (!sorted && !(no_room && k <= MVFGPU_K_BY_PASSES)) return rc;
         }
-        c->launches_known = false;
+        sc.launches_known = false;
         if (!sorted) {
-            rc = search_large_k(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s);
+            rc = search_large_k(c, sc);
             if (rc != MVF_OK) return rc;
             scans = (k + MVFGPU_K_PER_PASS - 1) / MVFGPU_K_PER_PASS;
         }
         if (wps && c->prof_next == prof_before + 1) {
-            HIP_TRY(hipEventRecord(wps->e[4], s));
+            MVF_HIP_TRY(hipEventRecord(wps->e[4], s));
             wps->whole = true;
             c->timing.search_flops = 2ull * nq * c->n * c->dim * scans;
             if (sorted) c->timing.scan_kernel = 8u;  // the streaming kernel as a dump + the whole-shard sort
@@ -2546,7 +2484,7 @@ int search_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
     // whole call, in front of whatever it builds first.  The route is only known behind those builds: where it was expected to time
     // itself and cannot (no room for the shadow, non-finite maxima) and the batched route answers, e[3] is recorded behind them too
     if (wps && !(stream_qs_wanted(c, nq, k) || (!stream_shadow_wanted(c, nq) && !use_batched_path(c, metric, nq)))) {
-        HIP_TRY(hipEventRecord(wps->e[3], s));
+        MVF_HIP_TRY(hipEventRecord(wps->e[3], s));
         e3_recorded = true;
     }
     if (stream_qs_wanted(c, nq, k)) {
@@ -2557,8 +2495,8 @@ int search_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
         qs_stream = c->shadow8_state == 1;
         if (qs_stream && c->scan_path == 0 && c->shadow8_finite < 0) {  // once per shadow: its bound maxima (one small wait)
             float st[4] = {0.f, 0.f, 0.f, 0.f};
-            HIP_TRY(hipMemcpyAsync(st, c->qs_stats.p, sizeof(st), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
+            MVF_HIP_TRY(hipMemcpyAsync(st, c->qs_stats.p, sizeof(st), hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipStreamSynchronize(s));
             c->shadow8_finite = std::isfinite(st[0]) && std::isfinite(st[1]) && std::isfinite(st[2]) && std::isfinite(st[3]) ? 1 : 0;
         }
         if (qs_stream && c->scan_path == 0 && c->shadow8_finite == 0) qs_stream = false;  // a row holds Inf / NaN: the stored rows
@@ -2572,21 +2510,21 @@ int search_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
     if (by_clock) {
         rc = prof_ts_ensure(c, s);
         if (rc != MVF_OK) return rc;
-        c->whole_by_clock = true;
+        sc.whole_by_clock = true;
     } else if (wps && !e3_recorded) {
-        HIP_TRY(hipEventRecord(wps->e[3], s));
+        MVF_HIP_TRY(hipEventRecord(wps->e[3], s));
     }
-    rc = qs_stream                           ? search_stream_qs_path(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s)
-         : shadow_stream                     ? search_stream_shadow_path(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s)
-         : use_batched_path(c, metric, nq) ? search_batched_path(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s)
-                                           : search_stream_path(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s);
+    rc = qs_stream                           ? search_stream_qs_path(c, sc)
+         : shadow_stream                     ? search_stream_shadow_path(c, sc)
+         : use_batched_path(c, metric, nq) ? search_batched_path(c, sc)
+                                           : search_stream_path(c, sc);
     if (rc != MVF_OK) return rc;
-    if (c->launches_known && (qs_stream || !(shadow_stream || use_batched_path(c, metric, nq)))) c->search_launches = c->launches;
+    if (sc.launches_known && (qs_stream || !(shadow_stream || use_batched_path(c, metric, nq)))) c->search_launches = sc.launches;
     if (wps && c->prof_next == prof_before + 1) {  // the path filled this slot
         if (by_clock) {
             wps->ts_whole = wps->ts_scan;  // (an empty corpus launches no scan: nothing to time)
         } else {
-            HIP_TRY(hipEventRecord(wps->e[4], s));
+            MVF_HIP_TRY(hipEventRecord(wps->e[4], s));
             wps->whole = true;
         }
         c->timing.search_flops = 2ull * nq * c->n * c->dim;
@@ -2599,28 +2537,15 @@ int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries,
                   uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, void* hip_stream, HostFlagReq* req) {
     int rc = check_query_args(c, metric, d_queries, query_dtype, query_dim, nq, k, d_scores, d_indices);
     if (rc != MVF_OK) return rc;
-    DeviceGuard guard(c->device);
+    DevScope guard(c->device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->work_gen++;
-    struct ReqGuard {  // the request belongs to this call only
-        const mvfgpu_corpus* c;
-        ~ReqGuard() { c->flag_req = nullptr; }
-    } req_guard{c};
-    c->flag_req = req;
-    c->one_search_call = true;
-    if (req) req->gen = c->work_gen;
-    // the scratch buffers are stream-ordered: a call on another stream waits for the previous one
-    if (c->has_done && c->last_stream != s) HIP_TRY(hipStreamWaitEvent(s, c->ev_done[c->done_idx], 0));
-    // Whatever happens below, work may already sit on the stream (norms, a shadow build, scratch): the next call on
-    // ANOTHER stream orders itself behind ev_done, so it is recorded on every way out.
-    struct DoneGuard {
-        const mvfgpu_corpus* c;
-        hipStream_t s;
-        ~DoneGuard() { record_done(c, s); }
-    } done_guard{c, s};
-    return search_locked(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s);  // ev_done: DoneGuard
+    return device_call(c, s, [&]() {  // a call that holds this one search
+        SearchCall sc{metric, d_queries, nq, k, d_scores, d_indices, d_raw, s};
+        sc.flag_req = req;
+        if (req) req->gen = c->work_gen;
+        return search_locked(c, sc);
+    });
 }
 }  // namespace
 
@@ -2630,7 +2555,7 @@ int search_host(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uin
                 uint32_t k, float* out_scores, uint64_t* out_indices, int32_t* out_raw, void* out_vectors) {
     int rc = check_query_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
     if (rc != MVF_OK) return rc;
-    DeviceGuard guard(c->device);
+    DevScope guard(c->device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     const size_t qbytes = (size_t)nq * c->dim * (is_int_dtype(c->dtype) ? 1 : 4);
     const size_t nres = (size_t)nq * k;
@@ -2664,41 +2589,41 @@ int search_host(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uin
         std::lock_guard<std::mutex> lk(c->mu);
         // wait for any in-flight user of the mirrors before (re)allocating them (nothing is in flight when the newest work
         // was seen complete through the flag: its event would only be signalled a few microseconds from now)
-        if (c->has_done && c->confirmed_gen != c->work_gen) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+        if (c->has_done && c->confirmed_gen != c->work_gen) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
         fused_fetch = out_vectors && c->h_ids.empty();
         if (zc_q) {
-            HIP_TRY(c->pin_q.reserve(qbytes));
+            MVF_HIP_TRY(c->pin_q.reserve(qbytes));
             memcpy(c->pin_q.p, queries, qbytes);
             dq = c->pin_q.p;
             if (mirror_q) {
-                HIP_TRY(c->h_q.reserve(qbytes));
+                MVF_HIP_TRY(c->h_q.reserve(qbytes));
                 dq = c->h_q.p;
-                HIP_TRY(hipMemcpyAsync(dq, c->pin_q.p, qbytes, hipMemcpyHostToDevice, c->own_stream));
+                MVF_HIP_TRY(hipMemcpyAsync(dq, c->pin_q.p, qbytes, hipMemcpyHostToDevice, c->own_stream));
             }
         } else {
-            HIP_TRY(c->h_q.reserve(qbytes));
+            MVF_HIP_TRY(c->h_q.reserve(qbytes));
             dq = c->h_q.p;
-            HIP_TRY(hipMemcpyAsync(dq, queries, qbytes, hipMemcpyHostToDevice, c->own_stream));
+            MVF_HIP_TRY(hipMemcpyAsync(dq, queries, qbytes, hipMemcpyHostToDevice, c->own_stream));
         }
         if (zc_out) {
-            HIP_TRY(c->pin_out.reserve(nres * 16));
+            MVF_HIP_TRY(c->pin_out.reserve(nres * 16));
             di = c->pin_out.p;  // u64[nres] | f32[nres] | i32[nres]
             ds = static_cast<unsigned char*>(c->pin_out.p) + nres * 8;
             dr = static_cast<unsigned char*>(c->pin_out.p) + nres * 12;
         } else {
-            HIP_TRY(c->h_s.reserve(nres * 4));
-            HIP_TRY(c->h_i.reserve(nres * 8));
-            HIP_TRY(c->h_r.reserve(nres * 4));
+            MVF_HIP_TRY(c->h_s.reserve(nres * 4));
+            MVF_HIP_TRY(c->h_i.reserve(nres * 8));
+            MVF_HIP_TRY(c->h_r.reserve(nres * 4));
             ds = c->h_s.p;
             di = c->h_i.p;
             dr = c->h_r.p;
         }
         if (fused_fetch) {
             if (zc_vec) {
-                HIP_TRY(c->pin_vec.reserve(vec_bytes));
+                MVF_HIP_TRY(c->pin_vec.reserve(vec_bytes));
                 dv = c->pin_vec.p;
             } else {
-                HIP_TRY(c->h_v.reserve(vec_bytes));
+                MVF_HIP_TRY(c->h_v.reserve(vec_bytes));
                 dv = c->h_v.p;
             }
         }
@@ -2708,10 +2633,10 @@ int search_host(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uin
     if (zc_out && c->tune.host_flag_wait && (!out_vectors || (fused_fetch && zc_vec && kv == k))) {
         std::lock_guard<std::mutex> lk(c->mu);
         if (!c->pin_flag.p) {
-            HIP_TRY(c->pin_flag.reserve(64));
+            MVF_HIP_TRY(c->pin_flag.reserve(64));
             *static_cast<volatile uint32_t*>(c->pin_flag.p) = 0;
-            HIP_TRY(c->done_ticket.reserve(256));
-            HIP_TRY(hipMemsetAsync(c->done_ticket.p, 0, 256, c->own_stream));
+            MVF_HIP_TRY(c->done_ticket.reserve(256));
+            MVF_HIP_TRY(hipMemsetAsync(c->done_ticket.p, 0, 256, c->own_stream));
         }
         req.flag = static_cast<uint32_t*>(c->pin_flag.p);
         req.ticket = static_cast<uint32_t*>(c->done_ticket.p);
@@ -2735,7 +2660,7 @@ int search_host(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uin
             if ((spins & 255u) == 255u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(300)) break;
             __builtin_ia32_pause();
         }
-        if (!seen) HIP_TRY(hipStreamSynchronize(c->own_stream));
+        if (!seen) MVF_HIP_TRY(hipStreamSynchronize(c->own_stream));
         {
             std::lock_guard<std::mutex> lk(c->mu);
             c->confirmed_gen = req.gen;  // == work_gen unless another thread has enqueued a search meanwhile
@@ -2747,19 +2672,19 @@ int search_host(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uin
         return MVF_OK;
     }
     if (fused_fetch)  // padding entries (index UINT64_MAX) among a query's first kv results give zero rows
-        HIP_TRY(launch_gather_rows(c->d_rows, c->n, c->pitch, row_bytes, c->index_base, static_cast<const uint64_t*>(di), (uint32_t)nvec,
+        MVF_HIP_TRY(launch_gather_rows(c->d_rows, c->n, c->pitch, row_bytes, c->index_base, static_cast<const uint64_t*>(di), (uint32_t)nvec,
                                    static_cast<unsigned char*>(dv), c->own_stream, k, kv));
     if (!zc_out) {
-        HIP_TRY(hipMemcpyAsync(out_scores, ds, nres * 4, hipMemcpyDeviceToHost, c->own_stream));
-        HIP_TRY(hipMemcpyAsync(out_indices, di, nres * 8, hipMemcpyDeviceToHost, c->own_stream));
-        if (out_raw) HIP_TRY(hipMemcpyAsync(out_raw, dr, nres * 4, hipMemcpyDeviceToHost, c->own_stream));
+        MVF_HIP_TRY(hipMemcpyAsync(out_scores, ds, nres * 4, hipMemcpyDeviceToHost, c->own_stream));
+        MVF_HIP_TRY(hipMemcpyAsync(out_indices, di, nres * 8, hipMemcpyDeviceToHost, c->own_stream));
+        if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(out_raw, dr, nres * 4, hipMemcpyDeviceToHost, c->own_stream));
     }
     if (fused_fetch && !zc_vec) {
-        if (kv == k) HIP_TRY(hipMemcpyAsync(out_vectors, dv, vec_bytes, hipMemcpyDeviceToHost, c->own_stream));
-        else HIP_TRY(hipMemcpy2DAsync(out_vectors, (size_t)k * row_bytes, dv, (size_t)kv * row_bytes, (size_t)kv * row_bytes, nq,
+        if (kv == k) MVF_HIP_TRY(hipMemcpyAsync(out_vectors, dv, vec_bytes, hipMemcpyDeviceToHost, c->own_stream));
+        else MVF_HIP_TRY(hipMemcpy2DAsync(out_vectors, (size_t)k * row_bytes, dv, (size_t)kv * row_bytes, (size_t)kv * row_bytes, nq,
                                       hipMemcpyDeviceToHost, c->own_stream));
     }
-    HIP_TRY(hipStreamSynchronize(c->own_stream));
+    MVF_HIP_TRY(hipStreamSynchronize(c->own_stream));
     if (zc_out) {
         memcpy(out_scores, ds, nres * 4);
         memcpy(out_indices, di, nres * 8);
@@ -2797,8 +2722,7 @@ int mvfgpu_merge_topk_host(const float* scores, const uint64_t* indices, const i
                            uint32_t nq, uint32_t k, uint8_t metric, uint8_t data_type, float* out_scores,
                            uint64_t* out_indices, int32_t* out_raw) {
     if (!scores || !indices || !out_scores || !out_indices) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code");
+    if (const int mrc = check_metric(metric)) return mrc;
     if (nlists == 0 || nq == 0 || k == 0) return fail(MVF_ERR_INVALID_ARGUMENT, "nlists, nq and k must be > 0");
     const bool use_raw = key_is_raw(data_type, metric) && raw != nullptr;
     struct Ent {
@@ -2843,14 +2767,13 @@ int merge_topk_device_impl(const float* d_scores, const uint64_t* d_indices, con
                            uint8_t data_type, float* d_out_scores, uint64_t* d_out_indices, int32_t* d_out_raw, int device,
                            void* hip_stream) {
     if (!d_scores || !d_indices || !d_out_scores || !d_out_indices) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code");
+    if (const int mrc = check_metric(metric)) return mrc;
     if (nlists == 0 || nq == 0 || k == 0) return fail(MVF_ERR_INVALID_ARGUMENT, "nlists, nq and k must be > 0");
     const uint64_t total = (uint64_t)nlists * k;
     if (total > 0xFFFFFFFFull) return fail(MVF_ERR_INVALID_ARGUMENT, "nlists * k exceeds 2^32 - 1");
     const bool large = total > kMergeMaxEntries;  // beyond one block's LDS: a device-wide sort per query
     const uint32_t P = large ? 0u : next_pow2(std::max(2u, nlists * k));
-    DeviceGuard guard(device);
+    DevScope guard(device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     ShardMergeParams p{};
     p.scores = d_scores;
@@ -2870,16 +2793,16 @@ int merge_topk_device_impl(const float* d_scores, const uint64_t* d_indices, con
     p.out_raw = d_out_raw;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (!large) {
-        HIP_TRY(launch_merge_shards(p, s));
+        MVF_HIP_TRY(launch_merge_shards(p, s));
         return MVF_OK;
     }
     // the sort's buffers live for this call only, in stream order (this entry point has no handle to keep them in)
     size_t tmp_bytes = 0;
-    HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)total, (size_t)p.k, nullptr, s));
+    MVF_HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, (size_t)total, (size_t)p.k, nullptr, s));
     tmp_bytes = std::max<size_t>(tmp_bytes, 256);
     const size_t cb = ((size_t)total * 8 + 255) & ~(size_t)255;
     void* scratch = nullptr;
-    HIP_TRY(hipMallocAsync(&scratch, 2 * cb + tmp_bytes, s));
+    MVF_HIP_TRY(hipMallocAsync(&scratch, 2 * cb + tmp_bytes, s));
     uint64_t *a = static_cast<uint64_t*>(scratch), *b = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(scratch) + cb);
     void* tmp = static_cast<unsigned char*>(scratch) + 2 * cb;
     hipError_t e = hipSuccess;
@@ -2891,8 +2814,8 @@ int merge_topk_device_impl(const float* d_scores, const uint64_t* d_indices, con
         if (e == hipSuccess) e = launch_merge_write(p, q, sorted, s);
     }
     const hipError_t ef = hipFreeAsync(scratch, s);
-    HIP_TRY(e);
-    HIP_TRY(ef);
+    MVF_HIP_TRY(e);
+    MVF_HIP_TRY(ef);
     return MVF_OK;
 }
 }  // namespace
@@ -2922,10 +2845,10 @@ int mvfgpu_synth_queries_device(void* d_queries, uint32_t nq, uint32_t dimension
                                 int device, void* hip_stream) {
     if (!d_queries) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
     if (elem_size(data_type) == 0) return fail(MVF_ERR_BUILD, "Unsupported vector data type");
-    DeviceGuard guard(device);
+    DevScope guard(device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     const uint8_t qd = is_int_dtype(data_type) ? data_type : (uint8_t)MVF_DTYPE_FLOAT32;
-    HIP_TRY(launch_synth_packed(d_queries, (uint64_t)nq * dimension, qd, seed, static_cast<hipStream_t>(hip_stream)));
+    MVF_HIP_TRY(launch_synth_packed(d_queries, (uint64_t)nq * dimension, qd, seed, static_cast<hipStream_t>(hip_stream)));
     return MVF_OK;
 }
 
@@ -2943,15 +2866,15 @@ int mvfgpu_last_timing(const mvfgpu_corpus* c, mvfgpu_timing* out) {
     std::lock_guard<std::mutex> lk(c->mu);
     mvfgpu_timing tm = c->timing;
     if (c->last_redo_cnt) {  // the newest batched search's repair count (waits for the handle's last search)
-        DeviceGuard guard(c->device);
-        if (c->has_done) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+        DevScope guard(c->device);
+        if (c->has_done) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
         uint32_t n = 0;
-        HIP_TRY(hipMemcpy(&n, c->last_redo_cnt, 4, hipMemcpyDeviceToHost));
+        MVF_HIP_TRY(hipMemcpy(&n, c->last_redo_cnt, 4, hipMemcpyDeviceToHost));
         tm.repaired_queries = n;
     }
     tm.search_launches = c->search_launches;
     if (c->prof_next > 0) {
-        DeviceGuard guard(c->device);
+        DevScope guard(c->device);
         const uint64_t newest = c->prof_next - 1;
         const uint64_t oldest = c->prof_next > mvfgpu_corpus::kProfSlots ? c->prof_next - mvfgpu_corpus::kProfSlots : 0;
         double ssum = 0, lsum = 0, wsum = 0;
@@ -2959,9 +2882,9 @@ int mvfgpu_last_timing(const mvfgpu_corpus* c, mvfgpu_timing* out) {
         std::vector<uint64_t> clk;  // the clock entries of the searches that timed themselves, behind the handle's newest call
         for (uint64_t i = oldest; i <= newest && clk.empty(); i++)
             if (c->prof[i % mvfgpu_corpus::kProfSlots].ts_scan && c->prof_ts.p) {
-                if (c->has_done) HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+                if (c->has_done) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
                 clk.resize((size_t)mvfgpu_corpus::kProfSlots * 4);
-                HIP_TRY(hipMemcpy(clk.data(), c->prof_ts.p, clk.size() * 8, hipMemcpyDeviceToHost));
+                MVF_HIP_TRY(hipMemcpy(clk.data(), c->prof_ts.p, clk.size() * 8, hipMemcpyDeviceToHost));
             }
         for (uint64_t i = newest + 1; i-- > oldest;) {
             const auto& ps = c->prof[i % mvfgpu_corpus::kProfSlots];
@@ -2976,15 +2899,15 @@ int mvfgpu_last_timing(const mvfgpu_corpus* c, mvfgpu_timing* out) {
                     wcnt++;
                 }
             } else {
-                HIP_TRY(hipEventSynchronize(ps.whole ? ps.e[4] : ps.e[2]));
+                MVF_HIP_TRY(hipEventSynchronize(ps.whole ? ps.e[4] : ps.e[2]));
             }
             if (ps.scanned && !ps.ts_scan) {
-                HIP_TRY(hipEventElapsedTime(&a, ps.e[0], ps.e[1]));
-                HIP_TRY(hipEventElapsedTime(&b, ps.e[1], ps.e[2]));
+                MVF_HIP_TRY(hipEventElapsedTime(&a, ps.e[0], ps.e[1]));
+                MVF_HIP_TRY(hipEventElapsedTime(&b, ps.e[1], ps.e[2]));
             }
             if (ps.whole) {
-                if (ps.ts_scan) HIP_TRY(hipEventSynchronize(ps.e[4]));
-                HIP_TRY(hipEventElapsedTime(&w, ps.e[3], ps.e[4]));
+                if (ps.ts_scan) MVF_HIP_TRY(hipEventSynchronize(ps.e[4]));
+                MVF_HIP_TRY(hipEventElapsedTime(&w, ps.e[3], ps.e[4]));
                 wsum += w;
                 wcnt++;
             }
@@ -3064,8 +2987,7 @@ int mvfgpu_selftest_route(uint64_t rows, uint32_t dimension, uint8_t data_type, 
     if (!out_route) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
     if (elem_size(data_type) == 0 || dimension == 0 || nq == 0 || k == 0 || k > MVFGPU_MAX_K)
         return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported type or empty dimension / batch / k");
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code");
+    if (const int mrc = check_metric(metric)) return mrc;
     // a handle that owns nothing on a device: the route is a function of these fields and the DEFAULT tuning (not the environment)
     std::unique_ptr<mvfgpu_corpus> c(new mvfgpu_corpus());
     c->n = rows;
@@ -3084,8 +3006,7 @@ int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_
     if (!out_rows) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
     if (elem_size(data_type) == 0 || dimension == 0 || nq == 0 || k == 0 || k > MVFGPU_MAX_K)
         return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported type or empty dimension / batch / k");
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code");
+    if (const int mrc = check_metric(metric)) return mrc;
     *out_rows = stream_i8_shape(rows, dimension, data_type, nq, k) ? 1u : 0u;
     return MVF_OK;
 }
@@ -3095,12 +3016,9 @@ int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_
 namespace mvf {
 int search_positions_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
                             uint64_t* d_indices, int32_t* d_raw, void* stream) {
-    struct Guard {  // the switch belongs to this search only
-        const mvfgpu_corpus* c;
-        ~Guard() { c->positions_only = false; }
-    } guard{c};
-    c->positions_only = true;
-    c->flag_req = nullptr;
-    return search_locked(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, static_cast<hipStream_t>(stream));
+    SearchCall sc{metric, d_queries, nq, k, d_scores, d_indices, d_raw, static_cast<hipStream_t>(stream)};
+    sc.positions_only = true;
+    sc.shared_call = true;  // corpus_device_call's body may run any number of searches
+    return search_locked(c, sc);
 }
 }  // namespace mvf

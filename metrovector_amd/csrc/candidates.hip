@@ -33,45 +33,12 @@ constexpr size_t kHostWindowBytes = 256ull << 20;   // the host call's device co
 constexpr size_t kPinnedBytes = 1ull << 20;         // host windows up to this size travel through the handle's pinned mirrors
 constexpr uint32_t kSelectMaxLists = 2048;          // chunk lists select_final merges (its P = 4096 >= lists + k)
 
-#define CAND_TRY(expr)                                                                                \
-    do {                                                                                              \
-        hipError_t e__ = (expr);                                                                      \
-        if (e__ != hipSuccess)                                                                        \
-            return set_fail(MVF_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));      \
-    } while (0)
-
-struct DevScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DevScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DevScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-// stream-ordered scratch, released on every way out
-struct AsyncBuf {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    hipError_t alloc(size_t bytes, hipStream_t st) {
-        s = st;
-        return bytes ? hipMallocAsync(&p, bytes, st) : hipSuccess;
-    }
-    ~AsyncBuf() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
 int check_candidate_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                          uint32_t nq, const uint64_t* candidates, uint32_t m, uint32_t k, const void* out_scores,
                          const void* out_indices) {
     // what needs no handle first (mvfgpu_search's codes and messages), then mvfgpu_search's own checks: nothing below
     // touches the device on a refusal
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code " + std::to_string(metric));
+    if (const int mrc = check_metric(metric)) return mrc;
     if (nq == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
     if (k == 0 || k > MVFGPU_MAX_K) return set_fail(MVF_ERR_INVALID_ARGUMENT, "k must be in 1..2^31");
     if (!queries || !out_scores || !out_indices) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
@@ -84,10 +51,10 @@ int candidates_core(const CorpusView& v, uint8_t metric, const void* d_queries, 
                     uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, uint64_t* d_counts, hipStream_t s) {
     const size_t nres = (size_t)nq * k;
     if (m == 0) {  // nothing listed: counts 0, every entry padding
-        CAND_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores), (int)f32_bits(pad_score(metric)), nres, s));
-        CAND_TRY(hipMemsetAsync(d_indices, 0xFF, nres * 8, s));
-        if (d_raw) CAND_TRY(hipMemsetAsync(d_raw, 0, nres * 4, s));
-        if (d_counts) CAND_TRY(hipMemsetAsync(d_counts, 0, (size_t)nq * 8, s));
+        MVF_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores), (int)f32_bits(pad_score(metric)), nres, s));
+        MVF_HIP_TRY(hipMemsetAsync(d_indices, 0xFF, nres * 8, s));
+        if (d_raw) MVF_HIP_TRY(hipMemsetAsync(d_raw, 0, nres * 4, s));
+        if (d_counts) MVF_HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)nq * 8, s));
         return MVF_OK;
     }
     int G = 64;
@@ -101,17 +68,17 @@ int candidates_core(const CorpusView& v, uint8_t metric, const void* d_queries, 
     const size_t per_q = (size_t)m * 4 + 4 + ((long_lists || by_sort) ? (size_t)m * 16 : 0) + (by_sort ? 0 : (size_t)nch * kcap * 8);
     const uint32_t W = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)nq, (size_t)kWindow, kScratchBytes / per_q}));
     size_t tmp_bytes = 0;
-    if (long_lists || by_sort) CAND_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, m, m, nullptr, s, W, m));
+    if (long_lists || by_sort) MVF_HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, m, m, nullptr, s, W, m));
 
     AsyncBuf drows, dcnt, da, db, dtmp, dlists;
-    CAND_TRY(drows.alloc((size_t)W * m * 4, s));
-    CAND_TRY(dcnt.alloc((size_t)W * 4, s));
+    MVF_HIP_TRY(drows.alloc((size_t)W * m * 4, s));
+    MVF_HIP_TRY(dcnt.alloc((size_t)W * 4, s));
     if (long_lists || by_sort) {
-        CAND_TRY(da.alloc((size_t)W * m * 8, s));
-        CAND_TRY(db.alloc((size_t)W * m * 8, s));
-        CAND_TRY(dtmp.alloc(tmp_bytes, s));
+        MVF_HIP_TRY(da.alloc((size_t)W * m * 8, s));
+        MVF_HIP_TRY(db.alloc((size_t)W * m * 8, s));
+        MVF_HIP_TRY(dtmp.alloc(tmp_bytes, s));
     }
-    if (!by_sort) CAND_TRY(dlists.alloc((size_t)W * nch * kcap * 8, s));
+    if (!by_sort) MVF_HIP_TRY(dlists.alloc((size_t)W * nch * kcap * 8, s));
 
     SelectParams fp{};
     fp.k = k;
@@ -136,13 +103,13 @@ int candidates_core(const CorpusView& v, uint8_t metric, const void* d_queries, 
         pp.counts = static_cast<uint32_t*>(dcnt.p);
         pp.out_counts = d_counts ? d_counts + w0 : nullptr;
         if (!long_lists) {
-            CAND_TRY(cand_prep_launch(pp, wn, s));
+            MVF_HIP_TRY(cand_prep_launch(pp, wn, s));
         } else {
-            CAND_TRY(cand_map_launch(pp, wn, s));
+            MVF_HIP_TRY(cand_map_launch(pp, wn, s));
             size_t tb = tmp_bytes;
             uint64_t* sorted = nullptr;
-            CAND_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), m, m, &sorted, s, wn, m));
-            CAND_TRY(cand_compact_launch(pp, sorted, wn, s));
+            MVF_HIP_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), m, m, &sorted, s, wn, m));
+            MVF_HIP_TRY(cand_compact_launch(pp, sorted, wn, s));
         }
         // C1
         CandScoreParams sp{};
@@ -158,7 +125,7 @@ int candidates_core(const CorpusView& v, uint8_t metric, const void* d_queries, 
         if (!by_sort) {
             sp.lists = static_cast<uint64_t*>(dlists.p);
             sp.kcap = kcap;
-            CAND_TRY(cand_score_launch(v.dtype, metric, G, sp, wn, s));
+            MVF_HIP_TRY(cand_score_launch(v.dtype, metric, G, sp, wn, s));
             // K3: the chunks' lists merged, formatted (ids, index_base, raw, padding)
             fp.lists = sp.lists;
             fp.nlists = nch;
@@ -168,15 +135,15 @@ int candidates_core(const CorpusView& v, uint8_t metric, const void* d_queries, 
             fp.out_scores = d_scores + (size_t)w0 * k;
             fp.out_indices = d_indices + (size_t)w0 * k;
             fp.out_raw = d_raw ? d_raw + (size_t)w0 * k : nullptr;
-            CAND_TRY(launch_select_final(fp, wn, s));
+            MVF_HIP_TRY(launch_select_final(fp, wn, s));
         } else {
             sp.dump = static_cast<uint64_t*>(da.p);
-            CAND_TRY(cand_score_launch(v.dtype, metric, G, sp, wn, s));
+            MVF_HIP_TRY(cand_score_launch(v.dtype, metric, G, sp, wn, s));
             size_t tb = tmp_bytes;
             uint64_t* sorted = nullptr;
-            CAND_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), m,
+            MVF_HIP_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), m,
                                      std::min<size_t>(k, m), &sorted, s, wn, m));
-            for (uint32_t i = 0; i < wn; i++) CAND_TRY(launch_write_sorted(fp, sorted + (size_t)i * m, m, (size_t)(w0 + i) * k, s));
+            for (uint32_t i = 0; i < wn; i++) MVF_HIP_TRY(launch_write_sorted(fp, sorted + (size_t)i * m, m, (size_t)(w0 + i) * k, s));
         }
     }
     return MVF_OK;
@@ -213,12 +180,12 @@ int mvfgpu_search_candidates(const mvfgpu_corpus* c, uint8_t metric, const void*
     const size_t in_q = qrow + (size_t)m * 8, out_q = (size_t)k * 16 + 8;  // bytes per query in / out
     const uint32_t W = (uint32_t)std::max<size_t>(1, std::min<size_t>(nq, kHostWindowBytes / (in_q + out_q)));
     AsyncBuf dq, dcand, dsc, didx, draw, dcnt;
-    CAND_TRY(dq.alloc((size_t)W * qrow, s));
-    CAND_TRY(dcand.alloc((size_t)W * m * 8, s));
-    CAND_TRY(dsc.alloc((size_t)W * k * 4, s));
-    CAND_TRY(didx.alloc((size_t)W * k * 8, s));
-    if (out_raw) CAND_TRY(draw.alloc((size_t)W * k * 4, s));
-    CAND_TRY(dcnt.alloc((size_t)W * 8, s));
+    MVF_HIP_TRY(dq.alloc((size_t)W * qrow, s));
+    MVF_HIP_TRY(dcand.alloc((size_t)W * m * 8, s));
+    MVF_HIP_TRY(dsc.alloc((size_t)W * k * 4, s));
+    MVF_HIP_TRY(didx.alloc((size_t)W * k * 8, s));
+    if (out_raw) MVF_HIP_TRY(draw.alloc((size_t)W * k * 4, s));
+    MVF_HIP_TRY(dcnt.alloc((size_t)W * 8, s));
     std::vector<uint64_t> mapped;
     for (uint32_t w0 = 0; w0 < nq; w0 += W) {
         const uint32_t wn = std::min(W, nq - w0);
@@ -244,27 +211,27 @@ int mvfgpu_search_candidates(const mvfgpu_corpus* c, uint8_t metric, const void*
         }
         const size_t o_sc = nr * 8, o_raw = nr * 12, o_cnt = nr * 16;
         const int rc = corpus_device_call(c, s, [&]() -> int {
-            CAND_TRY(hipMemcpyAsync(dq.p, pinned ? pin_in : hq, (size_t)wn * qrow, hipMemcpyHostToDevice, s));
-            if (nl) CAND_TRY(hipMemcpyAsync(dcand.p, pinned ? pin_in + (size_t)wn * qrow : reinterpret_cast<const unsigned char*>(hc), nl * 8,
+            MVF_HIP_TRY(hipMemcpyAsync(dq.p, pinned ? pin_in : hq, (size_t)wn * qrow, hipMemcpyHostToDevice, s));
+            if (nl) MVF_HIP_TRY(hipMemcpyAsync(dcand.p, pinned ? pin_in + (size_t)wn * qrow : reinterpret_cast<const unsigned char*>(hc), nl * 8,
                                             hipMemcpyHostToDevice, s));
             const int rc1 = candidates_core(v, metric, dq.p, wn, static_cast<const uint64_t*>(dcand.p), m, k, static_cast<float*>(dsc.p),
                                             static_cast<uint64_t*>(didx.p), static_cast<int32_t*>(draw.p), static_cast<uint64_t*>(dcnt.p), s);
             if (rc1 != MVF_OK) return rc1;
             if (pinned) {
-                CAND_TRY(hipMemcpyAsync(pin_out, didx.p, nr * 8, hipMemcpyDeviceToHost, s));
-                CAND_TRY(hipMemcpyAsync(pin_out + o_sc, dsc.p, nr * 4, hipMemcpyDeviceToHost, s));
-                if (out_raw) CAND_TRY(hipMemcpyAsync(pin_out + o_raw, draw.p, nr * 4, hipMemcpyDeviceToHost, s));
-                CAND_TRY(hipMemcpyAsync(pin_out + o_cnt, dcnt.p, (size_t)wn * 8, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipMemcpyAsync(pin_out, didx.p, nr * 8, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipMemcpyAsync(pin_out + o_sc, dsc.p, nr * 4, hipMemcpyDeviceToHost, s));
+                if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(pin_out + o_raw, draw.p, nr * 4, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipMemcpyAsync(pin_out + o_cnt, dcnt.p, (size_t)wn * 8, hipMemcpyDeviceToHost, s));
             } else {
-                CAND_TRY(hipMemcpyAsync(out_indices + (size_t)w0 * k, didx.p, nr * 8, hipMemcpyDeviceToHost, s));
-                CAND_TRY(hipMemcpyAsync(out_scores + (size_t)w0 * k, dsc.p, nr * 4, hipMemcpyDeviceToHost, s));
-                if (out_raw) CAND_TRY(hipMemcpyAsync(out_raw + (size_t)w0 * k, draw.p, nr * 4, hipMemcpyDeviceToHost, s));
-                if (out_counts) CAND_TRY(hipMemcpyAsync(out_counts + w0, dcnt.p, (size_t)wn * 8, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipMemcpyAsync(out_indices + (size_t)w0 * k, didx.p, nr * 8, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipMemcpyAsync(out_scores + (size_t)w0 * k, dsc.p, nr * 4, hipMemcpyDeviceToHost, s));
+                if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(out_raw + (size_t)w0 * k, draw.p, nr * 4, hipMemcpyDeviceToHost, s));
+                if (out_counts) MVF_HIP_TRY(hipMemcpyAsync(out_counts + w0, dcnt.p, (size_t)wn * 8, hipMemcpyDeviceToHost, s));
             }
             return MVF_OK;
         });
         if (rc != MVF_OK) return rc;
-        CAND_TRY(hipStreamSynchronize(s));
+        MVF_HIP_TRY(hipStreamSynchronize(s));
         if (pinned) {
             std::memcpy(out_indices + (size_t)w0 * k, pin_out, nr * 8);
             std::memcpy(out_scores + (size_t)w0 * k, pin_out + o_sc, nr * 4);

@@ -3,6 +3,9 @@
 
 #include "../../include/mvf_status.h"
 
+#include "mvf_common.h"
+#include "scan_stream.h"
+
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -15,6 +18,47 @@ namespace mvf {
 
 // records the calling thread's failure detail (mvfgpu_last_error_message) and returns `status`
 int set_fail(int status, const std::string& msg);
+
+// a HIP call that fails ends the function with MVF_ERR_DEVICE and the call's text + the runtime's message as the detail
+#define MVF_HIP_TRY(expr)                                                                                  \
+    do {                                                                                                   \
+        hipError_t e__ = (expr);                                                                           \
+        if (e__ != hipSuccess)                                                                             \
+            return mvf::set_fail(MVF_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));      \
+    } while (0)
+
+// the metric code of every entry point that takes one
+inline int check_metric(uint8_t metric) {
+    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code " + std::to_string(metric));
+    return MVF_OK;
+}
+
+// the calling thread's current device set to `dev` for a scope
+struct DevScope {
+    int prev = -1;
+    bool ok = false;
+    explicit DevScope(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DevScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// stream-ordered scratch, released on every way out
+struct AsyncBuf {
+    void* p = nullptr;
+    hipStream_t s = nullptr;
+    hipError_t alloc(size_t bytes, hipStream_t st) {
+        s = st;
+        return bytes ? hipMallocAsync(&p, bytes, st) : hipSuccess;
+    }
+    ~AsyncBuf() {
+        if (p) (void)hipFreeAsync(p, s);
+    }
+};
 
 // Out-structs of the C ABI start with a caller-set `struct_size` (include/mvf_gpu.h "OUT-STRUCTS GROW"): copy at most
 // that many bytes of `full` and report how many were filled.
@@ -77,6 +121,26 @@ std::mutex& corpus_host_mutex(const mvfgpu_corpus* c);  // serialises the host-b
 int corpus_row_norms(const mvfgpu_corpus* c, void* stream, const float** xnorm, const float** xx2, const float** xxmax);
 // K1's lane-group width for rows of V 16-byte vectors and nqv queries per pass (MVF_K1_G forces one: `forced`)
 void k1_group(uint32_t V, int nqv, int forced, int* G, uint32_t* J);
+// The shape of one pass of K1 -- or of R1, the radius kernel built on it -- over rows of V vectors with `queries` queries
+// left to serve at list length k: four queries per pass from two queries on (one read of the rows instead of two to four),
+// one per pass where the four-query LDS tile exceeds 150 KiB.  lds_bytes(G, J, nqv, pmax) is the kernel's own LDS formula;
+// the caller refuses a shape whose `lds` exceeds the part's 160 KiB with its own message.
+struct K1Shape {
+    int nqv = 1, G = 64;                       // queries per pass, lanes per row
+    uint32_t J = 1, chunk_rows = 0, pmax = 0;  // 16-byte steps per lane and row, rows per chunk, LDS list entries per query
+    size_t lds = 0;
+};
+template <class LdsBytes>
+inline K1Shape k1_pass_shape(uint32_t V, uint32_t queries, uint32_t k, int forced, LdsBytes lds_bytes) {
+    K1Shape sh;
+    for (sh.nqv = queries >= 2 ? 4 : 1;; sh.nqv = 1) {
+        k1_group(V, sh.nqv, forced, &sh.G, &sh.J);  // the lane-group width depends on the queries per pass
+        sh.chunk_rows = scan_chunk_rows(sh.G, sh.J, sh.nqv);
+        sh.pmax = next_pow2(k + scan_chunk_safe(sh.G));
+        sh.lds = lds_bytes(sh.G, sh.J, sh.nqv, sh.pmax);
+        if (sh.nqv == 1 || sh.lds <= 150 * 1024) return sh;
+    }
+}
 // mvfgpu_search's argument checks (k = 1 .. MVFGPU_MAX_K, non-NULL query and output buffers)
 int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                       uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices);
@@ -87,8 +151,9 @@ bool corpus_ids_to_positions(const mvfgpu_corpus* c, const uint64_t* ids, uint64
 // The handle's pinned host mirrors of the host-buffer calls (search_host's), at least in_bytes / out_bytes; the caller holds
 // corpus_host_mutex.  Waits for the handle's newest work first: a search may still write the old ones in place.
 int corpus_pinned_mirrors(const mvfgpu_corpus* c, size_t in_bytes, size_t out_bytes, void** pin_in, void** pin_out);
-// mvfgpu_search_device's stream discipline around `body`, which enqueues work on `stream`: under the handle's lock, ordered
-// behind the handle's newest work on another stream (ev_done), and ev_done recorded on `stream` on every way out.
+// mvfgpu_search_device's stream discipline around `body`, which enqueues work on `stream` -- any number of searches among
+// it: under the handle's lock, ordered behind the handle's newest work on another stream (ev_done), and ev_done recorded on
+// `stream` on every way out.
 int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function<int()>& body);
 // mvfgpu_search_device's search -- its routes, kernels, repair feedback and timing -- for a caller that already runs under
 // corpus_device_call(c, stream, ...): no argument checks, the handle's lock is not taken again, and the id mapping of the final

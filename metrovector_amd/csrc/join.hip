@@ -27,38 +27,6 @@ namespace {
 
 constexpr size_t kPinnedWindowBytes = 64ull << 20;  // a window's results up to this size leave through pinned memory
 
-#define JOIN_TRY(expr)                                                                                \
-    do {                                                                                              \
-        hipError_t e__ = (expr);                                                                      \
-        if (e__ != hipSuccess)                                                                        \
-            return set_fail(MVF_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));      \
-    } while (0)
-
-struct DevScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DevScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DevScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-// stream-ordered scratch, released on every way out
-struct AsyncBuf {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    hipError_t alloc(size_t bytes, hipStream_t st) {
-        s = st;
-        return bytes ? hipMallocAsync(&p, bytes, st) : hipSuccess;
-    }
-    ~AsyncBuf() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
 struct PinnedBuf {
     void* p = nullptr;
     hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes, hipHostMallocDefault); }
@@ -103,8 +71,7 @@ int plan_join(const mvfgpu_corpus* c, const mvfgpu_corpus* qc, uint8_t metric, u
               const void* out_scores, const void* out_indices, JoinPlan* plan) {
     // what needs no handle first, as in the other searches
     if (flags & ~(uint32_t)MVFGPU_JOIN_EXCLUDE_SELF) return set_fail(MVF_ERR_INVALID_ARGUMENT, "unknown join flag bits " + std::to_string(flags));
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code " + std::to_string(metric));
+    if (const int mrc = check_metric(metric)) return mrc;
     const bool exclude = (flags & MVFGPU_JOIN_EXCLUDE_SELF) != 0;
     if (k == 0 || k > MVFGPU_MAX_K - (exclude ? 1u : 0u))
         return set_fail(MVF_ERR_INVALID_ARGUMENT, exclude ? "k must be in 1..2^31 - 1 with MVFGPU_JOIN_EXCLUDE_SELF" : "k must be in 1..2^31");
@@ -143,10 +110,10 @@ int both_device_call(const JoinPlan& p, hipStream_t s, const std::function<int()
 struct WindowScratch {
     AsyncBuf dq, ds, di, dr;
     int alloc(const JoinPlan& p, uint32_t W, bool raw, hipStream_t s) {
-        JOIN_TRY(dq.alloc((size_t)W * p.qrow, s));
-        JOIN_TRY(ds.alloc((size_t)W * p.kin * 4, s));
-        JOIN_TRY(di.alloc((size_t)W * p.kin * 8, s));
-        if (raw) JOIN_TRY(dr.alloc((size_t)W * p.kin * 4, s));
+        MVF_HIP_TRY(dq.alloc((size_t)W * p.qrow, s));
+        MVF_HIP_TRY(ds.alloc((size_t)W * p.kin * 4, s));
+        MVF_HIP_TRY(di.alloc((size_t)W * p.kin * 8, s));
+        if (raw) MVF_HIP_TRY(dr.alloc((size_t)W * p.kin * 4, s));
         return MVF_OK;
     }
 };
@@ -162,7 +129,7 @@ int join_window(const JoinPlan& p, uint8_t metric, uint64_t row0, uint32_t wn, c
     sp.dtype = p.vq.dtype;
     sp.first = row0;
     sp.queries = w.dq.p;
-    JOIN_TRY(join_stage_launch(sp, wn, s));
+    MVF_HIP_TRY(join_stage_launch(sp, wn, s));
     const int rc = search_positions_locked(p.C, metric, w.dq.p, wn, p.kin, static_cast<float*>(w.ds.p), static_cast<uint64_t*>(w.di.p),
                                            out_raw ? static_cast<int32_t*>(w.dr.p) : nullptr, s);
     if (rc != MVF_OK) return rc;
@@ -182,7 +149,7 @@ int join_window(const JoinPlan& p, uint8_t metric, uint64_t row0, uint32_t wn, c
     fp.out_scores = out_scores;
     fp.out_indices = out_indices;
     fp.out_raw = out_raw;
-    JOIN_TRY(join_finish_launch(fp, wn, s));
+    MVF_HIP_TRY(join_finish_launch(fp, wn, s));
     return MVF_OK;
 }
 
@@ -230,17 +197,17 @@ int mvfgpu_knn_join(const mvfgpu_corpus* corpus, const mvfgpu_corpus* query_corp
     AsyncBuf res[2];  // two windows of results: one is copied out while the other is written
     WindowScratch w;
     CopyLane lane;
-    JOIN_TRY(lane.create());
+    MVF_HIP_TRY(lane.create());
     if (pinned)
-        for (auto& b : pin) JOIN_TRY(b.alloc(wbytes));
+        for (auto& b : pin) MVF_HIP_TRY(b.alloc(wbytes));
     {
         const int rc = w.alloc(p, W, out_raw != nullptr, s);
         if (rc != MVF_OK) return rc;
-        for (auto& r : res) JOIN_TRY(r.alloc(wbytes, s));
+        for (auto& r : res) MVF_HIP_TRY(r.alloc(wbytes, s));
     }
     // window w's results are the caller's once its copy has finished: a wait on the COPY stream's event, never on the search stream
     auto drain = [&](uint64_t off, int b) -> int {
-        JOIN_TRY(hipEventSynchronize(lane.copied[b]));
+        MVF_HIP_TRY(hipEventSynchronize(lane.copied[b]));
         if (pinned) {
             const size_t nr = (size_t)std::min<uint64_t>(W, count - off) * k;
             const unsigned char* src = static_cast<const unsigned char*>(pin[b].p);
@@ -256,23 +223,23 @@ int mvfgpu_knn_join(const mvfgpu_corpus* corpus, const mvfgpu_corpus* query_corp
         const size_t nr = (size_t)wn * k;
         unsigned char* r = static_cast<unsigned char*>(res[b].p);
         int rc = both_device_call(p, s, [&]() -> int {
-            if (off >= 2ull * W) JOIN_TRY(hipStreamWaitEvent(s, lane.copied[b], 0));  // the copy of two windows ago read this buffer
+            if (off >= 2ull * W) MVF_HIP_TRY(hipStreamWaitEvent(s, lane.copied[b], 0));  // the copy of two windows ago read this buffer
             const int rc1 = join_window(p, metric, first + off, wn, w, reinterpret_cast<float*>(r + o_sc), reinterpret_cast<uint64_t*>(r),
                                         out_raw ? reinterpret_cast<int32_t*>(r + o_raw) : nullptr, s);
             if (rc1 != MVF_OK) return rc1;
-            JOIN_TRY(hipEventRecord(lane.finished[b], s));
+            MVF_HIP_TRY(hipEventRecord(lane.finished[b], s));
             return MVF_OK;
         });
         if (rc != MVF_OK) return rc;
-        JOIN_TRY(hipStreamWaitEvent(lane.cs, lane.finished[b], 0));
+        MVF_HIP_TRY(hipStreamWaitEvent(lane.cs, lane.finished[b], 0));
         if (pinned) {
-            JOIN_TRY(hipMemcpyAsync(pin[b].p, r, out_raw ? o_raw + nr * 4 : o_sc + nr * 4, hipMemcpyDeviceToHost, lane.cs));
+            MVF_HIP_TRY(hipMemcpyAsync(pin[b].p, r, out_raw ? o_raw + nr * 4 : o_sc + nr * 4, hipMemcpyDeviceToHost, lane.cs));
         } else {
-            JOIN_TRY(hipMemcpyAsync(out_indices + off * k, r, nr * 8, hipMemcpyDeviceToHost, lane.cs));
-            JOIN_TRY(hipMemcpyAsync(out_scores + off * k, r + o_sc, nr * 4, hipMemcpyDeviceToHost, lane.cs));
-            if (out_raw) JOIN_TRY(hipMemcpyAsync(out_raw + off * k, r + o_raw, nr * 4, hipMemcpyDeviceToHost, lane.cs));
+            MVF_HIP_TRY(hipMemcpyAsync(out_indices + off * k, r, nr * 8, hipMemcpyDeviceToHost, lane.cs));
+            MVF_HIP_TRY(hipMemcpyAsync(out_scores + off * k, r + o_sc, nr * 4, hipMemcpyDeviceToHost, lane.cs));
+            if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(out_raw + off * k, r + o_raw, nr * 4, hipMemcpyDeviceToHost, lane.cs));
         }
-        JOIN_TRY(hipEventRecord(lane.copied[b], lane.cs));
+        MVF_HIP_TRY(hipEventRecord(lane.copied[b], lane.cs));
         if (off > 0) {  // the window before this one, while this one is searched
             rc = drain(off - W, b ^ 1);
             if (rc != MVF_OK) return rc;

@@ -28,38 +28,6 @@ namespace {
 
 constexpr uint32_t kWindow = 1024;  // queries per window: lists 64 MiB, entries up to 128 MiB of device memory
 
-#define RAD_TRY(expr)                                                                                 \
-    do {                                                                                              \
-        hipError_t e__ = (expr);                                                                      \
-        if (e__ != hipSuccess)                                                                        \
-            return set_fail(MVF_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));      \
-    } while (0)
-
-struct DevScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DevScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DevScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-// stream-ordered scratch, released on every way out
-struct AsyncBuf {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    hipError_t alloc(size_t bytes, hipStream_t st) {
-        s = st;
-        return bytes ? hipMallocAsync(&p, bytes, st) : hipSuccess;
-    }
-    ~AsyncBuf() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-};
-
 // The largest R >= 0 with sqrtf((float)R) <= radius (L2 on the exact sum of squared differences); -1 when there is none.
 int32_t l2_raw_bound(float radius) {
     if (!(0.0f <= radius)) return -1;
@@ -148,8 +116,7 @@ extern "C" {
 int mvfgpu_selftest_radius_bound(uint8_t data_type, uint8_t metric, float radius, uint32_t* out_key, int32_t* out_raw) {
     if (!out_key) return set_fail(MVF_ERR_INVALID_ARGUMENT, "out_key is NULL");
     if (elem_size(data_type) == 0) return set_fail(MVF_ERR_BUILD, "Unsupported vector data type");
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code " + std::to_string(metric));
+    if (const int mrc = check_metric(metric)) return mrc;
     if (std::isnan(radius)) return set_fail(MVF_ERR_INVALID_ARGUMENT, "radius is NaN");
     *out_key = radius_bound_key(data_type, metric, radius, out_raw);
     return MVF_OK;
@@ -167,8 +134,7 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                          uint32_t nq, const float* radii, uint64_t max_per_query, uint64_t* out_counts, float* out_scores,
                          uint64_t* out_indices, int32_t* out_raw) {
     // everything that needs no handle first, then mvfgpu_search's own checks: nothing below touches the device on a refusal
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code " + std::to_string(metric));
+    if (const int mrc = check_metric(metric)) return mrc;
     if (nq == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
     if (!queries || !radii || !out_counts) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
     if (max_per_query > MVFGPU_MAX_K) return set_fail(MVF_ERR_INVALID_ARGUMENT, "max_per_query must be in 0..2^31");
@@ -195,21 +161,17 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
         std::vector<uint32_t> bound(nq);
         for (uint32_t q = 0; q < nq; q++) bound[q] = radius_bound_key(v.dtype, metric, radii[q], nullptr);
         hipStream_t s = static_cast<hipStream_t>(v.stream);
-        // R1's shape for this batch: four queries per pass from two on (one read of the rows instead of two or three)
-        int nqv = nq >= 2 ? 4 : 1, G = 64;
-        uint32_t J = 1;
-        k1_group(v.V, nqv, v.k1_g, &G, &J);
-        size_t lds = radius_scan_lds_bytes(v.dtype, G, J, nqv);
-        if (lds > 150 * 1024 && nqv == 4) {
-            nqv = 1;
-            k1_group(v.V, nqv, v.k1_g, &G, &J);
-            lds = radius_scan_lds_bytes(v.dtype, G, J, nqv);
-        }
+        // R1's shape for this batch: K1's rule with R1's LDS formula (it keeps no lists in LDS: k and pmax do not matter)
+        const K1Shape sh = k1_pass_shape(v.V, nq, 0, v.k1_g,
+                                         [&](int G, uint32_t J, int nqv, uint32_t) { return radius_scan_lds_bytes(v.dtype, G, J, nqv); });
+        const int nqv = sh.nqv, G = sh.G;
+        const uint32_t J = sh.J;
+        const size_t lds = sh.lds;
         if (lds > 160 * 1024) return set_fail(MVF_ERR_BUILD, "dimension too large for the radius kernel's LDS query tile");
         const void* fn = radius_scan_kernel_ptr(v.dtype, metric, G, nqv);
         if (!fn) return set_fail(MVF_ERR_BUILD, "no radius kernel for this shape");
         int occ = 1;
-        RAD_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, lds));
+        MVF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, lds));
         occ = std::max(occ, 1);
         const uint64_t rows_per_block_step = 16ull * 64u / (uint32_t)G;  // 4 waves x U = 4 groups x 64/G rows
         const uint32_t nblk = (uint32_t)std::max<uint64_t>(
@@ -217,14 +179,14 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
 
         const uint32_t W = std::min(nq, kWindow);
         AsyncBuf dq, dbound, dcnt, dlist, dsc, didx, draw;
-        RAD_TRY(dq.alloc((size_t)W * qbytes, s));
-        RAD_TRY(dbound.alloc((size_t)W * 4, s));
-        RAD_TRY(dcnt.alloc((size_t)W * 4, s));
+        MVF_HIP_TRY(dq.alloc((size_t)W * qbytes, s));
+        MVF_HIP_TRY(dbound.alloc((size_t)W * 4, s));
+        MVF_HIP_TRY(dcnt.alloc((size_t)W * 4, s));
         if (maxq > 0) {
-            RAD_TRY(dlist.alloc((size_t)W * cap * 8, s));
-            RAD_TRY(dsc.alloc((size_t)W * kk * 4, s));
-            RAD_TRY(didx.alloc((size_t)W * kk * 8, s));
-            RAD_TRY(draw.alloc((size_t)W * kk * 4, s));
+            MVF_HIP_TRY(dlist.alloc((size_t)W * cap * 8, s));
+            MVF_HIP_TRY(dsc.alloc((size_t)W * kk * 4, s));
+            MVF_HIP_TRY(didx.alloc((size_t)W * kk * 8, s));
+            MVF_HIP_TRY(draw.alloc((size_t)W * kk * 4, s));
         }
         std::vector<uint32_t> hcnt(W), hccnt(W);
         std::vector<float> hsc(maxq > 0 ? (size_t)W * kk : 0);
@@ -239,9 +201,9 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                 std::memcpy(hq.data() + (size_t)i * qbytes, static_cast<const unsigned char*>(queries) + (size_t)sel[w0 + i] * qbytes, qbytes);
                 hb[i] = bound[sel[w0 + i]];
             }
-            RAD_TRY(hipMemcpyAsync(dq.p, hq.data(), (size_t)wn * qbytes, hipMemcpyHostToDevice, s));
-            RAD_TRY(hipMemcpyAsync(dbound.p, hb.data(), (size_t)wn * 4, hipMemcpyHostToDevice, s));
-            RAD_TRY(hipMemsetAsync(dcnt.p, 0, (size_t)wn * 4, s));
+            MVF_HIP_TRY(hipMemcpyAsync(dq.p, hq.data(), (size_t)wn * qbytes, hipMemcpyHostToDevice, s));
+            MVF_HIP_TRY(hipMemcpyAsync(dbound.p, hb.data(), (size_t)wn * 4, hipMemcpyHostToDevice, s));
+            MVF_HIP_TRY(hipMemsetAsync(dcnt.p, 0, (size_t)wn * 4, s));
             return MVF_OK;
         };
         // R2 over the window's lists, results back, one wait; `repair` (nullable): the window's candidate counts, a query
@@ -261,14 +223,14 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                 pp.out_scores = static_cast<float*>(dsc.p);
                 pp.out_indices = static_cast<uint64_t*>(didx.p);
                 pp.out_raw = static_cast<int32_t*>(draw.p);
-                RAD_TRY(radius_pack_launch(pp, wn, s));
-                RAD_TRY(hipMemcpyAsync(hsc.data(), dsc.p, (size_t)wn * kk * 4, hipMemcpyDeviceToHost, s));
-                RAD_TRY(hipMemcpyAsync(hidx.data(), didx.p, (size_t)wn * kk * 8, hipMemcpyDeviceToHost, s));
-                RAD_TRY(hipMemcpyAsync(hraw.data(), draw.p, (size_t)wn * kk * 4, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(radius_pack_launch(pp, wn, s));
+                MVF_HIP_TRY(hipMemcpyAsync(hsc.data(), dsc.p, (size_t)wn * kk * 4, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipMemcpyAsync(hidx.data(), didx.p, (size_t)wn * kk * 8, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipMemcpyAsync(hraw.data(), draw.p, (size_t)wn * kk * 4, hipMemcpyDeviceToHost, s));
             }
-            RAD_TRY(hipMemcpyAsync(hcnt.data(), dcnt.p, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
-            if (dccnt) RAD_TRY(hipMemcpyAsync(hccnt.data(), dccnt, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
-            RAD_TRY(hipStreamSynchronize(s));
+            MVF_HIP_TRY(hipMemcpyAsync(hcnt.data(), dcnt.p, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
+            if (dccnt) MVF_HIP_TRY(hipMemcpyAsync(hccnt.data(), dccnt, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipStreamSynchronize(s));
             for (uint32_t i = 0; i < wn; i++) {
                 const uint32_t q = sel[w0 + i];
                 if (dccnt && hccnt[i] > kBatchCap) {
@@ -312,7 +274,7 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                     rp.J = J;
                     rp.q0 = 0;
                     rp.nq_total = wn;
-                    RAD_TRY(radius_scan_launch(v.dtype, metric, G, nqv, rp, dim3(nblk, (wn + nqv - 1) / nqv), lds, s));
+                    MVF_HIP_TRY(radius_scan_launch(v.dtype, metric, G, nqv, rp, dim3(nblk, (wn + nqv - 1) / nqv), lds, s));
                 }
                 rc = finish(sel, w0, wn, nullptr, nullptr);
                 if (rc != MVF_OK) return rc;
@@ -333,15 +295,15 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
             rc = corpus_row_norms(c, s, &xnorm, &xx2, &xxmax);
             if (rc != MVF_OK) return rc;
             float hxxmax = 0.0f;
-            RAD_TRY(hipMemcpyAsync(&hxxmax, xxmax, 4, hipMemcpyDeviceToHost, s));
-            RAD_TRY(hipStreamSynchronize(s));
+            MVF_HIP_TRY(hipMemcpyAsync(&hxxmax, xxmax, 4, hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipStreamSynchronize(s));
             const uint32_t nq_pad = (W + 127u) & ~127u, KT = (v.dim + 31u) / 32u, KP = KT * 32u;
             AsyncBuf dqmat, dqn, dtau, dccnt, dcand;
-            RAD_TRY(dqmat.alloc((size_t)nq_pad * KP * 4, s));
-            RAD_TRY(dqn.alloc((size_t)nq_pad * 4, s));
-            RAD_TRY(dtau.alloc((size_t)nq_pad * 4, s));
-            RAD_TRY(dccnt.alloc((size_t)nq_pad * 4, s));
-            RAD_TRY(dcand.alloc((size_t)nq_pad * kBatchCap * 8, s));
+            MVF_HIP_TRY(dqmat.alloc((size_t)nq_pad * KP * 4, s));
+            MVF_HIP_TRY(dqn.alloc((size_t)nq_pad * 4, s));
+            MVF_HIP_TRY(dtau.alloc((size_t)nq_pad * 4, s));
+            MVF_HIP_TRY(dccnt.alloc((size_t)nq_pad * 4, s));
+            MVF_HIP_TRY(dcand.alloc((size_t)nq_pad * kBatchCap * 8, s));
             std::vector<uint32_t> htau(nq_pad), redo;
             const double eps = (double)(std::max<uint32_t>(v.dim, 64) + 16) * 1.1920929e-7;  // the f32 kernel's bound (api.hip)
             for (uint32_t w0 = 0; w0 < nq && rc == MVF_OK; w0 += W) {
@@ -355,9 +317,9 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                     for (uint32_t e = 0; e < v.dim; e++) qq += (double)qv[e] * qv[e];
                     htau[i] = batched_tau(metric, radii[w0 + i], qq, hxxmax, eps);
                 }
-                RAD_TRY(hipMemcpyAsync(dtau.p, htau.data(), (size_t)wpad * 4, hipMemcpyHostToDevice, s));
-                RAD_TRY(hipMemsetAsync(dccnt.p, 0, (size_t)wpad * 4, s));
-                RAD_TRY(launch_prep_queries(static_cast<const float*>(dq.p), wn, wpad, v.dim, KP, static_cast<float*>(dqmat.p),
+                MVF_HIP_TRY(hipMemcpyAsync(dtau.p, htau.data(), (size_t)wpad * 4, hipMemcpyHostToDevice, s));
+                MVF_HIP_TRY(hipMemsetAsync(dccnt.p, 0, (size_t)wpad * 4, s));
+                MVF_HIP_TRY(launch_prep_queries(static_cast<const float*>(dq.p), wn, wpad, v.dim, KP, static_cast<float*>(dqmat.p),
                                             static_cast<float*>(dqn.p), s));
                 BatchParams bp{};
                 bp.qmat = static_cast<const float*>(dqmat.p);
@@ -381,7 +343,7 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                 bp.mtiles = wpad / 128u;
                 bp.cap = kBatchCap;
                 bp.direct = 0;  // every candidate passes the threshold test
-                RAD_TRY(launch_scan_mfma_f32(bp, metric, s));
+                MVF_HIP_TRY(launch_scan_mfma_f32(bp, metric, s));
                 RadiusRescoreParams rr{};
                 rr.cand = static_cast<const uint64_t*>(dcand.p);
                 rr.ccnt = static_cast<const uint32_t*>(dccnt.p);
@@ -396,7 +358,7 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                 rr.counts = static_cast<uint32_t*>(dcnt.p);
                 rr.lists = maxq > 0 ? static_cast<uint64_t*>(dlist.p) : nullptr;
                 rr.cap = cap;
-                RAD_TRY(radius_rescore_launch(metric, G, rr, wn, radius_scan_lds_bytes(MVF_DTYPE_FLOAT32, G, J, 1), s));
+                MVF_HIP_TRY(radius_rescore_launch(metric, G, rr, wn, radius_scan_lds_bytes(MVF_DTYPE_FLOAT32, G, J, 1), s));
                 rc = finish(all, w0, wn, static_cast<const uint32_t*>(dccnt.p), &redo);
             }
             if (rc == MVF_OK && !redo.empty()) rc = stream(redo);

@@ -37,12 +37,6 @@ using mvf::set_fail;
 
 namespace {
 
-#define SS_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) return set_fail(MVF_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
 struct Rccl {
     void* lib = nullptr;
     ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
@@ -354,8 +348,7 @@ int mvfgpu_shardset_search(mvfgpu_shardset* ss, uint8_t metric, const void* quer
     if (!ss) return set_fail(MVF_ERR_INVALID_ARGUMENT, "shard set is NULL");
     if (!queries || !out_scores || !out_indices) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
     if (nq == 0 || k == 0 || k > MVFGPU_MAX_K) return set_fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0 and k in 1..2^31");
-    if (metric != MVF_METRIC_L2 && metric != MVF_METRIC_INNER_PRODUCT && metric != MVF_METRIC_COSINE)
-        return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported distance metric code");
+    if (const int mrc = mvf::check_metric(metric)) return mrc;
     const bool int_space = ss->dtype == MVF_DTYPE_INT8 || ss->dtype == MVF_DTYPE_UINT8;
     const uint8_t want_q = int_space ? ss->dtype : (uint8_t)MVF_DTYPE_FLOAT32;
     if (query_dtype != want_q)
@@ -378,15 +371,15 @@ int mvfgpu_shardset_search(mvfgpu_shardset* ss, uint8_t metric, const void* quer
     const size_t qbytes = (size_t)nq * query_dim * (int_space ? 1u : 4u);
     const bool zc_q = qbytes <= ss->zc_query, zc_out = nres * 16 <= ss->zc_results;
     for (int s = 0; s < S; s++) {
-        if (!zc_q) SS_HIP(ss->d_q[s].reserve(ss->dev[s], qbytes));
-        SS_HIP(ss->d_gather[s].reserve(ss->dev[s], list_bytes * S));
+        if (!zc_q) MVF_HIP_TRY(ss->d_q[s].reserve(ss->dev[s], qbytes));
+        MVF_HIP_TRY(ss->d_gather[s].reserve(ss->dev[s], list_bytes * S));
     }
     if (zc_q) {
-        SS_HIP(ss->reserve_pinned(&ss->pin_q, &ss->pin_q_bytes, qbytes));
+        MVF_HIP_TRY(ss->reserve_pinned(&ss->pin_q, &ss->pin_q_bytes, qbytes));
         memcpy(ss->pin_q, queries, qbytes);
     }
-    if (zc_out) SS_HIP(ss->reserve_pinned(&ss->pin_out, &ss->pin_out_bytes, nres * 16));
-    else SS_HIP(ss->d_out.reserve(ss->dev[0], list_bytes));
+    if (zc_out) MVF_HIP_TRY(ss->reserve_pinned(&ss->pin_out, &ss->pin_out_bytes, nres * 16));
+    else MVF_HIP_TRY(ss->d_out.reserve(ss->dev[0], list_bytes));
 
     // ---- per-shard searches, concurrently: the calling thread drives shard 0, a persistent worker each of the others
     const auto t0 = std::chrono::steady_clock::now();
@@ -439,8 +432,8 @@ int mvfgpu_shardset_search(mvfgpu_shardset* ss, uint8_t metric, const void* quer
         // shards share a device (rehearsal): gather to shard 0's buffer with device-to-device copies
         (void)hipSetDevice(ss->dev[0]);
         for (int s = 1; s < S; s++) {
-            SS_HIP(hipStreamWaitEvent(ss->st[0], ss->ev[s], 0));
-            SS_HIP(hipMemcpyPeerAsync(static_cast<unsigned char*>(ss->d_gather[0].p) + list_bytes * s, ss->dev[0],
+            MVF_HIP_TRY(hipStreamWaitEvent(ss->st[0], ss->ev[s], 0));
+            MVF_HIP_TRY(hipMemcpyPeerAsync(static_cast<unsigned char*>(ss->d_gather[0].p) + list_bytes * s, ss->dev[0],
                                       static_cast<unsigned char*>(ss->d_gather[s].p) + list_bytes * s, ss->dev[s], list_bytes,
                                       ss->st[0]));
         }
@@ -454,16 +447,16 @@ int mvfgpu_shardset_search(mvfgpu_shardset* ss, uint8_t metric, const void* quer
     int32_t* mr = reinterpret_cast<int32_t*>(ob + 12 * nres);
     int rc = mvfgpu_merge_topk_packed_device(ss->d_gather[0].p, (uint32_t)S, nq, k, metric, ss->dtype, ms, mi, mr, ss->dev[0], ss->st[0]);
     if (rc != MVF_OK) return rc;
-    SS_HIP(hipEventRecord(ss->ev_merged, ss->st[0]));
+    MVF_HIP_TRY(hipEventRecord(ss->ev_merged, ss->st[0]));
     const auto t1 = std::chrono::steady_clock::now();  // everything is enqueued (a copy to pageable host memory blocks)
     if (!zc_out) {
-        SS_HIP(hipMemcpyAsync(out_scores, ms, nres * 4, hipMemcpyDeviceToHost, ss->st[0]));
-        SS_HIP(hipMemcpyAsync(out_indices, mi, nres * 8, hipMemcpyDeviceToHost, ss->st[0]));
-        if (out_raw) SS_HIP(hipMemcpyAsync(out_raw, mr, nres * 4, hipMemcpyDeviceToHost, ss->st[0]));
+        MVF_HIP_TRY(hipMemcpyAsync(out_scores, ms, nres * 4, hipMemcpyDeviceToHost, ss->st[0]));
+        MVF_HIP_TRY(hipMemcpyAsync(out_indices, mi, nres * 8, hipMemcpyDeviceToHost, ss->st[0]));
+        if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(out_raw, mr, nres * 4, hipMemcpyDeviceToHost, ss->st[0]));
     }
     for (int s = 0; s < S; s++) {  // every rank's part of the collective has to finish before the buffers are reused
         (void)hipSetDevice(ss->dev[s]);
-        SS_HIP(hipStreamSynchronize(ss->st[s]));
+        MVF_HIP_TRY(hipStreamSynchronize(ss->st[s]));
     }
     if (zc_out) {
         memcpy(out_scores, ms, nres * 4);
