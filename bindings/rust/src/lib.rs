@@ -18,6 +18,20 @@ pub struct MvfGpuCorpus {
     _private: [u8; 0],
 }
 
+/// Opaque `mvfgpu_filter` and the `mvfgpu_filter_info` out-struct (include/mvf_gpu.h; `struct_size` set by the caller).
+#[repr(C)]
+pub struct MvfGpuFilter {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct MvfGpuFilterInfo {
+    pub struct_size: u32,
+    pub has_row_list: u32,
+    pub rows: u64,
+    pub admitted: u64,
+    pub device_bytes: u64,
+}
+
 #[link(name = "mvf_gpu")]
 extern "C" {
     fn mvfgpu_corpus_create(rows: *const c_void, n: u64, dimension: u32, data_type: u8, stride_bytes: u64,
@@ -45,6 +59,22 @@ extern "C" {
     fn mvfgpu_knn_join_device(corpus: *const MvfGpuCorpus, query_corpus: *const MvfGpuCorpus, metric: u8, first: u64,
                               count: u64, k: u32, flags: u32, d_scores: *mut f32, d_indices: *mut u64, d_raw: *mut i32,
                               hip_stream: *mut c_void) -> c_int;
+    /// Filtered search (include/mvf_gpu.h, DESIGN.md section 3 "Filtered search"): an immutable set of admitted rows of one
+    /// handle -- host bits (bit `first_bit + r` admits local row r) or u32 words in device memory --, created once, used by
+    /// any number of searches, destroyed before its corpus; the searches are `mvfgpu_search` / `mvfgpu_search_device` among
+    /// the admitted rows.
+    fn mvfgpu_filter_create(corpus: *const MvfGpuCorpus, allow_bitmap: *const u8, first_bit: u64, nbits: u64,
+                            out: *mut *mut MvfGpuFilter) -> c_int;
+    fn mvfgpu_filter_create_device(corpus: *const MvfGpuCorpus, d_allow_words: *const u32, hip_stream: *mut c_void,
+                                   out: *mut *mut MvfGpuFilter) -> c_int;
+    fn mvfgpu_filter_destroy(filter: *mut MvfGpuFilter);
+    fn mvfgpu_filter_get_info(filter: *const MvfGpuFilter, out: *mut MvfGpuFilterInfo) -> c_int;
+    fn mvfgpu_search_filtered(corpus: *const MvfGpuCorpus, filter: *const MvfGpuFilter, metric: u8, queries: *const c_void,
+                              query_dtype: u8, query_dim: u32, nq: u32, k: u32, out_scores: *mut f32, out_indices: *mut u64,
+                              out_raw: *mut i32) -> c_int;
+    fn mvfgpu_search_filtered_device(corpus: *const MvfGpuCorpus, filter: *const MvfGpuFilter, metric: u8,
+                                     d_queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, k: u32,
+                                     d_scores: *mut f32, d_indices: *mut u64, d_raw: *mut i32, hip_stream: *mut c_void) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;
     /// `MVFGPU_ABI_VERSION` of the loaded library (include/mvf_gpu.h): struct layouts and signatures this file mirrors.
     fn mvfgpu_abi_version() -> u32;

@@ -348,6 +348,25 @@ public:
         for (size_t i = 0; i < k && i < count; i++) out.push_back({idx[i], scores[i], {}});
         return out;
     }
+    // find_top_k_similar among the rows a predicate admits (mvfgpu_search_filtered; DESIGN.md section 3, "Filtered search"):
+    // bit r of allow_bits (byte r >> 3, bit r & 7; at least one bit per row) admits row r.  Deleted rows are never returned;
+    // fewer than k admitted rows give fewer hits.  The filter lives for this call; the payload is not fetched.
+    std::vector<ScoredVector> find_top_k_filtered(const std::vector<float>& query, size_t k, const std::vector<uint8_t>& allow_bits) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "find_top_k_filtered takes f32 queries: Float32 / Float16 spaces");
+        if (k == 0) return {};
+        mvfgpu_filter* f = nullptr;
+        detail::check_gpu(mvfgpu_filter_create(c_, allow_bits.data(), 0, (uint64_t)allow_bits.size() * 8, &f));
+        std::vector<float> scores(k);
+        std::vector<uint64_t> idx(k);
+        const int rc = mvfgpu_search_filtered(c_, f, (uint8_t)metric_, query.data(), MVF_DTYPE_FLOAT32, (uint32_t)query.size(), 1, (uint32_t)k,
+                                              scores.data(), idx.data(), nullptr);
+        mvfgpu_filter_destroy(f);
+        detail::check_gpu(rc);
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < k && idx[i] != ~0ull; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
     // The k-NN graph (mvfgpu_knn_join; DESIGN.md section 3, "Join"): for each of the rows [first, first + count) -- count
     // UINT64_MAX: to the end of the space -- its k nearest OTHER rows under the space's metric, best first.  A row is never its
     // own neighbour (decided by position: its exact duplicates are); a deleted row gets an empty list; fewer than k live

@@ -406,6 +406,71 @@ int mvfgpu_search_candidates_device(const mvfgpu_corpus* corpus, uint8_t metric,
                                     float* d_scores, uint64_t* d_indices, int32_t* d_raw, uint64_t* d_counts,
                                     void* hip_stream);
 
+/* ---- filtered search (top-k among the rows a reusable filter admits) -------- */
+
+/*
+ * A filter: an immutable set of admitted rows of ONE corpus handle ("Filtered search").  Created once,
+ * used by any number of filtered searches from any thread, destroyed before its corpus.  A filter admits a row iff the row's
+ * allow bit is set AND the handle's tombstones do not delete it when the filter is created.
+ *   mvfgpu_filter_create        : host bits in the convention of mvfgpu_corpus_set_tombstones with the meaning inverted: bit
+ *                                 (first_bit + r) of `allow_bitmap` (byte b >> 3, bit b & 7) set = local row r admitted;
+ *                                 nbits >= first_bit + rows; first_bit need not be a multiple of 8 (a row-range shard passes
+ *                                 the whole space's bitmap and its first row); bits outside the shard's range are ignored.
+ *   mvfgpu_filter_create_device : u32 words over local rows in device memory (bit r & 31 of word r >> 5, ceil(rows / 32)
+ *                                 words), read on hip_stream (NULL = the null stream); bits at and beyond `rows` are ignored.
+ * Creation computes the exact admitted count on the device and WAITS for it: the one host wait that lets no filtered search
+ * wait on the host.  Where some batch size could choose the list route (below) it also builds the ascending list of admitted
+ * rows.  device memory: rows / 8 bytes of mask (+ 4 bytes per admitted row with the list): mvfgpu_filter_info::device_bytes.
+ * mvfgpu_corpus_set_tombstones starts a new tombstone generation: a filter of an older generation -- or of another handle --
+ * is refused by the searches, before any device call, with MVF_ERR_INVALID_ARGUMENT and a message naming the cause; create a
+ * new filter.  mvfgpu_filter_destroy (NULL is allowed) waits for the handle's newest work.
+ *
+ * mvfgpu_search_filtered / mvfgpu_search_filtered_device are mvfgpu_search / mvfgpu_search_device among the admitted rows:
+ * arguments, checks, error codes, order (best first, ties by ascending position, NaN last), padding where fewer than k rows
+ * are admitted, ids and index_base, out_raw, k up to MVFGPU_MAX_K and the stream discipline are theirs.  The answer is DEFINED
+ * as mvfgpu_search on a twin handle whose tombstones are `deleted | ~allow`: Int8 / UInt8 spaces are bit-exact to that twin
+ * on every route, float spaces return the same rows up to ties within the project tolerance, and ONE query on a Float32 space
+ * has the score bits of scan path 1 on the twin whichever route answers.  Two routes, chosen per call by a pure rule of
+ * rows, dimension, data type, nq, k and the admitted count (mvfgpu_selftest_filter_route; MVF_FILTER_ROUTE forces one):
+ *   mask : the plain search's routes and kernels with the filter's deny mask in the tombstones' place;
+ *   list : only the admitted rows are read, once per group of up to 4 queries, with the streaming kernel's one-query arithmetic.
+ * A filtered search leaves the handle's later plain searches as they were: it may build what a plain search builds (norms,
+ * shadows), but it neither reads nor feeds the repair feedback (mvfgpu_corpus_info::selection_state stays).
+ * Per-query filters are not an API: a filter serves every query of its call -- one call per filter.  Radius, candidate, join
+ * and fetch calls take no filter (a candidate list already is one; gather rows afterwards).
+ */
+typedef struct mvfgpu_filter mvfgpu_filter;
+
+typedef struct mvfgpu_filter_info {
+    uint32_t struct_size;  /* in: sizeof(mvfgpu_filter_info); out: bytes filled */
+    uint32_t has_row_list; /* 1: the ascending list of admitted rows was built (the list route is available) */
+    uint64_t rows;         /* rows of the handle the filter was created for */
+    uint64_t admitted;     /* rows the filter admits (allow bit set, not deleted at creation) */
+    uint64_t device_bytes; /* device memory the filter holds */
+} mvfgpu_filter_info;
+
+int mvfgpu_filter_create(const mvfgpu_corpus* corpus, const uint8_t* allow_bitmap, uint64_t first_bit, uint64_t nbits,
+                         mvfgpu_filter** out);
+int mvfgpu_filter_create_device(const mvfgpu_corpus* corpus, const uint32_t* d_allow_words, void* hip_stream,
+                                mvfgpu_filter** out);
+void mvfgpu_filter_destroy(mvfgpu_filter* filter);
+int mvfgpu_filter_get_info(const mvfgpu_filter* filter, mvfgpu_filter_info* out);
+int mvfgpu_search_filtered(const mvfgpu_corpus* corpus, const mvfgpu_filter* filter, uint8_t metric,
+                           const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t k,
+                           float* out_scores, uint64_t* out_indices, int32_t* out_raw);
+int mvfgpu_search_filtered_device(const mvfgpu_corpus* corpus, const mvfgpu_filter* filter, uint8_t metric,
+                                  const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t k,
+                                  float* d_scores, uint64_t* d_indices, int32_t* d_raw, void* hip_stream);
+
+/*
+ * Self-test of the route a filtered search takes (no GPU needed): *out_route = 1 (mask) or 2 (list) for `nq` queries and `k`
+ * results on a corpus of `rows` x `dimension` of `data_type` whose filter admits `admitted` rows, under the default tuning.
+ * For fixed other arguments the route is the list at and below some admitted count and the mask above it; admitted = rows is
+ * always the mask.
+ */
+int mvfgpu_selftest_filter_route(uint64_t rows, uint32_t dimension, uint8_t data_type, uint32_t nq, uint32_t k, uint64_t admitted,
+                                 uint32_t* out_route);
+
 /* ---- k-NN join (queries taken from resident rows) -------------------------- */
 
 #define MVFGPU_JOIN_WINDOW 1024u        /* query rows per search of a join, counted from `first` */
@@ -572,7 +637,7 @@ int mvfgpu_set_scan_path(mvfgpu_corpus* corpus, int path);
 
 /*
  * The tuning switches of the environment (MVF_K1_G, MVF_K2_*, MVF_I8_SHADOW, MVF_F16_SHADOW, MVF_QS_REFINE,
- * MVF_STREAM_I8, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
+ * MVF_STREAM_I8, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_FILTER_ROUTE, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
  * handle, when it is created: a search never calls getenv.  An A/B script that changes the environment of a live handle
  * calls this to have it read again.  A development aid: it waits for the handle's host-buffer searches, but
  * mvfgpu_search_device reads the switches unlocked -- do not call it beside device-pointer searches of the same handle.
@@ -585,7 +650,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * reload_tuning, k beyond 1024; the later lift of the k <= 16384 limit changed no layout and no signature, nor did the
  * radius search, which only ADDS mvfgpu_search_radius and mvfgpu_selftest_radius_bound, nor did the candidate search, which
  * only adds mvfgpu_search_candidates and mvfgpu_search_candidates_device, nor did the k-NN join, which only adds mvfgpu_knn_join and
- * mvfgpu_knn_join_device).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * mvfgpu_knn_join_device, nor did the filtered search, which only adds mvfgpu_filter_*, mvfgpu_search_filtered,
+ * mvfgpu_search_filtered_device and mvfgpu_selftest_filter_route).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

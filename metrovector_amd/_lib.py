@@ -35,6 +35,11 @@ class CorpusInfo(_OutStruct):
                 ("device_bytes", C.c_uint64), ("deleted_rows", C.c_uint64)]
 
 
+class FilterInfo(_OutStruct):
+    _fields_ = [("struct_size", C.c_uint32), ("has_row_list", C.c_uint32), ("rows", C.c_uint64), ("admitted", C.c_uint64),
+                ("device_bytes", C.c_uint64)]
+
+
 class UploadOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("chunk_mib", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -151,6 +156,20 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_knn_join.restype = C.c_int
     lib.mvfgpu_knn_join_device.argtypes = [vp, vp, u8, u64, u64, u32, u32, vp, vp, vp, vp]
     lib.mvfgpu_knn_join_device.restype = C.c_int
+    lib.mvfgpu_filter_create.argtypes = [vp, vp, u64, u64, pp]
+    lib.mvfgpu_filter_create.restype = C.c_int
+    lib.mvfgpu_filter_create_device.argtypes = [vp, vp, vp, pp]
+    lib.mvfgpu_filter_create_device.restype = C.c_int
+    lib.mvfgpu_filter_destroy.argtypes = [vp]
+    lib.mvfgpu_filter_destroy.restype = None
+    lib.mvfgpu_filter_get_info.argtypes = [vp, C.POINTER(FilterInfo)]
+    lib.mvfgpu_filter_get_info.restype = C.c_int
+    lib.mvfgpu_search_filtered.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, vp, vp]
+    lib.mvfgpu_search_filtered.restype = C.c_int
+    lib.mvfgpu_search_filtered_device.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_search_filtered_device.restype = C.c_int
+    lib.mvfgpu_selftest_filter_route.argtypes = [u64, u32, u8, u32, u32, u64, vp]
+    lib.mvfgpu_selftest_filter_route.restype = C.c_int
     lib.mvfgpu_selftest_radius_bound.argtypes = [u8, u8, C.c_float, vp, vp]
     lib.mvfgpu_selftest_radius_bound.restype = C.c_int
     lib.mvfgpu_selftest_radius_route.argtypes = [u8, u32, C.c_int, vp]

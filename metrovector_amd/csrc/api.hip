@@ -9,6 +9,8 @@
 
 #include "aux_kernels.h"
 #include "internal.h"
+#include "scan_candidates.h"
+#include "scan_filter.h"
 #include "mvf_common.h"
 #include "scan_mfma.h"
 #include "scan_stream.h"
@@ -114,6 +116,7 @@ Tuning read_tuning() {
     t.host_zc_results = (size_t)std::max(0l, num("MVF_HOST_ZC_RESULTS", 256l << 10));
     t.large_k = (int)std::min(2l, std::max(0l, num("MVF_LARGE_K", 0)));
     t.host_flag_wait = flag("MVF_HOST_FLAG_WAIT", true);
+    t.filter_route = (int)std::min(2l, std::max(0l, num("MVF_FILTER_ROUTE", 0)));
     return t;
 }
 }  // namespace mvf
@@ -156,6 +159,7 @@ struct mvfgpu_corpus {
     mutable DevBuf shadow, xscale;        // Float32 corpora: scaled-f16 shadow rows (selection only) + 2^-s_r per row
     DevBuf tomb, ids;                     // deletion bitmap (u32 words over local rows) / vector ids (u64 per local row)
     uint64_t deleted = 0;                 // bits set in the bitmap
+    uint64_t tomb_gen = 0;                // bumped by every mvfgpu_corpus_set_tombstones: a filter (filter.hip) holds the bitmap of ONE generation
     std::vector<uint64_t> h_ids;          // host copy of the ids ...
     mutable std::vector<std::pair<uint64_t, uint32_t>> id_index;  // ... and, built by the first gather, (id, row) sorted by id
     mutable int shadow_state = 0;         // 0 not built yet, 1 ready, -1 unavailable (no memory)
@@ -320,7 +324,20 @@ struct SearchCall {
     // stored rows or a shadow, the margin select, the K1-order re-scoring, the repair
     uint32_t launches = 0;
     bool launches_known = true;
+    // the rows the scans skip: the handle's deletion bitmap, or -- a filtered search (filter.hip) -- a filter's deny mask in the
+    // same layout (its tombstones included).  Set by new_search_call.
+    const uint32_t* deny = nullptr;
 };
+
+SearchCall new_search_call(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
+                           uint64_t* d_indices, int32_t* d_raw, hipStream_t s, const uint32_t* filter_deny = nullptr) {
+    SearchCall sc{metric, d_queries, nq, k, d_scores, d_indices, d_raw, s};
+    sc.deny = filter_deny ? filter_deny : static_cast<const uint32_t*>(c->tomb.p);
+    return sc;
+}
+
+// A filtered search: its repairs describe the filter, not the corpus -- it neither polls nor posts the repair feedback.
+bool is_filtered(const mvfgpu_corpus* c, const SearchCall& sc) { return sc.deny != static_cast<const uint32_t*>(c->tomb.p); }
 
 // A search inside `sc` for another k into other buffers (a shadow route's selection, a pass of a large k, one of two row
 // ranges): `route` runs on a copy changed so, and what it launches counts for `sc`.
@@ -391,7 +408,7 @@ ScanParams stored_scan_params(const mvfgpu_corpus* c, const SearchCall& sc, cons
     ScanParams sp{};
     sp.rows = c->d_rows;
     sp.queries = sc.d_queries;
-    sp.tomb = static_cast<const uint32_t*>(c->tomb.p);
+    sp.tomb = sc.deny;
     sp.cand = cand;
     sp.n = (uint32_t)c->n;
     sp.pitch = c->pitch;
@@ -895,8 +912,9 @@ int feedback_slots(const mvfgpu_corpus* c) {
 // The pinned slot the next post will use, for the repair pass's flag_compact_kernel to store its count into directly (round 5:
 // the 4-byte copy behind every batched search was a launch of its own, 4.1 us) -- NULL while that slot still holds a sample
 // nobody has consumed (the post will skip it too).
-uint32_t* feedback_mirror(const mvfgpu_corpus* c) {
+uint32_t* feedback_mirror(const mvfgpu_corpus* c, const SearchCall& sc) {
     c->fb_mirrored = nullptr;
+    if (is_filtered(c, sc)) return nullptr;
     if (feedback_slots(c) != MVF_OK || c->qs_redo_pending[c->qs_slot]) return nullptr;
     c->fb_mirrored = c->qs_redo_host + c->qs_slot;
     return c->qs_redo_host + c->qs_slot;
@@ -908,6 +926,7 @@ uint32_t* feedback_mirror(const mvfgpu_corpus* c) {
 int qs_feedback_post(const mvfgpu_corpus* c, const SearchCall& sc, bool used_bias = false, bool used_qs = true) {
     hipStream_t s = sc.stream;
     const uint32_t sl = c->qs_slot;
+    if (is_filtered(c, sc)) return MVF_OK;
     if (c->qs_redo_pending[sl] || !c->repair.p) return MVF_OK;  // (pending: this search did not poll -- it took another path first)
     {
         int rc = feedback_slots(c);
@@ -1124,7 +1143,7 @@ int repair_flagged_queries(const mvfgpu_corpus* c, SearchCall& sc, uint32_t* ove
     if (!pl.any) return MVF_OK;
     hipStream_t s = sc.stream;
     if (!compacted) {
-        MVF_HIP_TRY(launch_flag_compact(overflow, sc.nq, pl.redo_list, pl.redo_cnt, feedback_mirror(c), s));
+        MVF_HIP_TRY(launch_flag_compact(overflow, sc.nq, pl.redo_list, pl.redo_cnt, feedback_mirror(c, sc), s));
         sc.launches++;
     }
     c->last_redo_cnt = pl.redo_cnt;
@@ -1247,7 +1266,7 @@ int search_batched_range(const mvfgpu_corpus* c, SearchCall& sc, uint64_t lo, ui
     bp.xnorm = static_cast<const float*>(c->xnorm.p);
     bp.xx2 = xx2;
     bp.xxmax = xxmax;
-    bp.tomb = static_cast<const uint32_t*>(c->tomb.p);
+    bp.tomb = sc.deny;
     bp.tau = tau;
     bp.cand = static_cast<uint64_t*>(c->bcand.p);
     bp.cnt = cnt;
@@ -1452,7 +1471,7 @@ int merge_topk_device_impl(const float* d_scores, const uint64_t* d_indices, con
 int search_batched_path(const mvfgpu_corpus* c, SearchCall& sc) {
     const uint32_t nq = sc.nq, k = sc.k;
     hipStream_t s = sc.stream;
-    qs_feedback_poll(c);
+    if (!is_filtered(c, sc)) qs_feedback_poll(c);
     if (qs_wanted_batched(c, k)) {
         int rc = ensure_norms(c, s);
         if (rc != MVF_OK) return rc;
@@ -1623,7 +1642,7 @@ int search_stream_qs_path(const mvfgpu_corpus* c, SearchCall& sc) {
         rp.flags_nq = nq;
         rp.redo_list = plan.redo_list;
         rp.redo_cnt = plan.redo_cnt;
-        rp.redo_mirror = feedback_mirror(c);
+        rp.redo_mirror = feedback_mirror(c, sc);
     }
     MVF_HIP_TRY(launch_rescore_k1(rp, metric, nq, sh.G, sh.J, s));
     sc.launches += 2;
@@ -2049,6 +2068,8 @@ CorpusView corpus_view(const mvfgpu_corpus* c) {
     v.dim = c->dim, v.pitch = c->pitch, v.V = c->V, v.dtype = c->dtype;
     v.rows = c->d_rows;
     v.tomb = static_cast<const uint32_t*>(c->tomb.p);
+    v.tomb_gen = c->tomb_gen;
+    v.filter_route = c->tune.filter_route;
     v.ids = static_cast<const uint64_t*>(c->ids.p);
     v.stream = c->own_stream;
     v.scan_path = c->scan_path;
@@ -2093,6 +2114,11 @@ int corpus_pinned_mirrors(const mvfgpu_corpus* c, size_t in_bytes, size_t out_by
 }
 int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function<int()>& body) {
     return device_call(c, static_cast<hipStream_t>(stream), body);
+}
+int corpus_wait_newest(const mvfgpu_corpus* c) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->has_done) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+    return MVF_OK;
 }
 int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                       uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices) {
@@ -2379,6 +2405,7 @@ int mvfgpu_corpus_set_tombstones(mvfgpu_corpus* c, const uint8_t* bitmap, uint64
     if (!bitmap || nbits == 0) {
         c->tomb.release();
         c->deleted = 0;
+        c->tomb_gen++;
         return MVF_OK;
     }
     if (first_bit + c->n > nbits || first_bit + c->n < first_bit)
@@ -2393,6 +2420,7 @@ int mvfgpu_corpus_set_tombstones(mvfgpu_corpus* c, const uint8_t* bitmap, uint64
             dead++;
         }
     }
+    c->tomb_gen++;
     if (dead == 0) {
         c->tomb.release();
         c->deleted = 0;
@@ -2426,7 +2454,8 @@ int mvfgpu_corpus_set_vector_ids(mvfgpu_corpus* c, const void* ids_le, uint64_t 
 
 namespace {
 int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
-                  uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, void* hip_stream, HostFlagReq* req);
+                  uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, void* hip_stream, HostFlagReq* req,
+                  const FilterUse* flt = nullptr);
 }
 
 int mvfgpu_search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint8_t query_dtype,
@@ -2478,7 +2507,7 @@ int search_locked(const mvfgpu_corpus* c, SearchCall& sc) {
         return MVF_OK;
     }
     bool shadow_stream = false, qs_stream = false;
-    if (stream_qs_wanted(c, nq, k)) qs_feedback_poll(c);  // may switch the int8 selection off
+    if (stream_qs_wanted(c, nq, k) && !is_filtered(c, sc)) qs_feedback_poll(c);  // may switch the int8 selection off
     // K1 on the stored rows and the streamed int8 shadow time themselves (ProfSlot::ts_whole: from the search's first kernel, so
     // not the norms / the shadow a handle's first search builds in front of it); every other route keeps the event pair around the
     // whole call, in front of whatever it builds first.  The route is only known behind those builds: where it was expected to time
@@ -2534,25 +2563,31 @@ int search_locked(const mvfgpu_corpus* c, SearchCall& sc) {
 
 // mvfgpu_search_device, and -- with `req` -- the enqueue step of the host-buffer calls (search_host)
 int search_device(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
-                  uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, void* hip_stream, HostFlagReq* req) {
+                  uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, void* hip_stream, HostFlagReq* req,
+                  const FilterUse* flt) {
     int rc = check_query_args(c, metric, d_queries, query_dtype, query_dim, nq, k, d_scores, d_indices);
     if (rc != MVF_OK) return rc;
     DevScope guard(c->device);
     if (!guard.ok) return fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return device_call(c, s, [&]() {  // a call that holds this one search
-        SearchCall sc{metric, d_queries, nq, k, d_scores, d_indices, d_raw, s};
-        sc.flag_req = req;
         if (req) req->gen = c->work_gen;
+        // a filter's list route (filter.hip: F2 over the admitted rows), which also answers what admits no row at all
+        if (flt && (flt->by_list || flt->admitted == 0 || c->n == 0))
+            return filter_list_search(corpus_view(c), *flt, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s);
+        // ... or its mask route: the search a plain call runs, the filter's deny mask in the tombstones' place
+        SearchCall sc = new_search_call(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, s, flt ? flt->deny : nullptr);
+        sc.flag_req = req;
         return search_locked(c, sc);
     });
 }
 }  // namespace
 
 namespace {
-// mvfgpu_search / mvfgpu_search_fetch.  out_vectors (nullable): [nq][k] rows of the corpus in their stored type.
+// mvfgpu_search / mvfgpu_search_fetch / mvfgpu_search_filtered.  out_vectors (nullable): [nq][k] rows of the corpus in their
+// stored type.  flt (nullable): the filter of a filtered search, handed down to the search enqueued here.
 int search_host(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
-                uint32_t k, float* out_scores, uint64_t* out_indices, int32_t* out_raw, void* out_vectors) {
+                uint32_t k, float* out_scores, uint64_t* out_indices, int32_t* out_raw, void* out_vectors, const FilterUse* flt = nullptr) {
     int rc = check_query_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
     if (rc != MVF_OK) return rc;
     DevScope guard(c->device);
@@ -2646,7 +2681,7 @@ int search_host(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uin
         want_flag = true;
     }
     rc = search_device(c, metric, dq, query_dtype, query_dim, nq, k, static_cast<float*>(ds), static_cast<uint64_t*>(di),
-                       static_cast<int32_t*>(dr), c->own_stream, want_flag ? &req : nullptr);
+                       static_cast<int32_t*>(dr), c->own_stream, want_flag ? &req : nullptr, flt);
     if (rc != MVF_OK) return rc;
     if (req.armed && (!out_vectors || req.gathered)) {
         // the final select writes req.seq behind its results (and the payload rows it copied): spin on it (bounded: a long search falls back to the stream)
@@ -3001,6 +3036,16 @@ int mvfgpu_selftest_route(uint64_t rows, uint32_t dimension, uint8_t data_type, 
     return MVF_OK;
 }
 
+int mvfgpu_selftest_filter_route(uint64_t rows, uint32_t dimension, uint8_t data_type, uint32_t nq, uint32_t k, uint64_t admitted,
+                                 uint32_t* out_route) {
+    if (!out_route) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (elem_size(data_type) == 0 || dimension == 0 || nq == 0 || k == 0 || k > MVFGPU_MAX_K)
+        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported type or empty dimension / batch / k");
+    if (admitted > rows) return fail(MVF_ERR_INVALID_ARGUMENT, "more rows admitted than the corpus holds");
+    *out_route = filter_route_rule(rows, dimension, data_type, nq, k, admitted);
+    return MVF_OK;
+}
+
 int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq, uint32_t k,
                                 uint32_t* out_rows) {
     if (!out_rows) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
@@ -3014,11 +3059,68 @@ int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_
 }  // extern "C"
 
 namespace mvf {
+// Mask or list (DESIGN.md section 5 "F0 / F1 / F2"; every figure below: scripts/probe_filtered.py, profiles/r09_filtered.txt,
+// 10M x 768 f32 cosine and 50M x 768 int8 dot at k = 100).  Both routes are bound by the bytes of rows they read, so the rule
+// compares those: the list route reads the admitted rows' pitch once per group of queries F2 serves together; the mask route
+// reads what the plain search of this shape reads under the default tuning -- K1 the stored rows once per four queries (ONE
+// Float32 query from kStreamI8MinBytes on: the int8 shadow), the batched route one pass over the int8 shadow / the Int8 rows
+// per kFilterMaskTile queries (1024 queries cost 6.9 / 5.9 times one query's pass on the two shapes), a large k at least
+// K1's passes.  The metric is left out: it moves the plain route only for Float32 rows beyond kWideFinalMaxDim dimensions
+// (taken as InnerProduct here).
+//   * kFilterListCost: a byte gathered through the list costs this many streamed ones.  F2 holds 2.4-4.9 TB/s on lists of a
+//     million rows and more against the 6.6-7.0 TB/s of the one-query streamed passes, and the measured crossovers put the
+//     factor at 1.4 (int8, one query) .. 2.7 (f32, 16 queries): 2 decides every measured point but one the way the times do.
+//   * kFilterRepairDensity: a BATCHED search under a mask that admits few rows -- as under tombstones of that weight --
+//     flags nearly every query for the exact repair pass, K1 over the stored rows four queries at a time: 1024 queries
+//     take 0.6-3.1 s instead of 8-36 ms at every density measured from 1e-4 to 0.05, 256 queries 0.15-1.4 s from 0.015 to
+//     0.05 (and still 146 ms at 0.07 on the f32 shape); at 0.07 and above, and for 64 queries at every density, it does not
+//     happen.  The list route takes 9-160 ms there.  So more than 64 queries take the list up to a density of 1/16.
+//     Measured at k = 100 on these two shapes only.
+constexpr uint64_t kFilterListCost = 2, kFilterMaskTile = 128, kFilterRepairDensity = 16;
+uint32_t filter_route_rule(uint64_t rows, uint32_t dim, uint8_t dtype, uint32_t nq, uint32_t k, uint64_t admitted) {
+    if (rows == 0 || admitted >= rows) return 1u;
+    std::unique_ptr<mvfgpu_corpus> c(new mvfgpu_corpus());  // owns nothing on a device (mvfgpu_selftest_route's stub)
+    c->n = rows;
+    c->dim = dim;
+    c->dtype = dtype;
+    c->pitch = (dim * elem_size(dtype) + 15u) & ~15u;
+    c->V = c->pitch / 16;
+    c->tune = Tuning{};
+    int G = 64;
+    uint32_t J = 1;
+    choose_group(c->V, 1, &G, &J);
+    const uint32_t qg = filter_group_queries(cand_query_bytes(dtype, G, J));
+    const uint64_t pitch8 = ((uint64_t)dim + 15u) & ~15ull;  // a row of the int8 shadow, about
+    typedef unsigned __int128 u128;
+    const u128 list_bytes = (u128)admitted * c->pitch * ((nq + qg - 1) / qg);
+    u128 mask_bytes;
+    if (k > MVFGPU_K_PER_PASS) {
+        mask_bytes = (u128)rows * c->pitch * ((nq + 3) / 4);
+    } else if (use_batched_path(c.get(), MVF_METRIC_INNER_PRODUCT, nq)) {
+        if (nq > 64 && (u128)admitted * kFilterRepairDensity <= rows) return 2u;
+        mask_bytes = (u128)rows * pitch8 * ((nq + kFilterMaskTile - 1) / kFilterMaskTile);
+    } else if (stream_i8_shape(rows, dim, dtype, nq, k)) {
+        mask_bytes = (u128)rows * pitch8;
+    } else {
+        mask_bytes = (u128)rows * c->pitch * ((nq + 3) / 4);
+    }
+    return list_bytes * kFilterListCost <= mask_bytes ? 2u : 1u;
+}
+
 int search_positions_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
                             uint64_t* d_indices, int32_t* d_raw, void* stream) {
-    SearchCall sc{metric, d_queries, nq, k, d_scores, d_indices, d_raw, static_cast<hipStream_t>(stream)};
+    SearchCall sc = new_search_call(c, metric, d_queries, nq, k, d_scores, d_indices, d_raw, static_cast<hipStream_t>(stream));
     sc.positions_only = true;
     sc.shared_call = true;  // corpus_device_call's body may run any number of searches
     return search_locked(c, sc);
+}
+int search_filtered_host(const mvfgpu_corpus* c, const FilterUse& flt, uint8_t metric, const void* queries, uint8_t query_dtype,
+                         uint32_t query_dim, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_indices, int32_t* out_raw) {
+    return search_host(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices, out_raw, nullptr, &flt);
+}
+int search_filtered_device(const mvfgpu_corpus* c, const FilterUse& flt, uint8_t metric, const void* d_queries, uint8_t query_dtype,
+                           uint32_t query_dim, uint32_t nq, uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw,
+                           void* hip_stream) {
+    return search_device(c, metric, d_queries, query_dtype, query_dim, nq, k, d_scores, d_indices, d_raw, hip_stream, nullptr, &flt);
 }
 }  // namespace mvf

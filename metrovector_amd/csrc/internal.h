@@ -96,6 +96,7 @@ struct Tuning {
     size_t host_zc_query = 64u << 10;     // MVF_HOST_ZC_QUERY: mvfgpu_search reads queries up to this size in place (pinned host)
     size_t host_zc_results = 256u << 10;  // MVF_HOST_ZC_RESULTS: ... and writes results up to this size in place
     bool host_flag_wait = true; // MVF_HOST_FLAG_WAIT=0: the blocking host call always waits on its stream (not on the flag the final select writes)
+    int filter_route = 0;       // MVF_FILTER_ROUTE=1|2: a filtered search always by the mask route (1) / always by the list route (2; the list is then built whatever the count); 0: the rule (filter_route_rule)
     int large_k = 0;            // MVF_LARGE_K=1|2: k beyond one pass always by passes (1; k <= 16384) / always by the whole-shard sort (2); 0: the cheaper one
 };
 Tuning read_tuning();
@@ -113,6 +114,8 @@ struct CorpusView {
     const uint64_t* ids = nullptr;   // NULL = index_base + row
     void* stream = nullptr;          // hipStream_t of the host-buffer API (used under host_mutex)
     int scan_path = 0;               // mvfgpu_set_scan_path
+    uint64_t tomb_gen = 0;           // the generation of `tomb`: every mvfgpu_corpus_set_tombstones starts a new one
+    int filter_route = 0;            // Tuning::filter_route
 };
 CorpusView corpus_view(const mvfgpu_corpus* c);
 std::mutex& corpus_host_mutex(const mvfgpu_corpus* c);  // serialises the host-buffer calls of a handle
@@ -161,5 +164,32 @@ int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function
 // excludes by position and maps ids itself).
 int search_positions_locked(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
                             uint64_t* d_indices, int32_t* d_raw, void* stream);
+
+
+// ---- filtered search (filter.hip; DESIGN.md §3 "Filtered search")
+// What a search reads of a filter: its deny mask in the tombstone buffer's layout (the handle's tombstones included), the
+// ascending list of its admitted rows where it was built, and the route this search takes.
+struct FilterUse {
+    const uint32_t* deny = nullptr;
+    const uint32_t* list = nullptr;
+    uint64_t admitted = 0;
+    bool by_list = false;
+};
+// mvfgpu_search / mvfgpu_search_device restricted to the filter's rows (api.hip): the mask route runs the plain search's routes
+// and kernels with flt.deny in the tombstones' place; by_list, no admitted row or an empty corpus go to filter_list_search.
+// Neither polls nor posts the repair feedback.
+int search_filtered_host(const mvfgpu_corpus* c, const FilterUse& flt, uint8_t metric, const void* queries, uint8_t query_dtype,
+                         uint32_t query_dim, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_indices, int32_t* out_raw);
+int search_filtered_device(const mvfgpu_corpus* c, const FilterUse& flt, uint8_t metric, const void* d_queries, uint8_t query_dtype,
+                           uint32_t query_dim, uint32_t nq, uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw,
+                           void* hip_stream);
+// The list route (filter.hip): F2 over flt.list, the results merged and formatted as a search's; everything on `s`, no host
+// wait; the caller runs under corpus_device_call.
+int filter_list_search(const CorpusView& v, const FilterUse& flt, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
+                       float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s);
+// The route of a filtered search under the default tuning, a pure function (mvfgpu_selftest_filter_route): 1 = mask, 2 = list
+uint32_t filter_route_rule(uint64_t rows, uint32_t dim, uint8_t dtype, uint32_t nq, uint32_t k, uint64_t admitted);
+// waits for the newest work enqueued on the handle
+int corpus_wait_newest(const mvfgpu_corpus* c);
 
 }  // namespace mvf

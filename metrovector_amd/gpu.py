@@ -92,6 +92,65 @@ def stream_rows(rows: int, dim: int, data_type: int, metric: int, nq: int, k: in
     return out.value
 
 
+def filter_route(rows: int, dim: int, data_type: int, nq: int, k: int, admitted: int) -> int:
+    """1: a filtered search of this shape takes the mask route (the plain search's kernels under the filter's deny mask),
+    2: the list route (only the admitted rows are read) -- default tuning; `mvfgpu_selftest_filter_route`; no GPU needed."""
+    out = C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_filter_route(rows, dim, data_type, nq, k, admitted, C.byref(out)))
+    return out.value
+
+
+def pack_allow_mask(allow, rows: int | None = None) -> np.ndarray:
+    """The packed uint8 bitmap (`bitorder="little"`) of a filter's rows: a bool array has one entry per row and is packed;
+    a uint8 array is taken as already packed.  `rows` (a bool mask's required length) is checked when given.  Anything else
+    is refused with InvalidArgument."""
+    a = allow if isinstance(allow, np.ndarray) else np.asarray(allow)
+    if a.ndim != 1:
+        raise InvalidArgument(f"the allow mask must be 1-D, got shape {a.shape}")
+    if a.dtype == np.bool_:
+        if rows is not None and a.size != rows:
+            raise InvalidArgument(f"the allow mask holds {a.size} entries for {rows} rows")
+        return np.packbits(a, bitorder="little")
+    if a.dtype == np.uint8:
+        return np.ascontiguousarray(a)
+    raise InvalidArgument(f"the allow mask must be a bool array over rows or a packed uint8 bitmap, got {a.dtype}")
+
+
+class GpuFilter:
+    """An immutable set of admitted rows of one GpuCorpus (`mvfgpu_filter`): made once by `GpuCorpus.make_filter`, used by
+    any number of `search_filtered` calls, closed before its corpus.  A context manager."""
+
+    def __init__(self, handle: int, corpus: "GpuCorpus"):
+        self._h = C.c_void_p(handle)
+        self._corpus = corpus  # keeps the handle it belongs to alive
+
+    def info(self) -> _lib.FilterInfo:
+        out = _lib.FilterInfo()
+        _lib.gpu_check(_lib.gpu().mvfgpu_filter_get_info(self._h, C.byref(out)))
+        return out
+
+    @property
+    def admitted(self) -> int:
+        return self.info().admitted
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value and self._corpus._h is not None:
+            _lib.gpu().mvfgpu_filter_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class GpuCorpus:
     """One shard of a vector space, resident in HBM on one MI355X."""
 
@@ -342,6 +401,63 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_knn_join_device(self._h, None if queries_from is None else queries_from._h, metric, first,
                                                          count, k, JOIN_EXCLUDE_SELF if exclude_self else 0, opt(d_scores),
                                                          opt(d_indices), opt(d_raw), opt(stream)))
+
+    # ---- filtered search ---------------------------------------------------------
+    def make_filter(self, allow, first_bit: int = 0) -> GpuFilter:
+        """A reusable filter (`mvfgpu_filter_create`): `allow` is a bool array over this shard's rows, or a packed uint8
+        bitmap (`bitorder="little"`) in which bit (first_bit + r) admits local row r -- a row-range shard passes the whole
+        space's bitmap and its first row.  Rows deleted now are never admitted."""
+        a = allow if isinstance(allow, np.ndarray) else np.asarray(allow)
+        if first_bit < 0:
+            raise InvalidArgument("first_bit must be >= 0")
+        if a.dtype == np.bool_ and first_bit:
+            raise InvalidArgument("a bool mask covers this shard's rows only: first_bit applies to packed bitmaps")
+        b = pack_allow_mask(a, self.rows)
+        if b.size * 8 < first_bit + self.rows:
+            raise InvalidArgument(f"the allow bitmap holds {b.size * 8} bits, the shard needs {first_bit + self.rows}")
+        h = C.c_void_p()
+        _lib.gpu_check(_lib.gpu().mvfgpu_filter_create(self._h, b.ctypes.data_as(C.c_void_p), first_bit, b.size * 8, C.byref(h)))
+        return GpuFilter(h.value, self)
+
+    def make_filter_device(self, d_words: int, stream: int = 0) -> GpuFilter:
+        """A filter from u32 words over local rows in device memory (`mvfgpu_filter_create_device`): bit r & 31 of word
+        r >> 5, ceil(rows / 32) words, read on `stream`."""
+        if not d_words:
+            raise InvalidArgument("d_words is a NULL device pointer")
+        h = C.c_void_p()
+        _lib.gpu_check(_lib.gpu().mvfgpu_filter_create_device(self._h, C.c_void_p(d_words), C.c_void_p(stream) if stream else None,
+                                                              C.byref(h)))
+        return GpuFilter(h.value, self)
+
+    def search_filtered(self, queries: np.ndarray, k: int, metric: int, flt: GpuFilter) -> SearchResult:
+        """The exact top-k among the rows `flt` admits (`mvfgpu_search_filtered`): `search`'s results in every respect."""
+        if not isinstance(flt, GpuFilter) or flt._h is None:
+            raise InvalidArgument("flt must be an open GpuFilter of this corpus")
+        q = np.asarray(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, qdim = q.shape
+        sc = np.empty((nq, k), np.float32)
+        idx = np.empty((nq, k), np.uint64)
+        raw = np.empty((nq, k), np.int32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_filtered(self._h, flt._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
+                                                         sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                         raw.ctypes.data_as(C.c_void_p)))
+        return SearchResult(sc, idx, raw)
+
+    def search_filtered_device(self, flt: GpuFilter, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
+                               d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
+        """Device-pointer filtered search (`mvfgpu_search_filtered_device`), asynchronous on `stream`."""
+        if not isinstance(flt, GpuFilter) or flt._h is None:
+            raise InvalidArgument("flt must be an open GpuFilter of this corpus")
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_filtered_device(self._h, flt._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
+                                                                nq, k, C.c_void_p(d_scores), C.c_void_p(d_indices),
+                                                                C.c_void_p(d_raw) if d_raw else None,
+                                                                C.c_void_p(stream) if stream else None))
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
                       d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:

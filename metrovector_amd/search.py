@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .errors import BuildError, InvalidVectorType
-from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, SearchResult, query_dtype_code
+from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, SearchResult, pack_allow_mask, query_dtype_code
 from .reader import VectorSpace
 
 _NP_OF = {0: np.float32, 1: np.float16, 2: np.int8, 3: np.uint8}
@@ -184,6 +184,38 @@ def rerank_top_k(space: VectorSpace, queries, candidates, k: int, metric: int | 
                 r += 1
             hits.append(ScoredVector(int(res.indices[i][j]), float(res.scores[i][j]), payload))
         out.append(hits)
+    return out
+
+
+def find_top_k_filtered(space: VectorSpace, query, k: int, allow, metric: int | None = None, corpus: GpuCorpus | None = None,
+                        device: int = 0) -> list[ScoredVector]:
+    """`find_top_k_similar` among the rows a predicate admits (`mvfgpu_search_filtered`; DESIGN.md §3 "Filtered search"):
+    `allow` covers the WHOLE space -- a bool array with one entry per vector, or the packed uint8 bitmap of one
+    (`bitorder="little"`) -- and a `corpus` that holds a row range of the space reads its own part of it.  Deleted rows are
+    never returned; fewer than k admitted rows give fewer items.  The filter lives for this call: a caller with many
+    queries per predicate makes one with `GpuCorpus.make_filter` and calls `GpuCorpus.search_filtered`.  The row payloads
+    are fetched behind the search (`gather_rows`)."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    bits = pack_allow_mask(allow, space.total_vectors())  # malformed masks are refused before anything is uploaded
+    dt = int(space.data_type())
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        with corpus.make_filter(bits, first_bit=int(corpus.info().index_base)) as flt:
+            res = corpus.search_filtered(np.asarray(query, dtype=_NP_OF[query_dtype_code(dt)]), k, metric, flt)
+        valid = res.indices[0] != np.uint64(0xFFFFFFFFFFFFFFFF)
+        rows = corpus.gather_rows(res.indices[0][valid]) if int(valid.sum()) else np.empty((0, space.dimension()), _NP_OF[dt])
+    finally:
+        if own:
+            corpus.close()
+    out = []
+    for idx, score, row in zip(res.indices[0][valid], res.scores[0][valid], rows):
+        payload = row.astype(np.float32) if dt in (0, 1) else row.copy()
+        out.append(ScoredVector(int(idx), float(score), payload))
     return out
 
 
