@@ -1,9 +1,10 @@
 // candidates.hip — mvfgpu_search_candidates / mvfgpu_search_candidates_device: the exact top-k over given lists of rows
 // (include/mvf_gpu.h; DESIGN.md §3 "Candidate search", §5 "C0 / C1 — candidate search").
 //
-// Per window of queries (the scratch stays bounded whatever nq and m are), on one stream:
-//   1. C0 (scan_candidates.hip) turns each query's list into its distinct live local rows, ascending, and their count;
-//   2. C1 scores those rows with K1's one-query arithmetic, chunk by chunk;
+// Per window of queries (the scratch stays bounded whatever nq and m are), on one stream, gather_topk (scan_gather.hip) runs
+//   1. C0 (scan_candidates.hip; handed to it as the lists' preparation) that turns each query's list into its distinct live
+//      local rows, ascending, and their count;
+//   2. C1, the gathered-row kernel on those rows with K1's one-query arithmetic, chunk by chunk;
 //   3. k <= MVFGPU_K_PER_PASS: each chunk's sorted best k are merged and formatted by K3 (select_final_kernel);
 //      larger k (or more chunks than K3 merges): every row's rank entry is ranked by sort_composites and the first k
 //      formatted by write_sorted_kernel.
@@ -27,11 +28,8 @@ using namespace mvf;
 
 namespace {
 
-constexpr uint32_t kWindow = 1024;                  // queries per window at most
-constexpr size_t kScratchBytes = 512ull << 20;      // device scratch of a window (one query's needs may exceed it)
 constexpr size_t kHostWindowBytes = 256ull << 20;   // the host call's device copies of queries, lists and results per window
 constexpr size_t kPinnedBytes = 1ull << 20;         // host windows up to this size travel through the handle's pinned mirrors
-constexpr uint32_t kSelectMaxLists = 2048;          // chunk lists select_final merges (its P = 4096 >= lists + k)
 
 int check_candidate_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                          uint32_t nq, const uint64_t* candidates, uint32_t m, uint32_t k, const void* out_scores,
@@ -49,104 +47,38 @@ int check_candidate_args(const mvfgpu_corpus* c, uint8_t metric, const void* que
 // The device work of both calls: queries, lists and results in device memory, everything on `s`, no host wait.
 int candidates_core(const CorpusView& v, uint8_t metric, const void* d_queries, uint32_t nq, const uint64_t* d_cand, uint32_t m,
                     uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, uint64_t* d_counts, hipStream_t s) {
-    const size_t nres = (size_t)nq * k;
     if (m == 0) {  // nothing listed: counts 0, every entry padding
-        MVF_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores), (int)f32_bits(pad_score(metric)), nres, s));
-        MVF_HIP_TRY(hipMemsetAsync(d_indices, 0xFF, nres * 8, s));
-        if (d_raw) MVF_HIP_TRY(hipMemsetAsync(d_raw, 0, nres * 4, s));
+        if (const int rc = fill_padding(metric, nq, k, d_scores, d_indices, d_raw, s)) return rc;
         if (d_counts) MVF_HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)nq * 8, s));
         return MVF_OK;
     }
-    int G = 64;
-    uint32_t J = 1;
-    k1_group(v.V, 1, v.k1_g, &G, &J);  // K1's one-query lane group: its bits
-    const size_t qrow = (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4);
-    const uint32_t nch = (m + kCandChunk - 1) / kCandChunk;
-    const bool by_sort = k > MVFGPU_K_PER_PASS || nch > kSelectMaxLists;
-    const bool long_lists = m > kCandLdsSort;
-    const uint32_t kcap = by_sort ? 0u : next_pow2(k);
-    const size_t per_q = (size_t)m * 4 + 4 + ((long_lists || by_sort) ? (size_t)m * 16 : 0) + (by_sort ? 0 : (size_t)nch * kcap * 8);
-    const uint32_t W = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)nq, (size_t)kWindow, kScratchBytes / per_q}));
-    size_t tmp_bytes = 0;
-    if (long_lists || by_sort) MVF_HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, m, m, nullptr, s, W, m));
-
-    AsyncBuf drows, dcnt, da, db, dtmp, dlists;
-    MVF_HIP_TRY(drows.alloc((size_t)W * m * 4, s));
-    MVF_HIP_TRY(dcnt.alloc((size_t)W * 4, s));
-    if (long_lists || by_sort) {
-        MVF_HIP_TRY(da.alloc((size_t)W * m * 8, s));
-        MVF_HIP_TRY(db.alloc((size_t)W * m * 8, s));
-        MVF_HIP_TRY(dtmp.alloc(tmp_bytes, s));
-    }
-    if (!by_sort) MVF_HIP_TRY(dlists.alloc((size_t)W * nch * kcap * 8, s));
-
-    SelectParams fp{};
-    fp.k = k;
-    fp.metric = metric;
-    fp.dtype = v.dtype;
-    fp.index_base = v.index_base;
-    fp.ids = v.ids;
-    fp.out_scores = d_scores;
-    fp.out_indices = d_indices;
-    fp.out_raw = d_raw;
-    for (uint32_t w0 = 0; w0 < nq; w0 += W) {
-        const uint32_t wn = std::min(W, nq - w0);
-        // C0
+    const bool long_lists = m > kCandLdsSort;  // C0 ranks them through the window's sort buffers
+    GatherSource src;
+    src.m = m;
+    src.prep_sorts = long_lists;
+    src.prep = [&, long_lists](uint32_t w0, uint32_t wn, const GatherScratch& sc) -> int {  // C0
         CandPrepParams pp{};
         pp.cand = d_cand + (size_t)w0 * m;
         pp.m = m;
         pp.index_base = v.index_base;
         pp.n = v.n;
         pp.tomb = v.tomb;
-        pp.ent = static_cast<uint64_t*>(da.p);
-        pp.rows = static_cast<uint32_t*>(drows.p);
-        pp.counts = static_cast<uint32_t*>(dcnt.p);
+        pp.ent = sc.a;
+        pp.rows = sc.rows;
+        pp.counts = sc.counts;
         pp.out_counts = d_counts ? d_counts + w0 : nullptr;
         if (!long_lists) {
             MVF_HIP_TRY(cand_prep_launch(pp, wn, s));
         } else {
             MVF_HIP_TRY(cand_map_launch(pp, wn, s));
-            size_t tb = tmp_bytes;
+            size_t tb = sc.tmp_bytes;
             uint64_t* sorted = nullptr;
-            MVF_HIP_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), m, m, &sorted, s, wn, m));
+            MVF_HIP_TRY(sort_composites(sc.tmp, &tb, sc.a, sc.b, m, m, &sorted, s, wn, m));
             MVF_HIP_TRY(cand_compact_launch(pp, sorted, wn, s));
         }
-        // C1
-        CandScoreParams sp{};
-        sp.rows = v.rows;
-        sp.queries = static_cast<const unsigned char*>(d_queries) + (size_t)w0 * qrow;
-        sp.cand_rows = pp.rows;
-        sp.counts = pp.counts;
-        sp.m = m;
-        sp.dim = v.dim;
-        sp.pitch = v.pitch;
-        sp.V = v.V;
-        sp.J = J;
-        if (!by_sort) {
-            sp.lists = static_cast<uint64_t*>(dlists.p);
-            sp.kcap = kcap;
-            MVF_HIP_TRY(cand_score_launch(v.dtype, metric, G, sp, wn, s));
-            // K3: the chunks' lists merged, formatted (ids, index_base, raw, padding)
-            fp.lists = sp.lists;
-            fp.nlists = nch;
-            fp.kcap = kcap;
-            fp.heads = (k + nch - 1) / nch;
-            fp.P = 4096;
-            fp.out_scores = d_scores + (size_t)w0 * k;
-            fp.out_indices = d_indices + (size_t)w0 * k;
-            fp.out_raw = d_raw ? d_raw + (size_t)w0 * k : nullptr;
-            MVF_HIP_TRY(launch_select_final(fp, wn, s));
-        } else {
-            sp.dump = static_cast<uint64_t*>(da.p);
-            MVF_HIP_TRY(cand_score_launch(v.dtype, metric, G, sp, wn, s));
-            size_t tb = tmp_bytes;
-            uint64_t* sorted = nullptr;
-            MVF_HIP_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), m,
-                                     std::min<size_t>(k, m), &sorted, s, wn, m));
-            for (uint32_t i = 0; i < wn; i++) MVF_HIP_TRY(launch_write_sorted(fp, sorted + (size_t)i * m, m, (size_t)(w0 + i) * k, s));
-        }
-    }
-    return MVF_OK;
+        return MVF_OK;
+    };
+    return gather_topk(v, metric, d_queries, nq, src, k, d_scores, d_indices, d_raw, s);  // C1 and the selection
 }
 
 }  // namespace

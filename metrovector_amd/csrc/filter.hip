@@ -6,10 +6,8 @@
 // total is read back (creation's one host wait); where the route rule could ever choose the list route, F1 then lays the
 // admitted rows out as an ascending list.  A search takes one of two routes:
 //   mask: api.hip's search with the deny mask in the tombstones' place -- the plain search's routes and kernels;
-//   list: F2 scores the listed rows chunk by chunk for groups of queries with K1's one-query arithmetic; up to
-//         MVFGPU_K_PER_PASS results and kSelectMaxLists chunks, the chunks' sorted lists are merged and formatted by K3
-//         (select_final_kernel); beyond, every listed row's rank entry is ranked by sort_composites and the first k formatted by
-//         write_sorted_kernel -- the candidate search's two endings (candidates.hip).
+//   list: gather_topk (scan_gather.hip) -- F2, the gathered-row kernel, scores the listed rows chunk by chunk for groups of
+//         queries with K1's one-query arithmetic, and the results are selected as the candidate search's are (candidates.hip).
 // Both run under mvfgpu_search_device's stream discipline; the host call goes through search_host's staging.
 
 #include "../../include/mvf_gpu.h"
@@ -39,10 +37,6 @@ struct mvfgpu_filter {
 };
 
 namespace {
-
-constexpr uint32_t kWindow = 1024;              // queries per window of the list route at most
-constexpr size_t kScratchBytes = 512ull << 20;  // device scratch of a window (one group's needs may exceed it)
-constexpr uint32_t kSelectMaxLists = 2048;      // chunk lists select_final merges (its P = 4096 >= lists + k)
 
 // could any batch size send a filter of `admitted` rows down the list route?  (the rule falls with nq inside a route of the
 // plain search and jumps where that route changes: one to four queries and the powers of two cover its steps)
@@ -133,83 +127,15 @@ namespace mvf {
 
 int filter_list_search(const CorpusView& v, const FilterUse& flt, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
                        float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
-    const size_t nres = (size_t)nq * k;
-    if (flt.admitted == 0 || v.n == 0) {  // nothing admitted: every entry padding
-        MVF_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores), (int)f32_bits(pad_score(metric)), nres, s));
-        MVF_HIP_TRY(hipMemsetAsync(d_indices, 0xFF, nres * 8, s));
-        if (d_raw) MVF_HIP_TRY(hipMemsetAsync(d_raw, 0, nres * 4, s));
-        return MVF_OK;
-    }
-    const uint32_t m = (uint32_t)flt.admitted;  // a shard holds fewer than 2^32 rows
+    if (flt.admitted == 0 || v.n == 0) return fill_padding(metric, nq, k, d_scores, d_indices, d_raw, s);  // nothing admitted
     int G = 64;
     uint32_t J = 1;
-    k1_group(v.V, 1, v.k1_g, &G, &J);  // K1's one-query lane group: its bits
-    const uint32_t qg = filter_group_queries(cand_query_bytes(v.dtype, G, J));
-    const size_t qrow = (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4);
-    const uint32_t nch = (m + kFilterChunk - 1) / kFilterChunk;
-    const bool by_sort = k > MVFGPU_K_PER_PASS || nch > kSelectMaxLists;
-    const uint32_t kcap = by_sort ? 0u : next_pow2(k);
-    const size_t per_q = by_sort ? (size_t)m * 16 : (size_t)nch * kcap * 8;
-    uint32_t W = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)nq, (size_t)kWindow, kScratchBytes / per_q}));
-    if (W > qg) W -= W % qg;  // whole groups, so that no row is read for a short group in the middle of a call
-    size_t tmp_bytes = 0;
-    if (by_sort) MVF_HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, m, m, nullptr, s, W, m));
-
-    AsyncBuf da, db, dtmp, dlists;
-    if (by_sort) {
-        MVF_HIP_TRY(da.alloc((size_t)W * m * 8, s));
-        MVF_HIP_TRY(db.alloc((size_t)W * m * 8, s));
-        MVF_HIP_TRY(dtmp.alloc(tmp_bytes, s));
-    } else {
-        MVF_HIP_TRY(dlists.alloc((size_t)W * nch * kcap * 8, s));
-    }
-
-    SelectParams fp{};
-    fp.k = k;
-    fp.metric = metric;
-    fp.dtype = v.dtype;
-    fp.index_base = v.index_base;
-    fp.ids = v.ids;
-    fp.out_scores = d_scores;
-    fp.out_indices = d_indices;
-    fp.out_raw = d_raw;
-    for (uint32_t w0 = 0; w0 < nq; w0 += W) {
-        const uint32_t wn = std::min(W, nq - w0);
-        FilterScoreParams sp{};
-        sp.rows = v.rows;
-        sp.queries = static_cast<const unsigned char*>(d_queries) + (size_t)w0 * qrow;
-        sp.list = flt.list;
-        sp.m = m;
-        sp.nq = wn;
-        sp.dim = v.dim;
-        sp.pitch = v.pitch;
-        sp.V = v.V;
-        sp.J = J;
-        if (!by_sort) {
-            sp.lists = static_cast<uint64_t*>(dlists.p);
-            sp.kcap = kcap;
-            MVF_HIP_TRY(filter_score_launch(v.dtype, metric, G, sp, s));
-            // K3: the chunks' lists merged, formatted (ids, index_base, raw, padding)
-            fp.lists = sp.lists;
-            fp.nlists = nch;
-            fp.kcap = kcap;
-            fp.heads = (k + nch - 1) / nch;
-            fp.P = 4096;
-            fp.out_scores = d_scores + (size_t)w0 * k;
-            fp.out_indices = d_indices + (size_t)w0 * k;
-            fp.out_raw = d_raw ? d_raw + (size_t)w0 * k : nullptr;
-            MVF_HIP_TRY(launch_select_final(fp, wn, s));
-        } else {
-            sp.dump = static_cast<uint64_t*>(da.p);
-            MVF_HIP_TRY(filter_score_launch(v.dtype, metric, G, sp, s));
-            size_t tb = tmp_bytes;
-            uint64_t* sorted = nullptr;
-            MVF_HIP_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), m,
-                                     std::min<size_t>(k, m), &sorted, s, wn, m));
-            for (uint32_t i = 0; i < wn; i++) MVF_HIP_TRY(launch_write_sorted(fp, sorted + (size_t)i * m, m, (size_t)(w0 + i) * k, s));
-        }
-    }
-    return MVF_OK;
+    k1_group(v.V, 1, v.k1_g, &G, &J);
+    GatherSource src;
+    src.m = (uint32_t)flt.admitted;  // a shard holds fewer than 2^32 rows
+    src.qg = filter_group_queries(cand_query_bytes(v.dtype, G, J));
+    src.list = flt.list;
+    return gather_topk(v, metric, d_queries, nq, src, k, d_scores, d_indices, d_raw, s);
 }
 
 }  // namespace mvf

@@ -123,4 +123,31 @@ MVF_HD uint32_t next_pow2(uint32_t v) {
     return p;
 }
 
+// A count per wave (`wave_count`, the same in every lane) of a block of 1024 threads -> the counts of the waves in front of
+// the caller's (*before) and of the whole block (returned).  wsum: 16 words of LDS; holds one __syncthreads(), and the caller
+// puts another in front of the next use of wsum.
+__device__ __forceinline__ uint32_t block_counts_1024(uint32_t wave_count, uint32_t* wsum, uint32_t* before) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0) wsum[wave] = wave_count;
+    __syncthreads();
+    uint32_t off = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 16; w++) {
+        const uint32_t c = wsum[w];
+        off += w < wave ? c : 0u;
+        tot += c;
+    }
+    *before = off;
+    return tot;
+}
+
+// The same for one flag per thread: *rank = the threads in front of the caller that raise `keep`; returns how many do.
+__device__ __forceinline__ uint32_t block_rank_1024(bool keep, uint32_t* wsum, uint32_t* rank) {
+    const unsigned long long bm = __builtin_amdgcn_ballot_w64(keep);
+    uint32_t before;
+    const uint32_t tot = block_counts_1024((uint32_t)__builtin_popcountll(bm), wsum, &before);
+    *rank = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
+    return tot;
+}
+
 }  // namespace mvf

@@ -960,7 +960,7 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long mask, uint32_t n) 
 // F16: Float16 rows -- eight elements per 16-B vector, widened exactly, K1's fmaf order over them (k1_rowscore.h).
 template <int METRIC, int G, bool F16 = false>
 __global__ void __launch_bounds__(256) rescore_k1_kernel(RescoreParams p, uint32_t nq, uint32_t slices, uint32_t split, uint32_t J) {
-    constexpr int RPG = 64 / G, U = 4;
+    constexpr int RPG = 64 / G, U = 4, DT = F16 ? MVF_DTYPE_FLOAT16 : MVF_DTYPE_FLOAT32;
     constexpr uint32_t PER_ROUND = (uint32_t)(RPG * U);
     constexpr bool NEED_XX = METRIC == MVF_METRIC_COSINE;
     const int lane = threadIdx.x & 63, sub = lane % G, rsel = lane / G;
@@ -993,9 +993,9 @@ __global__ void __launch_bounds__(256) rescore_k1_kernel(RescoreParams p, uint32
                     src[u] = ok[u] ? nth_set_bit(mask, rank) : 0;
                     row[u] = (uint32_t)__shfl((int)(uint32_t)ce, src[u], 64);
                 }
-                float acc[U], xx[U];
+                float acc[1][U], xx[U];
 #pragma unroll
-                for (int u = 0; u < U; u++) acc[u] = 0.0f, xx[u] = 0.0f;
+                for (int u = 0; u < U; u++) acc[0][u] = 0.0f, xx[u] = 0.0f;
                 for (uint32_t j = 0; j < J; j++) {
                     const uint32_t v = j * G + (uint32_t)sub;
                     const bool vv = v < V;
@@ -1011,27 +1011,13 @@ __global__ void __launch_bounds__(256) rescore_k1_kernel(RescoreParams p, uint32
                         const uint32_t e = v * (uint32_t)EPV + (uint32_t)w;
                         qe[w] = e < p.dim ? qp[e] : 0.0f;
                     }
-                    if constexpr (F16) {
-                        const float4 qa = make_float4(qe[0], qe[1], qe[2], qe[3]), qb = make_float4(qe[4], qe[5], qe[6], qe[7]);
-#pragma unroll
-                        for (int u = 0; u < U; u++) {
-                            float xf[8];
-                            k1::widen_f16(x[u], xf);
-                            acc[u] = k1::acc8_f16<METRIC>(acc[u], qa, qb, xf);
-                            if constexpr (NEED_XX) xx[u] = k1::xx8_f16(xx[u], xf);
-                        }
-                    } else {
-                        const float4 qv = make_float4(qe[0], qe[1], qe[2], qe[3]);
-#pragma unroll
-                        for (int u = 0; u < U; u++) {
-                            acc[u] = k1::acc4<METRIC>(acc[u], qv, x[u]);
-                            if constexpr (NEED_XX) xx[u] = k1::xx4(xx[u], x[u]);
-                        }
-                    }
+                    k1::accumulate<DT, METRIC, U, 1>(acc, xx, x, [&](int, int half) __attribute__((always_inline)) {
+                        return make_float4(qe[half * 4], qe[half * 4 + 1], qe[half * 4 + 2], qe[half * 4 + 3]);
+                    });
                 }
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const float s = k1::group_sum<G>(acc[u]);
+                    const float s = k1::group_sum<G>(acc[0][u]);
                     const float xxs = NEED_XX ? k1::group_sum<G>(xx[u]) : 0.0f;
                     const uint32_t key = k1::key<METRIC>(s, xxs, qq);
                     if (sub == 0 && ok[u]) c[keep_cap + sl * 64u + (uint32_t)src[u]] = ((uint64_t)key << 32) | row[u];
@@ -1040,21 +1026,6 @@ __global__ void __launch_bounds__(256) rescore_k1_kernel(RescoreParams p, uint32
         }
     }
 }
-
-template <int METRIC, bool F16>
-const void* pick_rescore_k1(int G) {
-    switch (G) {
-    case 1: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 1, F16>);
-    case 4: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 4, F16>);
-    case 8: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 8, F16>);
-    case 16: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 16, F16>);
-    case 32: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 32, F16>);
-    case 64: return reinterpret_cast<const void*>(&rescore_k1_kernel<METRIC, 64, F16>);
-    default: return nullptr;
-    }
-}
-template <int METRIC>
-const void* pick_rescore_k1(int G, bool f16) { return f16 ? pick_rescore_k1<METRIC, true>(G) : pick_rescore_k1<METRIC, false>(G); }
 
 // One thread per query: tau[q] = the tighter of itself and ord(L -/+ delta), L = the worst exact score of its k best
 // approximate candidates (rescore_score_kernel<., true>); re-arms lkey.  The 2 % on delta covers the f32 rounding of the
@@ -1221,10 +1192,12 @@ hipError_t launch_rescore_k1(const RescoreParams& p, int metric, uint32_t nq, in
     if (nq == 0) return hipSuccess;
     if (p.dtype != MVF_DTYPE_FLOAT32 && p.dtype != MVF_DTYPE_FLOAT16) return hipErrorInvalidValue;
     const bool f16 = p.dtype == MVF_DTYPE_FLOAT16;
-    const void* fn = metric == MVF_METRIC_L2               ? pick_rescore_k1<MVF_METRIC_L2>(G, f16)
-                     : metric == MVF_METRIC_INNER_PRODUCT ? pick_rescore_k1<MVF_METRIC_INNER_PRODUCT>(G, f16)
-                     : metric == MVF_METRIC_COSINE        ? pick_rescore_k1<MVF_METRIC_COSINE>(G, f16)
-                                                          : nullptr;
+    const void* fn = k1::for_metric(metric, [&](auto m) {
+        return k1::for_group(G, [&](auto g) {
+            constexpr int M = decltype(m)::value, GG = decltype(g)::value;
+            return f16 ? reinterpret_cast<const void*>(&rescore_k1_kernel<M, GG, true>) : reinterpret_cast<const void*>(&rescore_k1_kernel<M, GG, false>);
+        });
+    });
     if (!fn) return hipErrorInvalidValue;
     // items as the final pass of launch_rescore_wave: a query's 64-candidate slices, `split` waves sharing a slice so that
     // ONE query's ~1000 candidates spread over the chip (nq = 1: 32 slices x 16 waves, 128 blocks)

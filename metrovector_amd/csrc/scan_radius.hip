@@ -2,9 +2,12 @@
 //
 // R1 reads the rows exactly as K1 does (scan_stream.inc): G lanes per row, each lane owning the 16-B vectors
 // v = j*G + sub, U = 4 row groups in flight per wave, non-temporal 16-B loads, the query staged in LDS (f32 / packed
-// int8), Float16 widened exactly, sdot4 / udot4 for Int8 / UInt8 rows.  The per-lane accumulation order, the G-lane
-// pairing of the partial sums and the score -> key arithmetic are K1's, so for the same lane-group width the keys are
-// bit-identical to those the top-k path ranks.  The epilogue differs: there is no running threshold, the bound is
+// int8), Float16 widened exactly, sdot4 / udot4 for Int8 / UInt8 rows.  The per-lane accumulation, the G-lane sums and
+// the score -> key arithmetic are K1's as k1_rowscore.h states them (the reduce-scatter below pairs the partial sums as
+// its butterfly does), so for the same lane-group width the keys are bit-identical to those the top-k path ranks.  Two
+// pieces stay written out here because the header's forms cost some one-query instantiations a wave per SIMD
+// (profiles/r10_k1_rowscore_refactor.txt): the staging loop (k1::stage_queries' order, four queries interleaved) and the
+// row's sum of squares of Float16 rows (k1::xx8_f16's line).  The epilogue differs: there is no running threshold, the bound is
 // fixed per query, and every row whose key is <= the bound -- and whose tombstone bit is clear, read only for such
 // rows -- is counted with ONE returning atomic per wave, query and row group that has a match (ballot + mbcnt give
 // every matching lane its slot).  A query's list holds `cap` composites; the counter keeps counting past it.
@@ -23,21 +26,6 @@
 namespace mvf {
 namespace {
 
-template <int DT> struct RTraits;
-template <> struct RTraits<MVF_DTYPE_FLOAT32> { static constexpr int ES = 4; static constexpr bool INT = false; using Q = float; using Acc = float; };
-template <> struct RTraits<MVF_DTYPE_FLOAT16> { static constexpr int ES = 2; static constexpr bool INT = false; using Q = float; using Acc = float; };
-template <> struct RTraits<MVF_DTYPE_INT8> { static constexpr int ES = 1; static constexpr bool INT = true; using Q = int8_t; using Acc = int32_t; };
-template <> struct RTraits<MVF_DTYPE_UINT8> { static constexpr int ES = 1; static constexpr bool INT = true; using Q = uint8_t; using Acc = int32_t; };
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <int G, typename T>
-__device__ __forceinline__ T rgroup_sum(T v) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // Wave-aggregated append: every lane with `hit` gets a slot of the query's list; one returning atomic per wave.
 // Must be reached by the whole wave (the ballot).
 __device__ __forceinline__ void radius_append(bool hit, uint64_t comp, uint32_t* cnt, uint64_t* list, uint32_t cap, int lane) {
@@ -54,14 +42,14 @@ __device__ __forceinline__ void radius_append(bool hit, uint64_t comp, uint32_t*
 
 template <int DT, int METRIC, int G, int NQ>
 __global__ void __launch_bounds__(256) radius_scan_kernel(RadiusParams p) {
-    using Tr = RTraits<DT>;
+    using Tr = k1::Traits<DT>;
     using Acc = typename Tr::Acc;
     constexpr int ES = Tr::ES;
     constexpr int EPV = 16 / ES;
     constexpr int RPG = 64 / G;
     constexpr int U = 4;
     constexpr int QB = Tr::INT ? 16 : EPV * 4;
-    constexpr bool NEED_XX = (METRIC == MVF_METRIC_COSINE) || (Tr::INT && METRIC == MVF_METRIC_L2);
+    constexpr bool NEED_XX = k1::kNeedXX<DT, METRIC>;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -108,7 +96,7 @@ __global__ void __launch_bounds__(256) radius_scan_kernel(RadiusParams p) {
     }
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
-        Acc s = rgroup_sum<64>(qq_part[q]);
+        Acc s = k1::group_sum<64>(qq_part[q]);
         if (lane == 0) red[q * 4 + wave] = s;
     }
     __syncthreads();
@@ -116,25 +104,6 @@ __global__ void __launch_bounds__(256) radius_scan_kernel(RadiusParams p) {
 #pragma unroll
     for (int q = 0; q < NQ; q++) qq[q] = red[q * 4 + 0] + red[q * 4 + 1] + red[q * 4 + 2] + red[q * 4 + 3];
 
-    auto make_key = [&](Acc s, Acc xxs, Acc qqv) __attribute__((always_inline)) -> uint32_t {
-        if constexpr (Tr::INT) {
-            if constexpr (METRIC == MVF_METRIC_L2) return key_from_raw(qqv + xxs - 2 * s, METRIC);
-            else if constexpr (METRIC == MVF_METRIC_INNER_PRODUCT) return key_from_raw(s, METRIC);
-            else {
-                const float den = sqrtf((float)qqv) * sqrtf((float)xxs);
-                return key_from_score(den > 0.0f ? (float)s / den : 0.0f, METRIC);
-            }
-        } else {
-            float sc;
-            if constexpr (METRIC == MVF_METRIC_L2) sc = sqrtf(s);
-            else if constexpr (METRIC == MVF_METRIC_INNER_PRODUCT) sc = s;
-            else {
-                const float den = sqrtf(qqv) * sqrtf(xxs);
-                sc = den > 0.0f ? s / den : 0.0f;
-            }
-            return key_from_score(sc, METRIC);
-        }
-    };
     auto live = [&](uint32_t r) __attribute__((always_inline)) -> bool {
         return !(p.tomb && ((p.tomb[r >> 5] >> (r & 31)) & 1u));
     };
@@ -162,73 +131,33 @@ __global__ void __launch_bounds__(256) radius_scan_kernel(RadiusParams p) {
         for (uint32_t j = 0; j < p.J; j++) {
             const uint32_t v = j * G + sub;
             const bool vv = v < p.V;
-            u32x4 x[U];
+            k1::u32x4 x[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
-                x[u] = u32x4{0, 0, 0, 0};
-                if (vv && rv[u]) x[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rp[u] + (size_t)v * 16));
+                x[u] = k1::u32x4{0, 0, 0, 0};
+                if (vv && rv[u]) x[u] = __builtin_nontemporal_load(reinterpret_cast<const k1::u32x4*>(rp[u] + (size_t)v * 16));
             }
             if constexpr (DT == MVF_DTYPE_FLOAT32) {
 #pragma unroll
                 for (int q = 0; q < NQ; q++) {
                     const float4 qv = *reinterpret_cast<const float4*>(qs + q * qstride + v * 16);
 #pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        const float x0 = __uint_as_float(x[u].x), x1 = __uint_as_float(x[u].y),
-                                    x2 = __uint_as_float(x[u].z), x3 = __uint_as_float(x[u].w);
-                        if constexpr (METRIC == MVF_METRIC_L2) {
-                            float t0 = qv.x - x0, t1 = qv.y - x1, t2 = qv.z - x2, t3 = qv.w - x3;
-                            acc[u][q] = fmaf(t0, t0, acc[u][q]);
-                            acc[u][q] = fmaf(t1, t1, acc[u][q]);
-                            acc[u][q] = fmaf(t2, t2, acc[u][q]);
-                            acc[u][q] = fmaf(t3, t3, acc[u][q]);
-                        } else {
-                            acc[u][q] = fmaf(qv.x, x0, acc[u][q]);
-                            acc[u][q] = fmaf(qv.y, x1, acc[u][q]);
-                            acc[u][q] = fmaf(qv.z, x2, acc[u][q]);
-                            acc[u][q] = fmaf(qv.w, x3, acc[u][q]);
-                        }
-                    }
+                    for (int u = 0; u < U; u++) acc[u][q] = k1::acc4<METRIC>(acc[u][q], qv, x[u]);
                 }
                 if constexpr (NEED_XX) {
 #pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        const float x0 = __uint_as_float(x[u].x), x1 = __uint_as_float(x[u].y),
-                                    x2 = __uint_as_float(x[u].z), x3 = __uint_as_float(x[u].w);
-                        xx[u] = fmaf(x0, x0, xx[u]);
-                        xx[u] = fmaf(x1, x1, xx[u]);
-                        xx[u] = fmaf(x2, x2, xx[u]);
-                        xx[u] = fmaf(x3, x3, xx[u]);
-                    }
+                    for (int u = 0; u < U; u++) xx[u] = k1::xx4(xx[u], x[u]);
                 }
             } else if constexpr (DT == MVF_DTYPE_FLOAT16) {
                 float xf[U][8];
 #pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const uint32_t w[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        xf[u][2 * i] = __half2float(__ushort_as_half((unsigned short)(w[i] & 0xFFFFu)));
-                        xf[u][2 * i + 1] = __half2float(__ushort_as_half((unsigned short)(w[i] >> 16)));
-                    }
-                }
+                for (int u = 0; u < U; u++) k1::widen_f16(x[u], xf[u]);
 #pragma unroll
                 for (int q = 0; q < NQ; q++) {
                     const float4 qa = *reinterpret_cast<const float4*>(qs + q * qstride + v * 32);
                     const float4 qb = *reinterpret_cast<const float4*>(qs + q * qstride + v * 32 + 16);
-                    const float qf[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
 #pragma unroll
-                    for (int u = 0; u < U; u++) {
-#pragma unroll
-                        for (int i = 0; i < 8; i++) {
-                            if constexpr (METRIC == MVF_METRIC_L2) {
-                                float t = qf[i] - xf[u][i];
-                                acc[u][q] = fmaf(t, t, acc[u][q]);
-                            } else {
-                                acc[u][q] = fmaf(qf[i], xf[u][i], acc[u][q]);
-                            }
-                        }
-                    }
+                    for (int u = 0; u < U; u++) acc[u][q] = k1::acc8_f16<METRIC>(acc[u][q], qa, qb, xf[u]);
                 }
                 if constexpr (NEED_XX) {
 #pragma unroll
@@ -237,39 +166,16 @@ __global__ void __launch_bounds__(256) radius_scan_kernel(RadiusParams p) {
                         for (int i = 0; i < 8; i++) xx[u] = fmaf(xf[u][i], xf[u][i], xx[u]);
                 }
             } else {  // Int8 / UInt8: exact i32
+                constexpr bool S = DT == MVF_DTYPE_INT8;
 #pragma unroll
                 for (int q = 0; q < NQ; q++) {
                     const uint4 qv = *reinterpret_cast<const uint4*>(qs + q * qstride + v * 16);
 #pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        if constexpr (DT == MVF_DTYPE_INT8) {
-                            acc[u][q] = __builtin_amdgcn_sdot4((int)qv.x, (int)x[u].x, acc[u][q], false);
-                            acc[u][q] = __builtin_amdgcn_sdot4((int)qv.y, (int)x[u].y, acc[u][q], false);
-                            acc[u][q] = __builtin_amdgcn_sdot4((int)qv.z, (int)x[u].z, acc[u][q], false);
-                            acc[u][q] = __builtin_amdgcn_sdot4((int)qv.w, (int)x[u].w, acc[u][q], false);
-                        } else {
-                            acc[u][q] = (int32_t)__builtin_amdgcn_udot4(qv.x, x[u].x, (uint32_t)acc[u][q], false);
-                            acc[u][q] = (int32_t)__builtin_amdgcn_udot4(qv.y, x[u].y, (uint32_t)acc[u][q], false);
-                            acc[u][q] = (int32_t)__builtin_amdgcn_udot4(qv.z, x[u].z, (uint32_t)acc[u][q], false);
-                            acc[u][q] = (int32_t)__builtin_amdgcn_udot4(qv.w, x[u].w, (uint32_t)acc[u][q], false);
-                        }
-                    }
+                    for (int u = 0; u < U; u++) acc[u][q] = k1::dot16_int<S>(acc[u][q], qv, x[u]);
                 }
                 if constexpr (NEED_XX) {
 #pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        if constexpr (DT == MVF_DTYPE_INT8) {
-                            xx[u] = __builtin_amdgcn_sdot4((int)x[u].x, (int)x[u].x, xx[u], false);
-                            xx[u] = __builtin_amdgcn_sdot4((int)x[u].y, (int)x[u].y, xx[u], false);
-                            xx[u] = __builtin_amdgcn_sdot4((int)x[u].z, (int)x[u].z, xx[u], false);
-                            xx[u] = __builtin_amdgcn_sdot4((int)x[u].w, (int)x[u].w, xx[u], false);
-                        } else {
-                            xx[u] = (int32_t)__builtin_amdgcn_udot4(x[u].x, x[u].x, (uint32_t)xx[u], false);
-                            xx[u] = (int32_t)__builtin_amdgcn_udot4(x[u].y, x[u].y, (uint32_t)xx[u], false);
-                            xx[u] = (int32_t)__builtin_amdgcn_udot4(x[u].z, x[u].z, (uint32_t)xx[u], false);
-                            xx[u] = (int32_t)__builtin_amdgcn_udot4(x[u].w, x[u].w, (uint32_t)xx[u], false);
-                        }
-                    }
+                    for (int u = 0; u < U; u++) xx[u] = k1::dot16_int<S>(xx[u], uint4{x[u].x, x[u].y, x[u].z, x[u].w}, x[u]);
                 }
             }
         }
@@ -296,18 +202,18 @@ __global__ void __launch_bounds__(256) radius_scan_kernel(RadiusParams p) {
                 for (int off = G / 8; off > 0; off >>= 1) xx1 += __shfl_xor(xx1, off, 64);
             }
             const uint32_t rl = (g0 + ul) * RPG + rsel;
-            const uint32_t key = make_key(s1, xx1, qq[0]);
+            const uint32_t key = k1::make_key<DT, METRIC>(s1, xx1, qq[0]);
             const bool hit = (sub & (G / 4 - 1)) == 0 && rl < p.n && qvalid[0] && key <= bnd[0] && live(rl);
             radius_append(hit, ((uint64_t)key << 32) | rl, p.counts + q0, p.lists ? p.lists + (size_t)q0 * p.cap : nullptr, p.cap, lane);
         } else {
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 Acc xxs = 0;
-                if constexpr (NEED_XX) xxs = rgroup_sum<G>(xx[u]);
+                if constexpr (NEED_XX) xxs = k1::group_sum<G>(xx[u]);
 #pragma unroll
                 for (int q = 0; q < NQ; q++) {
-                    const Acc s = rgroup_sum<G>(acc[u][q]);
-                    const uint32_t key = make_key(s, xxs, qq[q]);
+                    const Acc s = k1::group_sum<G>(acc[u][q]);
+                    const uint32_t key = k1::make_key<DT, METRIC>(s, xxs, qq[q]);
                     const bool hit = sub == 0 && rv[u] && qvalid[q] && key <= bnd[q] && live(r[u]);
                     radius_append(hit, ((uint64_t)key << 32) | r[u], p.counts + q0 + q,
                                   p.lists ? p.lists + (size_t)(q0 + q) * p.cap : nullptr, p.cap, lane);
@@ -350,7 +256,7 @@ __global__ void __launch_bounds__(1024) radius_pack_kernel(RadiusPackParams p) {
 }
 
 // R3: grid (nq), block 256, dynamic LDS radius_scan_lds_bytes(Float32, G, J, 1).  The per-row arithmetic is K1's, from
-// k1_rowscore.h (shared with the int8-shadow stream's re-scoring); the query's sum of squares is staged in K1's order below.
+// k1_rowscore.h, as R1's.
 template <int METRIC, int G>
 __global__ void __launch_bounds__(256) radius_rescore_kernel(RadiusRescoreParams p) {
     constexpr int RPG = 64 / G;
@@ -360,19 +266,12 @@ __global__ void __launch_bounds__(256) radius_rescore_kernel(RadiusRescoreParams
     const int sub = lane % G, rsel = lane / G;
     const uint32_t q = blockIdx.x;
     const uint32_t VP = p.J * G;
-    float* qs = reinterpret_cast<float*>(smem);
+    unsigned char* qs = smem;
     float* red = reinterpret_cast<float*>(smem + ((VP * 16u + 15u) & ~15u));
     // the query in LDS and its sum of squares, in R1's (K1's) order
-    float qq_part = 0.0f;
-    for (uint32_t e = tid; e < VP * 4u; e += 256) {
-        const float v = e < p.dim ? p.queries[(size_t)q * p.dim + e] : 0.0f;
-        qs[e] = v;
-        qq_part = fmaf(v, v, qq_part);
-    }
-    const float qsum = rgroup_sum<64>(qq_part);
-    if (lane == 0) red[wave] = qsum;
-    __syncthreads();
-    const float qq = red[0] + red[1] + red[2] + red[3];
+    const float* const src[1] = {p.queries + (size_t)q * p.dim};
+    float qq[1];
+    k1::stage_queries<MVF_DTYPE_FLOAT32, 1, true>(src, p.dim, VP * 4u, qs, 0, red, qq);
     const uint32_t bnd = p.bound[q];
     const uint32_t m = min(p.ccnt[q], p.ccap);
     const uint64_t* cand = p.cand + (size_t)q * p.ccap;
@@ -383,72 +282,43 @@ __global__ void __launch_bounds__(256) radius_rescore_kernel(RadiusRescoreParams
         const bool ok = c0 != kPadComposite;
         const uint32_t row = (uint32_t)c0;
         const unsigned char* rp = p.rows + (size_t)(ok ? row : 0u) * p.pitch;
-        float acc = 0.0f, xx = 0.0f;
+        float acc[1][1] = {{0.0f}}, xx[1] = {0.0f};
         for (uint32_t j = 0; j < p.J; j++) {
             const uint32_t v = j * G + sub;
-            k1::u32x4 x = k1::u32x4{0, 0, 0, 0};
-            if (ok && v < p.V) x = *reinterpret_cast<const k1::u32x4*>(rp + (size_t)v * 16);
-            const float4 qv = *reinterpret_cast<const float4*>(qs + v * 4);
-            acc = k1::acc4<METRIC>(acc, qv, x);
-            if constexpr (NEED_XX) xx = k1::xx4(xx, x);
+            k1::u32x4 x[1] = {k1::u32x4{0, 0, 0, 0}};
+            if (ok && v < p.V) x[0] = *reinterpret_cast<const k1::u32x4*>(rp + (size_t)v * 16);
+            k1::accumulate<MVF_DTYPE_FLOAT32, METRIC, 1, 1>(acc, xx, x, [&](int, int) __attribute__((always_inline)) {
+                return *reinterpret_cast<const float4*>(qs + v * 16);
+            });
         }
-        const float s = k1::group_sum<G>(acc);
-        const float xxs = NEED_XX ? k1::group_sum<G>(xx) : 0.0f;
-        const uint32_t key = k1::key<METRIC>(s, xxs, qq);
+        const float s = k1::group_sum<G>(acc[0][0]);
+        const float xxs = NEED_XX ? k1::group_sum<G>(xx[0]) : 0.0f;
+        const uint32_t key = k1::key<METRIC>(s, xxs, qq[0]);
         const bool hit = sub == 0 && ok && key <= bnd;
         radius_append(hit, ((uint64_t)key << 32) | row, p.counts + q, list, p.cap, lane);
     }
 }
 
-template <int METRIC>
-const void* pick_rescore(int G) {
-    switch (G) {
-        case 1: return reinterpret_cast<const void*>(&radius_rescore_kernel<METRIC, 1>);
-        case 4: return reinterpret_cast<const void*>(&radius_rescore_kernel<METRIC, 4>);
-        case 8: return reinterpret_cast<const void*>(&radius_rescore_kernel<METRIC, 8>);
-        case 16: return reinterpret_cast<const void*>(&radius_rescore_kernel<METRIC, 16>);
-        case 32: return reinterpret_cast<const void*>(&radius_rescore_kernel<METRIC, 32>);
-        case 64: return reinterpret_cast<const void*>(&radius_rescore_kernel<METRIC, 64>);
-        default: return nullptr;
-    }
-}
-
-template <int DT, int METRIC, int NQ>
-const void* pick_g(int G) {
-    switch (G) {
-        case 1: return reinterpret_cast<const void*>(&radius_scan_kernel<DT, METRIC, 1, NQ>);
-        case 4: return reinterpret_cast<const void*>(&radius_scan_kernel<DT, METRIC, 4, NQ>);
-        case 8: return reinterpret_cast<const void*>(&radius_scan_kernel<DT, METRIC, 8, NQ>);
-        case 16: return reinterpret_cast<const void*>(&radius_scan_kernel<DT, METRIC, 16, NQ>);
-        case 32: return reinterpret_cast<const void*>(&radius_scan_kernel<DT, METRIC, 32, NQ>);
-        case 64: return reinterpret_cast<const void*>(&radius_scan_kernel<DT, METRIC, 64, NQ>);
-        default: return nullptr;
-    }
-}
-
-template <int DT, int METRIC>
-const void* pick_nq(int G, int nqv) {
-    return nqv == 4 ? pick_g<DT, METRIC, 4>(G) : nqv == 1 ? pick_g<DT, METRIC, 1>(G) : nullptr;
-}
-
 template <int DT>
-const void* pick_metric(int metric, int G, int nqv) {
-    switch (metric) {
-        case MVF_METRIC_L2: return pick_nq<DT, MVF_METRIC_L2>(G, nqv);
-        case MVF_METRIC_INNER_PRODUCT: return pick_nq<DT, MVF_METRIC_INNER_PRODUCT>(G, nqv);
-        case MVF_METRIC_COSINE: return pick_nq<DT, MVF_METRIC_COSINE>(G, nqv);
-        default: return nullptr;
-    }
+const void* pick_scan(int metric, int G, int nqv) {
+    return k1::for_metric(metric, [&](auto m) {
+        return k1::for_group(G, [&](auto g) -> const void* {
+            constexpr int M = decltype(m)::value, GG = decltype(g)::value;
+            return nqv == 4   ? reinterpret_cast<const void*>(&radius_scan_kernel<DT, M, GG, 4>)
+                   : nqv == 1 ? reinterpret_cast<const void*>(&radius_scan_kernel<DT, M, GG, 1>)
+                              : nullptr;
+        });
+    });
 }
 
 }  // namespace
 
 const void* radius_scan_kernel_ptr(uint8_t dtype, int metric, int G, int nqv) {
     switch (dtype) {
-        case MVF_DTYPE_FLOAT32: return pick_metric<MVF_DTYPE_FLOAT32>(metric, G, nqv);
-        case MVF_DTYPE_FLOAT16: return pick_metric<MVF_DTYPE_FLOAT16>(metric, G, nqv);
-        case MVF_DTYPE_INT8: return pick_metric<MVF_DTYPE_INT8>(metric, G, nqv);
-        case MVF_DTYPE_UINT8: return pick_metric<MVF_DTYPE_UINT8>(metric, G, nqv);
+        case MVF_DTYPE_FLOAT32: return pick_scan<MVF_DTYPE_FLOAT32>(metric, G, nqv);
+        case MVF_DTYPE_FLOAT16: return pick_scan<MVF_DTYPE_FLOAT16>(metric, G, nqv);
+        case MVF_DTYPE_INT8: return pick_scan<MVF_DTYPE_INT8>(metric, G, nqv);
+        case MVF_DTYPE_UINT8: return pick_scan<MVF_DTYPE_UINT8>(metric, G, nqv);
         default: return nullptr;
     }
 }
@@ -469,9 +339,9 @@ hipError_t radius_scan_launch(uint8_t dtype, int metric, int G, int nqv, const R
 
 hipError_t radius_rescore_launch(int metric, int G, const RadiusRescoreParams& p, uint32_t nq, size_t lds, hipStream_t s) {
     if (nq == 0) return hipSuccess;
-    const void* fn = metric == MVF_METRIC_L2 ? pick_rescore<MVF_METRIC_L2>(G)
-                     : metric == MVF_METRIC_INNER_PRODUCT ? pick_rescore<MVF_METRIC_INNER_PRODUCT>(G)
-                     : metric == MVF_METRIC_COSINE ? pick_rescore<MVF_METRIC_COSINE>(G) : nullptr;
+    const void* fn = k1::for_metric(metric, [&](auto m) {
+        return k1::for_group(G, [&](auto g) { return reinterpret_cast<const void*>(&radius_rescore_kernel<decltype(m)::value, decltype(g)::value>); });
+    });
     if (!fn) return hipErrorInvalidValue;
     RadiusRescoreParams arg = p;
     void* args[] = {&arg};

@@ -164,6 +164,40 @@ def test_edge_entries(oracle):
         assert int(res.counts[0]) == 3 and res.indices[0][2] == base + 10 and np.isnan(res.scores[0][2])
 
 
+@pytest.mark.parametrize("dtype,metric", [(G.FLOAT32, G.L2), (G.INT8, G.COSINE)])
+@pytest.mark.parametrize("k", [10, 1500])
+def test_per_query_counts_next_to_full_chunks(oracle, dtype, metric, k):
+    """One launch of the gathered-row kernel with per-query counts: a list of three chunks (the last partial) of distinct
+    live rows, next to a list that holds one row (its chunks 1 and 2 are empty) and a list of dead entries only (count 0);
+    k = 10 merges the chunks' lists, k = 1500 sorts the dump.  The full list's results do not depend on its neighbours."""
+    n, dim, nq, m = 4001, 7, 3, 2 * 1024 + 5
+    rows = oracle.synth_rows(141, 0, n, dim, dtype)
+    qs = oracle.synth_queries(142, nq, dim, dtype)
+    dead = np.zeros(n, bool)
+    dead[77] = True
+    live = np.nonzero(~dead)[0]
+    lists = np.empty((nq, m), np.uint64)
+    lists[0] = np.random.default_rng(14).permutation(live)[:m]
+    lists[1] = 1234
+    lists[2] = np.resize(np.array([PAD, n, n + 9, 77, 2 ** 40], np.uint64), m)
+    with G.GpuCorpus.from_array(rows) as c:
+        c.set_tombstones(np.packbits(dead, bitorder="little"))
+        res = c.search_candidates(qs, lists, k, metric)
+        assert res.counts.tolist() == [m, 1, 0]
+        for j in range(nq):
+            all_s = oracle.scores(rows, dtype, metric, qs[j])
+            _check_oracle(oracle, rows, dtype, metric, qs[j], lists[j], k, res.scores[j], res.indices[j], res.raw[j],
+                          int(res.counts[j]), all_s, dead=dead)
+            cnt = int(res.counts[j])
+            assert (res.indices[j][cnt:] == PAD).all() and (res.raw[j][cnt:] == 0).all()
+            assert (res.scores[j][cnt:] == (np.inf if metric == G.L2 else -np.inf)).all()
+        assert res.indices[1][0] == 1234
+        alone = c.search_candidates(qs[:1], lists[:1], k, metric)
+        assert alone.indices.tobytes() == res.indices[:1].tobytes()
+        assert alone.scores.tobytes() == res.scores[:1].tobytes()
+        assert alone.raw.tobytes() == res.raw[:1].tobytes() and alone.counts[0] == res.counts[0]
+
+
 def test_ids_in_the_host_call_and_nothing_listed(oracle):
     n, dim = 3001, 24
     rows = oracle.synth_rows(91, 0, n, dim, G.INT8)

@@ -176,6 +176,29 @@ def test_the_int8_shadow_stream_answers_the_mask_route_with_the_twins_bits(oracl
     assert _same(res, yard)
 
 
+@pytest.mark.parametrize("dtype", [0, 1, 2, 3])
+@pytest.mark.parametrize("dim", [7, 100])
+def test_the_list_route_and_the_candidate_search_share_their_bits(oracle, monkeypatch, dtype, dim):
+    """The gathered-row kernel's two addressings on one handle: one list for groups of queries (the list route under a filter
+    that admits every row; five queries: a group of four and a short one) and a list and a count per query (the candidate
+    search given every row) write the same bytes."""
+    n, nq, k = 2 * 1024 + 33, 5, 10
+    rows = oracle.synth_rows(91, 0, n, dim, dtype)
+    q = oracle.synth_queries(92, nq, dim, dtype)
+    every = np.tile(np.arange(n, dtype=np.uint64), (nq, 1))
+    with G.GpuCorpus.from_array(rows) as c:
+        _force(monkeypatch, c, LIST)
+        with c.make_filter(np.ones(n, bool)) as f:
+            assert f.admitted == n and f.info().has_row_list == 1
+            for metric in (G.L2, G.COSINE):
+                a = c.search_filtered(q, k, metric, f)
+                b = c.search_candidates(q, every, k, metric)
+                assert (b.counts == n).all()
+                assert a.scores.tobytes() == b.scores.tobytes(), f"metric {metric}: scores"
+                assert a.indices.tobytes() == b.indices.tobytes(), f"metric {metric}: indices"
+                assert a.raw.tobytes() == b.raw.tobytes(), f"metric {metric}: raw"
+
+
 # ---- large k, short results --------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("dtype,metric", [(2, G.L2), (0, G.COSINE)])
