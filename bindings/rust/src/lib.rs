@@ -32,6 +32,30 @@ pub struct MvfGpuFilterInfo {
     pub device_bytes: u64,
 }
 
+/// Opaque `mvfgpu_column`, its `mvfgpu_column_info` out-struct and one clause of `mvfgpu_filter_create_where`
+/// (include/mvf_gpu.h, "metadata columns and filters from predicates").
+#[repr(C)]
+pub struct MvfGpuColumn {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct MvfGpuColumnInfo {
+    pub struct_size: u32,
+    pub data_type: u8,
+    pub reserved: [u8; 3],
+    pub rows: u64,
+    pub device_bytes: u64,
+}
+#[repr(C)]
+pub struct MvfGpuPredicate {
+    pub column: *const MvfGpuColumn,
+    pub op: u32,       // MVFGPU_OP_*: 0 EQ, 1 NE, 2 LT, 3 LE, 4 GT, 5 GE, 6 BETWEEN, 7 IN, 8 NOT_IN
+    pub n_values: u32,
+    pub a: u64,
+    pub b: u64,
+    pub values: *const u64,
+}
+
 #[link(name = "mvf_gpu")]
 extern "C" {
     fn mvfgpu_corpus_create(rows: *const c_void, n: u64, dimension: u32, data_type: u8, stride_bytes: u64,
@@ -75,6 +99,17 @@ extern "C" {
     fn mvfgpu_search_filtered_device(corpus: *const MvfGpuCorpus, filter: *const MvfGpuFilter, metric: u8,
                                      d_queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, k: u32,
                                      d_scores: *mut f32, d_indices: *mut u64, d_raw: *mut i32, hip_stream: *mut c_void) -> c_int;
+    /// Metadata columns (include/mvf_gpu.h, DESIGN.md section 3 "Column filters"): one UInt32 / UInt64 value per local row,
+    /// resident next to the rows; `mvfgpu_filter_create_where` builds an ordinary filter from predicates over them on the
+    /// device (`combine`: 0 = every clause holds, 1 = at least one; `base` nullable).
+    fn mvfgpu_column_create(corpus: *const MvfGpuCorpus, values_le: *const c_void, data_type: u8, first_value: u64,
+                            n_values: u64, out: *mut *mut MvfGpuColumn) -> c_int;
+    fn mvfgpu_column_create_device(corpus: *const MvfGpuCorpus, d_values: *const c_void, data_type: u8,
+                                   hip_stream: *mut c_void, out: *mut *mut MvfGpuColumn) -> c_int;
+    fn mvfgpu_column_destroy(column: *mut MvfGpuColumn);
+    fn mvfgpu_column_get_info(column: *const MvfGpuColumn, out: *mut MvfGpuColumnInfo) -> c_int;
+    fn mvfgpu_filter_create_where(corpus: *const MvfGpuCorpus, clauses: *const MvfGpuPredicate, n_clauses: u32, combine: u32,
+                                  base: *const MvfGpuFilter, out: *mut *mut MvfGpuFilter) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;
     /// `MVFGPU_ABI_VERSION` of the loaded library (include/mvf_gpu.h): struct layouts and signatures this file mirrors.
     fn mvfgpu_abi_version() -> u32;

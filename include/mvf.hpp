@@ -8,7 +8,7 @@
 //   MvfError (src/errors.rs:8-40)                             mvf::MvfError (one code per variant, mvf_status.h)
 //   MvfReader::open / version / num_vector_spaces /           mvf::MvfReader (src/reader.rs:45-172)
 //     vector_space_names / vector_space / file_size /
-//     has_metadata / metadata_column_names / validate /
+//     has_metadata / metadata_column_names / validate /       (+ metadata_column: the column's type and bytes)
 //     validate_with_checksum
 //   VectorSpace::name / dimension / total_vectors /           mvf::VectorSpace (src/vectors/vector_space.rs:62-188)
 //     vector_type / distance_metric / data_type /
@@ -126,6 +126,26 @@ private:
     mvf_vector_space s_;
 };
 
+// One metadata column of a file (MetadataColumn, schema/core.fbs:16-25): a borrowed view of its block, valid while the
+// reader is open.  UInt32 / UInt64 columns hold one little-endian value per row; `data` may be unaligned.
+struct MetadataColumn {
+    std::string name;
+    uint8_t data_type = 0;  // enum mvf_data_type as stored
+    uint32_t data_block_index = 0;
+    uint64_t null_count = 0;
+    const void* data = nullptr;
+    uint64_t size = 0;  // bytes
+};
+
+// One clause of GpuVectorSpace::find_top_k_where: `op` is MVFGPU_OP_*; EQ .. GE compare with `a`, BETWEEN takes a <= v <= b,
+// IN / NOT_IN take `values` (any order, repeats allowed).
+struct WhereClause {
+    MetadataColumn column;
+    uint32_t op = MVFGPU_OP_EQ;
+    uint64_t a = 0, b = 0;
+    std::vector<uint64_t> values;
+};
+
 // MvfReader (src/reader.rs:27-33): the mapping and the verified footer.
 class MvfReader {
 public:
@@ -194,6 +214,15 @@ public:
         }
         return out;
     }
+    MetadataColumn metadata_column(const std::string& name) const {  // the first of that name; VectorSpaceNotFound-style error
+        mvf_metadata_column c;
+        detail::check_host(mvf_reader_metadata_column(r_, name.c_str(), &c));
+        MetadataColumn out;
+        out.name.assign(c.name, c.name_len);
+        out.data_type = c.data_type, out.data_block_index = c.data_block_index, out.null_count = c.null_count;
+        out.data = c.data, out.size = c.size;
+        return out;
+    }
     void validate() const { detail::check_host(mvf_reader_validate(r_)); }                              // :149-162
     void validate_with_checksum() const { detail::check_host(mvf_reader_validate_with_checksum(r_)); }  // :172-220 (todo!() upstream)
 
@@ -256,6 +285,17 @@ public:
         }
         detail::check_host(mvf_builder_add_vectors_f32(b_, space_name.c_str(), flat.data(), vectors.size(), (uint32_t)dim));
         return *this;
+    }
+    // :211-236: the column's bytes as given; UInt32 / UInt64 columns are little-endian values, one per row
+    MvfBuilder& add_metadata_column(const std::string& name, uint8_t data_type, const void* bytes, uint64_t len) {
+        detail::check_host(mvf_builder_add_metadata_column(b_, name.c_str(), data_type, bytes, len));
+        return *this;
+    }
+    MvfBuilder& add_metadata_column(const std::string& name, const std::vector<uint32_t>& values) {
+        return add_metadata_column(name, MVF_DTYPE_UINT32, values.data(), (uint64_t)values.size() * 4);
+    }
+    MvfBuilder& add_metadata_column(const std::string& name, const std::vector<uint64_t>& values) {
+        return add_metadata_column(name, MVF_DTYPE_UINT64, values.data(), (uint64_t)values.size() * 8);
     }
     BuiltMvf build() {  // :241-308 (consumes the builder)
         mvf_builder* b = b_;
@@ -362,6 +402,49 @@ public:
         const int rc = mvfgpu_search_filtered(c_, f, (uint8_t)metric_, query.data(), MVF_DTYPE_FLOAT32, (uint32_t)query.size(), 1, (uint32_t)k,
                                               scores.data(), idx.data(), nullptr);
         mvfgpu_filter_destroy(f);
+        detail::check_gpu(rc);
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < k && idx[i] != ~0ull; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
+    // find_top_k_filtered with the predicate evaluated on the device from a file's metadata columns (mvfgpu_column_create,
+    // mvfgpu_filter_create_where; DESIGN.md section 3, "Column filters"): every clause holds, or with `any` at least one.  A
+    // column holds one UInt32 / UInt64 value per vector of the space (Build error otherwise).  The columns and the filter live
+    // for this call; the payload is not fetched.
+    std::vector<ScoredVector> find_top_k_where(const std::vector<float>& query, size_t k, const std::vector<WhereClause>& where,
+                                               bool any = false) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "find_top_k_where takes f32 queries: Float32 / Float16 spaces");
+        if (k == 0) return {};
+        mvfgpu_corpus_info inf;
+        MVFGPU_INIT(inf);
+        detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+        std::vector<mvfgpu_column*> cols;
+        std::vector<mvfgpu_predicate> preds;
+        mvfgpu_filter* f = nullptr;
+        std::vector<float> scores(k);
+        std::vector<uint64_t> idx(k);
+        int rc = MVF_OK;
+        for (const WhereClause& w : where) {
+            const uint64_t es = w.column.data_type == MVF_DTYPE_UINT32 ? 4 : w.column.data_type == MVF_DTYPE_UINT64 ? 8 : 0;
+            mvfgpu_column* col = nullptr;
+            if (!es || w.column.size / es < inf.rows) {
+                for (mvfgpu_column* c : cols) mvfgpu_column_destroy(c);
+                throw MvfError(MVF_ERR_BUILD, es ? "metadata column '" + w.column.name + "' holds fewer values than the space has vectors"
+                                                 : "Unsupported metadata column data type");
+            }
+            rc = mvfgpu_column_create(c_, w.column.data, w.column.data_type, 0, w.column.size / es, &col);
+            if (rc != MVF_OK) break;
+            cols.push_back(col);
+            preds.push_back({col, w.op, (uint32_t)w.values.size(), w.a, w.b, w.values.empty() ? nullptr : w.values.data()});
+        }
+        if (rc == MVF_OK)
+            rc = mvfgpu_filter_create_where(c_, preds.data(), (uint32_t)preds.size(), any ? MVFGPU_WHERE_ANY : MVFGPU_WHERE_ALL, nullptr, &f);
+        if (rc == MVF_OK)
+            rc = mvfgpu_search_filtered(c_, f, (uint8_t)metric_, query.data(), MVF_DTYPE_FLOAT32, (uint32_t)query.size(), 1, (uint32_t)k,
+                                        scores.data(), idx.data(), nullptr);
+        mvfgpu_filter_destroy(f);
+        for (mvfgpu_column* c : cols) mvfgpu_column_destroy(c);
         detail::check_gpu(rc);
         std::vector<ScoredVector> out;
         for (size_t i = 0; i < k && idx[i] != ~0ull; i++) out.push_back({idx[i], scores[i], {}});

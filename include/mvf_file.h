@@ -87,6 +87,29 @@ int mvf_reader_file_size(const mvf_reader* r, uint64_t* out);         /* :122-12
 int mvf_reader_has_metadata(const mvf_reader* r, int* out);           /* :127-129 */
 int mvf_reader_num_metadata_columns(const mvf_reader* r, uint64_t* out);
 int mvf_reader_metadata_column_name(const mvf_reader* r, uint64_t i, const char** name, uint32_t* len); /* :132-143 */
+/*
+ * One metadata column (MetadataColumn, schema/core.fbs:16-25) with its block's bytes.  The reference's builder writes
+ * columns (src/builder.rs:211-236, :501-520) and its reader lists their names only.  open() validates nothing of a column
+ * but its name; the block index and the block's range are checked by these two accessors:
+ *   block index past the manifest, or block outside the file  -> MVF_ERR_CORRUPTED_DATA
+ *   compressed block                                          -> MVF_ERR_BUILD (as everywhere)
+ *   i out of range                                            -> MVF_ERR_INDEX_OUT_OF_BOUNDS
+ *   unknown name -> MVF_ERR_SPACE_NOT_FOUND ("Metadata column not found: ..."): the reference has no variant for a missing
+ *                   column, VectorSpaceNotFound is its one "no such name" error.
+ * The bytes are the builder's, uninterpreted: UInt32 / UInt64 columns hold little-endian values, one per row, by this
+ * project's convention (mvfgpu_column_create consumes them); the reference defines no layout for the other types.
+ */
+typedef struct mvf_metadata_column {
+    const char* name;          /* borrowed from the reader; not NUL-terminated in general: use name_len */
+    uint32_t name_len;
+    uint8_t data_type;         /* enum mvf_data_type as stored */
+    uint32_t data_block_index;
+    uint64_t null_count;       /* as stored; this library gives it no meaning */
+    const void* data;          /* borrowed pointer into the mapping, possibly UNALIGNED */
+    uint64_t size;             /* bytes */
+} mvf_metadata_column;
+int mvf_reader_metadata_column_at(const mvf_reader* r, uint64_t i, mvf_metadata_column* out);
+int mvf_reader_metadata_column(const mvf_reader* r, const char* name, mvf_metadata_column* out); /* the first of that name */
 int mvf_reader_num_blocks(const mvf_reader* r, uint64_t* out);
 int mvf_reader_block(const mvf_reader* r, uint64_t i, mvf_data_block* out);
 int mvf_reader_validate(const mvf_reader* r);                         /* :149-162 */

@@ -471,6 +471,103 @@ int mvfgpu_search_filtered_device(const mvfgpu_corpus* corpus, const mvfgpu_filt
 int mvfgpu_selftest_filter_route(uint64_t rows, uint32_t dimension, uint8_t data_type, uint32_t nq, uint32_t k, uint64_t admitted,
                                  uint32_t* out_route);
 
+/* ---- metadata columns and filters from predicates ---------------------------- */
+
+/*
+ * A device column: one value per LOCAL row of ONE corpus handle, UInt32 or UInt64 (enum mvf_data_type), copied into device
+ * memory of its own next to the rows ("Column filters").  Immutable; used by any number of
+ * mvfgpu_filter_create_where calls from any thread; destroyed before its corpus.  The values are what an MVF file keeps in a
+ * metadata column (mvf_reader_metadata_column in mvf_file.h: little-endian values, one per row) -- tenant, category, timestamp.
+ *   mvfgpu_column_create        : host values; value (first_value + r) belongs to local row r, and first_value + rows <=
+ *                                 n_values (a row-range shard passes the whole space's column and its first row, as first_bit
+ *                                 does for bitmaps).  `values_le` may have ANY alignment: a file block starts at any byte.
+ *                                 The values are copied before the call returns.
+ *   mvfgpu_column_create_device : values over local rows in device memory, aligned to their element size, copied device-to-
+ *                                 device on hip_stream (NULL = the null stream).
+ * Any other data type (StringRef included: the format never defines its bytes) -> MVF_ERR_BUILD "Unsupported metadata column
+ * data type".  Columns do not depend on tombstones: mvfgpu_corpus_set_tombstones leaves them valid.  device memory: rows x
+ * element size, reported by mvfgpu_column_info::device_bytes and, like a filter's, not counted in mvfgpu_corpus_info.
+ * mvfgpu_column_destroy (NULL is allowed) waits for the handle's newest work.
+ */
+typedef struct mvfgpu_column mvfgpu_column;
+
+typedef struct mvfgpu_column_info {
+    uint32_t struct_size;  /* in: sizeof(mvfgpu_column_info); out: bytes filled */
+    uint8_t data_type;     /* MVF_DTYPE_UINT32 or MVF_DTYPE_UINT64 */
+    uint8_t reserved[3];
+    uint64_t rows;         /* rows of the handle the column was created for */
+    uint64_t device_bytes; /* device memory the column holds */
+} mvfgpu_column_info;
+
+int mvfgpu_column_create(const mvfgpu_corpus* corpus, const void* values_le, uint8_t data_type, uint64_t first_value,
+                         uint64_t n_values, mvfgpu_column** out);
+int mvfgpu_column_create_device(const mvfgpu_corpus* corpus, const void* d_values, uint8_t data_type, void* hip_stream,
+                                mvfgpu_column** out);
+void mvfgpu_column_destroy(mvfgpu_column* column);
+int mvfgpu_column_get_info(const mvfgpu_column* column, mvfgpu_column_info* out);
+
+/*
+ * A filter from predicates over device columns, evaluated on the device: no bitmap is built on the host.
+ *
+ *   "tenant == 7 AND ts >= T" from a file's columns:
+ *       mvf_metadata_column mc;  mvfgpu_column *tenant, *ts;  mvfgpu_filter* f;
+ *       mvf_reader_metadata_column(reader, "tenant", &mc);     // UInt32 or UInt64, one value per row of the space
+ *       mvfgpu_column_create(corpus, mc.data, mc.data_type, index_base, mc.size / 4, &tenant);   // / 8 for UInt64
+ *       mvf_reader_metadata_column(reader, "ts", &mc);
+ *       mvfgpu_column_create(corpus, mc.data, mc.data_type, index_base, mc.size / 8, &ts);
+ *       mvfgpu_predicate p[2] = {{tenant, MVFGPU_OP_EQ, 0, 7, 0, NULL}, {ts, MVFGPU_OP_GE, 0, T, 0, NULL}};
+ *       mvfgpu_filter_create_where(corpus, p, 2, MVFGPU_WHERE_ALL, NULL, &f);                    // once per predicate
+ *       mvfgpu_search_filtered(corpus, f, ...);                                                  // any number of searches
+ *
+ * v is the column's value of local row r, zero-extended to 64 bits; every comparison is unsigned 64-bit, so an operand of
+ * 2^32 or more on a UInt32 column is legal and means what the arithmetic says.  BETWEEN is inclusive and a > b admits nothing;
+ * IN with no values admits nothing, NOT_IN with no values every row.  Row r is admitted iff the clauses, combined by
+ * `combine`, hold AND `base` is NULL or admits r AND the handle's tombstones do not delete r at creation.  The result is an
+ * ordinary mvfgpu_filter, indistinguishable from the one mvfgpu_filter_create builds from the bitmap of that predicate: the
+ * same mvfgpu_filter_info, staleness rule, routes and search results.  It does not refer to the columns (or to `base`) after
+ * creation, which -- like every filter's -- waits for the admitted count.
+ * Refused before any device call, with MVF_ERR_INVALID_ARGUMENT and a message naming the cause: NULL arguments; n_clauses
+ * outside 1 .. MVFGPU_WHERE_MAX_CLAUSES; an unknown op or combine; more than MVFGPU_WHERE_MAX_SET_VALUES distinct IN / NOT_IN
+ * values over the clauses of the call (build the bitmap and call mvfgpu_filter_create for larger sets); a column of another
+ * handle; a `base` of another handle or of an older tombstone generation (the searches' own messages).
+ */
+enum {
+    MVFGPU_OP_EQ = 0, MVFGPU_OP_NE = 1, MVFGPU_OP_LT = 2, MVFGPU_OP_LE = 3, MVFGPU_OP_GT = 4, MVFGPU_OP_GE = 5,
+    MVFGPU_OP_BETWEEN = 6, MVFGPU_OP_IN = 7, MVFGPU_OP_NOT_IN = 8
+};
+
+typedef struct mvfgpu_predicate {
+    const mvfgpu_column* column;
+    uint32_t op;            /* MVFGPU_OP_* */
+    uint32_t n_values;      /* IN / NOT_IN: entries of `values` */
+    uint64_t a, b;          /* EQ .. GE: a;  BETWEEN: a <= v <= b */
+    const uint64_t* values; /* IN / NOT_IN: host array, any order, repeats allowed; may be NULL when n_values == 0 */
+} mvfgpu_predicate;
+
+#define MVFGPU_WHERE_ALL 0u              /* every clause holds */
+#define MVFGPU_WHERE_ANY 1u              /* at least one does */
+#define MVFGPU_WHERE_MAX_CLAUSES 8u
+#define MVFGPU_WHERE_MAX_SET_VALUES 4096u /* over all clauses of one call, each clause's repeats removed */
+
+int mvfgpu_filter_create_where(const mvfgpu_corpus* corpus, const mvfgpu_predicate* clauses, uint32_t n_clauses,
+                               uint32_t combine, const mvfgpu_filter* base, mvfgpu_filter** out);
+
+/*
+ * Self-test of the host-side normalisation (no GPU needed): every operator but IN / NOT_IN (MVF_ERR_INVALID_ARGUMENT) becomes
+ * one range test *out_lo <= v <= *out_hi on a column of `data_type`, negated where *out_negate is 1 (NE only).  The range is
+ * clamped to the type's values (hi <= 2^32 - 1 on UInt32); an empty range is reported as lo = 1, hi = 0.
+ */
+int mvfgpu_selftest_predicate_range(uint8_t data_type, uint32_t op, uint64_t a, uint64_t b, uint64_t* out_lo,
+                                    uint64_t* out_hi, uint32_t* out_negate);
+
+/*
+ * Measurement aid (scripts/probe_column_filters.py): the predicate kernel alone.  Checks and prepares the call as
+ * mvfgpu_filter_create_where does, then launches the kernel `repeats` times (1 .. 64) on the handle's stream between device
+ * events and reports each launch's milliseconds in out_ms[repeats].  No filter is built.
+ */
+int mvfgpu_selftest_where_kernel_ms(const mvfgpu_corpus* corpus, const mvfgpu_predicate* clauses, uint32_t n_clauses,
+                                    uint32_t combine, const mvfgpu_filter* base, uint32_t repeats, float* out_ms);
+
 /* ---- k-NN join (queries taken from resident rows) -------------------------- */
 
 #define MVFGPU_JOIN_WINDOW 1024u        /* query rows per search of a join, counted from `first` */
@@ -651,7 +748,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * radius search, which only ADDS mvfgpu_search_radius and mvfgpu_selftest_radius_bound, nor did the candidate search, which
  * only adds mvfgpu_search_candidates and mvfgpu_search_candidates_device, nor did the k-NN join, which only adds mvfgpu_knn_join and
  * mvfgpu_knn_join_device, nor did the filtered search, which only adds mvfgpu_filter_*, mvfgpu_search_filtered,
- * mvfgpu_search_filtered_device and mvfgpu_selftest_filter_route).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * mvfgpu_search_filtered_device and mvfgpu_selftest_filter_route, nor did the metadata columns, which only add mvfgpu_column_*,
+ * mvfgpu_filter_create_where, mvfgpu_selftest_predicate_range and mvfgpu_selftest_where_kernel_ms).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

@@ -40,6 +40,21 @@ class FilterInfo(_OutStruct):
                 ("device_bytes", C.c_uint64)]
 
 
+class ColumnInfo(_OutStruct):
+    _fields_ = [("struct_size", C.c_uint32), ("data_type", C.c_uint8), ("reserved", C.c_uint8 * 3), ("rows", C.c_uint64),
+                ("device_bytes", C.c_uint64)]
+
+
+class Predicate(C.Structure):
+    """mvfgpu_predicate: one clause of mvfgpu_filter_create_where."""
+    _fields_ = [("column", C.c_void_p), ("op", C.c_uint32), ("n_values", C.c_uint32), ("a", C.c_uint64), ("b", C.c_uint64),
+                ("values", C.c_void_p)]
+
+
+OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_BETWEEN, OP_IN, OP_NOT_IN = range(9)  # include/mvf_gpu.h MVFGPU_OP_*
+WHERE_ALL, WHERE_ANY, WHERE_MAX_CLAUSES, WHERE_MAX_SET_VALUES = 0, 1, 8, 4096
+
+
 class UploadOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("chunk_mib", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -170,6 +185,20 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_search_filtered_device.restype = C.c_int
     lib.mvfgpu_selftest_filter_route.argtypes = [u64, u32, u8, u32, u32, u64, vp]
     lib.mvfgpu_selftest_filter_route.restype = C.c_int
+    lib.mvfgpu_column_create.argtypes = [vp, vp, u8, u64, u64, pp]
+    lib.mvfgpu_column_create.restype = C.c_int
+    lib.mvfgpu_column_create_device.argtypes = [vp, vp, u8, vp, pp]
+    lib.mvfgpu_column_create_device.restype = C.c_int
+    lib.mvfgpu_column_destroy.argtypes = [vp]
+    lib.mvfgpu_column_destroy.restype = None
+    lib.mvfgpu_column_get_info.argtypes = [vp, C.POINTER(ColumnInfo)]
+    lib.mvfgpu_column_get_info.restype = C.c_int
+    lib.mvfgpu_filter_create_where.argtypes = [vp, C.POINTER(Predicate), u32, u32, vp, pp]
+    lib.mvfgpu_filter_create_where.restype = C.c_int
+    lib.mvfgpu_selftest_predicate_range.argtypes = [u8, u32, u64, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+    lib.mvfgpu_selftest_predicate_range.restype = C.c_int
+    lib.mvfgpu_selftest_where_kernel_ms.argtypes = [vp, C.POINTER(Predicate), u32, u32, vp, u32, vp]
+    lib.mvfgpu_selftest_where_kernel_ms.restype = C.c_int
     lib.mvfgpu_selftest_radius_bound.argtypes = [u8, u8, C.c_float, vp, vp]
     lib.mvfgpu_selftest_radius_bound.restype = C.c_int
     lib.mvfgpu_selftest_radius_route.argtypes = [u8, u32, C.c_int, vp]
@@ -196,6 +225,11 @@ class CVectorSpace(C.Structure):
                 ("vectors_block_index", C.c_uint32), ("vector_ids_block_index", C.c_uint32),
                 ("has_sparse_metadata", C.c_uint8), ("has_tombstones", C.c_uint8), ("tombstone_format", C.c_uint8),
                 ("tombstone_block_index", C.c_uint32), ("tombstone_deleted_count", C.c_uint64)]
+
+
+class CMetadataColumn(C.Structure):
+    _fields_ = [("name", C.c_void_p), ("name_len", C.c_uint32), ("data_type", C.c_uint8), ("data_block_index", C.c_uint32),
+                ("null_count", C.c_uint64), ("data", C.c_void_p), ("size", C.c_uint64)]
 
 
 class CVectorSlice(C.Structure):
@@ -228,6 +262,8 @@ def host() -> C.CDLL:
     lib.mvf_reader_has_metadata.argtypes = [vp, C.POINTER(i32)]
     lib.mvf_reader_num_metadata_columns.argtypes = [vp, C.POINTER(u64)]
     lib.mvf_reader_metadata_column_name.argtypes = [vp, u64, pp, C.POINTER(u32)]
+    lib.mvf_reader_metadata_column_at.argtypes = [vp, u64, C.POINTER(CMetadataColumn)]
+    lib.mvf_reader_metadata_column.argtypes = [vp, C.c_char_p, C.POINTER(CMetadataColumn)]
     lib.mvf_reader_num_blocks.argtypes = [vp, C.POINTER(u64)]
     lib.mvf_reader_block.argtypes = [vp, u64, C.POINTER(DataBlock)]
     lib.mvf_reader_validate.argtypes = [vp]

@@ -138,6 +138,19 @@ int filter_list_search(const CorpusView& v, const FilterUse& flt, uint8_t metric
     return gather_topk(v, metric, d_queries, nq, src, k, d_scores, d_indices, d_raw, s);
 }
 
+int filter_from_allow_words(const mvfgpu_corpus* c, const CorpusView& v, const uint32_t* d_allow, hipStream_t s, mvfgpu_filter** out) {
+    mvfgpu_filter* f = new_filter(c, v);
+    const int rc = build_filter(f, v, d_allow, 0u, s);
+    if (rc != MVF_OK) {
+        free_filter(f);
+        return rc;
+    }
+    *out = f;
+    return MVF_OK;
+}
+
+FilterOrigin filter_origin(const mvfgpu_filter* f) { return FilterOrigin{f->owner, f->tomb_gen, f->deny}; }
+
 }  // namespace mvf
 
 extern "C" {

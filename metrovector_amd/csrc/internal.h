@@ -13,6 +13,7 @@
 #include <string>
 
 typedef struct mvfgpu_corpus mvfgpu_corpus;
+typedef struct mvfgpu_filter mvfgpu_filter;
 
 namespace mvf {
 
@@ -189,6 +190,16 @@ int filter_list_search(const CorpusView& v, const FilterUse& flt, uint8_t metric
                        float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s);
 // The route of a filtered search under the default tuning, a pure function (mvfgpu_selftest_filter_route): 1 = mask, 2 = list
 uint32_t filter_route_rule(uint64_t rows, uint32_t dim, uint8_t dtype, uint32_t nq, uint32_t k, uint64_t admitted);
+// A filter of `c` from ALLOW words over local rows in device memory (mvfgpu_filter_create_device's layout), for a caller that
+// already runs under corpus_device_call(c, s, ...) with `v` read there: F0 / F1 on `s` and the one wait for the admitted count.
+int filter_from_allow_words(const mvfgpu_corpus* c, const CorpusView& v, const uint32_t* d_allow, hipStream_t s, mvfgpu_filter** out);
+// what the column filters (columns.hip) read of a base filter: whose it is, its tombstone generation, its deny mask
+struct FilterOrigin {
+    const mvfgpu_corpus* owner;
+    uint64_t tomb_gen;
+    const uint32_t* deny;
+};
+FilterOrigin filter_origin(const mvfgpu_filter* f);
 // waits for the newest work enqueued on the handle
 int corpus_wait_newest(const mvfgpu_corpus* c);
 

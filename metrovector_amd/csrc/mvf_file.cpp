@@ -418,6 +418,13 @@ struct SpaceRec {
     uint64_t tomb_deleted_count = 0;
 };
 
+// MetadataColumn, schema/core.fbs:16-25, as stored: open() checks none of the numbers, the accessors do
+struct ColumnRec {
+    uint8_t data_type = 0;
+    uint32_t data_block_index = 0;
+    uint64_t null_count = 0;
+};
+
 }  // namespace
 
 struct mvf_reader {
@@ -430,6 +437,7 @@ struct mvf_reader {
     std::vector<mvf_data_block> blocks;
     bool has_metadata = false;
     std::vector<std::string> metadata_names;
+    std::vector<ColumnRec> columns;  // one per name
 };
 
 namespace {
@@ -521,6 +529,12 @@ int parse_footer(mvf_reader* r, size_t fs, size_t fe) {
             size_t fn = mt.field(0);
             if (!fn || !fb_string(v, fn, &nm, &nl)) return bad("metadata column name missing or malformed");
             r->metadata_names.emplace_back(nm, nl);
+            ColumnRec c;
+            size_t p1 = mt.field(1), p2 = mt.field(2), p3 = mt.field(3);
+            c.data_type = p1 && v.in(p1, 1) ? v.b[p1] : 0;
+            c.data_block_index = p2 && v.in(p2, 4) ? rd32(v.b + p2) : 0;
+            c.null_count = p3 && v.in(p3, 8) ? rd64(v.b + p3) : 0;
+            r->columns.push_back(c);
         }
     }
     return MVF_OK;
@@ -736,6 +750,39 @@ int mvf_reader_metadata_column_name(const mvf_reader* r, uint64_t i, const char*
     *name = r->metadata_names[i].c_str();
     *len = (uint32_t)r->metadata_names[i].size();
     return MVF_OK;
+}
+
+static int manifest_block(const mvf_reader* r, uint32_t index, const char* what, const uint8_t** block, uint64_t* block_len);
+
+// the column's footer fields and its block's bytes; the block index and range are checked here, not by open()
+static int fill_column(const mvf_reader* r, size_t i, mvf_metadata_column* out) {
+    const ColumnRec& c = r->columns[i];
+    const uint8_t* block;
+    uint64_t len;
+    int rc = manifest_block(r, c.data_block_index, "metadata column", &block, &len);
+    if (rc) return rc;
+    out->name = r->metadata_names[i].c_str();
+    out->name_len = (uint32_t)r->metadata_names[i].size();
+    out->data_type = c.data_type;
+    out->data_block_index = c.data_block_index;
+    out->null_count = c.null_count;
+    out->data = block;
+    out->size = len;
+    return MVF_OK;
+}
+
+int mvf_reader_metadata_column_at(const mvf_reader* r, uint64_t i, mvf_metadata_column* out) {
+    if (!r || !out) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (i >= r->columns.size())
+        return fail(MVF_ERR_INDEX_OUT_OF_BOUNDS, "Index out of bounds: " + std::to_string(i) + " >= " + std::to_string(r->columns.size()));
+    return fill_column(r, (size_t)i, out);
+}
+
+int mvf_reader_metadata_column(const mvf_reader* r, const char* name, mvf_metadata_column* out) {
+    if (!r || !name || !out) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (size_t i = 0; i < r->columns.size(); i++)
+        if (r->metadata_names[i] == name) return fill_column(r, i, out);
+    return fail(MVF_ERR_SPACE_NOT_FOUND, std::string("Metadata column not found: ") + name);
 }
 
 int mvf_reader_num_blocks(const mvf_reader* r, uint64_t* out) {

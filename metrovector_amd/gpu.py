@@ -151,6 +151,90 @@ class GpuFilter:
         self.close()
 
 
+UINT32, UINT64 = 4, 5  # schema/types.fbs: the data types of a device column
+_COLUMN_CODE_OF = {np.dtype(np.uint32): UINT32, np.dtype(np.uint64): UINT64}
+_OP_OF = {"==": _lib.OP_EQ, "!=": _lib.OP_NE, "<": _lib.OP_LT, "<=": _lib.OP_LE, ">": _lib.OP_GT, ">=": _lib.OP_GE,
+          "between": _lib.OP_BETWEEN, "in": _lib.OP_IN, "not in": _lib.OP_NOT_IN}
+
+
+def predicate_range(data_type: int, op: str | int, a: int = 0, b: int = 0) -> tuple[int, int, int]:
+    """(lo, hi, negate) of a comparison after the host-side normalisation: lo <= v <= hi, negated where negate is 1; an
+    empty range is (1, 0) -- `mvfgpu_selftest_predicate_range`; no GPU needed."""
+    lo, hi, neg = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    code = _OP_OF[op] if isinstance(op, str) else int(op)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_predicate_range(data_type, code, a, b, C.byref(lo), C.byref(hi), C.byref(neg)))
+    return lo.value, hi.value, neg.value
+
+
+class GpuColumn:
+    """One UInt32 / UInt64 value per row of one GpuCorpus, resident next to the rows (`mvfgpu_column`): made by
+    `GpuCorpus.attach_column`, used by any number of `make_filter_where` calls, closed before its corpus.  A context manager."""
+
+    def __init__(self, handle: int, corpus: "GpuCorpus"):
+        self._h = C.c_void_p(handle)
+        self._corpus = corpus  # keeps the handle it belongs to alive
+
+    def info(self) -> _lib.ColumnInfo:
+        out = _lib.ColumnInfo()
+        _lib.gpu_check(_lib.gpu().mvfgpu_column_get_info(self._h, C.byref(out)))
+        return out
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value and self._corpus._h is not None:
+            _lib.gpu().mvfgpu_column_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _u64(x, what: str) -> int:
+    v = int(x)
+    if v < 0 or v >= 1 << 64:
+        raise InvalidArgument(f"{what} {v} is no unsigned 64-bit value")
+    return v
+
+
+def _pack_clauses(clauses) -> tuple[C.Array, list]:
+    """(mvfgpu_predicate array, the arrays it points into) of [(column, op, operand), ...]"""
+    clauses = list(clauses)
+    arr = (_lib.Predicate * max(len(clauses), 1))()
+    keep = []
+    for i, cl in enumerate(clauses):
+        if not isinstance(cl, (tuple, list)) or len(cl) != 3:
+            raise InvalidArgument("a clause is (column, op, operand)")
+        col, op, operand = cl
+        if not isinstance(col, GpuColumn) or col._h is None:
+            raise InvalidArgument("a clause's column must be an open GpuColumn of this corpus")
+        code = _OP_OF.get(op) if isinstance(op, str) else None
+        if code is None:
+            raise InvalidArgument(f"unknown predicate op {op!r}: one of {', '.join(_OP_OF)}")
+        arr[i].column, arr[i].op = col._h, code
+        if code in (_lib.OP_IN, _lib.OP_NOT_IN):
+            if isinstance(operand, np.ndarray) and operand.dtype == np.uint64 and operand.ndim == 1:
+                vals = np.ascontiguousarray(operand)
+            else:
+                vals = np.array([_u64(x, "set value") for x in operand], dtype=np.uint64)
+            keep.append(vals)
+            arr[i].n_values = vals.size
+            arr[i].values = vals.ctypes.data if vals.size else None
+        elif code == _lib.OP_BETWEEN:
+            lo, hi = operand
+            arr[i].a, arr[i].b = _u64(lo, "operand"), _u64(hi, "operand")
+        else:
+            arr[i].a = _u64(operand, "operand")
+    return arr, keep
+
+
 class GpuCorpus:
     """One shard of a vector space, resident in HBM on one MI355X."""
 
@@ -428,6 +512,68 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_filter_create_device(self._h, C.c_void_p(d_words), C.c_void_p(stream) if stream else None,
                                                               C.byref(h)))
         return GpuFilter(h.value, self)
+
+    # ---- metadata columns and filters from predicates -------------------------------------
+    def attach_column(self, values: np.ndarray, first_value: int = 0) -> GpuColumn:
+        """A device column (`mvfgpu_column_create`): `values` is a 1-D uint32 / uint64 array in which entry
+        (first_value + r) belongs to local row r -- a row-range shard passes the whole space's column and its first row."""
+        if not isinstance(values, np.ndarray) or values.ndim != 1 or values.dtype not in _COLUMN_CODE_OF:
+            raise InvalidArgument("a column is a 1-D numpy array of uint32 or uint64 values")
+        if first_value < 0:
+            raise InvalidArgument("first_value must be >= 0")
+        if values.size < first_value + self.rows:
+            raise InvalidArgument(f"the column holds {values.size} values, the shard needs {first_value + self.rows}")
+        a = np.ascontiguousarray(values)
+        h = C.c_void_p()
+        _lib.gpu_check(_lib.gpu().mvfgpu_column_create(self._h, a.ctypes.data_as(C.c_void_p), _COLUMN_CODE_OF[a.dtype], first_value,
+                                                       a.size, C.byref(h)))
+        return GpuColumn(h.value, self)
+
+    def attach_column_pointer(self, ptr: int, data_type: int, first_value: int, n_values: int) -> GpuColumn:
+        """`attach_column` from an address of little-endian values of ANY alignment -- a file's column block in place
+        (`MetadataColumn.as_ptr`)."""
+        if not ptr:
+            raise InvalidArgument("ptr is NULL")
+        h = C.c_void_p()
+        _lib.gpu_check(_lib.gpu().mvfgpu_column_create(self._h, C.c_void_p(ptr), int(data_type), first_value, n_values, C.byref(h)))
+        return GpuColumn(h.value, self)
+
+    def attach_column_device(self, ptr: int, data_type: int, stream: int = 0) -> GpuColumn:
+        """A device column from values over local rows in device memory (`mvfgpu_column_create_device`), copied on `stream`."""
+        if not ptr:
+            raise InvalidArgument("ptr is a NULL device pointer")
+        h = C.c_void_p()
+        _lib.gpu_check(_lib.gpu().mvfgpu_column_create_device(self._h, C.c_void_p(ptr), int(data_type),
+                                                              C.c_void_p(stream) if stream else None, C.byref(h)))
+        return GpuColumn(h.value, self)
+
+    def make_filter_where(self, clauses, any: bool = False, base: GpuFilter | None = None) -> GpuFilter:  # noqa: A002
+        """A filter from predicates over this corpus' columns, evaluated on the device (`mvfgpu_filter_create_where`).  A
+        clause is (column, op, operand): op "==", "!=", "<", "<=", ">", ">=" with an integer, "between" with (lo, hi),
+        inclusive, "in" / "not in" with a sequence of integers.  All clauses hold (`any`: at least one), `base` admits the
+        row where given, and rows deleted now are never admitted.  The result is an ordinary GpuFilter."""
+        clauses = list(clauses)
+        arr, keep = _pack_clauses(clauses)
+        if base is not None and (not isinstance(base, GpuFilter) or base._h is None):
+            raise InvalidArgument("base must be an open GpuFilter of this corpus")
+        h = C.c_void_p()
+        _lib.gpu_check(_lib.gpu().mvfgpu_filter_create_where(self._h, arr, len(clauses),
+                                                             _lib.WHERE_ANY if any else _lib.WHERE_ALL,
+                                                             None if base is None else base._h, C.byref(h)))
+        del keep
+        return GpuFilter(h.value, self)
+
+    def where_kernel_ms(self, clauses, any: bool = False, base: GpuFilter | None = None, repeats: int = 8) -> np.ndarray:  # noqa: A002
+        """Milliseconds of `repeats` launches of the predicate kernel alone (`mvfgpu_selftest_where_kernel_ms`): a
+        measurement aid, no filter is built."""
+        clauses = list(clauses)
+        arr, keep = _pack_clauses(clauses)
+        out = np.zeros(repeats, np.float32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_where_kernel_ms(self._h, arr, len(clauses), _lib.WHERE_ANY if any else _lib.WHERE_ALL,
+                                                                  None if base is None else base._h, repeats,
+                                                                  out.ctypes.data_as(C.c_void_p)))
+        del keep
+        return out
 
     def search_filtered(self, queries: np.ndarray, k: int, metric: int, flt: GpuFilter) -> SearchResult:
         """The exact top-k among the rows `flt` admits (`mvfgpu_search_filtered`): `search`'s results in every respect."""

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .errors import InvalidArgument
+from .errors import BuildError, InvalidArgument
 
 
 class DataType(enum.IntEnum):  # schema/types.fbs:3-11
@@ -206,6 +206,39 @@ class VectorSpace:
         return VectorSpace(cs, self._reader)
 
 
+class MetadataColumn:
+    """One metadata column of a file (MetadataColumn, schema/core.fbs:16-25): a borrowed view, valid while the reader is
+    open.  UInt32 / UInt64 columns hold one little-endian value per row; the bytes of other types are the builder's."""
+
+    def __init__(self, c: _lib.CMetadataColumn, reader: "MvfReader"):
+        self._c = c
+        self._reader = reader
+        self.name = C.string_at(c.name, c.name_len).decode("utf-8")
+        self.data_type = _enum(DataType, c.data_type)
+        self.data_block_index = c.data_block_index
+        self.null_count = c.null_count
+        self.size = c.size
+
+    def as_ptr(self) -> int:
+        """The address of the block's bytes in the mapping -- any alignment."""
+        _alive(self._reader)
+        return self._c.data or 0
+
+    def as_bytes(self) -> bytes:
+        _alive(self._reader)
+        return C.string_at(self._c.data, self._c.size) if self._c.size else b""
+
+    def values(self) -> np.ndarray:
+        """A numpy copy of a UInt32 / UInt64 column; any other type, or a block that is no whole number of values, raises
+        BuildError."""
+        np_t = {4: "<u4", 5: "<u8"}.get(int(self.data_type))
+        if np_t is None:
+            raise BuildError("Unsupported metadata column data type")
+        if self.size % np.dtype(np_t).itemsize:
+            raise BuildError(f"metadata column '{self.name}' holds {self.size} bytes: no whole number of {np.dtype(np_t).itemsize}-byte values")
+        return np.frombuffer(self.as_bytes(), dtype=np_t).astype(np.uint32 if np_t == "<u4" else np.uint64)
+
+
 class MvfReader:
     """Reader for MVF files (reference src/reader.rs:27-31); mmap-backed."""
 
@@ -284,6 +317,17 @@ class MvfReader:
             _lib.host_check(_lib.host().mvf_reader_metadata_column_name(self._h, i, C.byref(p), C.byref(ln)))
             out.append(C.string_at(p.value, ln.value).decode("utf-8"))
         return out
+
+    def metadata_column(self, name: str) -> "MetadataColumn":
+        """The first metadata column of that name with its block's bytes (`mvf_reader_metadata_column`)."""
+        c = _lib.CMetadataColumn()
+        _lib.host_check(_lib.host().mvf_reader_metadata_column(self._h, name.encode("utf-8"), C.byref(c)))
+        return MetadataColumn(c, self)
+
+    def metadata_column_at(self, i: int) -> "MetadataColumn":
+        c = _lib.CMetadataColumn()
+        _lib.host_check(_lib.host().mvf_reader_metadata_column_at(self._h, i, C.byref(c)))
+        return MetadataColumn(c, self)
 
     def blocks(self) -> list[_lib.DataBlock]:
         n = C.c_uint64()

@@ -219,6 +219,56 @@ def find_top_k_filtered(space: VectorSpace, query, k: int, allow, metric: int | 
     return out
 
 
+def find_top_k_where(space: VectorSpace, query, k: int, where, any: bool = False, metric: int | None = None,  # noqa: A002
+                     corpus: GpuCorpus | None = None, device: int = 0) -> list[ScoredVector]:
+    """`find_top_k_filtered` with the predicate evaluated on the device from the file's metadata columns
+    (`mvfgpu_filter_create_where`; DESIGN.md §3 "Column filters"): `where` maps column names of the space's file to
+    (op, operand) -- op "==", "!=", "<", "<=", ">", ">=" with an integer, "between" with (lo, hi), "in" / "not in" with a
+    sequence of integers; every clause holds, or with `any` at least one.  A column holds one UInt32 / UInt64 value per vector
+    of the WHOLE space; a `corpus` that holds a row range reads its own part.  The columns and the filter live for this call:
+    a caller with many predicates attaches the columns once (`GpuCorpus.attach_column`, `make_filter_where`)."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    total = space.total_vectors()
+    cols = {}
+    for name in where:  # everything about the file's columns is refused before anything is uploaded
+        mc = space._reader.metadata_column(name)
+        es = {4: 4, 5: 8}.get(int(mc.data_type))
+        if es is None:
+            raise BuildError("Unsupported metadata column data type")
+        if mc.size // es < total:
+            raise BuildError(f"metadata column '{name}' holds {mc.size // es} values, the space has {total} vectors")
+        cols[name] = (mc, mc.size // es)
+    dt = int(space.data_type())
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    attached = []
+    try:
+        base = int(corpus.info().index_base)
+        clauses = []
+        for name, (op, operand) in where.items():
+            mc, count = cols[name]
+            attached.append(corpus.attach_column_pointer(mc.as_ptr(), int(mc.data_type), base, count))
+            clauses.append((attached[-1], op, operand))
+        with corpus.make_filter_where(clauses, any=any) as flt:
+            res = corpus.search_filtered(np.asarray(query, dtype=_NP_OF[query_dtype_code(dt)]), k, metric, flt)
+        valid = res.indices[0] != np.uint64(0xFFFFFFFFFFFFFFFF)
+        rows = corpus.gather_rows(res.indices[0][valid]) if int(valid.sum()) else np.empty((0, space.dimension()), _NP_OF[dt])
+    finally:
+        for col in attached:
+            col.close()
+        if own:
+            corpus.close()
+    out = []
+    for idx, score, row in zip(res.indices[0][valid], res.scores[0][valid], rows):
+        payload = row.astype(np.float32) if dt in (0, 1) else row.copy()
+        out.append(ScoredVector(int(idx), float(score), payload))
+    return out
+
+
 def build_knn_graph(space: VectorSpace, k: int, metric: int | None = None, corpus: GpuCorpus | None = None, first: int = 0,
                     count: int | None = None, device: int = 0) -> SearchResult:
     """The k-NN graph of a space (`mvfgpu_knn_join`; DESIGN.md §3 "Join"): for rows [first, first + count) (local rows of
