@@ -82,12 +82,14 @@ typedef struct mvfgpu_corpus_info {
     uint8_t data_type;    /* enum mvf_data_type */
     uint8_t has_vector_ids; /* 1 when vector ids are attached (searches then report ids, not positions) */
     uint8_t shadows;      /* bit 0: the int8 selection shadow is resident (all rows), bit 1: the scaled-f16 one, bit 2: an int8
-                             shadow of a PREFIX of the rows (all rows did not fit: batched searches run as two row ranges) */
+                             shadow of a PREFIX of the rows (all rows did not fit: batched searches run as two row ranges),
+                             bit 3: the 6-bit selection shadow of a Float32 corpus is resident (one streamed query) */
     uint8_t selection_state; /* bit 0: the repair feedback has switched the int8-shadow selection off for this corpus,
-                                bit 1: it has switched the folded pre-filter of the int8 kernels off */
+                                bit 1: it has switched the folded pre-filter of the int8 kernels off,
+                                bit 2: it has sent one-query searches from the 6-bit shadow back to the int8 shadow */
     uint32_t reserved2;
     uint64_t device_bytes; /* HBM held by the handle: rows, deletion bitmap, ids, norms, every scratch buffer and the
-                              selection shadows (int8: +dimension bytes per row; scaled f16: +2*dimension) with their
+                              selection shadows (int8: +dimension bytes per row; scaled f16: +2*dimension; 6-bit: +0.75*dimension) with their
                               per-row scales and bound statistics, once built */
     uint64_t deleted_rows; /* rows masked by the tombstone bitmap */
 } mvfgpu_corpus_info;
@@ -112,7 +114,9 @@ typedef struct mvfgpu_timing {
                              corpus (scan path 4); MFMA batched (K2): 2 = f32 kernel on Float32 rows,
                              3 = f16/int8 kernel on the stored rows, 4 = f16 kernel on the f16 shadow,
                              6 = int8 kernel on the int8 shadow of a Float32 / Float16 corpus (scan path 5);
-                             7 = K1 on the int8 shadow (scan path 6; one query once the shadow exists);
+                             7 = K1 on a selection shadow, int8 or 6-bit (scan paths 6 and 7; one query on path 0 once
+                             the shadow exists) -- scan_bytes tells the two apart: rows * dimension on the int8 shadow,
+                             ceil(rows / 64) * ceil(dimension / 64) * 3072 on the 6-bit one;
                              8 = K1 writing every row's order key + the whole-shard sort (k > MVFGPU_K_PER_PASS) */
     uint32_t scan_launches; /* scan launches of one search (timing covers the first) */
     uint64_t scan_bytes; /* algorithmic bytes one scan launch reads */
@@ -127,7 +131,7 @@ typedef struct mvfgpu_timing {
                                   keeps producing them goes back to the slower selection paths by itself) */
     uint32_t search_launches; /* newest search (whether profiled or not): kernel launches it enqueued, counted on the host,
                                  on the routes that count them -- the streaming kernel on the stored rows (2: scan + select)
-                                 or on the int8 shadow (scan_kernel 7: scan, margin select, re-scoring, final select,
+                                 or on a selection shadow (scan_kernel 7: scan, margin select, re-scoring, final select,
                                  the repair pair); 0 = the route does not count (batched searches, scan path 4,
                                  k > MVFGPU_K_PER_PASS).  (`reserved` until round 7.) */
 } mvfgpu_timing;
@@ -719,6 +723,20 @@ int mvfgpu_last_timing(const mvfgpu_corpus* corpus, mvfgpu_timing* out);
  * MVF_STREAM_I8=1 also takes the route below 512 MiB, and on Float16 corpora,
  * once the corpus holds a whole int8 shadow.  Two to four queries are served
  * as fast by the 64-query MFMA tile.
+ * From 4 GiB of Float32 rows on, path 0 sends that ONE query over a 6-BIT SHADOW
+ * instead (0.75 x the int8 shadow's bytes, tiled for the scan; the query is
+ * taken at sixteen bits, the bound is proven as before, the re-scoring is K1's:
+ * the same bits once more) -- where the margin of the 6-bit bound is predicted
+ * to hold at most 8192 rows (10M x 768 at k = 100: ~5 300; k = 204 there and
+ * 10M x 1024 stay on int8).  It is built by the first such query straight from
+ * the stored rows (+19 % of the rows' HBM; whole or not at all, the same
+ * free-memory rule), needs no int8 shadow and leaves one alone.  MVF_STREAM_6B=0
+ * keeps path 0 on the int8 shadow, MVF_STREAM_I8=0 on the stored rows.  A corpus
+ * whose queries keep overflowing the 6-bit margin goes back to the int8 route
+ * by itself (selection_state bit 2).  Filtered, radius, candidate and join
+ * searches and two to four queries stay on the int8 shadow.
+ * 7 = as 6, but ONE unfiltered Float32 query streams the 6-bit shadow at any
+ * size (tests), until the handle's 6-bit switch goes off.
  *
  * Selection shadows: batched searches on a Float32 / Float16 corpus select
  * candidates on an INT8 copy of the rows (path 5's, the default: built by the
@@ -734,7 +752,7 @@ int mvfgpu_set_scan_path(mvfgpu_corpus* corpus, int path);
 
 /*
  * The tuning switches of the environment (MVF_K1_G, MVF_K2_*, MVF_I8_SHADOW, MVF_F16_SHADOW, MVF_QS_REFINE,
- * MVF_STREAM_I8, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_FILTER_ROUTE, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
+ * MVF_STREAM_I8, MVF_STREAM_6B, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_FILTER_ROUTE, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
  * handle, when it is created: a search never calls getenv.  An A/B script that changes the environment of a live handle
  * calls this to have it read again.  A development aid: it waits for the handle's host-buffer searches, but
  * mvfgpu_search_device reads the switches unlocked -- do not call it beside device-pointer searches of the same handle.
@@ -782,6 +800,24 @@ int mvfgpu_selftest_route(uint64_t rows, uint32_t dimension, uint8_t data_type, 
  */
 int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq, uint32_t k,
                                 uint32_t* out_rows);
+
+/*
+ * ... and WHICH shadow (no GPU needed; the same arguments): *out_bits = 0 where K1 reads the stored rows, 8 where the one
+ * query streams the int8 shadow, 6 where it streams the 6-bit shadow -- at least 4 GiB of rows and at most 8192 rows predicted
+ * inside the 6-bit bound's margin (a Gaussian-tail model with per-metric constants measured on the oracle's rows: api.hip,
+ * stream_6b_shape).  The shape part of the rule only, as above.
+ */
+int mvfgpu_selftest_stream_bits(uint64_t rows, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq, uint32_t k,
+                                uint32_t* out_bits);
+
+/*
+ * The 6-bit shadow's layout on the host (no GPU needed; csrc/shadow_6b.h): the bytes the shadow of `rows` x `dimension`
+ * holds; `codes` (rows x dimension values in [-31, 31]) packed into `out` as the build kernel packs them (the bytes
+ * behind the last row zero); and the codes read back out of such a shadow.
+ */
+uint64_t mvfgpu_selftest_shadow6_bytes(uint64_t rows, uint32_t dimension);
+int mvfgpu_selftest_shadow6_pack(const int8_t* codes, uint64_t rows, uint32_t dimension, uint8_t* out, uint64_t out_bytes);
+int mvfgpu_selftest_shadow6_unpack(const uint8_t* shadow, uint64_t shadow_bytes, uint64_t rows, uint32_t dimension, int8_t* out_codes);
 
 /*
  * Self-test of a batched search's phase schedule (no GPU needed): the row boundaries R_1 .. R_last = rows of the geometric phases a

@@ -205,6 +205,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_radius_route.restype = C.c_int
     lib.mvfgpu_selftest_stream_rows.argtypes = [u64, u32, u8, u8, u32, u32, vp]
     lib.mvfgpu_selftest_stream_rows.restype = C.c_int
+    lib.mvfgpu_selftest_stream_bits.argtypes = [u64, u32, u8, u8, u32, u32, vp]
+    lib.mvfgpu_selftest_stream_bits.restype = C.c_int
+    lib.mvfgpu_selftest_shadow6_bytes.argtypes = [u64, u32]
+    lib.mvfgpu_selftest_shadow6_bytes.restype = u64
+    lib.mvfgpu_selftest_shadow6_pack.argtypes = [vp, u64, u32, vp, u64]
+    lib.mvfgpu_selftest_shadow6_pack.restype = C.c_int
+    lib.mvfgpu_selftest_shadow6_unpack.argtypes = [vp, u64, u64, u32, vp]
+    lib.mvfgpu_selftest_shadow6_unpack.restype = C.c_int
     sched = getattr(lib, "mvfgpu_selftest_schedule", None)  # added within ABI 3 (round 5): a diagnostic entry point, no layout changed
     if sched is not None:
         sched.argtypes = [u64, u32, u32, C.c_int, vp, u32, vp, vp, vp]

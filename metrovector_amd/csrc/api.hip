@@ -14,6 +14,7 @@
 #include "mvf_common.h"
 #include "scan_mfma.h"
 #include "scan_stream.h"
+#include "shadow_6b.h"
 
 #include <algorithm>
 #include <cmath>
@@ -111,6 +112,7 @@ Tuning read_tuning() {
     t.repair_window = (uint32_t)std::max(0l, num("MVF_REPAIR_WINDOW", 0));
     if (const char* e = getenv("MVF_K2_REGION_RECORDS")) t.region_records = strtoull(e, nullptr, 10);
     t.stream_i8 = getenv("MVF_STREAM_I8") ? (flag("MVF_STREAM_I8", false) ? 1 : 0) : -1;
+    t.stream_6b = flag("MVF_STREAM_6B", true);
     t.upload_threads = (unsigned)std::max(0l, num("MVF_UPLOAD_THREADS", 0));
     t.host_zc_query = (size_t)std::max(0l, num("MVF_HOST_ZC_QUERY", 64l << 10));
     t.host_zc_results = (size_t)std::max(0l, num("MVF_HOST_ZC_RESULTS", 256l << 10));
@@ -168,6 +170,9 @@ struct mvfgpu_corpus {
     mutable uint64_t shadow8_rows = 0;         // rows the int8 shadow covers
     mutable int shadow8_finite = -1;           // the shadow's four bound maxima are finite: -1 not read back yet, 0 no (a row holds Inf / NaN), 1 yes
     mutable DevBuf split_out;                  // partial shadow: the two row ranges' result lists before their merge
+    mutable DevBuf shadow6, xscale6, qs6_stats;  // Float32 corpora: the 6-bit shadow in 64-row tiles (shadow_6b.h), s_r per row, its 4 bound maxima
+    mutable int shadow6_state = 0;               // 0 not tried, 1 all rows, -1 no room (whole or none: no prefix shadows on this route)
+    mutable int shadow6_finite = -1;             // as shadow8_finite
     // feedback for the automatic choice: after a search that selected on the int8 shadow the number of queries the
     // repair launches had to redo is copied to pinned host memory (no wait); a later search that finds it large
     // (the data defeats the int8 bound: near-duplicates everywhere, heavy-tailed rows) switches this corpus back to the
@@ -192,6 +197,10 @@ struct mvfgpu_corpus {
     // to the repair pass -- exact, but 50x slower; such a corpus goes back to round 2's epilogue first (fb_bias: the
     // search the pending count belongs to used the folded pre-filter; fb_qs: it selected on the int8 shadow)
     mutable bool bias_disabled = false, fb_bias[2] = {false, false}, fb_qs[2] = {false, false};
+    // the 6-bit shadow stream posts into the same two slots (fb_s6) but feeds a switch and totals of its own: a corpus that
+    // defeats the 6-bit bound goes back to the int8 route, whose own switch its repairs never touch
+    mutable bool s6_disabled = false, fb_s6[2] = {false, false};
+    mutable uint32_t s6_seen = 0, s6_redone = 0;
     mutable const uint32_t* last_redo_cnt = nullptr;  // device: the count the newest repair pass produced
     mutable const uint32_t* fb_mirrored = nullptr;    // the pinned slot flag_compact_kernel of the newest repair pass stored that count into itself (no copy then)
     mutable bool xnorm_ready = false;
@@ -397,6 +406,17 @@ K1Shape k1_shape(const mvfgpu_corpus* c, uint32_t queries, uint32_t k, uint32_t 
                          [dtype](int G, uint32_t J, int nqv, uint32_t pmax) { return scan_lds_bytes(dtype, G, J, nqv, pmax); });
 }
 K1Shape k1_shape(const mvfgpu_corpus* c, uint32_t queries, uint32_t k) { return k1_shape(c, queries, k, c->V, c->dtype); }
+// ... of the pass over the 6-bit shadow (scan_stream.inc, S6): one query, one lane per row, a step per 64-element unit
+K1Shape k1_shape_6b(uint32_t units, uint32_t k) {
+    K1Shape sh;
+    sh.nqv = 1;
+    sh.G = 1;
+    sh.J = units;
+    sh.chunk_rows = scan_chunk_rows(1, units, 1);
+    sh.pmax = next_pow2(k + scan_chunk_safe(1));
+    sh.lds = scan_lds_bytes_6b(units, sh.pmax);
+    return sh;
+}
 int k1_shape_fits(const K1Shape& sh) {
     if (sh.lds > 160 * 1024) return fail(MVF_ERR_BUILD, "dimension too large for the streaming kernel's LDS query tile");
     return MVF_OK;
@@ -462,6 +482,7 @@ struct ShadowStream {
     // int8 shadow (dt2x unit) only: K1's prologue quantises the f32 queries itself and leaves their scale / norm / bound in
     // qaux0 / qaux1 / delta (qstats, xxmax: what the bound is made of); xrow: the rows' norm array
     bool i8;
+    bool s6;  // ... in 6-bit tiles (dt2y unit: pitch = a tile's bytes, V = the units per row)
     float *qaux0, *qaux1;
     const float *qstats, *xxmax, *xrow;
     // ... and select_final's margin mode instead of the k best: every row within 2 delta[q] of the rank_k-th best
@@ -522,7 +543,7 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
     hipStream_t s = sc.stream;
     const uint32_t kcap = next_pow2(k);
     const uint32_t ostride = out_stride ? out_stride : k;
-    const bool alt8 = alt && alt->i8;
+    const bool alt8 = alt && alt->i8, alt6 = alt8 && alt->s6;
     const uint8_t kdtype = alt8 ? (uint8_t)MVF_DTYPE_INT8 : alt ? (uint8_t)MVF_DTYPE_FLOAT16 : c->dtype;
     const uint32_t kV = alt ? alt->V : c->V;
 
@@ -547,7 +568,7 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
 
     for (uint32_t q0 = 0; q0 < nq;) {
         // (the f16 shadow's unit and a one-query dump take one query per pass)
-        K1Shape sh = k1_shape(c, (!alt || alt8) && !(rank && rank->nqv == 1) ? nq - q0 : 1u, k, kV, kdtype);
+        K1Shape sh = alt6 ? k1_shape_6b(kV, k) : k1_shape(c, (!alt || alt8) && !(rank && rank->nqv == 1) ? nq - q0 : 1u, k, kV, kdtype);
         const int G = sh.G, nqv = sh.nqv;
         const size_t lds = sh.lds;
         uint32_t& chunk_rows = sh.chunk_rows;  // (the small-corpus rule below may shorten it)
@@ -558,7 +579,8 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
 
         uint32_t nblocks = 0;
         if (nchunks > 0) {
-            const void* kfn = alt8  ? scan_stream_kernel_ptr_dt2x(metric, G, nqv)
+            const void* kfn = alt6  ? scan_stream_kernel_ptr_dt2y(metric, G, nqv)
+                              : alt8  ? scan_stream_kernel_ptr_dt2x(metric, G, nqv)
                               : alt ? scan_stream_kernel_ptr_dt1x(metric, G, nqv)
                                     : scan_kernel(c->dtype, metric, G, nqv, /*redo=*/false, floor1 != nullptr || rank != nullptr);
             int occ = 1;
@@ -623,14 +645,15 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
             sp.dump = rank ? rank->a : nullptr;
             if (ps && first && ts_work) sp.ts = ts_work;
             else if (ps && first) MVF_HIP_TRY(hipEventRecord(ps->e[0], s));
-            if (alt8) MVF_HIP_TRY(scan_stream_launch_dt2x(sp, metric, G, nqv, dim3(nblocks), lds, s));
+            if (alt6) MVF_HIP_TRY(scan_stream_launch_dt2y(sp, metric, G, nqv, dim3(nblocks), lds, s));
+            else if (alt8) MVF_HIP_TRY(scan_stream_launch_dt2x(sp, metric, G, nqv, dim3(nblocks), lds, s));
             else if (alt) MVF_HIP_TRY(scan_stream_launch_dt1x(sp, metric, G, nqv, dim3(nblocks), lds, s));
             else MVF_HIP_TRY(scan_launch(c->dtype, sp, metric, G, nqv, dim3(nblocks, npass), lds, s));
             if (ps && first) {
                 if (!ts_work) MVF_HIP_TRY(hipEventRecord(ps->e[1], s));
                 ps->scanned = true;
                 ps->ts_scan = ts_work != nullptr;
-                tm.scan_bytes = (uint64_t)c->n * c->dim * elem_size(kdtype);
+                tm.scan_bytes = alt6 ? (uint64_t)s6_bytes(c->n, c->dim) : (uint64_t)c->n * c->dim * elem_size(kdtype);
                 tm.scan_flops = 2ull * nq_here * c->n * c->dim;
                 if (npass > 1) tm.scan_bytes *= npass;
             }
@@ -809,26 +832,30 @@ constexpr uint32_t kBatchCapQS = 8192;  // candidate slots per query with int8 s
 constexpr uint32_t kQsMaxK = kBatchCapQS / 2 / 10;        // batched: 4096 kept candidates per query
 constexpr uint32_t kQsStreamMaxK = kBatchCap / 2 / 10;    // streamed (select_final's margin mode): 2048
 
+// Scan paths 6 and 7 both insist on the streamed int8 shadow for one to four queries (7 sends ONE unfiltered Float32 query over
+// the 6-bit shadow instead, while the handle's 6-bit switch is on: stream_6b_wanted)
+bool path_streams_i8(const mvfgpu_corpus* c) { return c->scan_path == 6 || c->scan_path == 7; }
+
 // everything but the shadow's own state
 bool qs_possible(const mvfgpu_corpus* c, uint32_t k) {
     if (is_int_dtype(c->dtype) || c->n == 0) return false;
     if (k > kQsMaxK) return false;
     if ((size_t)((c->dim + 7u) & ~7u) * 4 + kBatchCapQS * 4 > 64 * 1024) return false;  // re-scoring: query + candidates in LDS
-    if (c->scan_path == 5 || c->scan_path == 6) return true;
+    if (c->scan_path == 5 || path_streams_i8(c)) return true;
     if (c->scan_path != 0 && c->scan_path != 4) return false;
     return !c->qs_disabled && c->tune.i8_shadow;
 }
 
 bool qs_wanted(const mvfgpu_corpus* c, uint32_t k = 0) {
     if (!qs_possible(c, k)) return false;
-    return c->scan_path == 5 || c->scan_path == 6 || c->shadow8_state >= 0;
+    return c->scan_path == 5 || path_streams_i8(c) || c->shadow8_state >= 0;
 }
 
 // The batched path alone can live with a shadow of a PREFIX of the rows (search_batched_path): where all rows did not fit
 // (state -1) it still asks, once, for what does.
 bool qs_wanted_batched(const mvfgpu_corpus* c, uint32_t k) {
     if (!qs_possible(c, k)) return false;
-    return c->scan_path == 5 || c->scan_path == 6 || c->shadow8_state >= 0 || (c->shadow8_state == -1 && c->tune.i8_shadow_partial);
+    return c->scan_path == 5 || path_streams_i8(c) || c->shadow8_state >= 0 || (c->shadow8_state == -1 && c->tune.i8_shadow_partial);
 }
 
 // The decision itself, a pure function of the sequence of samples (mvfgpu_selftest_feedback runs it without a GPU).
@@ -895,6 +922,14 @@ void qs_feedback_poll(const mvfgpu_corpus* c) {
         return;
     }
     c->qs_redo_pending[sl] = false;
+    if (c->fb_s6[sl]) {  // a 6-bit stream's sample: its own totals, its own switch
+        bool no_bias = false;
+        const bool was = c->s6_disabled;
+        feedback_consume(c->s6_seen, c->s6_redone, no_bias, c->s6_disabled, c->qs_redo_nq[sl], c->qs_redo_host[sl], false, true);
+        if (c->tune.debug_repair && was != c->s6_disabled)
+            fprintf(stderr, "[mvfgpu] 6-bit shadow stream switched off for this corpus: too many queries needed the repair path\n");
+        return;
+    }
     const bool bias_was = c->bias_disabled, qs_was = c->qs_disabled;
     feedback_consume(c->qs_seen, c->qs_redone, c->bias_disabled, c->qs_disabled, c->qs_redo_nq[sl], c->qs_redo_host[sl],
                      c->fb_bias[sl], c->fb_qs[sl]);
@@ -923,7 +958,7 @@ uint32_t* feedback_mirror(const mvfgpu_corpus* c, const SearchCall& sc) {
 // ... and the request for it: the repair count of the search just enqueued, in pinned memory behind the event its call
 // records on the way out (record_done) where the call holds this search alone (search_device), behind an event of the
 // search's own otherwise (the windows of a join).
-int qs_feedback_post(const mvfgpu_corpus* c, const SearchCall& sc, bool used_bias = false, bool used_qs = true) {
+int qs_feedback_post(const mvfgpu_corpus* c, const SearchCall& sc, bool used_bias = false, bool used_qs = true, bool used_s6 = false) {
     hipStream_t s = sc.stream;
     const uint32_t sl = c->qs_slot;
     if (is_filtered(c, sc)) return MVF_OK;
@@ -934,6 +969,7 @@ int qs_feedback_post(const mvfgpu_corpus* c, const SearchCall& sc, bool used_bia
     }
     c->fb_bias[sl] = used_bias;
     c->fb_qs[sl] = used_qs;
+    c->fb_s6[sl] = used_s6;
     if (c->fb_mirrored != c->qs_redo_host + sl)  // (the repair pass could not store it there itself)
         MVF_HIP_TRY(hipMemcpyAsync(c->qs_redo_host + sl, c->last_redo_cnt, 4, hipMemcpyDeviceToHost, s));
     c->fb_mirrored = nullptr;
@@ -994,6 +1030,40 @@ hipError_t ensure_shadow8(const mvfgpu_corpus* c, hipStream_t s, bool insist, bo
         c->shadow8_rows = rows;
         c->shadow8_state = rows == std::max<uint64_t>(c->n, 1) ? 1 : 2;
         c->shadow8_finite = -1;
+    }
+    return e;
+}
+
+// The 6-bit shadow (shadow_6b.hip), built straight from the stored rows beside whatever int8 shadow exists: ensure_shadow8's
+// free-memory rule (its bytes + 2 GiB must be free unless the caller insists), all rows or none.
+hipError_t ensure_shadow6(const mvfgpu_corpus* c, hipStream_t s, bool insist) {
+    if (c->shadow6_state == -1 && insist) c->shadow6_state = 0;
+    if (c->shadow6_state != 0) return hipSuccess;
+    const uint64_t rows = std::max<uint64_t>(c->n, 1);
+    const size_t need = s6_bytes(rows, c->dim);
+    if (!insist) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)2 << 30)) {
+            (void)hipGetLastError();
+            c->shadow6_state = -1;
+            return hipSuccess;
+        }
+    }
+    if (c->shadow6.reserve(need) != hipSuccess || c->xscale6.reserve(((size_t)rows + 256) * 4) != hipSuccess ||
+        c->qs6_stats.reserve(16) != hipSuccess) {
+        (void)hipGetLastError();
+        c->shadow6.release();
+        c->xscale6.release();
+        c->shadow6_state = -1;
+        return hipSuccess;
+    }
+    hipError_t e = hipMemsetAsync(c->qs6_stats.p, 0, 16, s);
+    if (e == hipSuccess)
+        e = launch_shadow_6b(c->d_rows, (uint32_t)c->n, c->pitch, c->dim, static_cast<unsigned char*>(c->shadow6.p),
+                             static_cast<float*>(c->xscale6.p), static_cast<float*>(c->qs6_stats.p), s);
+    if (e == hipSuccess) {
+        c->shadow6_state = 1;
+        c->shadow6_finite = -1;
     }
     return e;
 }
@@ -1449,12 +1519,12 @@ int search_batched_range(const mvfgpu_corpus* c, SearchCall& sc, uint64_t lo, ui
     if (dr) {
         dr->overflow = overflow;
         dr->used_bias |= used_bias;
-        dr->used_qs |= use_qs && c->scan_path != 5 && c->scan_path != 6;
+        dr->used_qs |= use_qs && c->scan_path != 5 && !path_streams_i8(c);
     }
     if (defer) return MVF_OK;
     int rc = repair_flagged_queries(c, sc, overflow);
-    if (rc == MVF_OK && ((use_qs && c->scan_path != 5 && c->scan_path != 6) || used_bias))
-        rc = qs_feedback_post(c, sc, used_bias, use_qs && c->scan_path != 5 && c->scan_path != 6);
+    if (rc == MVF_OK && ((use_qs && c->scan_path != 5 && !path_streams_i8(c)) || used_bias))
+        rc = qs_feedback_post(c, sc, used_bias, use_qs && c->scan_path != 5 && !path_streams_i8(c));
     return rc;
 }
 
@@ -1475,7 +1545,7 @@ int search_batched_path(const mvfgpu_corpus* c, SearchCall& sc) {
     if (qs_wanted_batched(c, k)) {
         int rc = ensure_norms(c, s);
         if (rc != MVF_OK) return rc;
-        MVF_HIP_TRY(ensure_shadow8(c, s, c->scan_path == 5 || c->scan_path == 6, /*allow_partial=*/true));
+        MVF_HIP_TRY(ensure_shadow8(c, s, c->scan_path == 5 || path_streams_i8(c), /*allow_partial=*/true));
     }
     if (!(c->shadow8_state == 2 && qs_wanted(c, k) && c->shadow8_rows < c->n))
         return search_batched_range(c, sc, 0, c->n, true, false, true, nullptr);
@@ -1580,13 +1650,22 @@ int search_stream_shadow_path(const mvfgpu_corpus* c, SearchCall& sc) {
 // and gathers every entry within 2 delta of it; a list that was cut inside the bound (rows beyond the cut may be inside
 // too: clustered rows, tiny corpora) or more than 2048 rows inside it flag the query, which the exact K1 then redoes.
 // rescore_kernel re-scores what was gathered from the stored rows and the f32 query.
-uint32_t stream_qs_klist(uint32_t k) { return std::max(k, 32u); }
+// (the 6-bit route: 128 -- its margin is twice as wide, and on short rows, whose scores are far from Gaussian, it holds a
+// few per cent of ALL rows whatever k is: 28 of every 1024 rows of 3-dimensional uniform rows under Cosine)
+uint32_t stream_qs_klist(uint32_t k, bool s6 = false) { return std::max(k, s6 ? 128u : 32u); }
 
-int search_stream_qs_path(const mvfgpu_corpus* c, SearchCall& sc) {
+// s6: ONE query over the 6-BIT shadow instead (shadow_6b.hip: K1's dt2y unit, the query at sixteen bits).  Its bound is twice
+// the int8 route's, ~50 x k rows of the benchmark's corpus ride in the margin: the lists hold kStream6Cap kept candidates, the
+// re-scoring spreads over them and the final select picks the k best before it sorts (rescore_select_wide_kernel).  The
+// same launches in the same order; a flagged query is redone by K1 exactly as on the int8 route, and the repair count feeds
+// the 6-bit route's own switch (s6_disabled), never qs_disabled.
+constexpr uint32_t kStream6Cap = 16384;  // kept candidates per query on the 6-bit route (the list holds twice that: the exact keys go to its upper half)
+
+int search_stream_qs_path(const mvfgpu_corpus* c, SearchCall& sc, bool s6 = false) {
     const uint8_t metric = sc.metric;
     const uint32_t nq = sc.nq, k = sc.k;
     hipStream_t s = sc.stream;
-    const uint32_t cap = kBatchCap;
+    const uint32_t cap = s6 ? 2u * kStream6Cap : kBatchCap;
     const uint32_t nq_pad = (nq + 255u) & ~255u;
     const uint32_t n = (uint32_t)c->n;
     int rc = ensure_bstate(c, nq_pad, s);
@@ -1616,6 +1695,14 @@ int search_stream_qs_path(const mvfgpu_corpus* c, SearchCall& sc) {
     alt.xrow = metric == MVF_METRIC_L2 ? xn + nn : xn;  // sum x^2 | |x| of the stored rows
     alt.pitch = KPB;
     alt.V = KPB / 16;
+    if (s6) {
+        alt.s6 = true;
+        alt.rows = static_cast<const unsigned char*>(c->shadow6.p);
+        alt.xscale = static_cast<const float*>(c->xscale6.p);
+        alt.qstats = static_cast<const float*>(c->qs6_stats.p);
+        alt.pitch = (uint32_t)s6_tile_bytes(c->dim);
+        alt.V = s6_units(c->dim);
+    }
     alt.cand = static_cast<uint64_t*>(c->bcand.p);
     alt.cnt = bs.cnt;
     alt.cand_cap = cap;
@@ -1624,7 +1711,7 @@ int search_stream_qs_path(const mvfgpu_corpus* c, SearchCall& sc) {
     alt.overflow = bs.overflow;
     alt.rank_k = k;
     uint64_t* ts_end = sc.whole_by_clock ? prof_ts_entry(c, c->prof_next) + 3 : nullptr;  // (this search's entry: prof_next moves below)
-    rc = inner_search(sc, stream_qs_klist(k), nullptr, nullptr, nullptr,
+    rc = inner_search(sc, stream_qs_klist(k, s6), nullptr, nullptr, nullptr,
                       [&](SearchCall& in) { return search_stream_path(c, in, /*profile=*/true, &alt); });
     if (rc != MVF_OK) return rc;
 
@@ -1647,7 +1734,8 @@ int search_stream_qs_path(const mvfgpu_corpus* c, SearchCall& sc) {
     MVF_HIP_TRY(launch_rescore_k1(rp, metric, nq, sh.G, sh.J, s));
     sc.launches += 2;
     rc = repair_flagged_queries(c, sc, bs.overflow, sh.nqv, &plan, ts_end);
-    if (rc == MVF_OK && c->scan_path != 6) rc = qs_feedback_post(c, sc);
+    if (rc == MVF_OK && s6) rc = qs_feedback_post(c, sc, false, false, /*used_s6=*/true);
+    else if (rc == MVF_OK && !path_streams_i8(c)) rc = qs_feedback_post(c, sc);
     return rc;
 }
 
@@ -1680,12 +1768,68 @@ bool stream_i8_shape(uint64_t rows, uint32_t dim, uint8_t dtype, uint32_t nq, ui
 // profiles/r02_stream_int8_shadow_1to4_queries.txt).
 bool stream_qs_wanted(const mvfgpu_corpus* c, uint32_t nq, uint32_t k) {
     if (nq < 1 || nq > 4 || k > kQsStreamMaxK || !qs_wanted(c, k)) return false;
-    if (c->scan_path == 6) return true;
+    // (a 6-bit shadow whose maxima are non-finite has seen a row holding Inf / NaN: the int8 shadow's are non-finite too and
+    // every query would be flagged and repaired -- the stored rows, except where scan path 6 insists)
+    if (c->shadow6_state == 1 && c->shadow6_finite == 0 && c->scan_path != 6) return false;
+    if (path_streams_i8(c)) return true;
     if (c->scan_path != 0 || nq != 1 || c->tune.stream_i8 == 0) return false;
     if (c->shadow8_state != 0 && c->shadow8_state != 1) return false;
     if (c->shadow8_state == 1 && c->shadow8_finite == 0) return false;
     if (c->tune.stream_i8 == 1 && c->shadow8_state == 1) return true;
     return stream_i8_shape(c->n, c->dim, c->dtype, nq, k);
+}
+
+// ONE Float32 query on a corpus of at least kStream6MinBytes of rows streams the 6-BIT shadow instead (0.75 x the int8
+// shadow's bytes, the same bits as K1 on the stored rows) -- where the margin of the 6-bit bound is predicted to hold at most
+// HALF the kStream6Cap candidates the route carries: a query whose margin overflows is redone by K1 on the stored rows at four
+// times the int8 route's cost, so shapes near the capacity stay on int8.
+// The prediction: scores ~ Gaussian, the k-th best of `rows` at z(k / rows) sigma, the margin 2 delta = 2 c sqrt(dim) sigma wide,
+// so  rows Q(z(k / rows) - 2 c sqrt(dim))  rows inside it (Q: the Gaussian tail).  c per metric from the oracle's rows
+// (scripts/model_stream_6b_bound.py, 200k x 768, 8 queries: delta = 0.486 / 0.496 / 0.444 sigma for InnerProduct / Cosine /
+// L2's squared distance): the headline (10M x 768, k = 100) 5 300 rows -- 6 bit; k = 204 there 9 400, 10M x 1024 at k = 100
+// 9 100 -- int8.
+// kStream6MinBytes, measured (scripts/probe_stream_6b_crossover.py, profiles/r10_stream_6b.txt; 768-dim cosine, top-100, device
+// time per search, int8 / 6-bit): 1 GiB 0.093 / 0.103 ms, 2 GiB 0.136 / 0.138 (inside the spread), 4 GiB 0.214 / 0.189 (ranges
+// disjoint), 8 GiB 0.403 / 0.321, 16 GiB 0.708 / 0.562, 10M rows 1.205 / 0.948.  One lane per row needs 1024 rows per block
+// and step, so small corpora fill the chip late: the scan holds 3.4 TB/s at 1 GiB, 5.6 at 4 GiB, 6.5 at 10M rows.
+constexpr uint64_t kStream6MinBytes = 4ull << 30;
+constexpr double kStream6C[3] = {0.01601, 0.01754, 0.01791};  // by metric code: L2, InnerProduct, Cosine
+
+double gauss_tail(double z) { return 0.5 * std::erfc(z / std::sqrt(2.0)); }
+double gauss_tail_inv(double p) {  // z with Q(z) = p, by bisection (a pure function of p: the same on every host)
+    double lo = -10.0, hi = 10.0;
+    for (int i = 0; i < 100; i++) {
+        const double mid = 0.5 * (lo + hi);
+        if (gauss_tail(mid) > p) lo = mid;
+        else hi = mid;
+    }
+    return 0.5 * (lo + hi);
+}
+double stream_6b_margin_rows(uint64_t rows, uint32_t dim, uint8_t metric, uint32_t k) {
+    if (k >= rows) return (double)rows;
+    const double z = gauss_tail_inv((double)k / (double)rows);
+    return (double)rows * gauss_tail(z - 2.0 * kStream6C[metric <= 2 ? metric : 2] * std::sqrt((double)dim));
+}
+// The shape part of the rule, a pure function (mvfgpu_selftest_stream_bits pins it without a GPU); the caller has checked
+// Float32 rows, one query and k <= kQsStreamMaxK (stream_i8_shape)
+bool stream_6b_shape(uint64_t rows, uint32_t dim, uint8_t metric, uint32_t k) {
+    if (rows * (uint64_t)dim * 4u < kStream6MinBytes) return false;
+    return stream_6b_margin_rows(rows, dim, metric, k) <= kStream6Cap / 2;
+}
+
+// Who takes the 6-bit route: ONE unfiltered Float32 query of a search of its own (the windows of a join, radius and candidate
+// searches, filtered searches and two to four queries stay on int8) on scan path 0 where stream_6b_shape holds -- unless
+// MVF_STREAM_I8=0 (out of both shadow routes) or MVF_STREAM_6B=0 -- and on scan path 7 at any size (tests).  Only over a WHOLE
+// shadow, held or buildable now (ensure_shadow6), whose bound maxima are finite; a corpus whose queries keep needing the
+// repair pass switches itself back to the int8 route (s6_disabled) -- as does one the int8 route has given up on already.
+bool stream_6b_wanted(const mvfgpu_corpus* c, const SearchCall& sc) {
+    if (c->dtype != MVF_DTYPE_FLOAT32 || sc.nq != 1 || sc.k == 0 || sc.k > kQsStreamMaxK || c->n == 0 || sc.shared_call) return false;
+    if (sc.deny != static_cast<const uint32_t*>(c->tomb.p)) return false;  // a filtered search
+    if ((size_t)((c->dim + 7u) & ~7u) * 4 + kBatchCapQS * 4 > 64 * 1024) return false;  // qs_possible's row length
+    if (c->s6_disabled || c->shadow6_state < 0 || (c->shadow6_state == 1 && c->shadow6_finite == 0)) return false;
+    if (c->scan_path == 7) return true;
+    if (c->scan_path != 0 || c->qs_disabled || !c->tune.i8_shadow || c->tune.stream_i8 == 0 || !c->tune.stream_6b) return false;
+    return stream_6b_shape(c->n, c->dim, sc.metric, sc.k);
 }
 
 constexpr uint32_t kWideFinalMaxDim = 16384;  // widest Float32 row whose InnerProduct / Cosine keys the f32 MFMA kernel may finalise (use_batched_path)
@@ -1716,7 +1860,7 @@ bool use_batched_path(const mvfgpu_corpus* c, uint8_t metric, uint32_t nq) {
     if (c->dtype == MVF_DTYPE_FLOAT32 && metric != MVF_METRIC_L2 && c->dim > kWideFinalMaxDim) supported = false;
     if (!supported) return false;
     if (c->scan_path == 2 || c->scan_path == 3 || (c->scan_path == 5 && !is_int_dtype(c->dtype))) return true;
-    if (c->scan_path == 6 && !is_int_dtype(c->dtype)) return nq > 4;
+    if (path_streams_i8(c) && !is_int_dtype(c->dtype)) return nq > 4;
     // K1 takes up to 4 queries per pass over the rows; K2 costs a flat padded-tile time -- since the streaming MFMA kernel
     // (scan_mfma16_sb.hip) about ONE pass over the int8 shadow / the Int8 rows for up to 64 queries, plus ~0.1 ms of phase
     // launches.  Measured crossovers (scripts/probe_small_corpora.py, profiles/r02_small_corpora_crossover.txt): Float32 /
@@ -2268,6 +2412,9 @@ void mvfgpu_corpus_destroy(mvfgpu_corpus* c) {
         c->shadow8.release();
         c->xscale8.release();
         c->qs_stats.release();
+        c->shadow6.release();
+        c->xscale6.release();
+        c->qs6_stats.release();
         c->h_q.release();
         c->h_s.release();
         c->h_i.release();
@@ -2306,10 +2453,10 @@ int mvfgpu_corpus_get_info(const mvfgpu_corpus* c, mvfgpu_corpus_info* out) {
     {
         std::lock_guard<std::mutex> lk(c->mu);
         inf.has_vector_ids = c->ids.p ? 1 : 0;
-        inf.shadows = (uint8_t)((c->shadow8_state == 1 ? 1 : 0) | (c->shadow_state == 1 ? 2 : 0) | (c->shadow8_state == 2 ? 4 : 0));
-        inf.selection_state = (uint8_t)((c->qs_disabled ? 1 : 0) | (c->bias_disabled ? 2 : 0));
+        inf.shadows = (uint8_t)((c->shadow8_state == 1 ? 1 : 0) | (c->shadow_state == 1 ? 2 : 0) | (c->shadow8_state == 2 ? 4 : 0) | (c->shadow6_state == 1 ? 8 : 0));
+        inf.selection_state = (uint8_t)((c->qs_disabled ? 1 : 0) | (c->bias_disabled ? 2 : 0) | (c->s6_disabled ? 4 : 0));
         inf.device_bytes = c->tomb.bytes + c->ids.bytes + c->rows_bytes + c->cand.bytes + c->bq.bytes + c->bstate.bytes + c->bcand.bytes +
-                           c->xnorm.bytes + c->repair.bytes + c->floor1.bytes + c->rank_a.bytes + c->rank_b.bytes + c->rank_tmp.bytes + c->blk.bytes + c->shadow8.bytes + c->xscale8.bytes + c->qs_stats.bytes + c->split_out.bytes +
+                           c->xnorm.bytes + c->repair.bytes + c->floor1.bytes + c->rank_a.bytes + c->rank_b.bytes + c->rank_tmp.bytes + c->blk.bytes + c->shadow8.bytes + c->xscale8.bytes + c->qs_stats.bytes + c->split_out.bytes + c->shadow6.bytes + c->xscale6.bytes + c->qs6_stats.bytes +
                            c->shadow.bytes + c->xscale.bytes + c->h_q.bytes + c->h_s.bytes + c->h_i.bytes + c->h_r.bytes + c->h_v.bytes;
     }
     return copy_out_struct(out, inf);
@@ -2506,20 +2653,35 @@ int search_locked(const mvfgpu_corpus* c, SearchCall& sc) {
         }
         return MVF_OK;
     }
-    bool shadow_stream = false, qs_stream = false;
-    if (stream_qs_wanted(c, nq, k) && !is_filtered(c, sc)) qs_feedback_poll(c);  // may switch the int8 selection off
+    bool shadow_stream = false, qs_stream = false, s6_stream = false;
+    if ((stream_qs_wanted(c, nq, k) || stream_6b_wanted(c, sc)) && !is_filtered(c, sc)) qs_feedback_poll(c);  // may switch the int8 selection / the 6-bit stream off
     // K1 on the stored rows and the streamed int8 shadow time themselves (ProfSlot::ts_whole: from the search's first kernel, so
     // not the norms / the shadow a handle's first search builds in front of it); every other route keeps the event pair around the
     // whole call, in front of whatever it builds first.  The route is only known behind those builds: where it was expected to time
     // itself and cannot (no room for the shadow, non-finite maxima) and the batched route answers, e[3] is recorded behind them too
-    if (wps && !(stream_qs_wanted(c, nq, k) || (!stream_shadow_wanted(c, nq) && !use_batched_path(c, metric, nq)))) {
+    if (wps && !(stream_qs_wanted(c, nq, k) || stream_6b_wanted(c, sc) || (!stream_shadow_wanted(c, nq) && !use_batched_path(c, metric, nq)))) {
         MVF_HIP_TRY(hipEventRecord(wps->e[3], s));
         e3_recorded = true;
     }
-    if (stream_qs_wanted(c, nq, k)) {
+    if (stream_6b_wanted(c, sc)) {  // the 6-bit shadow first; where it cannot be had (no room, a non-finite row) the rules below decide as before
         rc = ensure_norms(c, s);
         if (rc != MVF_OK) return rc;
-        hipError_t e = ensure_shadow8(c, s, c->scan_path == 6);
+        hipError_t e = ensure_shadow6(c, s, c->scan_path == 7);
+        if (e != hipSuccess) return fail(MVF_ERR_DEVICE, std::string("6-bit shadow build: ") + hipGetErrorString(e));
+        s6_stream = c->shadow6_state == 1;
+        if (s6_stream && c->shadow6_finite < 0) {  // once per shadow: its bound maxima (one small wait)
+            float st[4] = {0.f, 0.f, 0.f, 0.f};
+            MVF_HIP_TRY(hipMemcpyAsync(st, c->qs6_stats.p, sizeof(st), hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipStreamSynchronize(s));
+            c->shadow6_finite = std::isfinite(st[0]) && std::isfinite(st[1]) && std::isfinite(st[2]) && std::isfinite(st[3]) ? 1 : 0;
+        }
+        if (s6_stream && c->shadow6_finite == 0) s6_stream = false;  // a row holds Inf / NaN
+        qs_stream = s6_stream;
+    }
+    if (!s6_stream && stream_qs_wanted(c, nq, k)) {
+        rc = ensure_norms(c, s);
+        if (rc != MVF_OK) return rc;
+        hipError_t e = ensure_shadow8(c, s, path_streams_i8(c));
         if (e != hipSuccess) return fail(MVF_ERR_DEVICE, std::string("int8 shadow build: ") + hipGetErrorString(e));
         qs_stream = c->shadow8_state == 1;
         if (qs_stream && c->scan_path == 0 && c->shadow8_finite < 0) {  // once per shadow: its bound maxima (one small wait)
@@ -2543,7 +2705,7 @@ int search_locked(const mvfgpu_corpus* c, SearchCall& sc) {
     } else if (wps && !e3_recorded) {
         MVF_HIP_TRY(hipEventRecord(wps->e[3], s));
     }
-    rc = qs_stream                           ? search_stream_qs_path(c, sc)
+    rc = qs_stream                           ? search_stream_qs_path(c, sc, s6_stream)
          : shadow_stream                     ? search_stream_shadow_path(c, sc)
          : use_batched_path(c, metric, nq) ? search_batched_path(c, sc)
                                            : search_stream_path(c, sc);
@@ -2966,7 +3128,7 @@ int mvfgpu_last_timing(const mvfgpu_corpus* c, mvfgpu_timing* out) {
 
 int mvfgpu_set_scan_path(mvfgpu_corpus* c, int path) {
     if (!c) return fail(MVF_ERR_INVALID_ARGUMENT, "corpus is NULL");
-    if (path < 0 || path > 6) return fail(MVF_ERR_INVALID_ARGUMENT, "path must be 0..6");
+    if (path < 0 || path > 7) return fail(MVF_ERR_INVALID_ARGUMENT, "path must be 0..7");
     std::lock_guard<std::mutex> lk(c->mu);
     c->scan_path = path;
     return MVF_OK;
@@ -3053,6 +3215,16 @@ int mvfgpu_selftest_stream_rows(uint64_t rows, uint32_t dimension, uint8_t data_
         return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported type or empty dimension / batch / k");
     if (const int mrc = check_metric(metric)) return mrc;
     *out_rows = stream_i8_shape(rows, dimension, data_type, nq, k) ? 1u : 0u;
+    return MVF_OK;
+}
+
+int mvfgpu_selftest_stream_bits(uint64_t rows, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq, uint32_t k,
+                                uint32_t* out_bits) {
+    if (!out_bits) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (elem_size(data_type) == 0 || dimension == 0 || nq == 0 || k == 0 || k > MVFGPU_MAX_K)
+        return fail(MVF_ERR_INVALID_ARGUMENT, "unsupported type or empty dimension / batch / k");
+    if (const int mrc = check_metric(metric)) return mrc;
+    *out_bits = !stream_i8_shape(rows, dimension, data_type, nq, k) ? 0u : stream_6b_shape(rows, dimension, metric, k) ? 6u : 8u;
     return MVF_OK;
 }
 

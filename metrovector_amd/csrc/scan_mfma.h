@@ -183,6 +183,10 @@ hipError_t launch_shadow_f16(const unsigned char* rows32, uint32_t n, uint32_t p
 // int8 shadow of a Float32 / Float16 corpus + its queries (shadow_i8.hip); stats: 4 floats, zeroed by the caller
 hipError_t launch_shadow_i8(const unsigned char* rows, int src_dtype, uint32_t n, uint32_t pitch, uint32_t dim, unsigned char* rows8,
                             uint32_t pitch8, float* xscale8, float* stats, hipStream_t s);
+// 6-bit shadow of a Float32 corpus in the tiled layout of shadow_6b.h (shadow_6b.hip): rows6 holds s6_bytes(n, dim) bytes;
+// stats: 4 floats, zeroed by the caller
+hipError_t launch_shadow_6b(const unsigned char* rows, uint32_t n, uint32_t pitch, uint32_t dim, unsigned char* rows6, float* xscale6,
+                            float* stats, hipStream_t s);
 hipError_t launch_prep_queries_i8s(const float* q, uint32_t nq, uint32_t nq_pad, uint32_t dim, uint32_t KPB, int metric,
                                    const float* stats, const float* xxmax, unsigned char* qprep, float* qaux0, float* qaux1,
                                    float* delta, hipStream_t s);

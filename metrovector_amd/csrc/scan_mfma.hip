@@ -1088,6 +1088,124 @@ __global__ void __launch_bounds__(1024) rescore_select_kernel(RescoreParams p, i
     }
 }
 
+// rescore_select_kernel for lists too long to sort in one block (the 6-bit shadow stream: up to 16384 exact keys, ~5 000 on
+// the benchmark's rows, ALL of them live -- the margin select gathered nothing outside the threshold): SELECT, then sort.
+// The live entries are compacted into LDS; a radix select over the 64-bit composites (select_final_kernel's: four 8-bit
+// histogram passes over the key, and -- only where several entries share the k-th key -- four over the row among those)
+// finds the k-th smallest; the k entries up to it (composites are distinct) are sorted by rank counting and formatted.
+// Dynamic LDS: cap / 2 entries.
+__global__ void __launch_bounds__(1024) rescore_select_wide_kernel(RescoreParams p, int metric) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* buf = reinterpret_cast<uint64_t*>(smem);
+    __shared__ uint32_t hist[256];
+    __shared__ uint64_t top[1024];
+    __shared__ uint32_t live_s, top_s, sel_prefix, sel_remaining, sel_count;
+    __shared__ uint64_t sel_tau;
+    const int tid = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    const uint32_t keep_cap = p.cap / 2;
+    const uint32_t m0 = min(p.cnt[q], keep_cap);
+    const uint64_t* c = p.cand + (size_t)q * p.cap + keep_cap;  // the scoring pass's output: the list's upper half
+    if (tid == 0) live_s = 0, top_s = 0, sel_prefix = 0, sel_remaining = p.k;
+    __syncthreads();
+    for (uint32_t i = tid; i < m0; i += 1024) {
+        const uint64_t e = c[i];
+        if (e != kPadComposite) buf[atomicAdd(&live_s, 1u)] = e;
+    }
+    __syncthreads();
+    const uint32_t m = live_s;
+    uint64_t tau = kPadComposite;  // m <= k: every live entry is a result
+    if (m > p.k) {
+        uint32_t key_k = 0;
+        for (int word = 1; word >= 0; word--) {
+            uint32_t mask = 0;
+            if (tid == 0) sel_prefix = 0;
+            __syncthreads();
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                if (tid < 256) hist[tid] = 0;
+                __syncthreads();
+                const uint32_t prefix = sel_prefix;
+                for (uint32_t i = tid; i < m; i += 1024) {
+                    const uint64_t e = buf[i];
+                    const uint32_t w = word ? (uint32_t)(e >> 32) : (uint32_t)e;
+                    if ((word || (uint32_t)(e >> 32) == key_k) && ((w ^ prefix) & mask) == 0) atomicAdd(&hist[(w >> shift) & 255u], 1u);
+                }
+                __syncthreads();
+                if (tid < 64) {  // one wave: bin of the k-th among the entries that share the prefix
+                    const uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+                    uint32_t incl = h0 + h1 + h2 + h3;
+                    for (int off = 1; off < 64; off <<= 1) {
+                        const uint32_t v = __shfl_up(incl, off, 64);
+                        if (tid >= off) incl += v;
+                    }
+                    const uint32_t excl = incl - (h0 + h1 + h2 + h3), rem = sel_remaining;
+                    if (excl < rem && rem <= incl) {  // exactly one lane
+                        uint32_t r = rem - excl, bin = 4 * tid, hb = h0;
+                        if (r > h0) { r -= h0; bin++; hb = h1; if (r > h1) { r -= h1; bin++; hb = h2; if (r > h2) { r -= h2; bin++; hb = h3; } } }
+                        sel_prefix = prefix | (bin << shift);
+                        sel_remaining = r;
+                        sel_count = hb;
+                    }
+                }
+                mask |= 255u << shift;
+                __syncthreads();
+            }
+            const uint32_t found = sel_prefix, found_count = sel_count;
+            __syncthreads();  // everyone has read the selection before the next word's passes reset it
+            if (word) {
+                key_k = found;
+                if (found_count == 1) {  // block-uniform: the k-th key is unique
+                    for (uint32_t i = tid; i < m; i += 1024)
+                        if ((uint32_t)(buf[i] >> 32) == key_k) sel_tau = buf[i];
+                    __syncthreads();
+                    break;
+                }
+            } else {
+                if (tid == 0) sel_tau = ((uint64_t)key_k << 32) | found;
+                __syncthreads();
+            }
+        }
+        tau = sel_tau;
+    }
+    for (uint32_t i = tid; i < m; i += 1024) {
+        const uint64_t e = buf[i];
+        if (e <= tau) {
+            const uint32_t slot = atomicAdd(&top_s, 1u);
+            if (slot < 1024u) top[slot] = e;
+        }
+    }
+    __syncthreads();
+    const uint32_t mk = min(top_s, 1024u);  // = min(m, k): k <= 1024 on this route
+    {   // rank counting: one survivor per thread
+        const uint64_t mine = (uint32_t)tid < mk ? top[tid] : kPadComposite;
+        uint32_t rank = 0;
+        for (uint32_t i = 0; i < mk; i++) rank += top[i] < mine ? 1u : 0u;
+        __syncthreads();
+        if ((uint32_t)tid < mk) top[rank] = mine;
+        __syncthreads();
+    }
+    for (uint32_t i = tid; i < p.k; i += 1024) {
+        const uint32_t o = q * p.k + i;
+        const uint64_t comp = i < mk ? top[i] : kPadComposite;
+        if (comp == kPadComposite) {
+            p.out_scores[o] = pad_score(metric);
+            p.out_indices[o] = ~0ull;
+        } else {
+            p.out_scores[o] = score_from_key((uint32_t)(comp >> 32), metric);
+            p.out_indices[o] = p.ids ? p.ids[(uint32_t)comp] : p.index_base + (uint32_t)comp;
+        }
+        if (p.out_raw) p.out_raw[o] = 0;
+    }
+    if (tid == 0) {
+        p.cnt[q] = 0;
+        p.tau[q] = kNanKey;
+    }
+    if (p.flags && q == 0) {  // block-uniform
+        __shared__ uint32_t flagged_s;
+        compact_flags(p.flags, p.flags_nq, p.redo_list, p.redo_cnt, p.redo_mirror, &flagged_s);
+    }
+}
+
 }  // namespace
 
 size_t scan_mfma_lds_bytes() { return kLdsBytes; }
@@ -1188,6 +1306,8 @@ hipError_t launch_rescore(const RescoreParams& p, int metric, uint32_t nq, hipSt
     return hipGetLastError();
 }
 
+constexpr uint32_t kSelectSortMax = 4096;  // kept candidates per query rescore_select_kernel sorts in one block (the batched int8 selection's cap / 2)
+
 hipError_t launch_rescore_k1(const RescoreParams& p, int metric, uint32_t nq, int G, uint32_t J, hipStream_t s) {
     if (nq == 0) return hipSuccess;
     if (p.dtype != MVF_DTYPE_FLOAT32 && p.dtype != MVF_DTYPE_FLOAT16) return hipErrorInvalidValue;
@@ -1210,6 +1330,14 @@ hipError_t launch_rescore_k1(const RescoreParams& p, int metric, uint32_t nq, in
     void* args[] = {&arg, &a_nq, &a_slices, &a_split, &a_j};
     hipError_t e = hipLaunchKernel(fn, grid, dim3(256), args, 0, s);
     if (e != hipSuccess) return e;
+    if (p.cap / 2 > kSelectSortMax) {  // the 6-bit route's lists: select, then sort
+        if (p.k > 1024u) return hipErrorInvalidValue;
+        const size_t lds = (size_t)(p.cap / 2) * 8;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rescore_select_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(rescore_select_wide_kernel, dim3(nq), dim3(1024), lds, s, p, metric);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(rescore_select_kernel, dim3(nq), dim3(1024), (size_t)(p.cap / 2) * 8, s, p, metric);
     return hipGetLastError();
 }

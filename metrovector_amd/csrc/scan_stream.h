@@ -71,6 +71,7 @@ MVF_DECL_SCAN(2)
 MVF_DECL_SCAN(3)
 MVF_DECL_SCAN(1x)  // Float16 rows of an f32 corpus' shadow, scaled back by ScanParams::xscale; nqv = 1 only
 MVF_DECL_SCAN(2x)  // Int8 shadow rows of a float corpus: exact i32 dot, float keys dot * xscale[r] * qaux0[q]; nqv = 1 or 4
+MVF_DECL_SCAN(2y)  // the 6-bit shadow of a Float32 corpus in 64-row tiles (shadow_6b.h): G = 1, nqv = 1 only; pitch = a tile's bytes, V = J = units per row
 #undef MVF_DECL_SCAN
 
 // Rows per SAFE piece for a lane-group width G (multiple of the 16*64/G rows a block covers per iteration): the candidate
@@ -97,5 +98,8 @@ inline size_t scan_lds_bytes(int dtype, int G, uint32_t J, int nqv, uint32_t pma
     size_t q = ((size_t)nqv * J * G * qb + 15u) & ~(size_t)15u;
     return q + (size_t)nqv * pmax * 8u + (size_t)nqv * 32u;
 }
+
+// ... of the 6-bit-shadow unit: both int8 planes of the 16-bit query, 64 bytes per unit each
+inline size_t scan_lds_bytes_6b(uint32_t units, uint32_t pmax) { return (size_t)units * 128u + (size_t)pmax * 8u + 32u; }
 
 }  // namespace mvf

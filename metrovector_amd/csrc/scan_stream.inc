@@ -26,6 +26,8 @@
 #include "scan_stream.h"
 #include "bitonic.h"
 #include "query_i8s.h"
+#include "query_16s.h"
+#include "shadow_6b.h"
 
 #include <hip/hip_fp16.h>
 
@@ -66,6 +68,12 @@ constexpr bool XS = MVF_SCAN_XS != 0;
 // quantised to int8 in the prologue (query_i8s.h), exact i32 dot products, FLOAT keys dot * xscale[r] * qaux0[q] (cosine: / (|q| |x_r|); L2: the
 // GEMM-form squared distance qq + xx - 2 dot) for the margin compaction + exact re-scoring that follow.
 constexpr bool QSK = XS && MVF_SCAN_DT == MVF_DTYPE_INT8;
+// S6: the QSK unit over the 6-BIT shadow of a Float32 corpus (MVF_SCAN_XS == 2; shadow_6b.h has the layout, shadow_6b.hip the
+// bound).  One lane per row (G = 1) and one query: a "step" j is a 64-element UNIT -- three wave-loads of one aligned KiB each,
+// plane p of unit j of the tile's 64 rows -- ScanParams::pitch is the TILE's size and V = J the units per row.  The query is
+// quantised to sixteen bits in the prologue (query_16s.h) and sits in LDS as two int8 planes in natural element order, 64
+// bytes per unit each: per row two exact i32 sums, combined exactly with the per-query constant 32 sum Q, then QSK's keys.
+constexpr bool S6 = QSK && MVF_SCAN_XS == 2;
 
 // Short rows (G <= 8: one step per row) are latency-bound -- a wave has 4 KiB in flight and its iteration is load -> wait ->
 // sums -> keys in sequence -- so those instantiations of the narrow types ask for more waves per SIMD than the 3-4 the
@@ -80,15 +88,16 @@ constexpr bool QSK = XS && MVF_SCAN_DT == MVF_DTYPE_INT8;
 #define MVF_K1_SHORT_ROW_WAVES 5  // A/B builds: -DMVF_K1_SHORT_ROW_WAVES=8|7|6|1
 #endif
 template <int DT, int METRIC, int G, int NQ, bool REDO = false, bool FLOOR = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((G <= 8 && NQ == 1 && DT != MVF_DTYPE_FLOAT32) ? MVF_K1_SHORT_ROW_WAVES : 1, 8)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((G <= 8 && NQ == 1 && DT != MVF_DTYPE_FLOAT32 && !S6) ? MVF_K1_SHORT_ROW_WAVES : 1, 8)))
 scan_stream_kernel(ScanParams p) {
     using Tr = DtTraits<DT>;
     using Acc = typename Tr::Acc;
     constexpr int ES = Tr::ES;
-    constexpr int EPV = 16 / ES;  // corpus elements per 16-B vector
+    static_assert(!S6 || (G == 1 && NQ == 1 && !REDO && !FLOOR), "the 6-bit unit: one lane per row, one query");
+    constexpr int EPV = S6 ? 64 : 16 / ES;  // corpus elements per 16-B vector (S6: per unit)
     constexpr int RPG = 64 / G;   // rows per wave-load
     constexpr int U = 4;          // row groups in flight per wave (8 for one-step rows measured SLOWER: 128-B rows 4.4 vs 5.3 TB/s)
-    constexpr int QB = Tr::INT ? 16 : EPV * 4;  // query bytes per corpus vector in LDS
+    constexpr int QB = S6 ? 128 : Tr::INT ? 16 : EPV * 4;  // query bytes per corpus vector in LDS (S6: per unit, both planes)
     constexpr bool NEED_XX = !QSK && ((METRIC == MVF_METRIC_COSINE) || (Tr::INT && METRIC == MVF_METRIC_L2));
     constexpr bool NEED_QQ = NEED_XX;
 
@@ -126,6 +135,7 @@ scan_stream_kernel(ScanParams p) {
     // ---- stage the queries in LDS (f32 / packed int8, zero padded) -----------
     Acc qq_part[NQ];
     float qsf[NQ], qnf[NQ];  // QSK: query scale and |q|
+    [[maybe_unused]] int64_t qbias6 = 0;  // S6: 32 sum Q
     // composites at or in front of the query's floor are not candidates (passes of a k > 1024 search); as ONE unsigned
     // compare: (comp - fl1) < (tau - fl1) with fl1 = floor + 1, which is comp < tau without a floor (fl1 = 0) and rejects
     // comp <= floor by wrapping (tau > floor always: the k-th best of the rows behind the floor, or the padding value)
@@ -143,6 +153,12 @@ scan_stream_kernel(ScanParams p) {
             const uint32_t qi = min(q0 + q, p.nq_total - 1u);  // padding lanes repeat the last query
             const bool owner = blockIdx.x == 0 && blockIdx.y == 0 && q0 + q < p.nq_total;
             float d = 0.f;
+            if constexpr (S6) {  // both planes: lo at qs, hi behind it (VP * 64 bytes each)
+                int32_t qsum = 0;
+                prep_query_16s(reinterpret_cast<const float*>(p.queries) + (size_t)qi * p.dim, p.dim, VP * EPV, METRIC, p.qstats, p.xxmax,
+                               reinterpret_cast<int8_t*>(qs), reinterpret_cast<int8_t*>(qs) + VP * EPV, prep_red, owner, &qsf[q], &qnf[q], &qsum, &d);
+                qbias6 = (int64_t)kS6Bias * qsum;
+            } else
             prep_query_i8s(reinterpret_cast<const float*>(p.queries) + (size_t)qi * p.dim, p.dim, VP * EPV, METRIC, p.qstats, p.xxmax,
                            reinterpret_cast<int8_t*>(qs + q * qstride), prep_red + (q & 1) * 12, owner, &qsf[q], &qnf[q], &d);
             if (owner && tid == 0) {
@@ -237,8 +253,10 @@ scan_stream_kernel(ScanParams p) {
                 r[u] = c0 + (g0 + u) * RPG + rsel;
                 rv[u] = r[u] < p.n;
                 rp[u] = rows + (size_t)(rv[u] ? r[u] : 0u) * p.pitch;
+                if constexpr (S6) rp[u] = rows + (size_t)((rv[u] ? r[u] : 0u) / kS6TileRows) * p.pitch + (size_t)lane * 16;  // the row's 16 bytes in plane 0 of unit 0 of its tile
             }
             Acc acc[U][NQ];
+            [[maybe_unused]] int32_t acch[U];  // S6: the high plane's sums
             Acc xx[U];
             float rs[U], rn[U];
 #pragma unroll
@@ -248,10 +266,45 @@ scan_stream_kernel(ScanParams p) {
                 if constexpr (XS) rs[u] = rv[u] ? p.xscale[r[u]] : 0.0f;
                 if constexpr (QSK && METRIC != MVF_METRIC_INNER_PRODUCT) rn[u] = rv[u] ? p.xrow[r[u]] : 0.0f;
                 xx[u] = 0;
+                acch[u] = 0;
 #pragma unroll
                 for (int q = 0; q < NQ; q++) acc[u][q] = 0;
             }
 
+            if constexpr (S6) {
+                for (uint32_t j = 0; j < p.J; j++) {
+                    u32x4 x[U][3];
+#pragma unroll
+                    for (int u = 0; u < U; u++)
+#pragma unroll
+                        for (int pl = 0; pl < 3; pl++) {
+                            x[u][pl] = u32x4{0, 0, 0, 0};
+                            if (rv[u]) x[u][pl] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rp[u] + ((size_t)j * 3 + pl) * 1024));
+                        }
+                    u32x4 ql[4], qh[4];  // the unit's 64 query elements, low and high plane: [i] = elements 16 i .. 16 i + 15
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        ql[i] = *reinterpret_cast<const u32x4*>(qs + j * 64 + i * 16);
+                        qh[i] = *reinterpret_cast<const u32x4*>(qs + VP * 64 + j * 64 + i * 16);
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; u++)
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const uint32_t p0 = x[u][0][i], p1 = x[u][1][i], p2 = x[u][2][i];
+                            const uint32_t ya = p0 & 0x3F3F3F3Fu, yb = p1 & 0x3F3F3F3Fu, yc = p2 & 0x3F3F3F3Fu;
+                            const uint32_t yd = ((p0 >> 6) & 0x03030303u) | ((p1 >> 4) & 0x0C0C0C0Cu) | ((p2 >> 2) & 0x30303030u);
+                            acc[u][0] = dot4_i8(ql[0][i], ya, acc[u][0]);
+                            acc[u][0] = dot4_i8(ql[1][i], yb, acc[u][0]);
+                            acc[u][0] = dot4_i8(ql[2][i], yc, acc[u][0]);
+                            acc[u][0] = dot4_i8(ql[3][i], yd, acc[u][0]);
+                            acch[u] = dot4_i8(qh[0][i], ya, acch[u]);
+                            acch[u] = dot4_i8(qh[1][i], yb, acch[u]);
+                            acch[u] = dot4_i8(qh[2][i], yc, acch[u]);
+                            acch[u] = dot4_i8(qh[3][i], yd, acch[u]);
+                        }
+                }
+            } else
             for (uint32_t j = 0; j < p.J; j++) {
                 const uint32_t v = j * G + sub;
                 const bool vv = v < p.V;
@@ -376,7 +429,8 @@ scan_stream_kernel(ScanParams p) {
             // ---- finish the rows: G-lane sums, score -> key, threshold filter
             auto make_key = [&](Acc s, Acc xxs, Acc qqv, float rsv, float rnv, float sqv, float qnv) __attribute__((always_inline)) -> uint32_t {
                 if constexpr (QSK) {
-                    const float dotf = (float)s * rsv * sqv;
+                    // (S6: `s` carries the bits of the f32 the exact combine of the two planes was rounded to)
+                    const float dotf = (S6 ? __int_as_float((int)s) : (float)s) * rsv * sqv;
                     float sc;
                     if constexpr (METRIC == MVF_METRIC_INNER_PRODUCT) sc = dotf;
                     else if constexpr (METRIC == MVF_METRIC_COSINE) {
@@ -573,7 +627,8 @@ scan_stream_kernel(ScanParams p) {
                     if constexpr (NEED_XX) xxs = group_sum<G>(xx[u]);
 #pragma unroll
                     for (int q = 0; q < NQ; q++) {
-                        const Acc s = group_sum<G>(acc[u][q]);
+                        Acc s = group_sum<G>(acc[u][q]);
+                        if constexpr (S6) s = (Acc)__float_as_int((float)(128ll * (int64_t)acch[u] + (int64_t)s - qbias6));  // Q.x6, exact; one rounding
                         const uint64_t comp = ((uint64_t)make_key(s, xxs, qq[q], rs[u], rn[u], qsf[q], qnf[q]) << 32) | r[u];
                         if constexpr (FLOOR) {
                             if (p.dump) {
@@ -689,10 +744,10 @@ hipError_t launch_nq(const ScanParams& p, int nq_variant, dim3 grid, size_t lds,
             return hipGetLastError();
         }
     }
-    if ((XS && !QSK) || nq_variant == 1)  // the f16-shadow unit only carries the one-query variant
+    if ((XS && !QSK) || S6 || nq_variant == 1)  // the f16-shadow and 6-bit-shadow units only carry the one-query variant
         hipLaunchKernelGGL((scan_stream_kernel<DT, METRIC, G, 1>), grid, dim3(256), lds, stream, p);
     else
-        hipLaunchKernelGGL((scan_stream_kernel<DT, METRIC, G, (XS && !QSK) ? 1 : 4>), grid, dim3(256), lds, stream, p);
+        hipLaunchKernelGGL((scan_stream_kernel<DT, METRIC, G, ((XS && !QSK) || S6) ? 1 : 4>), grid, dim3(256), lds, stream, p);
     return hipGetLastError();
 }
 
@@ -706,12 +761,14 @@ const void* kernel_ptr(int nq_variant, bool redo, bool floor) {
             return nq_variant == 1 ? reinterpret_cast<const void*>(&scan_stream_kernel<DT, METRIC, G, 1, true>)
                                    : reinterpret_cast<const void*>(&scan_stream_kernel<DT, METRIC, G, 4, true>);
     }
-    return ((XS && !QSK) || nq_variant == 1) ? reinterpret_cast<const void*>(&scan_stream_kernel<DT, METRIC, G, 1>)
-                                             : reinterpret_cast<const void*>(&scan_stream_kernel<DT, METRIC, G, (XS && !QSK) ? 1 : 4>);
+    return ((XS && !QSK) || S6 || nq_variant == 1) ? reinterpret_cast<const void*>(&scan_stream_kernel<DT, METRIC, G, 1>)
+                                                   : reinterpret_cast<const void*>(&scan_stream_kernel<DT, METRIC, G, ((XS && !QSK) || S6) ? 1 : 4>);
 }
 
 template <int DT, int METRIC>
 hipError_t launch_g(const ScanParams& p, int G, int nqv, dim3 grid, size_t lds, hipStream_t s) {
+    if constexpr (S6) return G == 1 ? launch_nq<DT, METRIC, 1>(p, nqv, grid, lds, s) : hipErrorInvalidValue;  // one lane per row only
+    else
     switch (G) {
     case 1: return launch_nq<DT, METRIC, 1>(p, nqv, grid, lds, s);
     case 4: return launch_nq<DT, METRIC, 4>(p, nqv, grid, lds, s);
@@ -724,6 +781,8 @@ hipError_t launch_g(const ScanParams& p, int G, int nqv, dim3 grid, size_t lds, 
 
 template <int DT, int METRIC>
 const void* kernel_g(int G, int nqv, bool redo, bool floor) {
+    if constexpr (S6) return kernel_ptr<DT, METRIC, 1>(nqv, redo, floor);
+    else
     switch (G) {
     case 1: return kernel_ptr<DT, METRIC, 1>(nqv, redo, floor);
     case 4: return kernel_ptr<DT, METRIC, 4>(nqv, redo, floor);
@@ -736,7 +795,9 @@ const void* kernel_g(int G, int nqv, bool redo, bool floor) {
 
 }  // namespace
 
-#if MVF_SCAN_XS
+#if MVF_SCAN_XS == 2
+#define MVF_SCAN_FN2(name, dt) name##dt##y
+#elif MVF_SCAN_XS
 #define MVF_SCAN_FN2(name, dt) name##dt##x
 #else
 #define MVF_SCAN_FN2(name, dt) name##dt

@@ -92,6 +92,36 @@ def stream_rows(rows: int, dim: int, data_type: int, metric: int, nq: int, k: in
     return out.value
 
 
+def stream_bits(rows: int, dim: int, data_type: int, metric: int, nq: int, k: int) -> int:
+    """Which rows ONE search on scan path 0 streams: 0 the stored rows, 8 the int8 shadow, 6 the 6-bit shadow -- the shape part
+    of the rule, default tuning; `mvfgpu_selftest_stream_bits`; no GPU needed."""
+    out = C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_stream_bits(rows, dim, data_type, metric, nq, k, C.byref(out)))
+    return out.value
+
+
+def shadow6_bytes(rows: int, dim: int) -> int:
+    """Bytes of the 6-bit shadow of `rows` x `dim` (64-row tiles of 64-element units: csrc/shadow_6b.h); no GPU needed."""
+    return int(_lib.gpu().mvfgpu_selftest_shadow6_bytes(rows, dim))
+
+
+def shadow6_pack(codes: np.ndarray) -> np.ndarray:
+    """`codes` (rows x dim int8 in [-31, 31]) in the 6-bit shadow's layout, as the build kernel packs them; no GPU needed."""
+    codes = np.ascontiguousarray(codes, dtype=np.int8)
+    rows, dim = codes.shape
+    out = np.empty(shadow6_bytes(rows, dim), np.uint8)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_shadow6_pack(codes.ctypes.data, rows, dim, out.ctypes.data, out.size))
+    return out
+
+
+def shadow6_unpack(shadow: np.ndarray, rows: int, dim: int) -> np.ndarray:
+    """The codes (rows x dim int8) held by a 6-bit shadow; no GPU needed."""
+    shadow = np.ascontiguousarray(shadow, dtype=np.uint8)
+    out = np.empty((rows, dim), np.int8)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_shadow6_unpack(shadow.ctypes.data, shadow.size, rows, dim, out.ctypes.data))
+    return out
+
+
 def filter_route(rows: int, dim: int, data_type: int, nq: int, k: int, admitted: int) -> int:
     """1: a filtered search of this shape takes the mask route (the plain search's kernels under the filter's deny mask),
     2: the list route (only the admitted rows are read) -- default tuning; `mvfgpu_selftest_filter_route`; no GPU needed."""
