@@ -767,7 +767,7 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * only adds mvfgpu_search_candidates and mvfgpu_search_candidates_device, nor did the k-NN join, which only adds mvfgpu_knn_join and
  * mvfgpu_knn_join_device, nor did the filtered search, which only adds mvfgpu_filter_*, mvfgpu_search_filtered,
  * mvfgpu_search_filtered_device and mvfgpu_selftest_filter_route, nor did the metadata columns, which only add mvfgpu_column_*,
- * mvfgpu_filter_create_where, mvfgpu_selftest_predicate_range and mvfgpu_selftest_where_kernel_ms).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * mvfgpu_filter_create_where, mvfgpu_selftest_predicate_range and mvfgpu_selftest_where_kernel_ms, nor did mvfgpu_selftest_poison).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u
@@ -828,6 +828,14 @@ int mvfgpu_selftest_shadow6_unpack(const uint8_t* shadow, uint64_t shadow_bytes,
  */
 int mvfgpu_selftest_schedule(uint64_t rows, uint32_t nq, uint32_t k, int int8_selection, uint64_t* out_bounds, uint32_t max_bounds,
                              uint32_t* out_n_bounds, uint32_t* out_growth, uint32_t* out_refined_mask);
+
+/*
+ * The debug switch MVF_DEBUG_POISON=<0..255> as this process read it (no GPU needed): the byte every allocation of the library
+ * is filled with before its first use, or -1 when the variable is unset, not a number or out of range (nothing is filled then).
+ * Read once per process, at the first allocation or the first call of this function.  Tests start a child process with the
+ * variable set and assert through this that the child really ran poisoned ("Poisoned allocations").
+ */
+int mvfgpu_selftest_poison(void);
 
 #ifdef __cplusplus
 }

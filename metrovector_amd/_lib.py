@@ -213,6 +213,10 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_shadow6_pack.restype = C.c_int
     lib.mvfgpu_selftest_shadow6_unpack.argtypes = [vp, u64, u64, u32, vp]
     lib.mvfgpu_selftest_shadow6_unpack.restype = C.c_int
+    poison = getattr(lib, "mvfgpu_selftest_poison", None)  # added within ABI 3 as well: a diagnostic entry point
+    if poison is not None:
+        poison.argtypes = []
+        poison.restype = C.c_int
     sched = getattr(lib, "mvfgpu_selftest_schedule", None)  # added within ABI 3 (round 5): a diagnostic entry point, no layout changed
     if sched is not None:
         sched.argtypes = [u64, u32, u32, C.c_int, vp, u32, vp, vp, vp]

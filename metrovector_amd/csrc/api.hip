@@ -47,7 +47,7 @@ struct DevBuf {
         p = nullptr;
         bytes = 0;
         hipError_t e = hipMalloc(&p, need);
-        if (e == hipSuccess) bytes = need;
+        if (e == hipSuccess) bytes = need, e = poison_fill(p, need);
         return e;
     }
     void release() {
@@ -69,7 +69,7 @@ struct PinBuf {
         bytes = 0;
         need = (need + 4095) & ~(size_t)4095;
         hipError_t e = hipHostMalloc(&p, need, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = need;
+        if (e == hipSuccess) bytes = need, poison_fill_host(p, need);
         return e;
     }
     void release() {
@@ -83,6 +83,36 @@ struct PinBuf {
 
 namespace mvf {
 int set_fail(int status, const std::string& msg) { return fail(status, msg); }
+
+hipError_t scratch_pool(hipMemPool_t* out) {
+    constexpr int kMaxDevices = 64;
+    static std::mutex mu;
+    static hipMemPool_t pools[kMaxDevices] = {};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!pools[dev]) {
+        hipMemPoolProps props{};
+        props.allocType = hipMemAllocationTypePinned;
+        props.handleTypes = hipMemHandleTypeNone;
+        props.location.type = hipMemLocationTypeDevice;
+        props.location.id = dev;
+        hipMemPool_t pool = nullptr;
+        e = hipMemPoolCreate(&pool, &props);
+        if (e != hipSuccess) return e;
+        uint64_t keep = ~0ull;  // never trimmed at a synchronisation
+        e = hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
+        if (e != hipSuccess) {
+            (void)hipMemPoolDestroy(pool);
+            return e;
+        }
+        pools[dev] = pool;
+    }
+    *out = pools[dev];
+    return hipSuccess;
+}
 
 Tuning read_tuning() {
     Tuning t;
@@ -306,6 +336,7 @@ int alloc_rows(mvfgpu_corpus* c) {
     choose_group(c->V, 1, &c->G, &c->J, c->tune.k1_g);
     c->rows_bytes = (size_t)c->n * c->pitch;
     if (c->rows_bytes) MVF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_rows), c->rows_bytes));
+    MVF_HIP_TRY(poison_fill(c->d_rows, c->rows_bytes));  // the upload and repack_rows write every byte, the pitch padding included
     return MVF_OK;
 }
 
@@ -941,6 +972,7 @@ void qs_feedback_poll(const mvfgpu_corpus* c) {
 int feedback_slots(const mvfgpu_corpus* c) {
     if (c->qs_redo_host) return MVF_OK;
     MVF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->qs_redo_host), 64, hipHostMallocDefault));
+    poison_fill_host(c->qs_redo_host, 64);
     return MVF_OK;
 }
 
@@ -2015,9 +2047,15 @@ int upload_rows(mvfgpu_corpus* c, const void* rows, uint64_t stride, const mvfgp
     for (auto& e : ev.e) MVF_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const uint64_t span_max = (std::min(chunk_rows, n) - 1) * stride + row_bytes;  // bytes of one chunk as it lies
     if (!direct && !sparse)
-        for (auto& q : stage.p) MVF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q), span_max));
+        for (auto& q : stage.p) {
+            MVF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q), span_max));
+            MVF_HIP_TRY(poison_fill(q, span_max));
+        }
     if (pinned)
-        for (auto& q : pin.p) MVF_HIP_TRY(hipHostMalloc(&q, span_max, hipHostMallocDefault));
+        for (auto& q : pin.p) {
+            MVF_HIP_TRY(hipHostMalloc(&q, span_max, hipHostMallocDefault));
+            poison_fill_host(q, span_max);
+        }
     if (sparse && c->pitch != row_bytes) MVF_HIP_TRY(hipMemsetAsync(c->d_rows, 0, c->rows_bytes, s_copy));  // the 16-B padding
     unsigned threads = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
     if (c->tune.upload_threads) threads = c->tune.upload_threads;
@@ -2122,6 +2160,7 @@ int search_sorted_k(const mvfgpu_corpus* c, SearchCall& sc, bool* no_room) {
         if (2 * bytes + tmp_bytes > kKeep) {
             void* scratch = nullptr;
             if (hipMallocAsync(&scratch, 2 * bytes + tmp_bytes, s) == hipSuccess) {
+                MVF_HIP_TRY(poison_fill(scratch, 2 * bytes + tmp_bytes, s));
                 ra.nqv = nqv;
                 ra.a = static_cast<uint64_t*>(scratch);
                 ra.b = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(scratch) + bytes);
@@ -3000,6 +3039,7 @@ int merge_topk_device_impl(const float* d_scores, const uint64_t* d_indices, con
     const size_t cb = ((size_t)total * 8 + 255) & ~(size_t)255;
     void* scratch = nullptr;
     MVF_HIP_TRY(hipMallocAsync(&scratch, 2 * cb + tmp_bytes, s));
+    MVF_HIP_TRY(poison_fill(scratch, 2 * cb + tmp_bytes, s));
     uint64_t *a = static_cast<uint64_t*>(scratch), *b = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(scratch) + cb);
     void* tmp = static_cast<unsigned char*>(scratch) + 2 * cb;
     hipError_t e = hipSuccess;
@@ -3144,6 +3184,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* c) {
     choose_group(c->V, 1, &c->G, &c->J, c->tune.k1_g);
     return MVF_OK;
 }
+
+int mvfgpu_selftest_poison(void) { return mvf::debug_poison_byte(); }
 
 uint32_t mvfgpu_abi_version(void) { return MVFGPU_ABI_VERSION; }
 

@@ -47,6 +47,7 @@ void free_column(mvfgpu_column* col) {
 int alloc_column(mvfgpu_column* col) {
     col->device_bytes = (size_t)col->rows * column_elem_size(col->dtype);
     MVF_HIP_TRY(hipMalloc(&col->values, std::max<size_t>(col->device_bytes, 16)));
+    MVF_HIP_TRY(poison_fill(col->values, std::max<size_t>(col->device_bytes, 16)));
     return MVF_OK;
 }
 

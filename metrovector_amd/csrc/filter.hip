@@ -53,6 +53,7 @@ int build_filter(mvfgpu_filter* f, const CorpusView& v, const uint32_t* d_allow,
     const size_t words = (size_t)((n + 31) / 32) + 1;
     const uint32_t nb = filter_blocks(n);
     MVF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f->deny), words * 4));
+    MVF_HIP_TRY(poison_fill(f->deny, words * 4));
     f->device_bytes = words * 4;
     AsyncBuf cnt, off, tot;
     MVF_HIP_TRY(cnt.alloc((size_t)nb * 4, s));
@@ -74,6 +75,7 @@ int build_filter(mvfgpu_filter* f, const CorpusView& v, const uint32_t* d_allow,
     const bool want_list = f->forced_route == 2 || (f->forced_route == 0 && list_possible(n, v.dim, v.dtype, admitted));
     if (want_list && admitted > 0) {
         MVF_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f->list), (size_t)admitted * 4));
+        MVF_HIP_TRY(poison_fill(f->list, (size_t)admitted * 4));
         f->device_bytes += (size_t)admitted * 4;
         MVF_HIP_TRY(filter_compact_launch(f->deny, n, static_cast<const uint64_t*>(off.p), f->list, s));
     }

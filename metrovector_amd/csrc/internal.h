@@ -7,6 +7,7 @@
 #include "scan_stream.h"
 
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -48,13 +49,59 @@ struct DevScope {
     }
 };
 
+// MVF_DEBUG_POISON=<0..255> (debug only; DESIGN.md §2 "Poisoned allocations"): every allocation the library makes is filled
+// with that byte before its first use, so that a test can tell whether an answer depends on memory nobody wrote.  Read ONCE
+// per process -- not per handle, not through Tuning: AsyncBuf has no handle, and nothing on the per-search path calls getenv.
+// -1 = unset (or not a number in 0..255): one predictable branch per allocation.
+inline int debug_poison_byte() {
+    static const int byte = [] {
+        const char* e = getenv("MVF_DEBUG_POISON");
+        if (!e || !*e) return -1;
+        char* end = nullptr;
+        const long v = strtol(e, &end, 0);
+        return (*end || v < 0 || v > 255) ? -1 : (int)v;
+    }();
+    return byte;
+}
+// The fill itself, directly behind the allocation; explicit initialisations stay where they are and run after it.
+// stream-ordered memory: on the allocation's own stream
+inline hipError_t poison_fill(void* p, size_t bytes, hipStream_t s) {
+    const int b = debug_poison_byte();
+    return (b < 0 || !p || !bytes) ? hipSuccess : hipMemsetAsync(p, b, bytes, s);
+}
+// hipMalloc memory: a synchronous fill and a host wait (a poisoned run tests dependence on CONTENT, not on timing)
+inline hipError_t poison_fill(void* p, size_t bytes) {
+    const int b = debug_poison_byte();
+    if (b < 0 || !p || !bytes) return hipSuccess;
+    const hipError_t e = hipMemset(p, b, bytes);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+// pinned host memory
+inline void poison_fill_host(void* p, size_t bytes) {
+    const int b = debug_poison_byte();
+    if (b >= 0 && p && bytes) memset(p, b, bytes);
+}
+
+// The stream-ordered pool the library's scratch comes from: its own pool on the calling thread's current device, created on
+// first use and kept for the life of the process, which never hands memory back to the OS between calls.  The device's DEFAULT
+// pool releases everything unused at every synchronisation, so each call's scratch was memory fresh from the OS -- and under
+// the platform's HIP runtime a kernel's stores into such memory were intermittently lost to the next kernel on the same
+// stream (zeros read back: an all-padding or all-NaN answer from the filter's list route, an admitted count of 0;
+// profiles/r13_fresh_process.txt).  A pool that keeps its memory also spares every search the OS allocation.  What it holds
+// is bounded by the largest scratch a call takes (the 512-MiB windows of scan_gather.hip, the radius lists).
+hipError_t scratch_pool(hipMemPool_t* out);
+
 // stream-ordered scratch, released on every way out
 struct AsyncBuf {
     void* p = nullptr;
     hipStream_t s = nullptr;
     hipError_t alloc(size_t bytes, hipStream_t st) {
         s = st;
-        return bytes ? hipMallocAsync(&p, bytes, st) : hipSuccess;
+        if (!bytes) return hipSuccess;
+        hipMemPool_t pool = nullptr;
+        hipError_t e = scratch_pool(&pool);
+        if (e == hipSuccess) e = hipMallocFromPoolAsync(&p, bytes, pool, st);
+        return e != hipSuccess ? e : poison_fill(p, bytes, st);
     }
     ~AsyncBuf() {
         if (p) (void)hipFreeAsync(p, s);

@@ -29,7 +29,11 @@ constexpr size_t kPinnedWindowBytes = 64ull << 20;  // a window's results up to 
 
 struct PinnedBuf {
     void* p = nullptr;
-    hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes, hipHostMallocDefault); }
+    hipError_t alloc(size_t bytes) {
+        const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) poison_fill_host(p, bytes);
+        return e;
+    }
     ~PinnedBuf() {
         if (p) (void)hipHostFree(p);
     }

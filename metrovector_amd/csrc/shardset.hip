@@ -89,7 +89,7 @@ struct DevBuf {
         bytes = 0;
         dev = device;
         hipError_t e = hipMalloc(&p, need);
-        if (e == hipSuccess) bytes = need;
+        if (e == hipSuccess) bytes = need, e = mvf::poison_fill(p, need);
         return e;
     }
     void release() {
@@ -130,7 +130,7 @@ struct mvfgpu_shardset {
         *have = 0;
         need = (need + 4095) & ~(size_t)4095;
         hipError_t e = hipHostMalloc(p, need, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent);  // coherent like api.hip's PinBuf: kernels on every device read / write it in place
-        if (e == hipSuccess) *have = need;
+        if (e == hipSuccess) *have = need, mvf::poison_fill_host(*p, need);
         return e;
     }
     mvfgpu_shardset_timing tm{};

@@ -100,6 +100,12 @@ def stream_bits(rows: int, dim: int, data_type: int, metric: int, nq: int, k: in
     return out.value
 
 
+def selftest_poison() -> int:
+    """The byte MVF_DEBUG_POISON makes this process fill every allocation of the library with before its first use, or -1
+    where the switch is unset -- `mvfgpu_selftest_poison`; no GPU needed."""
+    return int(_lib.gpu().mvfgpu_selftest_poison())
+
+
 def shadow6_bytes(rows: int, dim: int) -> int:
     """Bytes of the 6-bit shadow of `rows` x `dim` (64-row tiles of 64-element units: csrc/shadow_6b.h); no GPU needed."""
     return int(_lib.gpu().mvfgpu_selftest_shadow6_bytes(rows, dim))

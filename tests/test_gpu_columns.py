@@ -14,6 +14,7 @@ import metrovector_amd as M
 from metrovector_amd import errors as E
 from metrovector_amd import gpu as G
 
+from _children import RUNNER
 from _columns import OPS, TOP, U32, U64, edge_values, odd_address, where_mask
 from _filtered import PAD
 
@@ -372,6 +373,28 @@ def test_cpp_find_top_k_where(tmp_path):
     out = subprocess.run(cmd, capture_output=True, text=True)
     assert out.returncode == 0, out.stderr
     out = subprocess.run([exe, str(tmp_path / "where.mvf")], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = out.stdout.splitlines()
+    assert lines[0].split() == ["20:1.0", "25:4.0", "30:9.0", "35:14.0"]
+    assert lines[1] == "8"                       # 20, 25, .., 55
+    assert lines[2] == str(24 + 40 - 16)         # tenant in {1, 4}: 24 rows; ts >= 1020: 40 rows; both: 16
+    assert lines[3] == "short column refused" and lines[4] == "4"
+
+
+@pytest.mark.parametrize("poison", [None, 0x00, 0xFF])
+def test_cpp_find_top_k_where_with_poisoned_allocations(tmp_path, poison):
+    """The same executable, its process started with every allocation of the library filled with a byte before its first use
+    (MVF_DEBUG_POISON): the answer does not depend on what the memory held."""
+    src, exe = tmp_path / "where.cpp", str(tmp_path / "where_cpp")
+    src.write_text(_CPP)
+    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
+           "-L", LIBDIR, "-lmvf_gpu", "-lmvf_host", f"-Wl,-rpath,{LIBDIR}", "-o", exe]
+    out = subprocess.run(cmd, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    env = {k: v for k, v in os.environ.items() if k != "MVF_DEBUG_POISON"}
+    if poison is not None:
+        env["MVF_DEBUG_POISON"] = str(poison)
+    out = RUNNER.run([exe, str(tmp_path / "where.mvf")], env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = out.stdout.splitlines()
     assert lines[0].split() == ["20:1.0", "25:4.0", "30:9.0", "35:14.0"]

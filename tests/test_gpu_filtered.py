@@ -12,6 +12,7 @@ import pytest
 from metrovector_amd import errors as E
 from metrovector_amd import gpu as G
 
+from _children import RUNNER
 from _filtered import PAD, admitted_mask, assert_float_filtered, device_words, mask_patterns, oracle_filtered, shard_bitmap
 from _util import assert_exact
 
@@ -450,6 +451,26 @@ def test_cpp_find_top_k_filtered(tmp_path):
     out = subprocess.run(cmd, capture_output=True, text=True)
     assert out.returncode == 0, out.stderr
     out = subprocess.run([exe, str(tmp_path / "filtered.mvf")], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = out.stdout.splitlines()
+    assert lines[0].split() == ["20:1.0", "25:4.0", "15:6.0", "30:9.0"]
+    assert lines[1] == "12" and lines[2] == "short query refused" and lines[3] == "short bitmap refused"
+
+
+@pytest.mark.parametrize("poison", [None, 0x00, 0xFF])
+def test_cpp_find_top_k_filtered_with_poisoned_allocations(tmp_path, poison):
+    """The same executable, its process started with every allocation of the library filled with a byte before its first use
+    (MVF_DEBUG_POISON): the answer does not depend on what the memory held."""
+    src, exe = tmp_path / "filtered.cpp", str(tmp_path / "filtered_cpp")
+    src.write_text(_CPP)
+    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
+           "-L", LIBDIR, "-lmvf_gpu", "-lmvf_host", f"-Wl,-rpath,{LIBDIR}", "-o", exe]
+    out = subprocess.run(cmd, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    env = {k: v for k, v in os.environ.items() if k != "MVF_DEBUG_POISON"}
+    if poison is not None:
+        env["MVF_DEBUG_POISON"] = str(poison)
+    out = RUNNER.run([exe, str(tmp_path / "filtered.mvf")], env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = out.stdout.splitlines()
     assert lines[0].split() == ["20:1.0", "25:4.0", "15:6.0", "30:9.0"]
