@@ -57,12 +57,37 @@ def boundary_band(metric, all_scores, rows_f32, q_f32, kk):
     return key, kth, 2 * btol
 
 
+def order_key(metric, scores):
+    """(nan, key) of DESIGN.md §3 "Order", written from its words and not from the library's u32 key: `key` ascends
+    best-first -- L2 ascending, InnerProduct / Cosine descending, -0.0 == +0.0 (float comparison already says so) -- and a NaN
+    score (nan = True, key 0) comes behind every other score, +inf and -inf included."""
+    s = np.asarray(scores, np.float64)
+    nan = np.isnan(s)
+    key = np.where(nan, 0.0, s if metric == 0 else -s) + 0.0
+    return nan, key
+
+
+def first_out_of_order(metric, scores, positions):
+    """Rank r >= 1 of the first entry that does not come STRICTLY behind its predecessor in (order key of the score, row
+    position), NaN last -- None where the whole list ascends.  Equal keys in descending (or equal) position are out of order."""
+    nan, key = order_key(metric, scores)
+    pos = np.asarray(positions).astype(np.int64)
+    if len(key) < 2:
+        return None
+    a_nan, b_nan, a, b = nan[:-1], nan[1:], key[:-1], key[1:]
+    ok = (~a_nan & b_nan) | ((a_nan == b_nan) & ((a < b) | ((a == b) & (pos[:-1] < pos[1:]))))
+    bad = np.nonzero(~ok)[0]
+    return int(bad[0]) + 1 if bad.size else None
+
+
 def assert_float_topk(metric, got_scores, got_idx, all_scores, rows_f32, q_f32, k, index_base=0):
     """GPU top-k of ONE query vs the oracle's score of every row.
 
     all_scores: the reference's score per local row (the oracle's f32, or float64: tests/_wide.py).  Checks: padding, uniqueness,
-    per-entry score within tolerance, best-first order, and set equality up to
-    rows whose oracle score is within tolerance of the k-th best."""
+    per-entry score within tolerance (L2: a +inf / NaN reference score is returned as +inf / NaN; InnerProduct and Cosine are
+    exempt there, DESIGN.md §3 "Tolerance"), the whole list -- non-finite scores included -- strictly ascending in (order
+    key, position) with NaN last, and set equality up to rows whose oracle score is within tolerance of the k-th best.
+    got_idx holds positions (or a monotone remapping of them: ties are ordered by it)."""
     n = len(all_scores)
     kk = min(k, n)
     got_idx = np.asarray(got_idx)
@@ -77,10 +102,13 @@ def assert_float_topk(metric, got_scores, got_idx, all_scores, rows_f32, q_f32, 
     tol = score_tolerance(metric, ref, rows_f32, q_f32, li)
     fin = np.isfinite(ref)
     assert (np.abs(sc[fin] - ref[fin]) <= tol[fin]).all(), f"score mismatch max={np.max(np.abs(sc[fin]-ref[fin]))}"
-    sign = 1.0 if metric == 0 else -1.0
-    order = sign * sc
-    finite_order = order[np.isfinite(order)]
-    assert (np.diff(finite_order) >= 0).all(), "not sorted best-first"
+    if metric == 0:
+        inf, nan = np.isposinf(ref), np.isnan(ref)
+        assert np.isposinf(sc[inf]).all(), f"L2 beyond the f32 range is not +inf: {sc[inf][~np.isposinf(sc[inf])][:5]}"
+        assert np.isnan(sc[nan]).all(), f"L2 of a NaN row is not NaN: {sc[nan][~np.isnan(sc[nan])][:5]}"
+    r = first_out_of_order(metric, got_scores[:kk], li)
+    assert r is None, (f"not sorted best-first, ties by position, NaN last: rank {r - 1} = (score {got_scores[r - 1]!r}, row "
+                       f"{li[r - 1]}), rank {r} = (score {got_scores[r]!r}, row {li[r]})")
     # set equality modulo near-ties at the boundary
     key, kth, btol = boundary_band(metric, all_scores, rows_f32, q_f32, kk)
     must = set(np.nonzero(key < kth - btol)[0].tolist())
