@@ -56,6 +56,24 @@ pub struct MvfGpuPredicate {
     pub values: *const u64,
 }
 
+/// Opaque `mvfgpu_partition` and its `mvfgpu_partition_info` out-struct (include/mvf_gpu.h, "partitioned search").
+#[repr(C)]
+pub struct MvfGpuPartition {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct MvfGpuPartitionInfo {
+    pub struct_size: u32,
+    pub key_type: u8,
+    pub reserved: [u8; 3],
+    pub rows: u64,
+    pub live_rows: u64,
+    pub n_keys: u64,
+    pub largest: u64,
+    pub device_bytes: u64,
+    pub host_bytes: u64,
+}
+
 #[link(name = "mvf_gpu")]
 extern "C" {
     fn mvfgpu_corpus_create(rows: *const c_void, n: u64, dimension: u32, data_type: u8, stride_bytes: u64,
@@ -110,6 +128,21 @@ extern "C" {
     fn mvfgpu_column_get_info(column: *const MvfGpuColumn, out: *mut MvfGpuColumnInfo) -> c_int;
     fn mvfgpu_filter_create_where(corpus: *const MvfGpuCorpus, clauses: *const MvfGpuPredicate, n_clauses: u32, combine: u32,
                                   base: *const MvfGpuFilter, out: *mut *mut MvfGpuFilter) -> c_int;
+    /// Partitioned search (include/mvf_gpu.h, DESIGN.md section 3 "Partitioned search"): the live rows grouped by a column's
+    /// value, and the top-k of every query among the rows that carry the query's own key (`keys`: host, one per query).
+    fn mvfgpu_partition_create(corpus: *const MvfGpuCorpus, column: *const MvfGpuColumn, out: *mut *mut MvfGpuPartition) -> c_int;
+    fn mvfgpu_partition_destroy(partition: *mut MvfGpuPartition);
+    fn mvfgpu_partition_get_info(partition: *const MvfGpuPartition, out: *mut MvfGpuPartitionInfo) -> c_int;
+    fn mvfgpu_partition_lookup(partition: *const MvfGpuPartition, keys: *const u64, n: u64, out_counts: *mut u64) -> c_int;
+    fn mvfgpu_partition_keys(partition: *const MvfGpuPartition, first: u64, count: u64, out_keys: *mut u64,
+                             out_counts: *mut u64) -> c_int;
+    fn mvfgpu_search_partitioned(corpus: *const MvfGpuCorpus, partition: *const MvfGpuPartition, metric: u8,
+                                 queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, keys: *const u64, k: u32,
+                                 out_scores: *mut f32, out_indices: *mut u64, out_raw: *mut i32) -> c_int;
+    fn mvfgpu_search_partitioned_device(corpus: *const MvfGpuCorpus, partition: *const MvfGpuPartition, metric: u8,
+                                        d_queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, keys: *const u64,
+                                        k: u32, d_scores: *mut f32, d_indices: *mut u64, d_raw: *mut i32,
+                                        hip_stream: *mut c_void) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;
     /// `MVFGPU_ABI_VERSION` of the loaded library (include/mvf_gpu.h): struct layouts and signatures this file mirrors.
     fn mvfgpu_abi_version() -> u32;

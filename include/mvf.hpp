@@ -450,6 +450,41 @@ public:
         for (size_t i = 0; i < k && idx[i] != ~0ull; i++) out.push_back({idx[i], scores[i], {}});
         return out;
     }
+    // The top-k of every query among the vectors whose value in `column` equals the query's own key (mvfgpu_partition_create,
+    // mvfgpu_search_partitioned; DESIGN.md section 3, "Partitioned search"): queries.size() / dimension queries, one key each; a
+    // key no live vector carries gives an empty list.  The column holds one UInt32 / UInt64 value per vector of the space
+    // (Build error otherwise).  The column and the index live for this call; the payload is not fetched.
+    std::vector<std::vector<ScoredVector>> find_top_k_per_key(const std::vector<float>& queries, const std::vector<uint64_t>& keys, size_t k,
+                                                              const MetadataColumn& column) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "find_top_k_per_key takes f32 queries: Float32 / Float16 spaces");
+        const size_t nq = keys.size();
+        if (queries.size() != nq * (size_t)dim_) throw MvfError(MVF_ERR_DIMENSION_MISMATCH, "find_top_k_per_key takes one key per query");
+        std::vector<std::vector<ScoredVector>> out(nq);
+        if (k == 0 || nq == 0) return out;
+        mvfgpu_corpus_info inf;
+        MVFGPU_INIT(inf);
+        detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+        const uint64_t es = column.data_type == MVF_DTYPE_UINT32 ? 4 : column.data_type == MVF_DTYPE_UINT64 ? 8 : 0;
+        if (!es || column.size / es < inf.rows)
+            throw MvfError(MVF_ERR_BUILD, es ? "metadata column '" + column.name + "' holds fewer values than the space has vectors"
+                                             : "Unsupported metadata column data type");
+        mvfgpu_column* col = nullptr;
+        mvfgpu_partition* part = nullptr;
+        std::vector<float> scores(nq * k);
+        std::vector<uint64_t> idx(nq * k);
+        int rc = mvfgpu_column_create(c_, column.data, column.data_type, 0, column.size / es, &col);
+        if (rc == MVF_OK) rc = mvfgpu_partition_create(c_, col, &part);
+        if (rc == MVF_OK)
+            rc = mvfgpu_search_partitioned(c_, part, (uint8_t)metric_, queries.data(), MVF_DTYPE_FLOAT32, dim_, (uint32_t)nq, keys.data(),
+                                           (uint32_t)k, scores.data(), idx.data(), nullptr);
+        mvfgpu_partition_destroy(part);
+        mvfgpu_column_destroy(col);
+        detail::check_gpu(rc);
+        for (size_t i = 0; i < nq; i++)
+            for (size_t j = 0; j < k && idx[i * k + j] != ~0ull; j++) out[i].push_back({idx[i * k + j], scores[i * k + j], {}});
+        return out;
+    }
     // The k-NN graph (mvfgpu_knn_join; DESIGN.md section 3, "Join"): for each of the rows [first, first + count) -- count
     // UINT64_MAX: to the end of the space -- its k nearest OTHER rows under the space's metric, best first.  A row is never its
     // own neighbour (decided by position: its exact duplicates are); a deleted row gets an empty list; fewer than k live

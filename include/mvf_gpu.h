@@ -440,7 +440,8 @@ int mvfgpu_search_candidates_device(const mvfgpu_corpus* corpus, uint8_t metric,
  *   list : only the admitted rows are read, once per group of up to 4 queries, with the streaming kernel's one-query arithmetic.
  * A filtered search leaves the handle's later plain searches as they were: it may build what a plain search builds (norms,
  * shadows), but it neither reads nor feeds the repair feedback (mvfgpu_corpus_info::selection_state stays).
- * Per-query filters are not an API: a filter serves every query of its call -- one call per filter.  Radius, candidate, join
+ * Per-query filters are not an API: a filter serves every query of its call -- one call per filter (one KEY per query: the
+ * partitioned search below).  Radius, candidate, join
  * and fetch calls take no filter (a candidate list already is one; gather rows afterwards).
  */
 typedef struct mvfgpu_filter mvfgpu_filter;
@@ -555,6 +556,72 @@ typedef struct mvfgpu_predicate {
 
 int mvfgpu_filter_create_where(const mvfgpu_corpus* corpus, const mvfgpu_predicate* clauses, uint32_t n_clauses,
                                uint32_t combine, const mvfgpu_filter* base, mvfgpu_filter** out);
+
+/* ---- partitioned search: one key per query ------------------------------------ */
+
+/*
+ * A partition index: the rows of ONE corpus handle that are live when it is created, grouped by the value of ONE device column
+ * (UInt32 or UInt64), the rows of a group in ascending position ("Partitioned search").  Built once, on
+ * the device; immutable; used by any number of searches from any thread; destroyed before its corpus.  It does not refer to
+ * the column after creation, which -- like a filter's -- waits on the host (twice).  Like a filter it is bound to the handle's
+ * tombstone generation: a partition of an older generation -- or of another handle -- is refused by the searches, before any
+ * device call, with MVF_ERR_INVALID_ARGUMENT and a message naming the cause; create a new one.  A column of another handle is
+ * refused at creation like a where-clause's.  device memory: 4 bytes per live row + 16 bytes per distinct key (+ 8); the key
+ * table is mirrored on the host (host_bytes), and lookup / keys / the searches' plans read the mirror: no device work.
+ * mvfgpu_partition_destroy (NULL is allowed) waits for the handle's newest work.
+ *
+ * mvfgpu_search_partitioned / mvfgpu_search_partitioned_device are mvfgpu_search / mvfgpu_search_device with one key per query:
+ * the result row of query q is the exact top-k among the live rows whose column value, zero-extended to 64 bits, equals keys[q]
+ * (unsigned 64-bit comparison: a key of 2^32 or more matches nothing on a UInt32 column, as in mvfgpu_filter_create_where).
+ * Arguments, checks, error codes, order (best first, ties by ascending position, NaN last), padding, ids and index_base,
+ * out_raw, k up to MVFGPU_MAX_K and the stream discipline are mvfgpu_search's; NULL `keys` is MVF_ERR_INVALID_ARGUMENT.  A key
+ * no live row carries gives a row of padding.  `keys` is a HOST array in both calls, read before the call returns.  Every
+ * score is the one a one-query mvfgpu_search on the stored rows reports for that (query, row) -- the candidate search's rule --
+ * so query q's row equals, byte for byte, the row of mvfgpu_search_candidates for a list of exactly the rows with that key,
+ * and what mvfgpu_search_filtered returns for that one query through mvfgpu_filter_create_where(column == keys[q]) of the same
+ * tombstone generation.  No search waits on the host (but, where searches pile up, for the previous search's 12-byte-per-query
+ * plan to have left the index's pinned buffer).
+ * Cost: keys of up to 1024 live rows (and k <= MVFGPU_K_PER_PASS) share a fixed number of launches per 1024 queries whatever
+ * the number of keys; every other distinct key of the batch costs what a filtered search by the list route costs.  A key that
+ * holds a large share of the rows is served faster by a filter and mvfgpu_search_filtered (`largest` shows such keys).
+ * Radius, candidate, join and shard-set calls take no partition; keys in device memory are not an API.
+ */
+typedef struct mvfgpu_partition mvfgpu_partition;
+
+typedef struct mvfgpu_partition_info {
+    uint32_t struct_size;   /* in: sizeof(mvfgpu_partition_info); out: bytes filled */
+    uint8_t key_type;       /* MVF_DTYPE_UINT32 or MVF_DTYPE_UINT64 */
+    uint8_t reserved[3];
+    uint64_t rows;          /* rows of the handle */
+    uint64_t live_rows;     /* rows the index holds (not deleted at creation) */
+    uint64_t n_keys;        /* distinct values among them */
+    uint64_t largest;       /* rows of the largest partition */
+    uint64_t device_bytes;  /* 4 B per live row + the key table */
+    uint64_t host_bytes;    /* the host mirror of the key table */
+} mvfgpu_partition_info;
+
+int mvfgpu_partition_create(const mvfgpu_corpus* corpus, const mvfgpu_column* column, mvfgpu_partition** out);
+void mvfgpu_partition_destroy(mvfgpu_partition* partition);
+int mvfgpu_partition_get_info(const mvfgpu_partition* partition, mvfgpu_partition_info* out);
+/* no device work: out_counts[i] = live rows carrying keys[i] (0 for an unknown key) */
+int mvfgpu_partition_lookup(const mvfgpu_partition* partition, const uint64_t* keys, uint64_t n, uint64_t* out_counts);
+/* the distinct keys in ascending order with their row counts, [first, first + count) of n_keys: the column's group-by */
+int mvfgpu_partition_keys(const mvfgpu_partition* partition, uint64_t first, uint64_t count, uint64_t* out_keys,
+                          uint64_t* out_counts);
+int mvfgpu_search_partitioned(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                              const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                              const uint64_t* keys, uint32_t k, float* out_scores, uint64_t* out_indices, int32_t* out_raw);
+int mvfgpu_search_partitioned_device(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                     const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                                     const uint64_t* keys, uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw,
+                                     void* hip_stream);
+/*
+ * Self-test of a partitioned search's plan (no GPU needed): for queries whose keys hold counts[q] live rows, out_tier[q] =
+ * 0 (padding), 1 (small tier: count <= 1024 and k <= MVFGPU_K_PER_PASS) or 2 (large tier), and *out_groups = the large tier's
+ * distinct keys -- the gathered searches the call makes.
+ */
+int mvfgpu_selftest_partition_plan(const uint64_t* counts, const uint64_t* keys, uint32_t nq, uint32_t k, uint32_t* out_tier,
+                                   uint32_t* out_groups);
 
 /*
  * Self-test of the host-side normalisation (no GPU needed): every operator but IN / NOT_IN (MVF_ERR_INVALID_ARGUMENT) becomes
@@ -767,7 +834,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * only adds mvfgpu_search_candidates and mvfgpu_search_candidates_device, nor did the k-NN join, which only adds mvfgpu_knn_join and
  * mvfgpu_knn_join_device, nor did the filtered search, which only adds mvfgpu_filter_*, mvfgpu_search_filtered,
  * mvfgpu_search_filtered_device and mvfgpu_selftest_filter_route, nor did the metadata columns, which only add mvfgpu_column_*,
- * mvfgpu_filter_create_where, mvfgpu_selftest_predicate_range and mvfgpu_selftest_where_kernel_ms, nor did mvfgpu_selftest_poison).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * mvfgpu_filter_create_where, mvfgpu_selftest_predicate_range and mvfgpu_selftest_where_kernel_ms, nor did mvfgpu_selftest_poison, nor did the partitioned search, which only
+ * adds mvfgpu_partition_*, mvfgpu_search_partitioned, mvfgpu_search_partitioned_device and mvfgpu_selftest_partition_plan).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

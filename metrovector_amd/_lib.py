@@ -45,6 +45,12 @@ class ColumnInfo(_OutStruct):
                 ("device_bytes", C.c_uint64)]
 
 
+class PartitionInfo(_OutStruct):
+    _fields_ = [("struct_size", C.c_uint32), ("key_type", C.c_uint8), ("reserved", C.c_uint8 * 3), ("rows", C.c_uint64),
+                ("live_rows", C.c_uint64), ("n_keys", C.c_uint64), ("largest", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("host_bytes", C.c_uint64)]
+
+
 class Predicate(C.Structure):
     """mvfgpu_predicate: one clause of mvfgpu_filter_create_where."""
     _fields_ = [("column", C.c_void_p), ("op", C.c_uint32), ("n_values", C.c_uint32), ("a", C.c_uint64), ("b", C.c_uint64),
@@ -199,6 +205,22 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_predicate_range.restype = C.c_int
     lib.mvfgpu_selftest_where_kernel_ms.argtypes = [vp, C.POINTER(Predicate), u32, u32, vp, u32, vp]
     lib.mvfgpu_selftest_where_kernel_ms.restype = C.c_int
+    lib.mvfgpu_partition_create.argtypes = [vp, vp, pp]
+    lib.mvfgpu_partition_create.restype = C.c_int
+    lib.mvfgpu_partition_destroy.argtypes = [vp]
+    lib.mvfgpu_partition_destroy.restype = None
+    lib.mvfgpu_partition_get_info.argtypes = [vp, C.POINTER(PartitionInfo)]
+    lib.mvfgpu_partition_get_info.restype = C.c_int
+    lib.mvfgpu_partition_lookup.argtypes = [vp, vp, u64, vp]
+    lib.mvfgpu_partition_lookup.restype = C.c_int
+    lib.mvfgpu_partition_keys.argtypes = [vp, u64, u64, vp, vp]
+    lib.mvfgpu_partition_keys.restype = C.c_int
+    lib.mvfgpu_search_partitioned.argtypes = [vp, vp, u8, vp, u8, u32, u32, vp, u32, vp, vp, vp]
+    lib.mvfgpu_search_partitioned.restype = C.c_int
+    lib.mvfgpu_search_partitioned_device.argtypes = [vp, vp, u8, vp, u8, u32, u32, vp, u32, vp, vp, vp, vp]
+    lib.mvfgpu_search_partitioned_device.restype = C.c_int
+    lib.mvfgpu_selftest_partition_plan.argtypes = [vp, vp, u32, u32, vp, vp]
+    lib.mvfgpu_selftest_partition_plan.restype = C.c_int
     lib.mvfgpu_selftest_radius_bound.argtypes = [u8, u8, C.c_float, vp, vp]
     lib.mvfgpu_selftest_radius_bound.restype = C.c_int
     lib.mvfgpu_selftest_radius_route.argtypes = [u8, u32, C.c_int, vp]

@@ -164,6 +164,10 @@ struct WhereBuffers {
 
 }  // namespace
 
+namespace mvf {
+ColumnOrigin column_origin(const mvfgpu_column* col) { return ColumnOrigin{col->owner, col->dtype, col->values}; }
+}  // namespace mvf
+
 extern "C" {
 
 int mvfgpu_column_create(const mvfgpu_corpus* c, const void* values_le, uint8_t data_type, uint64_t first_value, uint64_t n_values,

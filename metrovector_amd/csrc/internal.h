@@ -15,6 +15,7 @@
 
 typedef struct mvfgpu_corpus mvfgpu_corpus;
 typedef struct mvfgpu_filter mvfgpu_filter;
+typedef struct mvfgpu_column mvfgpu_column;
 
 namespace mvf {
 
@@ -248,6 +249,13 @@ struct FilterOrigin {
     const uint32_t* deny;
 };
 FilterOrigin filter_origin(const mvfgpu_filter* f);
+// what the partition index (partition.hip) reads of a column when it is created: whose it is, its type, its values [rows]
+struct ColumnOrigin {
+    const mvfgpu_corpus* owner;
+    uint8_t dtype;
+    const void* values;
+};
+ColumnOrigin column_origin(const mvfgpu_column* col);
 // waits for the newest work enqueued on the handle
 int corpus_wait_newest(const mvfgpu_corpus* c);
 

@@ -233,6 +233,69 @@ class GpuColumn:
         self.close()
 
 
+class GpuPartition:
+    """The live rows of one GpuCorpus grouped by a column's value (`mvfgpu_partition`): made once by
+    `GpuCorpus.make_partition`, used by any number of `search_partitioned` calls, closed before its corpus.  A context manager."""
+
+    def __init__(self, handle: int, corpus: "GpuCorpus"):
+        self._h = C.c_void_p(handle)
+        self._corpus = corpus  # keeps the handle it belongs to alive
+
+    def info(self) -> _lib.PartitionInfo:
+        out = _lib.PartitionInfo()
+        _lib.gpu_check(_lib.gpu().mvfgpu_partition_get_info(self._h, C.byref(out)))
+        return out
+
+    def lookup(self, keys) -> np.ndarray:
+        """The live rows carrying each of `keys` (0 for an unknown key), from the host mirror: no device work."""
+        kk = _keys_u64(keys)
+        out = np.zeros(kk.size, np.uint64)
+        _lib.gpu_check(_lib.gpu().mvfgpu_partition_lookup(self._h, kk.ctypes.data_as(C.c_void_p), kk.size, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def keys(self) -> tuple[np.ndarray, np.ndarray]:
+        """(the distinct keys in ascending order, their row counts): the column's group-by over the live rows."""
+        n = self.info().n_keys
+        kk, cnt = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        _lib.gpu_check(_lib.gpu().mvfgpu_partition_keys(self._h, 0, n, kk.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
+        return kk, cnt
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value and self._corpus._h is not None:
+            _lib.gpu().mvfgpu_partition_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def partition_plan(counts, keys, k: int) -> tuple[np.ndarray, int]:
+    """(tier per query: 0 padding / 1 small / 2 large, gathered searches of the large tier) of a partitioned search whose
+    queries' keys hold `counts` live rows -- `mvfgpu_selftest_partition_plan`; no GPU needed."""
+    cc, kk = _keys_u64(counts), _keys_u64(keys)
+    if cc.size != kk.size:
+        raise InvalidArgument("counts and keys must have one entry per query")
+    tier, groups = np.zeros(max(cc.size, 1), np.uint32), C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_partition_plan(cc.ctypes.data_as(C.c_void_p), kk.ctypes.data_as(C.c_void_p), cc.size, k,
+                                                             tier.ctypes.data_as(C.c_void_p), C.byref(groups)))
+    return tier[:cc.size], groups.value
+
+
+def _keys_u64(keys) -> np.ndarray:
+    if isinstance(keys, np.ndarray) and keys.dtype.kind == "u":
+        return np.ascontiguousarray(keys.reshape(-1), dtype=np.uint64)
+    return np.array([_u64(x, "key") for x in np.asarray(keys, dtype=object).reshape(-1)], dtype=np.uint64)
+
+
 def _u64(x, what: str) -> int:
     v = int(x)
     if v < 0 or v >= 1 << 64:
@@ -640,6 +703,55 @@ class GpuCorpus:
                                                                 nq, k, C.c_void_p(d_scores), C.c_void_p(d_indices),
                                                                 C.c_void_p(d_raw) if d_raw else None,
                                                                 C.c_void_p(stream) if stream else None))
+
+    # ---- partitioned search: one key per query -------------------------------------------
+    def make_partition(self, column: GpuColumn) -> GpuPartition:
+        """The index of this corpus' live rows grouped by `column`'s value (`mvfgpu_partition_create`); rows deleted now are
+        not in it, and a later `set_tombstones` makes it stale."""
+        if not isinstance(column, GpuColumn) or column._h is None:
+            raise InvalidArgument("column must be an open GpuColumn of this corpus")
+        h = C.c_void_p()
+        _lib.gpu_check(_lib.gpu().mvfgpu_partition_create(self._h, column._h, C.byref(h)))
+        return GpuPartition(h.value, self)
+
+    def search_partitioned(self, queries: np.ndarray, keys, k: int, metric: int, part: GpuPartition) -> SearchResult:
+        """The exact top-k of every query among the live rows whose column value equals the query's own key
+        (`mvfgpu_search_partitioned`): `search`'s results in every respect; a key no live row carries gives padding."""
+        if not isinstance(part, GpuPartition) or part._h is None:
+            raise InvalidArgument("part must be an open GpuPartition of this corpus")
+        q = np.asarray(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, qdim = q.shape
+        kk = _keys_u64(keys)
+        if kk.size != nq:
+            raise InvalidArgument(f"{kk.size} keys for {nq} queries: a partitioned search takes one key per query")
+        sc = np.empty((nq, k), np.float32)
+        idx = np.empty((nq, k), np.uint64)
+        raw = np.empty((nq, k), np.int32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_partitioned(self._h, part._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
+                                                            kk.ctypes.data_as(C.c_void_p), k, sc.ctypes.data_as(C.c_void_p),
+                                                            idx.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p)))
+        return SearchResult(sc, idx, raw)
+
+    def search_partitioned_device(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, keys, k: int,
+                                  metric: int, d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
+        """Device-pointer partitioned search (`mvfgpu_search_partitioned_device`), asynchronous on `stream`; `keys` is a host
+        array, read before the call returns."""
+        if not isinstance(part, GpuPartition) or part._h is None:
+            raise InvalidArgument("part must be an open GpuPartition of this corpus")
+        kk = _keys_u64(keys)
+        if kk.size != nq:
+            raise InvalidArgument(f"{kk.size} keys for {nq} queries: a partitioned search takes one key per query")
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_partitioned_device(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype,
+                                                                   query_dim, nq, kk.ctypes.data_as(C.c_void_p), k,
+                                                                   C.c_void_p(d_scores), C.c_void_p(d_indices),
+                                                                   C.c_void_p(d_raw) if d_raw else None,
+                                                                   C.c_void_p(stream) if stream else None))
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
                       d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:

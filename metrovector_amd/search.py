@@ -269,6 +269,39 @@ def find_top_k_where(space: VectorSpace, query, k: int, where, any: bool = False
     return out
 
 
+def find_top_k_per_key(space: VectorSpace, queries, keys, k: int, column: str, metric: int | None = None,
+                       corpus: GpuCorpus | None = None, device: int = 0) -> SearchResult:
+    """The top-k of every query among the vectors whose value in the file's metadata column `column` equals the query's own
+    key (`mvfgpu_search_partitioned`; DESIGN.md §3 "Partitioned search"): `keys` holds one unsigned integer per query, a key
+    no live vector carries gives a row of padding.  The column is read as `find_top_k_where` reads it -- one UInt32 / UInt64
+    value per vector of the WHOLE space, a `corpus` that holds a row range reads its own part -- with the same refusals.
+    Returns [nq, k] arrays like a search.  The column and the index live for this call: a caller with many batches attaches
+    the column and builds the index once (`GpuCorpus.attach_column`, `make_partition`, `search_partitioned`)."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    total = space.total_vectors()
+    mc = space._reader.metadata_column(column)  # everything about the file's column is refused before anything is uploaded
+    es = {4: 4, 5: 8}.get(int(mc.data_type))
+    if es is None:
+        raise BuildError("Unsupported metadata column data type")
+    if mc.size // es < total:
+        raise BuildError(f"metadata column '{column}' holds {mc.size // es} values, the space has {total} vectors")
+    dt = int(space.data_type())
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        base = int(corpus.info().index_base)
+        with corpus.attach_column_pointer(mc.as_ptr(), int(mc.data_type), base, mc.size // es) as col:
+            with corpus.make_partition(col) as part:
+                return corpus.search_partitioned(np.asarray(queries, dtype=_NP_OF[query_dtype_code(dt)]), keys, k, metric, part)
+    finally:
+        if own:
+            corpus.close()
+
+
 def build_knn_graph(space: VectorSpace, k: int, metric: int | None = None, corpus: GpuCorpus | None = None, first: int = 0,
                     count: int | None = None, device: int = 0) -> SearchResult:
     """The k-NN graph of a space (`mvfgpu_knn_join`; DESIGN.md §3 "Join"): for rows [first, first + count) (local rows of
