@@ -143,6 +143,16 @@ extern "C" {
                                         d_queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, keys: *const u64,
                                         k: u32, d_scores: *mut f32, d_indices: *mut u64, d_raw: *mut i32,
                                         hip_stream: *mut c_void) -> c_int;
+    /// Grouped search (include/mvf_gpu.h, "grouped search"): at most `per_key` (1..=64) results per key of the partition.
+    fn mvfgpu_search_grouped(corpus: *const MvfGpuCorpus, partition: *const MvfGpuPartition, metric: u8,
+                             queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, k: u32, per_key: u32,
+                             out_scores: *mut f32, out_indices: *mut u64, out_raw: *mut i32) -> c_int;
+    fn mvfgpu_search_grouped_device(corpus: *const MvfGpuCorpus, partition: *const MvfGpuPartition, metric: u8,
+                                    d_queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, k: u32, per_key: u32,
+                                    d_scores: *mut f32, d_indices: *mut u64, d_raw: *mut i32,
+                                    hip_stream: *mut c_void) -> c_int;
+    /// The column's values (zero-extended) of the rows a search reported; padding gives 0.
+    fn mvfgpu_column_gather(column: *const MvfGpuColumn, indices: *const u64, count: u64, out_values: *mut u64) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;
     /// `MVFGPU_ABI_VERSION` of the loaded library (include/mvf_gpu.h): struct layouts and signatures this file mirrors.
     fn mvfgpu_abi_version() -> u32;

@@ -485,6 +485,49 @@ public:
             for (size_t j = 0; j < k && idx[i * k + j] != ~0ull; j++) out[i].push_back({idx[i * k + j], scores[i * k + j], {}});
         return out;
     }
+    // The top-k of every query with at most per_key vectors of any one value of `column` (mvfgpu_search_grouped; DESIGN.md
+    // section 3, "Grouped search"): the k best documents of a corpus of passages (per_key 1), or the k best passages with at
+    // most per_key per document.  queries.size() / dimension queries; the column as in find_top_k_per_key.  hit_keys, where
+    // given, receives every hit's column value (mvfgpu_column_gather).  The column and the index live for this call; the
+    // payload is not fetched.
+    std::vector<std::vector<ScoredVector>> find_top_k_grouped(const std::vector<float>& queries, size_t k, size_t per_key,
+                                                              const MetadataColumn& column,
+                                                              std::vector<std::vector<uint64_t>>* hit_keys = nullptr) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "find_top_k_grouped takes f32 queries: Float32 / Float16 spaces");
+        if (dim_ == 0 || queries.size() % (size_t)dim_)
+            throw MvfError(MVF_ERR_DIMENSION_MISMATCH, "find_top_k_grouped takes whole queries of the space's dimension");
+        const size_t nq = queries.size() / (size_t)dim_;
+        std::vector<std::vector<ScoredVector>> out(nq);
+        if (hit_keys) hit_keys->assign(nq, {});
+        if (k == 0 || nq == 0) return out;
+        mvfgpu_corpus_info inf;
+        MVFGPU_INIT(inf);
+        detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+        const uint64_t es = column.data_type == MVF_DTYPE_UINT32 ? 4 : column.data_type == MVF_DTYPE_UINT64 ? 8 : 0;
+        if (!es || column.size / es < inf.rows)
+            throw MvfError(MVF_ERR_BUILD, es ? "metadata column '" + column.name + "' holds fewer values than the space has vectors"
+                                             : "Unsupported metadata column data type");
+        mvfgpu_column* col = nullptr;
+        mvfgpu_partition* part = nullptr;
+        std::vector<float> scores(nq * k);
+        std::vector<uint64_t> idx(nq * k), vals(nq * k);
+        int rc = mvfgpu_column_create(c_, column.data, column.data_type, 0, column.size / es, &col);
+        if (rc == MVF_OK) rc = mvfgpu_partition_create(c_, col, &part);
+        if (rc == MVF_OK)
+            rc = mvfgpu_search_grouped(c_, part, (uint8_t)metric_, queries.data(), MVF_DTYPE_FLOAT32, dim_, (uint32_t)nq, (uint32_t)k,
+                                       (uint32_t)per_key, scores.data(), idx.data(), nullptr);
+        if (rc == MVF_OK && hit_keys) rc = mvfgpu_column_gather(col, idx.data(), idx.size(), vals.data());
+        mvfgpu_partition_destroy(part);
+        mvfgpu_column_destroy(col);
+        detail::check_gpu(rc);
+        for (size_t i = 0; i < nq; i++)
+            for (size_t j = 0; j < k && idx[i * k + j] != ~0ull; j++) {
+                out[i].push_back({idx[i * k + j], scores[i * k + j], {}});
+                if (hit_keys) (*hit_keys)[i].push_back(vals[i * k + j]);
+            }
+        return out;
+    }
     // The k-NN graph (mvfgpu_knn_join; DESIGN.md section 3, "Join"): for each of the rows [first, first + count) -- count
     // UINT64_MAX: to the end of the space -- its k nearest OTHER rows under the space's metric, best first.  A row is never its
     // own neighbour (decided by position: its exact duplicates are); a deleted row gets an empty list; fewer than k live

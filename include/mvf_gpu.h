@@ -623,6 +623,67 @@ int mvfgpu_search_partitioned_device(const mvfgpu_corpus* corpus, const mvfgpu_p
 int mvfgpu_selftest_partition_plan(const uint64_t* counts, const uint64_t* keys, uint32_t nq, uint32_t k, uint32_t* out_tier,
                                    uint32_t* out_groups);
 
+/* ---- grouped search: at most per_key results per key -------------------------- */
+
+/*
+ * mvfgpu_search_grouped / mvfgpu_search_grouped_device are mvfgpu_search / mvfgpu_search_device with a cap per key of a
+ * partition index ("Grouped search"): the rows are passages, the column holds the document, and the caller
+ * wants the k best passages with at most per_key of any one document (per_key = 1: the k best documents).
+ *   Result row of query q: walk the rows the partition holds (the handle's rows that were live at its creation) in
+ *   mvfgpu_search's order for q -- best first, ties by ascending position, NaN last, -0.0 == +0.0 --, take a row iff fewer than
+ *   per_key rows with the same column value have been taken, stop after k rows, pad as mvfgpu_search pads.  Equivalently: the
+ *   top-k of the union over keys of each key's top-per_key.
+ * Exact for every distribution of key sizes: every held row is scored, nothing is over-fetched.  Arguments, checks, error
+ * codes, ids and index_base, out_raw, k up to MVFGPU_MAX_K and the stream discipline are mvfgpu_search's; generation and
+ * ownership are the partitioned search's (a NULL partition, one of another handle or of an older tombstone generation is
+ * refused before any device call, with the same messages).  per_key is 1 .. MVFGPU_GROUP_MAX_PER_KEY (one wave's lanes hold a
+ * key's running best); 0 or more is MVF_ERR_INVALID_ARGUMENT with a message naming the range.  per_key -> infinity is a plain
+ * search.
+ * Every score is the one a one-query mvfgpu_search on the stored rows reports for that (query, row) -- the candidate search's
+ * rule -- so, byte for byte (indices, score bits, raw), for every data type and batch composition:
+ *   1. with C = mvfgpu_search_candidates over the list of ALL rows the partition holds and k = that count, the grouped result
+ *      is the walk above applied to C's row;
+ *   2. with per_key >= the partition's `largest`, the result is that candidate search cut at k;
+ *   3. with k >= per_key x n_keys, the entries carrying key g, in order, are the row of mvfgpu_search_partitioned for key g
+ *      with k = per_key, minus its padding.
+ * No search waits on the host; the device call is asynchronous on the caller's stream.  The handle's later searches stay as
+ * they were: no repair feedback is read or posted (mvfgpu_corpus_info::selection_state stays).
+ * Cost: one gathered pass over all held rows per four queries (one per query where four padded queries exceed 40 KiB), 8 bytes
+ * per held row and 8 per row of the handle written and read a few times per query beside it.
+ * Not built: per_key above 64; a route over the selection shadows or the batched kernels; grouping by a column without a
+ * partition index; radius, join and shard-set calls with a cap; keys in device memory.
+ *
+ * mvfgpu_column_gather: out_values[i] = the column's value, zero-extended to 64 bits, of the row indices[i] names -- what a
+ * search on the column's handle reports: global positions, or vector ids where attached (mapped as mvfgpu_corpus_gather_rows
+ * maps them).  UINT64_MAX (padding) gives 0 -- tell it from a real 0 by the index; any other index outside the shard is
+ * MVF_ERR_INDEX_OUT_OF_BOUNDS.  Blocking; host buffers.
+ */
+#define MVFGPU_GROUP_MAX_PER_KEY 64u
+int mvfgpu_search_grouped(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                          const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                          uint32_t k, uint32_t per_key, float* out_scores, uint64_t* out_indices, int32_t* out_raw);
+int mvfgpu_search_grouped_device(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                 const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                                 uint32_t k, uint32_t per_key, float* d_scores, uint64_t* d_indices, int32_t* d_raw,
+                                 void* hip_stream);
+int mvfgpu_column_gather(const mvfgpu_column* column, const uint64_t* indices, uint64_t count, uint64_t* out_values);
+/*
+ * Self-test of G1's tier rule (no GPU needed).  G1 cuts the key-ordered list into tiles of 1024 entries; a RUN is what one
+ * tile holds of one key's rows.  out_tier[i] for a run of run_lengths[i] entries (1 .. 1024) whose key does (crossing[i] != 0)
+ * or does not go on in another tile: 0 (the whole key in the tile, at most per_key rows: all kept), 1 (the whole key in the
+ * tile, at most 128 rows: ranked by counting) or 2 (longer, or crossing: one wave keeps the running best 64).
+ */
+int mvfgpu_selftest_group_plan(const uint64_t* run_lengths, const uint8_t* crossing, uint32_t n, uint32_t per_key,
+                               uint32_t* out_tier);
+/*
+ * Stage timer of a grouped search (scripts/probe_grouped.py): mvfgpu_search_grouped_device without d_raw, for a batch that fits
+ * one window of the device work (MVF_ERR_INVALID_ARGUMENT otherwise), with events between its stages; waits for the stream.
+ * out_ms[0..3] = the segment bounds (once per call), G0 (scoring), G1 (the per-key best), the tail (select, sort, format).
+ */
+int mvfgpu_selftest_grouped_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                     const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t k,
+                                     uint32_t per_key, float* d_scores, uint64_t* d_indices, void* hip_stream, float* out_ms);
+
 /*
  * Self-test of the host-side normalisation (no GPU needed): every operator but IN / NOT_IN (MVF_ERR_INVALID_ARGUMENT) becomes
  * one range test *out_lo <= v <= *out_hi on a column of `data_type`, negated where *out_negate is 1 (NE only).  The range is
@@ -835,7 +896,9 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * mvfgpu_knn_join_device, nor did the filtered search, which only adds mvfgpu_filter_*, mvfgpu_search_filtered,
  * mvfgpu_search_filtered_device and mvfgpu_selftest_filter_route, nor did the metadata columns, which only add mvfgpu_column_*,
  * mvfgpu_filter_create_where, mvfgpu_selftest_predicate_range and mvfgpu_selftest_where_kernel_ms, nor did mvfgpu_selftest_poison, nor did the partitioned search, which only
- * adds mvfgpu_partition_*, mvfgpu_search_partitioned, mvfgpu_search_partitioned_device and mvfgpu_selftest_partition_plan).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * adds mvfgpu_partition_*, mvfgpu_search_partitioned, mvfgpu_search_partitioned_device and mvfgpu_selftest_partition_plan, nor did
+ * the grouped search, which only adds mvfgpu_search_grouped, mvfgpu_search_grouped_device, mvfgpu_column_gather,
+ * mvfgpu_selftest_group_plan and mvfgpu_selftest_grouped_stage_ms).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

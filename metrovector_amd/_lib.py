@@ -221,6 +221,16 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_search_partitioned_device.restype = C.c_int
     lib.mvfgpu_selftest_partition_plan.argtypes = [vp, vp, u32, u32, vp, vp]
     lib.mvfgpu_selftest_partition_plan.restype = C.c_int
+    lib.mvfgpu_search_grouped.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, u32, vp, vp, vp]
+    lib.mvfgpu_search_grouped.restype = C.c_int
+    lib.mvfgpu_search_grouped_device.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_search_grouped_device.restype = C.c_int
+    lib.mvfgpu_column_gather.argtypes = [vp, vp, u64, vp]
+    lib.mvfgpu_column_gather.restype = C.c_int
+    lib.mvfgpu_selftest_group_plan.argtypes = [vp, vp, u32, u32, vp]
+    lib.mvfgpu_selftest_group_plan.restype = C.c_int
+    lib.mvfgpu_selftest_grouped_stage_ms.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_grouped_stage_ms.restype = C.c_int
     lib.mvfgpu_selftest_radius_bound.argtypes = [u8, u8, C.c_float, vp, vp]
     lib.mvfgpu_selftest_radius_bound.restype = C.c_int
     lib.mvfgpu_selftest_radius_route.argtypes = [u8, u32, C.c_int, vp]

@@ -16,6 +16,7 @@
 typedef struct mvfgpu_corpus mvfgpu_corpus;
 typedef struct mvfgpu_filter mvfgpu_filter;
 typedef struct mvfgpu_column mvfgpu_column;
+typedef struct mvfgpu_partition mvfgpu_partition;
 
 namespace mvf {
 
@@ -256,6 +257,16 @@ struct ColumnOrigin {
     const void* values;
 };
 ColumnOrigin column_origin(const mvfgpu_column* col);
+// what the grouped search (grouped.hip) reads of a partition index: whose it is, its tombstone generation, the live rows grouped
+// by key (ascending inside a key), the device key table (keys[n_keys] ascending, then offsets[n_keys + 1]) and its counts
+struct PartitionView {
+    const mvfgpu_corpus* owner;
+    uint64_t tomb_gen;
+    const uint32_t* rows_by_key;
+    const uint64_t* table;
+    uint64_t live, n_keys, largest;
+};
+PartitionView partition_view(const mvfgpu_partition* part);
 // waits for the newest work enqueued on the handle
 int corpus_wait_newest(const mvfgpu_corpus* c);
 

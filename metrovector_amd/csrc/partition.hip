@@ -326,6 +326,12 @@ int partitioned_core(const CorpusView& v, const mvfgpu_partition* part, uint8_t 
 
 }  // namespace
 
+namespace mvf {
+PartitionView partition_view(const mvfgpu_partition* part) {
+    return PartitionView{part->owner, part->tomb_gen, part->rows_by_key, part->table, part->live, part->n_keys, part->largest};
+}
+}  // namespace mvf
+
 extern "C" {
 
 int mvfgpu_partition_create(const mvfgpu_corpus* c, const mvfgpu_column* column, mvfgpu_partition** out) {

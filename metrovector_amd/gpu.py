@@ -215,6 +215,16 @@ class GpuColumn:
         _lib.gpu_check(_lib.gpu().mvfgpu_column_get_info(self._h, C.byref(out)))
         return out
 
+    def gather(self, indices) -> np.ndarray:
+        """The column's values, as uint64, of the rows `indices` name -- what a search on the column's corpus reports (global
+        positions, or vector ids where attached), in any shape (`mvfgpu_column_gather`).  Padding (UINT64_MAX) gives 0."""
+        if self._h is None:
+            raise InvalidArgument("the column is closed")
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        out = np.zeros(idx.shape, np.uint64)
+        _lib.gpu_check(_lib.gpu().mvfgpu_column_gather(self._h, idx.ctypes.data_as(C.c_void_p), idx.size, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def close(self) -> None:
         if self._h is not None and self._h.value and self._corpus._h is not None:
             _lib.gpu().mvfgpu_column_destroy(self._h)
@@ -288,6 +298,20 @@ def partition_plan(counts, keys, k: int) -> tuple[np.ndarray, int]:
     _lib.gpu_check(_lib.gpu().mvfgpu_selftest_partition_plan(cc.ctypes.data_as(C.c_void_p), kk.ctypes.data_as(C.c_void_p), cc.size, k,
                                                              tier.ctypes.data_as(C.c_void_p), C.byref(groups)))
     return tier[:cc.size], groups.value
+
+
+def group_plan(run_lengths, crossing, per_key: int) -> np.ndarray:
+    """The tier (0 all kept / 1 ranked by counting / 2 one wave's running best) of every run -- what one 1024-entry tile of a
+    grouped search's key-ordered list holds of one key -- of `run_lengths` entries whose key does (`crossing`) or does not go
+    on in another tile: `mvfgpu_selftest_group_plan`; no GPU needed."""
+    ll = _keys_u64(run_lengths)
+    cr = np.ascontiguousarray(np.asarray(crossing).reshape(-1), dtype=np.uint8)
+    if ll.size != cr.size:
+        raise InvalidArgument("run_lengths and crossing must have one entry per run")
+    tier = np.zeros(max(ll.size, 1), np.uint32)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_group_plan(ll.ctypes.data_as(C.c_void_p), cr.ctypes.data_as(C.c_void_p), ll.size, per_key,
+                                                         tier.ctypes.data_as(C.c_void_p)))
+    return tier[:ll.size]
 
 
 def _keys_u64(keys) -> np.ndarray:
@@ -752,6 +776,48 @@ class GpuCorpus:
                                                                    C.c_void_p(d_scores), C.c_void_p(d_indices),
                                                                    C.c_void_p(d_raw) if d_raw else None,
                                                                    C.c_void_p(stream) if stream else None))
+
+    # ---- grouped search: at most per_key results per key ----------------------------------
+    def search_grouped(self, queries: np.ndarray, k: int, per_key: int, metric: int, part: GpuPartition) -> SearchResult:
+        """The exact top-k of every query with at most `per_key` rows of any one key of `part` (`mvfgpu_search_grouped`):
+        `search`'s results in every respect over the rows the partition holds; `GpuColumn.gather` gives the hits' keys."""
+        if not isinstance(part, GpuPartition) or part._h is None:
+            raise InvalidArgument("part must be an open GpuPartition of this corpus")
+        q = np.asarray(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, qdim = q.shape
+        sc = np.empty((nq, k), np.float32)
+        idx = np.empty((nq, k), np.uint64)
+        raw = np.empty((nq, k), np.int32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_grouped(self._h, part._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
+                                                        per_key, sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                        raw.ctypes.data_as(C.c_void_p)))
+        return SearchResult(sc, idx, raw)
+
+    def search_grouped_device(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int,
+                              per_key: int, metric: int, d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
+        """Device-pointer grouped search (`mvfgpu_search_grouped_device`), asynchronous on `stream`."""
+        if not isinstance(part, GpuPartition) or part._h is None:
+            raise InvalidArgument("part must be an open GpuPartition of this corpus")
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_grouped_device(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
+                                                               nq, k, per_key, C.c_void_p(d_scores), C.c_void_p(d_indices),
+                                                               C.c_void_p(d_raw) if d_raw else None,
+                                                               C.c_void_p(stream) if stream else None))
+
+    def grouped_stage_ms(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, per_key: int,
+                         metric: int, d_scores: int, d_indices: int, stream: int = 0) -> tuple[float, float, float, float]:
+        """(segment bounds, G0, G1, tail) in ms of one grouped search that fits one window (`mvfgpu_selftest_grouped_stage_ms`);
+        waits for the stream."""
+        out = (C.c_float * 4)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_grouped_stage_ms(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
+                                                                   nq, k, per_key, C.c_void_p(d_scores), C.c_void_p(d_indices),
+                                                                   C.c_void_p(stream) if stream else None, out))
+        return tuple(float(x) for x in out)
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
                       d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:

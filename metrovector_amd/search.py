@@ -302,6 +302,40 @@ def find_top_k_per_key(space: VectorSpace, queries, keys, k: int, column: str, m
             corpus.close()
 
 
+def find_top_k_grouped(space: VectorSpace, queries, k: int, column: str, per_key: int = 1, metric: int | None = None,
+                       corpus: GpuCorpus | None = None, device: int = 0) -> tuple[SearchResult, np.ndarray]:
+    """The top-k of every query with at most `per_key` vectors of any one value of the file's metadata column `column`
+    (`mvfgpu_search_grouped`; DESIGN.md §3 "Grouped search"): the k best documents of a corpus of passages (`per_key` 1), or
+    the k best passages with at most `per_key` per document.  The column is read as `find_top_k_per_key` reads it, with the
+    same refusals.  Returns ([nq, k] arrays like a search, the hits' keys as uint64 [nq, k]; a padding entry's key is 0).
+    The column and the index live for this call: a caller with many batches attaches the column and builds the index once
+    (`GpuCorpus.attach_column`, `make_partition`, `search_grouped`, `GpuColumn.gather`)."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    total = space.total_vectors()
+    mc = space._reader.metadata_column(column)  # everything about the file's column is refused before anything is uploaded
+    es = {4: 4, 5: 8}.get(int(mc.data_type))
+    if es is None:
+        raise BuildError("Unsupported metadata column data type")
+    if mc.size // es < total:
+        raise BuildError(f"metadata column '{column}' holds {mc.size // es} values, the space has {total} vectors")
+    dt = int(space.data_type())
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        base = int(corpus.info().index_base)
+        with corpus.attach_column_pointer(mc.as_ptr(), int(mc.data_type), base, mc.size // es) as col:
+            with corpus.make_partition(col) as part:
+                res = corpus.search_grouped(np.asarray(queries, dtype=_NP_OF[query_dtype_code(dt)]), k, per_key, metric, part)
+            return res, col.gather(res.indices)
+    finally:
+        if own:
+            corpus.close()
+
+
 def build_knn_graph(space: VectorSpace, k: int, metric: int | None = None, corpus: GpuCorpus | None = None, first: int = 0,
                     count: int | None = None, device: int = 0) -> SearchResult:
     """The k-NN graph of a space (`mvfgpu_knn_join`; DESIGN.md §3 "Join"): for rows [first, first + count) (local rows of
