@@ -2227,10 +2227,7 @@ bool large_k_by_sort(const mvfgpu_corpus* c, uint32_t nq, uint32_t k) {
 int check_query_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype,
                      uint32_t query_dim, uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices) {
     if (!c) return fail(MVF_ERR_INVALID_ARGUMENT, "corpus is NULL");
-    if (const int mrc = check_metric(metric)) return mrc;
-    if (nq == 0) return fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
-    if (k == 0 || k > MVFGPU_MAX_K) return fail(MVF_ERR_INVALID_ARGUMENT, "k must be in 1..2^31");
-    if (!queries || !out_scores || !out_indices) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (const int rc = check_search_scalars(metric, nq, k, queries, out_scores, out_indices)) return rc;
     const uint8_t want = is_int_dtype(c->dtype) ? c->dtype : (uint8_t)MVF_DTYPE_FLOAT32;
     if (query_dtype != want)
         return fail(MVF_ERR_BUILD, "query data type must be Float32 for Float32/Float16 spaces and the space's own type for Int8/UInt8");
@@ -2301,6 +2298,13 @@ int corpus_device_call(const mvfgpu_corpus* c, void* stream, const std::function
 int corpus_wait_newest(const mvfgpu_corpus* c) {
     std::lock_guard<std::mutex> lk(c->mu);
     if (c->has_done) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+    return MVF_OK;
+}
+int check_search_scalars(uint8_t metric, uint32_t nq, uint32_t k, const void* queries, const void* out_scores, const void* out_indices) {
+    if (const int mrc = check_metric(metric)) return mrc;
+    if (nq == 0) return fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
+    if (k == 0 || k > MVFGPU_MAX_K) return fail(MVF_ERR_INVALID_ARGUMENT, "k must be in 1..2^31");
+    if (!queries || !out_scores || !out_indices) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
     return MVF_OK;
 }
 int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,

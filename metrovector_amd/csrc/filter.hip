@@ -103,10 +103,7 @@ void free_filter(mvfgpu_filter* f) {
 // the checks of both searches, none of which touches the device; then the route of this call
 int check_filtered_args(const mvfgpu_corpus* c, const mvfgpu_filter* f, uint8_t metric, const void* queries, uint8_t query_dtype,
                         uint32_t query_dim, uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices, FilterUse* use) {
-    if (const int mrc = check_metric(metric)) return mrc;
-    if (nq == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
-    if (k == 0 || k > MVFGPU_MAX_K) return set_fail(MVF_ERR_INVALID_ARGUMENT, "k must be in 1..2^31");
-    if (!queries || !out_scores || !out_indices) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (const int rc = check_search_scalars(metric, nq, k, queries, out_scores, out_indices)) return rc;
     if (!f) return set_fail(MVF_ERR_INVALID_ARGUMENT, "filter is NULL");
     const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
     if (rc != MVF_OK) return rc;
@@ -130,12 +127,9 @@ namespace mvf {
 int filter_list_search(const CorpusView& v, const FilterUse& flt, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
                        float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
     if (flt.admitted == 0 || v.n == 0) return fill_padding(metric, nq, k, d_scores, d_indices, d_raw, s);  // nothing admitted
-    int G = 64;
-    uint32_t J = 1;
-    k1_group(v.V, 1, v.k1_g, &G, &J);
     GatherSource src;
     src.m = (uint32_t)flt.admitted;  // a shard holds fewer than 2^32 rows
-    src.qg = filter_group_queries(cand_query_bytes(v.dtype, G, J));
+    src.qg = one_query_group(v).qg;
     src.list = flt.list;
     return gather_topk(v, metric, d_queries, nq, src, k, d_scores, d_indices, d_raw, s);
 }

@@ -7,10 +7,12 @@
 // entries of every key and writes them to a row-indexed array in which every other row is dead; the whole-list select and
 // sort (sort_topk.hip) rank that array and write_sorted formats the first k.  Exact for every distribution of key sizes:
 // nothing is over-fetched.  No host wait, no plan: the segments are read from the index's device key table.
+// The host call runs the same device work per host window (host_staging.h).
 
 #include "../../include/mvf_gpu.h"
 
 #include "aux_kernels.h"
+#include "host_staging.h"
 #include "internal.h"
 #include "mvf_common.h"
 #include "scan_filter.h"
@@ -28,28 +30,17 @@ namespace {
 
 constexpr uint32_t kWindow = 1024;                 // queries per window at most
 constexpr size_t kScratchBytes = 512ull << 20;     // device scratch of a window: scan_gather.hip's budget (one group of queries may exceed it)
-constexpr size_t kHostWindowBytes = 256ull << 20;  // the host call's device copies of queries and results per window
-constexpr size_t kPinnedBytes = 1ull << 20;        // host windows up to this size travel through the handle's pinned mirrors
 
 // the checks of both searches, none of which touches the device: mvfgpu_search_partitioned's, with per_key in the keys' place
 int check_grouped_args(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries, uint8_t query_dtype,
                        uint32_t query_dim, uint32_t nq, uint32_t k, uint32_t per_key, const void* out_scores, const void* out_indices) {
-    if (const int mrc = check_metric(metric)) return mrc;
-    if (nq == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
-    if (k == 0 || k > MVFGPU_MAX_K) return set_fail(MVF_ERR_INVALID_ARGUMENT, "k must be in 1..2^31");
-    if (!queries || !out_scores || !out_indices) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (const int rc = check_search_scalars(metric, nq, k, queries, out_scores, out_indices)) return rc;
     if (per_key == 0 || per_key > MVFGPU_GROUP_MAX_PER_KEY)
         return set_fail(MVF_ERR_INVALID_ARGUMENT,
                         "per_key must be in 1.." + std::to_string(MVFGPU_GROUP_MAX_PER_KEY) + ", got " + std::to_string(per_key));
     if (!part) return set_fail(MVF_ERR_INVALID_ARGUMENT, "partition is NULL");
-    const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
-    if (rc != MVF_OK) return rc;
-    const PartitionView pv = partition_view(part);
-    if (pv.owner != c) return set_fail(MVF_ERR_INVALID_ARGUMENT, "the partition was created for another corpus handle");
-    if (pv.tomb_gen != corpus_view(c).tomb_gen)
-        return set_fail(MVF_ERR_INVALID_ARGUMENT,
-                        "stale partition: mvfgpu_corpus_set_tombstones changed the handle's tombstones after the partition was created");
-    return MVF_OK;
+    if (const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices)) return rc;
+    return check_partition_use(c, part);
 }
 
 // The device work of both calls: queries and results in device memory; everything on `s`.  Runs under corpus_device_call.
@@ -57,11 +48,9 @@ int check_grouped_args(const mvfgpu_corpus* c, const mvfgpu_partition* part, uin
 int grouped_core(const CorpusView& v, const PartitionView& pv, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
                  uint32_t per_key, float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s, hipEvent_t* marks = nullptr) {
     if (v.n == 0 || pv.live == 0 || pv.n_keys == 0) return fill_padding(metric, nq, k, d_scores, d_indices, d_raw, s);
-    int G = 64;
-    uint32_t J = 1;
-    k1_group(v.V, 1, v.k1_g, &G, &J);  // K1's one-query lane group: its bits
-    const uint32_t qg = filter_group_queries(cand_query_bytes(v.dtype, G, J));
-    const size_t qrow = (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4);
+    const OneQueryGroup g1 = one_query_group(v);
+    const uint32_t qg = g1.qg;
+    const size_t qrow = query_row_bytes(v);
     const uint32_t live = (uint32_t)pv.live, n = (uint32_t)v.n;  // a shard holds fewer than 2^32 rows
     const uint32_t tiles = group_tiles(live);
     // per query: the two sort buffers over all rows (the second one is G0's dump first) and the crossing runs' lists
@@ -106,9 +95,9 @@ int grouped_core(const CorpusView& v, const PartitionView& pv, uint8_t metric, c
         sp.dim = v.dim;
         sp.pitch = v.pitch;
         sp.V = v.V;
-        sp.J = J;
+        sp.J = g1.J;
         sp.dump = b;
-        MVF_HIP_TRY(gather_score_launch(v.dtype, metric, G, qg, sp, s));
+        MVF_HIP_TRY(gather_score_launch(v.dtype, metric, g1.G, qg, sp, s));
         if (marks) MVF_HIP_TRY(hipEventRecord(marks[2], s));
         // G1: the per_key best of every key to a[q][n], row-indexed, every other row dead
         MVF_HIP_TRY(group_dead_fill_launch(a, n, wn, s));
@@ -161,56 +150,12 @@ int mvfgpu_search_grouped(const mvfgpu_corpus* c, const mvfgpu_partition* part, 
     const CorpusView v = corpus_view(c);
     const PartitionView pv = partition_view(part);
     hipStream_t s = static_cast<hipStream_t>(v.stream);
-    const size_t qrow = (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4);
-    const size_t out_q = (size_t)k * 16;  // result bytes per query
-    const uint32_t W = (uint32_t)std::max<size_t>(1, std::min<size_t>(nq, kHostWindowBytes / (qrow + out_q)));
-    AsyncBuf dq, dsc, didx, draw;
-    MVF_HIP_TRY(dq.alloc((size_t)W * qrow, s));
-    MVF_HIP_TRY(dsc.alloc((size_t)W * k * 4, s));
-    MVF_HIP_TRY(didx.alloc((size_t)W * k * 8, s));
-    if (out_raw) MVF_HIP_TRY(draw.alloc((size_t)W * k * 4, s));
-    for (uint32_t w0 = 0; w0 < nq; w0 += W) {
-        const uint32_t wn = std::min(W, nq - w0);
-        const size_t nr = (size_t)wn * k;
-        const unsigned char* hq = static_cast<const unsigned char*>(queries) + (size_t)w0 * qrow;
-        // small windows through the pinned mirrors: in = queries, out = indices | scores | raw
-        const size_t in_bytes = (size_t)wn * qrow, out_bytes = nr * 16;
-        const bool pinned = in_bytes + out_bytes <= kPinnedBytes;
-        unsigned char *pin_in = nullptr, *pin_out = nullptr;
-        if (pinned) {
-            void *pi = nullptr, *po = nullptr;
-            const int rc = corpus_pinned_mirrors(c, in_bytes, out_bytes, &pi, &po);
-            if (rc != MVF_OK) return rc;
-            pin_in = static_cast<unsigned char*>(pi);
-            pin_out = static_cast<unsigned char*>(po);
-            std::memcpy(pin_in, hq, in_bytes);
-        }
-        const size_t o_sc = nr * 8, o_raw = nr * 12;
-        const int rc = corpus_device_call(c, s, [&]() -> int {
-            MVF_HIP_TRY(hipMemcpyAsync(dq.p, pinned ? pin_in : hq, in_bytes, hipMemcpyHostToDevice, s));
-            const int rc1 = grouped_core(v, pv, metric, dq.p, wn, k, per_key, static_cast<float*>(dsc.p), static_cast<uint64_t*>(didx.p),
-                                         static_cast<int32_t*>(draw.p), s);
-            if (rc1 != MVF_OK) return rc1;
-            if (pinned) {
-                MVF_HIP_TRY(hipMemcpyAsync(pin_out, didx.p, nr * 8, hipMemcpyDeviceToHost, s));
-                MVF_HIP_TRY(hipMemcpyAsync(pin_out + o_sc, dsc.p, nr * 4, hipMemcpyDeviceToHost, s));
-                if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(pin_out + o_raw, draw.p, nr * 4, hipMemcpyDeviceToHost, s));
-            } else {
-                MVF_HIP_TRY(hipMemcpyAsync(out_indices + (size_t)w0 * k, didx.p, nr * 8, hipMemcpyDeviceToHost, s));
-                MVF_HIP_TRY(hipMemcpyAsync(out_scores + (size_t)w0 * k, dsc.p, nr * 4, hipMemcpyDeviceToHost, s));
-                if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(out_raw + (size_t)w0 * k, draw.p, nr * 4, hipMemcpyDeviceToHost, s));
-            }
-            return MVF_OK;
-        });
-        if (rc != MVF_OK) return rc;
-        MVF_HIP_TRY(hipStreamSynchronize(s));
-        if (pinned) {
-            std::memcpy(out_indices + (size_t)w0 * k, pin_out, nr * 8);
-            std::memcpy(out_scores + (size_t)w0 * k, pin_out + o_sc, nr * 4);
-            if (out_raw) std::memcpy(out_raw + (size_t)w0 * k, pin_out + o_raw, nr * 4);
-        }
-    }
-    return MVF_OK;
+    const HostIn in[] = {{queries, query_row_bytes(v)}};
+    const HostOut out[] = {{out_indices, (size_t)k * 8}, {out_scores, (size_t)k * 4}, {out_raw, (size_t)k * 4}};
+    return stage_host_windows(c, s, nq, in, out, stage_as_given, [&](uint32_t, uint32_t wn, void* const* d_in, void* const* d_out) {
+        return grouped_core(v, pv, metric, d_in[0], wn, k, per_key, static_cast<float*>(d_out[1]), static_cast<uint64_t*>(d_out[0]),
+                            static_cast<int32_t*>(d_out[2]), s);
+    });
 }
 
 int mvfgpu_selftest_grouped_stage_ms(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,

@@ -169,6 +169,8 @@ struct CorpusView {
     int filter_route = 0;            // Tuning::filter_route
 };
 CorpusView corpus_view(const mvfgpu_corpus* c);
+// bytes of one query of the handle's space: Float32, or the space's own type for Int8 / UInt8
+inline size_t query_row_bytes(const CorpusView& v) { return (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4); }
 std::mutex& corpus_host_mutex(const mvfgpu_corpus* c);  // serialises the host-buffer calls of a handle
 // Float32 / Float16 corpora: the row norms the batched kernels read (built on first use, on `stream`): xnorm[n] = |x|,
 // xx2[n] = sum x^2, xxmax[1] = max of xx2
@@ -195,7 +197,11 @@ inline K1Shape k1_pass_shape(uint32_t V, uint32_t queries, uint32_t k, int force
         if (sh.nqv == 1 || sh.lds <= 150 * 1024) return sh;
     }
 }
-// mvfgpu_search's argument checks (k = 1 .. MVFGPU_MAX_K, non-NULL query and output buffers)
+// The part of mvfgpu_search's argument checks that needs no handle, in its order: metric, nq, k = 1 .. MVFGPU_MAX_K, non-NULL
+// query and output buffers.  A search with arguments of its own calls it, then checks those, then check_search_args: what
+// needs no handle is refused before `corpus is NULL`.
+int check_search_scalars(uint8_t metric, uint32_t nq, uint32_t k, const void* queries, const void* out_scores, const void* out_indices);
+// mvfgpu_search's argument checks: `corpus is NULL`, check_search_scalars, then the query's type and dimension
 int check_search_args(const mvfgpu_corpus* c, uint8_t metric, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                       uint32_t nq, uint32_t k, const void* out_scores, const void* out_indices);
 // With vector ids attached (mvfgpu_corpus_set_vector_ids): out[i] = the global position (index_base + row) of the FIRST row
@@ -267,6 +273,8 @@ struct PartitionView {
     uint64_t live, n_keys, largest;
 };
 PartitionView partition_view(const mvfgpu_partition* part);
+// a search of `c` may use the index: it was created for this handle and holds the handle's current tombstones
+int check_partition_use(const mvfgpu_corpus* c, const mvfgpu_partition* part);
 // waits for the newest work enqueued on the handle
 int corpus_wait_newest(const mvfgpu_corpus* c);
 

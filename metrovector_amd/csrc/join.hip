@@ -98,7 +98,7 @@ int plan_join(const mvfgpu_corpus* c, const mvfgpu_corpus* qc, uint8_t metric, u
     plan->k = k;
     plan->exclude = exclude && meet;
     plan->kin = plan->exclude ? k + 1 : k;
-    plan->qrow = (size_t)vc.dim * (is_int_dtype(vc.dtype) ? 1 : 4);
+    plan->qrow = query_row_bytes(vc);
     return MVF_OK;
 }
 

@@ -12,10 +12,12 @@
 // filtered search's list route runs for a filter whose list is that key's segment.  The results are computed in the plan's
 // order and put into the caller's order, padding rows included, by one kernel.  The plan travels through a pinned buffer of
 // the index; no host wait but for that buffer's previous upload (an event that has long passed when searches do not pile up).
+// The host call runs the same device work per host window (host_staging.h).
 
 #include "../../include/mvf_gpu.h"
 
 #include "aux_kernels.h"
+#include "host_staging.h"
 #include "internal.h"
 #include "mvf_common.h"
 #include "scan_filter.h"
@@ -63,9 +65,7 @@ struct mvfgpu_partition {
 
 namespace {
 
-constexpr uint32_t kSmallWindow = 1024;            // small-tier queries per launch of S1 and K3
-constexpr size_t kHostWindowBytes = 256ull << 20;  // the host call's device copies of queries and results per window
-constexpr size_t kPinnedBytes = 1ull << 20;        // host windows up to this size travel through the handle's pinned mirrors
+constexpr uint32_t kSmallWindow = 1024;  // small-tier queries per launch of S1 and K3
 
 // ---- the plan: a pure function of every query's row count and key
 struct PartGroup {
@@ -191,19 +191,11 @@ int build_partition(mvfgpu_partition* p, const CorpusView& v, const void* values
 // the checks of both searches, none of which touches the device
 int check_partitioned_args(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries, uint8_t query_dtype,
                            uint32_t query_dim, uint32_t nq, const uint64_t* keys, uint32_t k, const void* out_scores, const void* out_indices) {
-    if (const int mrc = check_metric(metric)) return mrc;
-    if (nq == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
-    if (k == 0 || k > MVFGPU_MAX_K) return set_fail(MVF_ERR_INVALID_ARGUMENT, "k must be in 1..2^31");
-    if (!queries || !out_scores || !out_indices) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (const int rc = check_search_scalars(metric, nq, k, queries, out_scores, out_indices)) return rc;
     if (!keys) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer (keys)");
     if (!part) return set_fail(MVF_ERR_INVALID_ARGUMENT, "partition is NULL");
-    const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
-    if (rc != MVF_OK) return rc;
-    if (part->owner != c) return set_fail(MVF_ERR_INVALID_ARGUMENT, "the partition was created for another corpus handle");
-    if (part->tomb_gen != corpus_view(c).tomb_gen)
-        return set_fail(MVF_ERR_INVALID_ARGUMENT,
-                        "stale partition: mvfgpu_corpus_set_tombstones changed the handle's tombstones after the partition was created");
-    return MVF_OK;
+    if (const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices)) return rc;
+    return check_partition_use(c, part);
 }
 
 // The plan of `nq` queries into the index's pinned buffer and from there to `dst` on `s`.  The caller holds the owner's lock.
@@ -233,18 +225,15 @@ int upload_plan(const mvfgpu_partition* part, const PartPlan& plan, void* dst, h
 int partitioned_core(const CorpusView& v, const mvfgpu_partition* part, uint8_t metric, const void* d_queries, uint32_t nq,
                      const uint64_t* keys, uint32_t k, float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {
     if (part->n_keys == 0) return fill_padding(metric, nq, k, d_scores, d_indices, d_raw, s);
-    int G = 64;
-    uint32_t J = 1;
-    k1_group(v.V, 1, v.k1_g, &G, &J);  // K1's one-query lane group: its bits
-    const uint32_t qbytes = cand_query_bytes(v.dtype, G, J);
+    const OneQueryGroup g1 = one_query_group(v);
     std::vector<uint64_t> counts(nq), offsets(nq);
     for (uint32_t q = 0; q < nq; q++) part->find(keys[q], &offsets[q], &counts[q]);
     PartPlan plan;
-    plan_partitioned(counts.data(), offsets.data(), keys, nq, k, qbytes <= kCandQueryLdsMax, nullptr, &plan);
+    plan_partitioned(counts.data(), offsets.data(), keys, nq, k, g1.qbytes <= kCandQueryLdsMax, nullptr, &plan);
     const uint32_t n_scored = plan.n_small + plan.n_large;
     if (n_scored == 0) return fill_padding(metric, nq, k, d_scores, d_indices, d_raw, s);
 
-    const size_t qrow = (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4);
+    const size_t qrow = query_row_bytes(v);
     AsyncBuf dplan, csc, cidx, craw, dlists, dql;
     MVF_HIP_TRY(dplan.alloc((size_t)nq * sizeof(PartQuery), s));
     if (const int rc = upload_plan(part, plan, dplan.p, s)) return rc;
@@ -268,7 +257,7 @@ int partitioned_core(const CorpusView& v, const mvfgpu_partition* part, uint8_t 
         sp.dim = v.dim;
         sp.pitch = v.pitch;
         sp.V = v.V;
-        sp.J = J;
+        sp.J = g1.J;
         sp.lists = static_cast<uint64_t*>(dlists.p);
         sp.kcap = kcap;
         SelectParams fp{};
@@ -286,7 +275,7 @@ int partitioned_core(const CorpusView& v, const mvfgpu_partition* part, uint8_t 
             const uint32_t wn = std::min(W, plan.n_small - w0);
             sp.plan = d_plan + w0;
             sp.n = wn;
-            MVF_HIP_TRY(segment_score_launch(v.dtype, metric, G, sp, s));
+            MVF_HIP_TRY(segment_score_launch(v.dtype, metric, g1.G, sp, s));
             fp.out_scores = c_scores + (size_t)w0 * k;
             fp.out_indices = c_indices + (size_t)w0 * k;
             fp.out_raw = c_raw ? c_raw + (size_t)w0 * k : nullptr;
@@ -299,7 +288,7 @@ int partitioned_core(const CorpusView& v, const mvfgpu_partition* part, uint8_t 
         for (const PartGroup& g : plan.groups) {
             GatherSource src;
             src.m = (uint32_t)g.count;  // a shard holds fewer than 2^32 rows
-            src.qg = filter_group_queries(qbytes);
+            src.qg = g1.qg;
             src.list = part->rows_by_key + g.offset;
             const size_t l0 = g.first - plan.n_small;  // the group's first query among the gathered ones
             const int rc = gather_topk(v, metric, static_cast<const unsigned char*>(dql.p) + l0 * qrow, g.nq, src, k,
@@ -329,6 +318,13 @@ int partitioned_core(const CorpusView& v, const mvfgpu_partition* part, uint8_t 
 namespace mvf {
 PartitionView partition_view(const mvfgpu_partition* part) {
     return PartitionView{part->owner, part->tomb_gen, part->rows_by_key, part->table, part->live, part->n_keys, part->largest};
+}
+int check_partition_use(const mvfgpu_corpus* c, const mvfgpu_partition* part) {
+    if (part->owner != c) return set_fail(MVF_ERR_INVALID_ARGUMENT, "the partition was created for another corpus handle");
+    if (part->tomb_gen != corpus_view(c).tomb_gen)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT,
+                        "stale partition: mvfgpu_corpus_set_tombstones changed the handle's tombstones after the partition was created");
+    return MVF_OK;
 }
 }  // namespace mvf
 
@@ -430,56 +426,12 @@ int mvfgpu_search_partitioned(const mvfgpu_corpus* c, const mvfgpu_partition* pa
     std::lock_guard<std::mutex> host_lk(corpus_host_mutex(c));
     const CorpusView v = corpus_view(c);
     hipStream_t s = static_cast<hipStream_t>(v.stream);
-    const size_t qrow = (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4);
-    const size_t out_q = (size_t)k * 16;  // result bytes per query
-    const uint32_t W = (uint32_t)std::max<size_t>(1, std::min<size_t>(nq, kHostWindowBytes / (qrow + out_q)));
-    AsyncBuf dq, dsc, didx, draw;
-    MVF_HIP_TRY(dq.alloc((size_t)W * qrow, s));
-    MVF_HIP_TRY(dsc.alloc((size_t)W * k * 4, s));
-    MVF_HIP_TRY(didx.alloc((size_t)W * k * 8, s));
-    if (out_raw) MVF_HIP_TRY(draw.alloc((size_t)W * k * 4, s));
-    for (uint32_t w0 = 0; w0 < nq; w0 += W) {
-        const uint32_t wn = std::min(W, nq - w0);
-        const size_t nr = (size_t)wn * k;
-        const unsigned char* hq = static_cast<const unsigned char*>(queries) + (size_t)w0 * qrow;
-        // small windows through the pinned mirrors: in = queries, out = indices | scores | raw
-        const size_t in_bytes = (size_t)wn * qrow, out_bytes = nr * 16;
-        const bool pinned = in_bytes + out_bytes <= kPinnedBytes;
-        unsigned char *pin_in = nullptr, *pin_out = nullptr;
-        if (pinned) {
-            void *pi = nullptr, *po = nullptr;
-            const int rc = corpus_pinned_mirrors(c, in_bytes, out_bytes, &pi, &po);
-            if (rc != MVF_OK) return rc;
-            pin_in = static_cast<unsigned char*>(pi);
-            pin_out = static_cast<unsigned char*>(po);
-            std::memcpy(pin_in, hq, in_bytes);
-        }
-        const size_t o_sc = nr * 8, o_raw = nr * 12;
-        const int rc = corpus_device_call(c, s, [&]() -> int {
-            MVF_HIP_TRY(hipMemcpyAsync(dq.p, pinned ? pin_in : hq, in_bytes, hipMemcpyHostToDevice, s));
-            const int rc1 = partitioned_core(v, part, metric, dq.p, wn, keys + w0, k, static_cast<float*>(dsc.p),
-                                             static_cast<uint64_t*>(didx.p), static_cast<int32_t*>(draw.p), s);
-            if (rc1 != MVF_OK) return rc1;
-            if (pinned) {
-                MVF_HIP_TRY(hipMemcpyAsync(pin_out, didx.p, nr * 8, hipMemcpyDeviceToHost, s));
-                MVF_HIP_TRY(hipMemcpyAsync(pin_out + o_sc, dsc.p, nr * 4, hipMemcpyDeviceToHost, s));
-                if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(pin_out + o_raw, draw.p, nr * 4, hipMemcpyDeviceToHost, s));
-            } else {
-                MVF_HIP_TRY(hipMemcpyAsync(out_indices + (size_t)w0 * k, didx.p, nr * 8, hipMemcpyDeviceToHost, s));
-                MVF_HIP_TRY(hipMemcpyAsync(out_scores + (size_t)w0 * k, dsc.p, nr * 4, hipMemcpyDeviceToHost, s));
-                if (out_raw) MVF_HIP_TRY(hipMemcpyAsync(out_raw + (size_t)w0 * k, draw.p, nr * 4, hipMemcpyDeviceToHost, s));
-            }
-            return MVF_OK;
-        });
-        if (rc != MVF_OK) return rc;
-        MVF_HIP_TRY(hipStreamSynchronize(s));
-        if (pinned) {
-            std::memcpy(out_indices + (size_t)w0 * k, pin_out, nr * 8);
-            std::memcpy(out_scores + (size_t)w0 * k, pin_out + o_sc, nr * 4);
-            if (out_raw) std::memcpy(out_raw + (size_t)w0 * k, pin_out + o_raw, nr * 4);
-        }
-    }
-    return MVF_OK;
+    const HostIn in[] = {{queries, query_row_bytes(v)}};
+    const HostOut out[] = {{out_indices, (size_t)k * 8}, {out_scores, (size_t)k * 4}, {out_raw, (size_t)k * 4}};
+    return stage_host_windows(c, s, nq, in, out, stage_as_given, [&](uint32_t w0, uint32_t wn, void* const* d_in, void* const* d_out) {
+        return partitioned_core(v, part, metric, d_in[0], wn, keys + w0, k, static_cast<float*>(d_out[1]), static_cast<uint64_t*>(d_out[0]),
+                                static_cast<int32_t*>(d_out[2]), s);
+    });
 }
 
 int mvfgpu_selftest_partition_plan(const uint64_t* counts, const uint64_t* keys, uint32_t nq, uint32_t k, uint32_t* out_tier,

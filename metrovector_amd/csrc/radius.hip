@@ -134,9 +134,8 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
                          uint32_t nq, const float* radii, uint64_t max_per_query, uint64_t* out_counts, float* out_scores,
                          uint64_t* out_indices, int32_t* out_raw) {
     // everything that needs no handle first, then mvfgpu_search's own checks: nothing below touches the device on a refusal
-    if (const int mrc = check_metric(metric)) return mrc;
-    if (nq == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
-    if (!queries || !radii || !out_counts) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    // (its required buffers are the queries, the radii and the counts; it has no k)
+    if (const int rc = check_search_scalars(metric, nq, 1, queries, radii, out_counts)) return rc;
     if (max_per_query > MVFGPU_MAX_K) return set_fail(MVF_ERR_INVALID_ARGUMENT, "max_per_query must be in 0..2^31");
     if (max_per_query > 0 && (!out_scores || !out_indices))
         return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer (out_scores / out_indices are required when max_per_query > 0)");
@@ -151,13 +150,12 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
     const uint32_t cap = MVFGPU_RADIUS_LIST_CAP;
     const uint32_t kk = (uint32_t)std::min<uint64_t>(maxq, cap);  // entries R2 writes per query
     std::vector<uint32_t> over;  // queries whose list lost arrivals and that want entries
-    size_t qes = 4;
+    size_t qbytes = 0;  // of one query
 
     {
         std::lock_guard<std::mutex> lk(corpus_host_mutex(c));
         const CorpusView v = corpus_view(c);  // under the lock: mvfgpu_corpus_reload_tuning changes the tuning under it too
-        qes = is_int_dtype(v.dtype) ? 1 : 4;
-        const size_t qbytes = (size_t)v.dim * qes;
+        qbytes = query_row_bytes(v);
         std::vector<uint32_t> bound(nq);
         for (uint32_t q = 0; q < nq; q++) bound[q] = radius_bound_key(v.dtype, metric, radii[q], nullptr);
         hipStream_t s = static_cast<hipStream_t>(v.stream);
@@ -372,7 +370,6 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
         uint64_t kmax = 0;
         for (uint32_t q : over) kmax = std::max<uint64_t>(kmax, std::min<uint64_t>(out_counts[q], maxq));
         const uint32_t no = (uint32_t)over.size(), k = (uint32_t)kmax;
-        const size_t qbytes = (size_t)query_dim * qes;
         std::vector<unsigned char> qb((size_t)no * qbytes);
         for (uint32_t i = 0; i < no; i++)
             std::memcpy(qb.data() + (size_t)i * qbytes, static_cast<const unsigned char*>(queries) + (size_t)over[i] * qbytes, qbytes);

@@ -10,6 +10,7 @@
 #include "../../include/mvf_gpu.h"
 
 #include "internal.h"
+#include "scan_filter.h"
 
 namespace mvf {
 
@@ -55,6 +56,19 @@ struct GatherSource {
     bool prep_sorts = false;  // prep needs scratch.a / b / tmp
     std::function<int(uint32_t, uint32_t, const GatherScratch&)> prep;
 };
+// K1's one-query lane group of a handle's rows -- the gathered-row kernel scores with its bits -- with the bytes of a padded
+// query and the queries per block (GatherSource::qg) of a search that scores one list for all queries
+struct OneQueryGroup {
+    int G = 64;
+    uint32_t J = 1, qbytes = 0, qg = 1;
+};
+inline OneQueryGroup one_query_group(const CorpusView& v) {
+    OneQueryGroup g;
+    k1_group(v.V, 1, v.k1_g, &g.G, &g.J);
+    g.qbytes = cand_query_bytes(v.dtype, g.G, g.J);
+    g.qg = filter_group_queries(g.qbytes);
+    return g;
+}
 // The exact top-k of every query over its listed rows (m > 0), formatted as a search's results; in windows of queries so that
 // the scratch stays bounded, everything on `s`, no host wait.  k <= MVFGPU_K_PER_PASS and at most kSelectMaxLists chunks: each
 // chunk's sorted best k are merged and formatted by K3 (select_final_kernel); beyond, every position's rank entry is ranked by

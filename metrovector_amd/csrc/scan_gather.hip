@@ -245,7 +245,7 @@ int gather_topk(const CorpusView& v, uint8_t metric, const void* d_queries, uint
     int G = 64;
     uint32_t J = 1;
     k1_group(v.V, 1, v.k1_g, &G, &J);  // K1's one-query lane group: its bits
-    const size_t qrow = (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4);
+    const size_t qrow = query_row_bytes(v);
     const uint32_t nch = (m + kGatherChunk - 1) / kGatherChunk;
     const bool by_sort = k > MVFGPU_K_PER_PASS || nch > kSelectMaxLists;
     const bool sorts = by_sort || src.prep_sorts;

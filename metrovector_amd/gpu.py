@@ -136,6 +136,62 @@ def filter_route(rows: int, dim: int, data_type: int, nq: int, k: int, admitted:
     return out.value
 
 
+def _query_args(queries) -> tuple[np.ndarray, int, int, int]:
+    """(the queries as a contiguous 2-D array -- a 1-D array is one query --, their data type's code, nq, their dimension)"""
+    q = np.asarray(queries)
+    if q.ndim == 1:
+        q = q[None, :]
+    qcode = _CODE_OF.get(q.dtype)
+    if qcode is None:
+        raise BuildError(f"unsupported query dtype {q.dtype}")
+    q = np.ascontiguousarray(q)
+    return q, qcode, q.shape[0], q.shape[1]
+
+
+def _result_arrays(nq: int, k: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(scores, indices, raw) of a search, for the library to fill"""
+    return np.empty((nq, k), np.float32), np.empty((nq, k), np.uint64), np.empty((nq, k), np.int32)
+
+
+def _opt(p: int):
+    """an optional device pointer or stream: 0 is NULL"""
+    return C.c_void_p(p) if p else None
+
+
+class _OwnedHandle:
+    """What a GpuCorpus made and what is closed before it: the handle, the corpus it belongs to, and `_destroy`, the name of
+    the library function that frees it.  A context manager."""
+    _destroy = ""
+
+    def __init__(self, handle: int, corpus: "GpuCorpus"):
+        self._h = C.c_void_p(handle)
+        self._corpus = corpus  # keeps the handle it belongs to alive
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value and self._corpus._h is not None:
+            getattr(_lib.gpu(), self._destroy)(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _open_handle(obj, cls: type, what: str) -> C.c_void_p:
+    """the handle of `obj`, which must be an open `cls`"""
+    if not isinstance(obj, cls) or obj._h is None:
+        raise InvalidArgument(f"{what} must be an open {cls.__name__} of this corpus")
+    return obj._h
+
+
 def pack_allow_mask(allow, rows: int | None = None) -> np.ndarray:
     """The packed uint8 bitmap (`bitorder="little"`) of a filter's rows: a bool array has one entry per row and is packed;
     a uint8 array is taken as already packed.  `rows` (a bool mask's required length) is checked when given.  Anything else
@@ -152,13 +208,11 @@ def pack_allow_mask(allow, rows: int | None = None) -> np.ndarray:
     raise InvalidArgument(f"the allow mask must be a bool array over rows or a packed uint8 bitmap, got {a.dtype}")
 
 
-class GpuFilter:
+class GpuFilter(_OwnedHandle):
     """An immutable set of admitted rows of one GpuCorpus (`mvfgpu_filter`): made once by `GpuCorpus.make_filter`, used by
     any number of `search_filtered` calls, closed before its corpus.  A context manager."""
 
-    def __init__(self, handle: int, corpus: "GpuCorpus"):
-        self._h = C.c_void_p(handle)
-        self._corpus = corpus  # keeps the handle it belongs to alive
+    _destroy = "mvfgpu_filter_destroy"
 
     def info(self) -> _lib.FilterInfo:
         out = _lib.FilterInfo()
@@ -168,23 +222,6 @@ class GpuFilter:
     @property
     def admitted(self) -> int:
         return self.info().admitted
-
-    def close(self) -> None:
-        if self._h is not None and self._h.value and self._corpus._h is not None:
-            _lib.gpu().mvfgpu_filter_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 UINT32, UINT64 = 4, 5  # schema/types.fbs: the data types of a device column
@@ -202,13 +239,11 @@ def predicate_range(data_type: int, op: str | int, a: int = 0, b: int = 0) -> tu
     return lo.value, hi.value, neg.value
 
 
-class GpuColumn:
+class GpuColumn(_OwnedHandle):
     """One UInt32 / UInt64 value per row of one GpuCorpus, resident next to the rows (`mvfgpu_column`): made by
     `GpuCorpus.attach_column`, used by any number of `make_filter_where` calls, closed before its corpus.  A context manager."""
 
-    def __init__(self, handle: int, corpus: "GpuCorpus"):
-        self._h = C.c_void_p(handle)
-        self._corpus = corpus  # keeps the handle it belongs to alive
+    _destroy = "mvfgpu_column_destroy"
 
     def info(self) -> _lib.ColumnInfo:
         out = _lib.ColumnInfo()
@@ -225,31 +260,12 @@ class GpuColumn:
         _lib.gpu_check(_lib.gpu().mvfgpu_column_gather(self._h, idx.ctypes.data_as(C.c_void_p), idx.size, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def close(self) -> None:
-        if self._h is not None and self._h.value and self._corpus._h is not None:
-            _lib.gpu().mvfgpu_column_destroy(self._h)
-        self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class GpuPartition:
+class GpuPartition(_OwnedHandle):
     """The live rows of one GpuCorpus grouped by a column's value (`mvfgpu_partition`): made once by
     `GpuCorpus.make_partition`, used by any number of `search_partitioned` calls, closed before its corpus.  A context manager."""
 
-    def __init__(self, handle: int, corpus: "GpuCorpus"):
-        self._h = C.c_void_p(handle)
-        self._corpus = corpus  # keeps the handle it belongs to alive
+    _destroy = "mvfgpu_partition_destroy"
 
     def info(self) -> _lib.PartitionInfo:
         out = _lib.PartitionInfo()
@@ -269,23 +285,6 @@ class GpuPartition:
         kk, cnt = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         _lib.gpu_check(_lib.gpu().mvfgpu_partition_keys(self._h, 0, n, kk.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
         return kk, cnt
-
-    def close(self) -> None:
-        if self._h is not None and self._h.value and self._corpus._h is not None:
-            _lib.gpu().mvfgpu_partition_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def partition_plan(counts, keys, k: int) -> tuple[np.ndarray, int]:
@@ -336,12 +335,11 @@ def _pack_clauses(clauses) -> tuple[C.Array, list]:
         if not isinstance(cl, (tuple, list)) or len(cl) != 3:
             raise InvalidArgument("a clause is (column, op, operand)")
         col, op, operand = cl
-        if not isinstance(col, GpuColumn) or col._h is None:
-            raise InvalidArgument("a clause's column must be an open GpuColumn of this corpus")
+        hcol = _open_handle(col, GpuColumn, "a clause's column")
         code = _OP_OF.get(op) if isinstance(op, str) else None
         if code is None:
             raise InvalidArgument(f"unknown predicate op {op!r}: one of {', '.join(_OP_OF)}")
-        arr[i].column, arr[i].op = col._h, code
+        arr[i].column, arr[i].op = hcol, code
         if code in (_lib.OP_IN, _lib.OP_NOT_IN):
             if isinstance(operand, np.ndarray) and operand.dtype == np.uint64 and operand.ndim == 1:
                 vals = np.ascontiguousarray(operand)
@@ -479,17 +477,8 @@ class GpuCorpus:
     # ---- search ----------------------------------------------------------------
     def search(self, queries: np.ndarray, k: int, metric: int = L2) -> SearchResult:
         """Host-buffer search (`mvfgpu_search`)."""
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        qcode = _CODE_OF.get(q.dtype)
-        if qcode is None:
-            raise BuildError(f"unsupported query dtype {q.dtype}")
-        q = np.ascontiguousarray(q)
-        nq, qdim = q.shape
-        sc = np.empty((nq, k), np.float32)
-        idx = np.empty((nq, k), np.uint64)
-        raw = np.empty((nq, k), np.int32)
+        q, qcode, nq, qdim = _query_args(queries)
+        sc, idx, raw = _result_arrays(nq, k)
         _lib.gpu_check(_lib.gpu().mvfgpu_search(self._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
                                                 sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
                                                 raw.ctypes.data_as(C.c_void_p)))
@@ -498,18 +487,9 @@ class GpuCorpus:
     def search_fetch(self, queries: np.ndarray, k: int, metric: int = L2) -> tuple[SearchResult, np.ndarray]:
         """Search + payload in one call (`mvfgpu_search_fetch`): the results and the rows they name, [nq, k, dimension] in
         the stored type (zero rows behind a short result list)."""
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        qcode = _CODE_OF.get(q.dtype)
-        if qcode is None:
-            raise BuildError(f"unsupported query dtype {q.dtype}")
-        q = np.ascontiguousarray(q)
-        nq, qdim = q.shape
+        q, qcode, nq, qdim = _query_args(queries)
         _, dim, dt = self._fixed()
-        sc = np.empty((nq, k), np.float32)
-        idx = np.empty((nq, k), np.uint64)
-        raw = np.empty((nq, k), np.int32)
+        sc, idx, raw = _result_arrays(nq, k)
         vec = np.zeros((nq, k, dim), _NP_OF[dt])  # zeros, not empty: the library writes min(k, rows) rows per query; untouched pages stay unmapped
         _lib.gpu_check(_lib.gpu().mvfgpu_search_fetch(self._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
                                                       sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
@@ -519,22 +499,13 @@ class GpuCorpus:
     def search_radius(self, queries: np.ndarray, radius, max_per_query: int, metric: int = L2) -> RadiusResult:
         """Every row within `radius` of each query (`mvfgpu_search_radius`): L2 distance <= radius, InnerProduct /
         Cosine score >= radius.  `radius` is a scalar or one value per query; `max_per_query` = 0 asks for counts only."""
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        qcode = _CODE_OF.get(q.dtype)
-        if qcode is None:
-            raise BuildError(f"unsupported query dtype {q.dtype}")
-        q = np.ascontiguousarray(q)
-        nq, qdim = q.shape
+        q, qcode, nq, qdim = _query_args(queries)
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (nq,)), np.float32)
         m = int(max_per_query)
         if m < 0:
             raise InvalidArgument("max_per_query must be >= 0")
         counts = np.zeros(nq, np.uint64)
-        sc = np.empty((nq, m), np.float32)
-        idx = np.empty((nq, m), np.uint64)
-        raw = np.empty((nq, m), np.int32)
+        sc, idx, raw = _result_arrays(nq, m)
         ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if m else (lambda a: None)
         _lib.gpu_check(_lib.gpu().mvfgpu_search_radius(self._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
                                                        r.ctypes.data_as(C.c_void_p), m, counts.ctypes.data_as(C.c_void_p),
@@ -545,14 +516,7 @@ class GpuCorpus:
         """The exact top-k of each query over its own list of rows (`mvfgpu_search_candidates`): `candidates` is a 2-D
         [nq, m] uint64 array of global positions, or vector ids when ids are attached; UINT64_MAX pads a short list.
         Entries this shard does not hold and deleted rows are skipped, a row listed twice counts once."""
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        qcode = _CODE_OF.get(q.dtype)
-        if qcode is None:
-            raise BuildError(f"unsupported query dtype {q.dtype}")
-        q = np.ascontiguousarray(q)
-        nq, qdim = q.shape
+        q, qcode, nq, qdim = _query_args(queries)
         cand = candidates if isinstance(candidates, np.ndarray) else np.asarray(candidates)
         if cand.ndim != 2 or cand.dtype != np.uint64:
             raise InvalidArgument(f"candidates must be a 2-D uint64 array [nq, m], got {cand.dtype} of shape {cand.shape}")
@@ -562,9 +526,7 @@ class GpuCorpus:
             raise InvalidArgument("at most 2^32 - 1 candidates per query")
         cand = np.ascontiguousarray(cand)
         m = cand.shape[1]
-        sc = np.empty((nq, k), np.float32)
-        idx = np.empty((nq, k), np.uint64)
-        raw = np.empty((nq, k), np.int32)
+        sc, idx, raw = _result_arrays(nq, k)
         counts = np.zeros(nq, np.uint64)
         _lib.gpu_check(_lib.gpu().mvfgpu_search_candidates(self._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
                                                            cand.ctypes.data_as(C.c_void_p) if m else None, m, k,
@@ -577,10 +539,9 @@ class GpuCorpus:
                                  stream: int = 0) -> None:
         """Device-pointer candidate search (`mvfgpu_search_candidates_device`), asynchronous on `stream`; the lists are
         global positions."""
-        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
         _lib.gpu_check(_lib.gpu().mvfgpu_search_candidates_device(self._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
-                                                                  nq, opt(d_candidates), m, k, C.c_void_p(d_scores),
-                                                                  C.c_void_p(d_indices), opt(d_raw), opt(d_counts), opt(stream)))
+                                                                  nq, _opt(d_candidates), m, k, C.c_void_p(d_scores),
+                                                                  C.c_void_p(d_indices), _opt(d_raw), _opt(d_counts), _opt(stream)))
 
     def knn_join(self, k: int, metric: int = L2, first: int = 0, count: int | None = None,
                  queries_from: "GpuCorpus | None" = None, exclude_self: bool = True) -> SearchResult:
@@ -592,9 +553,7 @@ class GpuCorpus:
             count = src.rows - first
         if first < 0 or count < 0:
             raise InvalidArgument("first and count must be >= 0")
-        sc = np.empty((count, k), np.float32)
-        idx = np.empty((count, k), np.uint64)
-        raw = np.empty((count, k), np.int32)
+        sc, idx, raw = _result_arrays(count, k)
         _lib.gpu_check(_lib.gpu().mvfgpu_knn_join(self._h, None if queries_from is None else queries_from._h, metric, first, count, k,
                                                   JOIN_EXCLUDE_SELF if exclude_self else 0, sc.ctypes.data_as(C.c_void_p),
                                                   idx.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p)))
@@ -604,10 +563,9 @@ class GpuCorpus:
                         queries_from: "GpuCorpus | None" = None, exclude_self: bool = True, stream: int = 0) -> None:
         """Device-pointer join (`mvfgpu_knn_join_device`): [count, k] results in device memory, every window enqueued on
         `stream` without a host wait."""
-        opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
         _lib.gpu_check(_lib.gpu().mvfgpu_knn_join_device(self._h, None if queries_from is None else queries_from._h, metric, first,
-                                                         count, k, JOIN_EXCLUDE_SELF if exclude_self else 0, opt(d_scores),
-                                                         opt(d_indices), opt(d_raw), opt(stream)))
+                                                         count, k, JOIN_EXCLUDE_SELF if exclude_self else 0, _opt(d_scores),
+                                                         _opt(d_indices), _opt(d_raw), _opt(stream)))
 
     # ---- filtered search ---------------------------------------------------------
     def make_filter(self, allow, first_bit: int = 0) -> GpuFilter:
@@ -632,7 +590,7 @@ class GpuCorpus:
         if not d_words:
             raise InvalidArgument("d_words is a NULL device pointer")
         h = C.c_void_p()
-        _lib.gpu_check(_lib.gpu().mvfgpu_filter_create_device(self._h, C.c_void_p(d_words), C.c_void_p(stream) if stream else None,
+        _lib.gpu_check(_lib.gpu().mvfgpu_filter_create_device(self._h, C.c_void_p(d_words), _opt(stream),
                                                               C.byref(h)))
         return GpuFilter(h.value, self)
 
@@ -667,7 +625,7 @@ class GpuCorpus:
             raise InvalidArgument("ptr is a NULL device pointer")
         h = C.c_void_p()
         _lib.gpu_check(_lib.gpu().mvfgpu_column_create_device(self._h, C.c_void_p(ptr), int(data_type),
-                                                              C.c_void_p(stream) if stream else None, C.byref(h)))
+                                                              _opt(stream), C.byref(h)))
         return GpuColumn(h.value, self)
 
     def make_filter_where(self, clauses, any: bool = False, base: GpuFilter | None = None) -> GpuFilter:  # noqa: A002
@@ -677,12 +635,11 @@ class GpuCorpus:
         row where given, and rows deleted now are never admitted.  The result is an ordinary GpuFilter."""
         clauses = list(clauses)
         arr, keep = _pack_clauses(clauses)
-        if base is not None and (not isinstance(base, GpuFilter) or base._h is None):
-            raise InvalidArgument("base must be an open GpuFilter of this corpus")
+        hbase = None if base is None else _open_handle(base, GpuFilter, "base")
         h = C.c_void_p()
         _lib.gpu_check(_lib.gpu().mvfgpu_filter_create_where(self._h, arr, len(clauses),
                                                              _lib.WHERE_ANY if any else _lib.WHERE_ALL,
-                                                             None if base is None else base._h, C.byref(h)))
+                                                             hbase, C.byref(h)))
         del keep
         return GpuFilter(h.value, self)
 
@@ -700,20 +657,10 @@ class GpuCorpus:
 
     def search_filtered(self, queries: np.ndarray, k: int, metric: int, flt: GpuFilter) -> SearchResult:
         """The exact top-k among the rows `flt` admits (`mvfgpu_search_filtered`): `search`'s results in every respect."""
-        if not isinstance(flt, GpuFilter) or flt._h is None:
-            raise InvalidArgument("flt must be an open GpuFilter of this corpus")
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        qcode = _CODE_OF.get(q.dtype)
-        if qcode is None:
-            raise BuildError(f"unsupported query dtype {q.dtype}")
-        q = np.ascontiguousarray(q)
-        nq, qdim = q.shape
-        sc = np.empty((nq, k), np.float32)
-        idx = np.empty((nq, k), np.uint64)
-        raw = np.empty((nq, k), np.int32)
-        _lib.gpu_check(_lib.gpu().mvfgpu_search_filtered(self._h, flt._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
+        hflt = _open_handle(flt, GpuFilter, "flt")
+        q, qcode, nq, qdim = _query_args(queries)
+        sc, idx, raw = _result_arrays(nq, k)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_filtered(self._h, hflt, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
                                                          sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
                                                          raw.ctypes.data_as(C.c_void_p)))
         return SearchResult(sc, idx, raw)
@@ -721,43 +668,29 @@ class GpuCorpus:
     def search_filtered_device(self, flt: GpuFilter, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
                                d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
         """Device-pointer filtered search (`mvfgpu_search_filtered_device`), asynchronous on `stream`."""
-        if not isinstance(flt, GpuFilter) or flt._h is None:
-            raise InvalidArgument("flt must be an open GpuFilter of this corpus")
-        _lib.gpu_check(_lib.gpu().mvfgpu_search_filtered_device(self._h, flt._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
+        hflt = _open_handle(flt, GpuFilter, "flt")
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_filtered_device(self._h, hflt, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                 nq, k, C.c_void_p(d_scores), C.c_void_p(d_indices),
-                                                                C.c_void_p(d_raw) if d_raw else None,
-                                                                C.c_void_p(stream) if stream else None))
+                                                                _opt(d_raw), _opt(stream)))
 
     # ---- partitioned search: one key per query -------------------------------------------
     def make_partition(self, column: GpuColumn) -> GpuPartition:
         """The index of this corpus' live rows grouped by `column`'s value (`mvfgpu_partition_create`); rows deleted now are
         not in it, and a later `set_tombstones` makes it stale."""
-        if not isinstance(column, GpuColumn) or column._h is None:
-            raise InvalidArgument("column must be an open GpuColumn of this corpus")
         h = C.c_void_p()
-        _lib.gpu_check(_lib.gpu().mvfgpu_partition_create(self._h, column._h, C.byref(h)))
+        _lib.gpu_check(_lib.gpu().mvfgpu_partition_create(self._h, _open_handle(column, GpuColumn, "column"), C.byref(h)))
         return GpuPartition(h.value, self)
 
     def search_partitioned(self, queries: np.ndarray, keys, k: int, metric: int, part: GpuPartition) -> SearchResult:
         """The exact top-k of every query among the live rows whose column value equals the query's own key
         (`mvfgpu_search_partitioned`): `search`'s results in every respect; a key no live row carries gives padding."""
-        if not isinstance(part, GpuPartition) or part._h is None:
-            raise InvalidArgument("part must be an open GpuPartition of this corpus")
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        qcode = _CODE_OF.get(q.dtype)
-        if qcode is None:
-            raise BuildError(f"unsupported query dtype {q.dtype}")
-        q = np.ascontiguousarray(q)
-        nq, qdim = q.shape
+        hpart = _open_handle(part, GpuPartition, "part")
+        q, qcode, nq, qdim = _query_args(queries)
         kk = _keys_u64(keys)
         if kk.size != nq:
             raise InvalidArgument(f"{kk.size} keys for {nq} queries: a partitioned search takes one key per query")
-        sc = np.empty((nq, k), np.float32)
-        idx = np.empty((nq, k), np.uint64)
-        raw = np.empty((nq, k), np.int32)
-        _lib.gpu_check(_lib.gpu().mvfgpu_search_partitioned(self._h, part._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
+        sc, idx, raw = _result_arrays(nq, k)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_partitioned(self._h, hpart, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
                                                             kk.ctypes.data_as(C.c_void_p), k, sc.ctypes.data_as(C.c_void_p),
                                                             idx.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p)))
         return SearchResult(sc, idx, raw)
@@ -766,35 +699,23 @@ class GpuCorpus:
                                   metric: int, d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
         """Device-pointer partitioned search (`mvfgpu_search_partitioned_device`), asynchronous on `stream`; `keys` is a host
         array, read before the call returns."""
-        if not isinstance(part, GpuPartition) or part._h is None:
-            raise InvalidArgument("part must be an open GpuPartition of this corpus")
+        hpart = _open_handle(part, GpuPartition, "part")
         kk = _keys_u64(keys)
         if kk.size != nq:
             raise InvalidArgument(f"{kk.size} keys for {nq} queries: a partitioned search takes one key per query")
-        _lib.gpu_check(_lib.gpu().mvfgpu_search_partitioned_device(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype,
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_partitioned_device(self._h, hpart, metric, C.c_void_p(d_queries), query_dtype,
                                                                    query_dim, nq, kk.ctypes.data_as(C.c_void_p), k,
                                                                    C.c_void_p(d_scores), C.c_void_p(d_indices),
-                                                                   C.c_void_p(d_raw) if d_raw else None,
-                                                                   C.c_void_p(stream) if stream else None))
+                                                                   _opt(d_raw), _opt(stream)))
 
     # ---- grouped search: at most per_key results per key ----------------------------------
     def search_grouped(self, queries: np.ndarray, k: int, per_key: int, metric: int, part: GpuPartition) -> SearchResult:
         """The exact top-k of every query with at most `per_key` rows of any one key of `part` (`mvfgpu_search_grouped`):
         `search`'s results in every respect over the rows the partition holds; `GpuColumn.gather` gives the hits' keys."""
-        if not isinstance(part, GpuPartition) or part._h is None:
-            raise InvalidArgument("part must be an open GpuPartition of this corpus")
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        qcode = _CODE_OF.get(q.dtype)
-        if qcode is None:
-            raise BuildError(f"unsupported query dtype {q.dtype}")
-        q = np.ascontiguousarray(q)
-        nq, qdim = q.shape
-        sc = np.empty((nq, k), np.float32)
-        idx = np.empty((nq, k), np.uint64)
-        raw = np.empty((nq, k), np.int32)
-        _lib.gpu_check(_lib.gpu().mvfgpu_search_grouped(self._h, part._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
+        hpart = _open_handle(part, GpuPartition, "part")
+        q, qcode, nq, qdim = _query_args(queries)
+        sc, idx, raw = _result_arrays(nq, k)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_grouped(self._h, hpart, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
                                                         per_key, sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
                                                         raw.ctypes.data_as(C.c_void_p)))
         return SearchResult(sc, idx, raw)
@@ -802,12 +723,10 @@ class GpuCorpus:
     def search_grouped_device(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int,
                               per_key: int, metric: int, d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
         """Device-pointer grouped search (`mvfgpu_search_grouped_device`), asynchronous on `stream`."""
-        if not isinstance(part, GpuPartition) or part._h is None:
-            raise InvalidArgument("part must be an open GpuPartition of this corpus")
-        _lib.gpu_check(_lib.gpu().mvfgpu_search_grouped_device(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
+        hpart = _open_handle(part, GpuPartition, "part")
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_grouped_device(self._h, hpart, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                nq, k, per_key, C.c_void_p(d_scores), C.c_void_p(d_indices),
-                                                               C.c_void_p(d_raw) if d_raw else None,
-                                                               C.c_void_p(stream) if stream else None))
+                                                               _opt(d_raw), _opt(stream)))
 
     def grouped_stage_ms(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, per_key: int,
                          metric: int, d_scores: int, d_indices: int, stream: int = 0) -> tuple[float, float, float, float]:
@@ -816,7 +735,7 @@ class GpuCorpus:
         out = (C.c_float * 4)()
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_grouped_stage_ms(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                    nq, k, per_key, C.c_void_p(d_scores), C.c_void_p(d_indices),
-                                                                   C.c_void_p(stream) if stream else None, out))
+                                                                   _opt(stream), out))
         return tuple(float(x) for x in out)
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,
@@ -824,8 +743,7 @@ class GpuCorpus:
         """Device-pointer search (`mvfgpu_search_device`), asynchronous on `stream`."""
         _lib.gpu_check(_lib.gpu().mvfgpu_search_device(self._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                        nq, k, C.c_void_p(d_scores), C.c_void_p(d_indices),
-                                                       C.c_void_p(d_raw) if d_raw else None,
-                                                       C.c_void_p(stream) if stream else None))
+                                                       _opt(d_raw), _opt(stream)))
 
     # ---- profiling -------------------------------------------------------------
     def set_profiling(self, enabled: bool) -> None:
@@ -883,17 +801,8 @@ class ShardSet:
         return out
 
     def search(self, queries: np.ndarray, k: int, metric: int = L2) -> SearchResult:
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        qcode = _CODE_OF.get(q.dtype)
-        if qcode is None:
-            raise BuildError(f"unsupported query dtype {q.dtype}")
-        q = np.ascontiguousarray(q)
-        nq, qdim = q.shape
-        sc = np.empty((nq, k), np.float32)
-        idx = np.empty((nq, k), np.uint64)
-        raw = np.empty((nq, k), np.int32)
+        q, qcode, nq, qdim = _query_args(queries)
+        sc, idx, raw = _result_arrays(nq, k)
         _lib.gpu_check(_lib.gpu().mvfgpu_shardset_search(self._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
                                                          sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
                                                          raw.ctypes.data_as(C.c_void_p)))
@@ -908,9 +817,7 @@ def merge_topk_host(scores: np.ndarray, indices: np.ndarray, raw: np.ndarray | N
     nl, nq, k = scores.shape
     if raw is not None:
         raw = np.ascontiguousarray(raw, np.int32)
-    sc = np.empty((nq, k), np.float32)
-    idx = np.empty((nq, k), np.uint64)
-    rw = np.empty((nq, k), np.int32)
+    sc, idx, rw = _result_arrays(nq, k)
     _lib.gpu_check(_lib.gpu().mvfgpu_merge_topk_host(
         scores.ctypes.data_as(C.c_void_p), indices.ctypes.data_as(C.c_void_p),
         raw.ctypes.data_as(C.c_void_p) if raw is not None else None, nl, nq, k, metric, data_type,

@@ -198,6 +198,27 @@ def test_per_query_counts_next_to_full_chunks(oracle, dtype, metric, k):
         assert alone.raw.tobytes() == res.raw[:1].tobytes() and alone.counts[0] == res.counts[0]
 
 
+def test_a_second_host_window(oracle):
+    """The host-buffer calls of the list searches stage their queries, lists and results in windows of at most 256 MiB of
+    device copies (csrc/host_staging.h: kHostWindowBytes = 256 MiB; windows of up to kPinnedBytes = 1 MiB travel through
+    the handle's pinned mirrors).  Lists of 20000 entries make a query 160680 bytes, a window 1670 queries: 1700 queries
+    are windows of 1670 and 30.  The queries on both sides of the seam answer as they do alone, every count is right."""
+    n, dim, m, k, nq, metric = 4001, 128, 20000, 10, 1700, G.L2
+    W = (256 << 20) // (dim * 4 + m * 8 + k * 16 + 8)
+    assert W == 1670 and W < nq < 2 * W
+    rows = oracle.synth_rows(151, 0, n, dim, G.FLOAT32)
+    qs = oracle.synth_queries(152, nq, dim, G.FLOAT32)
+    lists = _lists(np.random.default_rng(15), n, nq, m)
+    with G.GpuCorpus.from_array(rows) as c:
+        res = c.search_candidates(qs, lists, k, metric)
+        for j in (0, W - 1, W, nq - 1):
+            alone = c.search_candidates(qs[j:j + 1], lists[j:j + 1], k, metric)
+            for name in ("scores", "indices", "raw", "counts"):
+                assert getattr(alone, name).tobytes() == getattr(res, name)[j:j + 1].tobytes(), f"{name} of query {j}"
+    for j in range(nq):
+        assert int(res.counts[j]) == candidate_rows(lists[j], n).size, f"count of query {j}"
+
+
 def test_ids_in_the_host_call_and_nothing_listed(oracle):
     n, dim = 3001, 24
     rows = oracle.synth_rows(91, 0, n, dim, G.INT8)

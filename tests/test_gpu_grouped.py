@@ -396,6 +396,21 @@ def test_more_queries_than_one_window(worlds):
         same_bytes(G.SearchResult(res.scores[j0:j0 + 100], res.indices[j0:j0 + 100], res.raw[j0:j0 + 100]), part, f"queries from {j0} of 1100")
 
 
+def test_a_host_window_beyond_the_pinned_mirrors_equals_its_pinned_slices(worlds):
+    """256 queries at k = 300 are 256 x 300 x 16 B = 1.17 MiB of results: over the 1 MiB up to which a host window travels
+    through the handle's pinned mirrors, so the call copies from and to the caller's buffers.  Slices of 32 queries (150 KiB)
+    take the mirrors; a query's row does not depend on its batch, so every byte is the same."""
+    w = worlds("f32", 8, "stock", "u32")
+    nq, k, per_key = 256, 300, 3
+    assert nq * k * 16 > 1 << 20 >= 32 * (k * 16 + 8 * 4)
+    q = P.make_queries(nq, 8, "f32")
+    whole = w.c.search_grouped(q, k, per_key, L2, w.part)
+    for j0 in range(0, nq, 32):
+        part = w.c.search_grouped(q[j0:j0 + 32], k, per_key, L2, w.part)
+        for name in ("scores", "indices", "raw"):
+            assert getattr(whole, name)[j0:j0 + 32].tobytes() == getattr(part, name).tobytes(), f"{name} of queries from {j0}"
+
+
 def test_a_fresh_process_gives_the_checked_answer_whatever_its_allocations_held(worlds, tmp_path):
     """the scenario of tests/_grouped.py with the grouped search as a child's first device work: plain, then with every
     allocation of the library filled with 0x00 and with 0xFF; one child at a time, none after a fault"""

@@ -192,6 +192,22 @@ def test_more_queries_than_one_window(oracle, worlds):
     check_batch(oracle, w, P.make_queries(1500, 8, "f32"), keys, 10, L2, "1500 queries")
 
 
+def test_a_host_window_beyond_the_pinned_mirrors_equals_its_pinned_slices(worlds):
+    """256 queries at k = 300 are 256 x 300 x 16 B = 1.17 MiB of results: over the 1 MiB up to which a host window travels
+    through the handle's pinned mirrors, so the call copies from and to the caller's buffers.  Slices of 32 queries (150 KiB)
+    take the mirrors; a query's row does not depend on its batch, so every byte is the same."""
+    w = worlds("f32", 8, "u32")
+    nq, k = 256, 300
+    assert nq * k * 16 > 1 << 20 >= 32 * (k * 16 + 8 * 4)
+    q, keys = P.make_queries(nq, 8, "f32"), P.mixed_keys(w.lay, nq)
+    assert w.lay["absent_key"] in keys.tolist()
+    whole = w.c.search_partitioned(q, keys, k, L2, w.part)
+    for j0 in range(0, nq, 32):
+        part = w.c.search_partitioned(q[j0:j0 + 32], keys[j0:j0 + 32], k, L2, w.part)
+        for name in ("scores", "indices", "raw"):
+            assert getattr(whole, name)[j0:j0 + 32].tobytes() == getattr(part, name).tobytes(), f"{name} of queries from {j0}"
+
+
 def test_vector_ids_and_index_base(oracle):
     ids = (np.random.default_rng(3).permutation(P.N).astype(np.uint64) * np.uint64(7) + np.uint64(5))
     w = World("i8", 64, "u64", index_base=1000, ids=ids)

@@ -90,6 +90,72 @@ def test_refusals_without_a_handle_precede_any_device_call_in_the_searchs_order(
     assert lib.mvfgpu_selftest_group_plan(p1, p1, 1, 1, None) == INV and _msg()
 
 
+_ONE = np.zeros(4, np.uint64)
+_P1 = _ONE.ctypes.data_as(C.c_void_p)
+_NAN, _RADII = np.full(1, np.nan, np.float32), np.ones(1, np.float32)
+_FAKE = C.c_void_p(16)  # a filter / partition that is never dereferenced: `corpus is NULL` is found first
+_BUFFERS = dict(q=_P1, sc=_P1, idx=_P1)
+_PER_KEY_0 = "per_key must be in 1..64, got 0"
+
+
+def _topk_ladder(own):
+    """everything wrong at once, then one fix after the other: (the message reported, the fix that follows it)"""
+    return [("unsupported distance metric code 9", dict(metric=0)), ("nq must be > 0", dict(nq=1)),
+            ("k must be in 1..2^31", dict(k=1)), ("NULL buffer", _BUFFERS)] + own
+
+
+def _candidates(device):
+    fn = getattr(_lib.gpu(), "mvfgpu_search_candidates" + ("_device" if device else ""))
+    return (lambda a: fn(None, a["metric"], a["q"], 0, 4, a["nq"], a["cand"], 5, a["k"], a["sc"], a["idx"], None, None, *[None] * device),
+            dict(cand=None), _topk_ladder([("NULL buffer (candidates)", dict(cand=_P1))]))
+
+
+def _filtered(device):
+    fn = getattr(_lib.gpu(), "mvfgpu_search_filtered" + ("_device" if device else ""))
+    return (lambda a: fn(None, a["flt"], a["metric"], a["q"], 0, 4, a["nq"], a["k"], a["sc"], a["idx"], None, *[None] * device),
+            dict(flt=None), _topk_ladder([("filter is NULL", dict(flt=_FAKE))]))
+
+
+def _partitioned(device):
+    fn = getattr(_lib.gpu(), "mvfgpu_search_partitioned" + ("_device" if device else ""))
+    return (lambda a: fn(None, a["part"], a["metric"], a["q"], 0, 4, a["nq"], a["keys"], a["k"], a["sc"], a["idx"], None, *[None] * device),
+            dict(part=None, keys=None), _topk_ladder([("NULL buffer (keys)", dict(keys=_P1)), ("partition is NULL", dict(part=_FAKE))]))
+
+
+def _grouped(device):
+    fn = getattr(_lib.gpu(), "mvfgpu_search_grouped" + ("_device" if device else ""))
+    return (lambda a: fn(None, a["part"], a["metric"], a["q"], 0, 4, a["nq"], a["k"], a["per_key"], a["sc"], a["idx"], None, *[None] * device),
+            dict(part=None, per_key=0), _topk_ladder([(_PER_KEY_0, dict(per_key=1)), ("partition is NULL", dict(part=_FAKE))]))
+
+
+def _radius(device):
+    """its three required buffers are the queries, the radii and the counts, and they come before its own range of
+    max_per_query (`k` here); the result buffers are required only where entries are asked for"""
+    fn = _lib.gpu().mvfgpu_search_radius
+    nan, radii = _NAN.ctypes.data_as(C.c_void_p), _RADII.ctypes.data_as(C.c_void_p)
+    return (lambda a: fn(None, a["metric"], a["q"], 0, 4, a["nq"], a["radii"], a["k"], a["counts"], a["sc"], a["idx"], None),
+            dict(radii=None, counts=None, k=(1 << 31) + 1),
+            [("unsupported distance metric code 9", dict(metric=0)), ("nq must be > 0", dict(nq=1)),
+             ("NULL buffer", dict(q=_P1, radii=nan, counts=_P1)), ("max_per_query must be in 0..2^31", dict(k=1)),
+             ("NULL buffer (out_scores / out_indices are required when max_per_query > 0)", dict(sc=_P1, idx=_P1)),
+             ("radius of query 0 is NaN", dict(radii=radii))])
+
+
+@pytest.mark.parametrize("make,device", [(_candidates, 0), (_candidates, 1), (_filtered, 0), (_filtered, 1), (_partitioned, 0),
+                                         (_partitioned, 1), (_grouped, 0), (_grouped, 1), (_radius, 0)],
+                         ids=lambda v: v.__name__.strip("_") if callable(v) else ("device" if v else "host"))
+def test_refusal_precedence_of_every_list_search_without_a_handle(make, device):
+    """corpus = NULL and every other argument bad as well: the metric is named first, then nq, the range of k, the required
+    buffers, the call's own argument(s), and `corpus is NULL` only once all of them are valid -- code and message at every
+    step.  The radius search names its buffers before its own range, as it always has."""
+    call, own, ladder = make(device)
+    state = {**dict(metric=9, nq=0, k=0, q=None, sc=None, idx=None), **own}
+    for message, fix in ladder:
+        assert call(state) == INV and _msg() == message, (message, _msg())
+        state = {**state, **fix}
+    assert call(state) == INV and _msg() == "corpus is NULL", _msg()
+
+
 def test_the_tier_rule_at_every_boundary():
     for per_key in GR.PER_KEYS:
         lengths = sorted({1, per_key - 1, per_key, per_key + 1, GR.RANK_MAX - 1, GR.RANK_MAX, GR.RANK_MAX + 1, GR.TILE - 1, GR.TILE} - {0})
