@@ -99,6 +99,15 @@ __device__ __forceinline__ void bitonic_sort_u64_reg(uint64_t* buf, uint32_t P, 
     __syncthreads();
 }
 
+// A block of 1024 threads sorts buf[0 .. P): in registers while four entries per thread hold the list, through LDS beyond.
+// On entry and on return as bitonic_sort_u64_reg.
+__device__ __forceinline__ void bitonic_sort_u64_1024(uint64_t* buf, uint32_t P, int tid) {
+    if (P <= 1024) bitonic_sort_u64_reg<1024, 1>(buf, P, tid);
+    else if (P <= 2048) bitonic_sort_u64_reg<1024, 2>(buf, P, tid);
+    else if (P <= 4096) bitonic_sort_u64_reg<1024, 4>(buf, P, tid);
+    else bitonic_sort_u64<1024>(buf, P, tid);
+}
+
 // Merge of a few new composites into a short sorted list, by counting instead of sorting: buf[0 .. kp) ascending (kp <= NT),
 // buf[kp .. kp + c) in any order (c <= NT), all composites distinct; afterwards buf[0 .. min(kp + c, k)) holds the smallest
 // of them ascending (whatever ranks at k or behind is dropped).  An element's place = the number of elements in front of it:

@@ -141,6 +141,14 @@ __device__ __forceinline__ uint32_t block_counts_1024(uint32_t wave_count, uint3
     return tot;
 }
 
+// The sum of `v` over the 1024 threads of a block, returned to every thread; wsum as above.
+__device__ __forceinline__ uint32_t block_sum_1024(uint32_t v, uint32_t* wsum) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    uint32_t before;
+    return block_counts_1024(v, wsum, &before);
+}
+
 // The same for one flag per thread: *rank = the threads in front of the caller that raise `keep`; returns how many do.
 __device__ __forceinline__ uint32_t block_rank_1024(bool keep, uint32_t* wsum, uint32_t* rank) {
     const unsigned long long bm = __builtin_amdgcn_ballot_w64(keep);
@@ -148,6 +156,23 @@ __device__ __forceinline__ uint32_t block_rank_1024(bool keep, uint32_t* wsum, u
     const uint32_t tot = block_counts_1024((uint32_t)__builtin_popcountll(bm), wsum, &before);
     *rank = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
     return tot;
+}
+
+// Block compaction: a block of 1024 threads walks the indices [lo, hi) (block-uniform) in steps of 1024 and calls
+// emit(i, slot) for every i that keep(i) admits, slot = base + the admitted indices in front of i -- the kept ones in
+// ascending order from `base` on.  Returns base + their count to every thread.  wsum: 16 words of LDS.
+template <class I, class Keep, class Emit>
+__device__ __forceinline__ I block_compact_1024(I lo, I hi, I base, uint32_t* wsum, Keep keep, Emit emit) {
+    for (I t0 = lo; t0 < hi; t0 += 1024u) {
+        const I i = t0 + threadIdx.x;
+        const bool kept = i < hi && keep(i);
+        uint32_t rank;
+        const uint32_t tot = block_rank_1024(kept, wsum, &rank);
+        if (kept) emit(i, base + rank);
+        base += tot;
+        __syncthreads();
+    }
+    return base;
 }
 
 }  // namespace mvf

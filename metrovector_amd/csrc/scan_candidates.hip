@@ -31,21 +31,12 @@ __device__ __forceinline__ uint32_t local_row(uint64_t g, const CandPrepParams& 
 // get(i): the list's row i.  wsum: 16 words of LDS.
 template <class Get>
 __device__ __forceinline__ void compact_rows(Get get, uint32_t m, uint32_t* out, uint32_t* cnt, uint64_t* cnt64, uint32_t* wsum) {
-    const uint32_t tid = threadIdx.x;
-    uint32_t base = 0;
-    for (uint32_t t0 = 0; t0 < m; t0 += 1024) {
-        const uint32_t i = t0 + tid;
-        const uint32_t r = i < m ? get(i) : kDeadRow;
-        const bool keep = r != kDeadRow && (i == 0 || get(i - 1) != r);
-        uint32_t rank;
-        const uint32_t tot = block_rank_1024(keep, wsum, &rank);
-        if (keep) out[base + rank] = r;
-        base += tot;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        *cnt = base;
-        if (cnt64) *cnt64 = base;
+    const uint32_t kept = block_compact_1024(
+        0u, m, 0u, wsum, [&](uint32_t i) { return get(i) != kDeadRow && (i == 0 || get(i - 1) != get(i)); },
+        [&](uint32_t i, uint32_t slot) { out[slot] = get(i); });
+    if (threadIdx.x == 0) {
+        *cnt = kept;
+        if (cnt64) *cnt64 = kept;
     }
 }
 
@@ -59,10 +50,7 @@ __global__ void __launch_bounds__(1024) cand_prep_kernel(CandPrepParams p) {
     const uint64_t* c = p.cand + (size_t)q * p.m;
     for (uint32_t i = tid; i < P; i += 1024) buf[i] = i < p.m ? (uint64_t)local_row(c[i], p) : (uint64_t)kDeadRow;
     __syncthreads();
-    if (P <= 1024) bitonic_sort_u64_reg<1024, 1>(buf, P, (int)tid);
-    else if (P <= 2048) bitonic_sort_u64_reg<1024, 2>(buf, P, (int)tid);
-    else if (P <= 4096) bitonic_sort_u64_reg<1024, 4>(buf, P, (int)tid);
-    else bitonic_sort_u64<1024>(buf, P, (int)tid);
+    bitonic_sort_u64_1024(buf, P, (int)tid);
     compact_rows([&](uint32_t i) { return (uint32_t)buf[i]; }, p.m, p.rows + (size_t)q * p.m, p.counts + q,
                  p.out_counts ? p.out_counts + q : nullptr, wsum);
 }

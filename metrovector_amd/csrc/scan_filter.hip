@@ -5,8 +5,8 @@
 // F0 re-bases the caller's bits to local rows -- a word of the mask is a funnel of two adjacent words of the upload, shifted by
 // 0 .. 31 -- and combines them with the handle's tombstones: deny = ~allow | tomb, zero at and beyond the last row, which is
 // the layout every scan kernel already takes as its deletion bitmap.  A block covers kFilterBlockRows rows and leaves their
-// admitted count.  F1 scans those counts and scatters every block's admitted rows in ascending order: a ballot per wave, the
-// waves' counts through LDS -- no sort.
+// admitted count.  F1 scans those counts and scatters every block's admitted rows in ascending order with the block compaction
+// (mvf_common.h: block_compact_1024; a ballot per wave, the waves' counts through LDS) -- no sort.
 
 #include "scan_filter.h"
 #include "aux_kernels.h"
@@ -17,14 +17,6 @@
 
 namespace mvf {
 namespace {
-
-// the sum of `v` over the 1024 threads of a block, returned to every thread; wsum: 16 words of LDS
-__device__ __forceinline__ uint32_t block_sum_1024(uint32_t v, uint32_t* wsum) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    uint32_t before;
-    return block_counts_1024(v, wsum, &before);
-}
 
 // F0: grid (filter_blocks(n)), block 1024; thread t of block b owns word b * 1024 + t of the mask
 __global__ void __launch_bounds__(1024) filter_mask_kernel(FilterMaskParams p) {
@@ -81,19 +73,10 @@ __global__ void __launch_bounds__(1024) filter_scan_kernel(const uint32_t* block
 // F1, step 2: grid (filter_blocks(n)), block 1024; block b scatters the admitted rows of [b, b + 1) * kFilterBlockRows
 __global__ void __launch_bounds__(1024) filter_compact_kernel(const uint32_t* deny, uint64_t n, const uint64_t* block_off, uint32_t* list) {
     __shared__ uint32_t wsum[16];
-    const uint32_t tid = threadIdx.x;
-    uint64_t base = block_off[blockIdx.x];
     const uint64_t r0 = (uint64_t)blockIdx.x * kFilterBlockRows;
-    for (uint32_t t0 = 0; t0 < kFilterBlockRows; t0 += 1024u) {
-        if (r0 + t0 >= n) break;  // block-uniform
-        const uint64_t r = r0 + t0 + tid;
-        const bool keep = r < n && !((deny[r >> 5] >> (r & 31u)) & 1u);
-        uint32_t rank;
-        const uint32_t tot = block_rank_1024(keep, wsum, &rank);
-        if (keep) list[base + rank] = (uint32_t)r;
-        base += tot;
-        __syncthreads();
-    }
+    block_compact_1024(
+        r0, min(r0 + kFilterBlockRows, n), block_off[blockIdx.x], wsum, [&](uint64_t r) { return !((deny[r >> 5] >> (r & 31u)) & 1u); },
+        [&](uint64_t r, uint64_t slot) { list[slot] = (uint32_t)r; });
 }
 
 }  // namespace

@@ -8,7 +8,7 @@
 namespace mvf {
 
 constexpr uint32_t kPartBlockRows = 8192;  // rows (or sorted entries) one 1024-thread block of the build kernels covers
-constexpr int kPartSortItems = 8, kPartSortTile = 256 * kPartSortItems;  // the pair sort: entries per thread / per block tile
+constexpr int kPartSortTile = 2048;        // pairs per block tile of the pair sort (radix_pass.h: kRsTile)
 inline uint32_t part_blocks(uint64_t n) { return (uint32_t)((n + kPartBlockRows - 1) / kPartBlockRows); }
 inline uint32_t part_sort_tiles(uint64_t m) { return (uint32_t)((m + kPartSortTile - 1) / kPartSortTile); }
 

@@ -2,12 +2,12 @@
 // "Partitioned search", §5 "B0 / B1 / B2 / S1 — partitioned search").
 //
 // Build.  B0 lays the live rows' (key, local row) pairs down in ascending position: a count per block (and the OR / AND of the
-// live keys, which tell the bits the keys differ in), F1's scan of the counts (scan_filter.hip), then a ballot per wave and
-// the waves' counts through LDS, as F1's compaction.  B1 is a stable LSD radix sort of the pairs by 8-bit digits of the 64-bit
-// key -- sort_topk.hip's histogram / scan / scatter restated for pairs (every 64-bit value is a legal key here; that file's
-// rank entries reserve two) -- which the host runs only for the digits the keys differ in.  The pairs arrive in position
-// order and the sort is stable, so the rows of a key stay in ascending position.  B2 flags the entries whose key differs from
-// the one in front, ranks the flags the same way and writes the key table.
+// live keys, which tell the bits the keys differ in), F1's scan of the counts (scan_filter.hip), then the block compaction
+// (mvf_common.h: block_compact_1024).  B1 is a stable LSD radix sort of the pairs by 8-bit digits of the 64-bit key -- the
+// radix pass of radix_pass.h, the digit taken from the whole key and the row moved as its payload (every 64-bit value is a
+// legal key here; sort_topk.hip's rank entries reserve two) -- which the host runs only for the digits the keys differ in.
+// The pairs arrive in position order and the sort is stable, so the rows of a key stay in ascending position.  B2 flags the
+// entries whose key differs from the one in front, compacts the flagged ones the same way and writes the key table.
 //
 // Search.  S1 is the gathered-row kernel (scan_gather.hip) for one query and one chunk per block: the block's list is a
 // segment of rows_by_key, its query lies anywhere in the caller's buffer.  The same staging loop, K1's per-row arithmetic
@@ -21,6 +21,7 @@
 #include "bitonic.h"
 #include "k1_rowscore.h"
 #include "mvf_common.h"
+#include "radix_pass.h"
 #include "scan_gather.h"
 
 namespace mvf {
@@ -49,16 +50,15 @@ __global__ void __launch_bounds__(1024) part_count_kernel(const void* values, bo
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-        cnt += __shfl_xor(cnt, off, 64);
         any |= __shfl_xor(any, off, 64);
         all &= __shfl_xor(all, off, 64);
     }
-    uint32_t before;
-    const uint32_t tot = block_counts_1024(cnt, wsum, &before);
-    if ((tid & 63u) == 0 && cnt) {
+    const bool wave_has_live = __builtin_amdgcn_ballot_w64(cnt != 0) != 0;
+    if ((tid & 63u) == 0 && wave_has_live) {
         atomicOr(reinterpret_cast<unsigned long long*>(&bits[0]), (unsigned long long)any);
         atomicAnd(reinterpret_cast<unsigned long long*>(&bits[1]), (unsigned long long)all);
     }
+    const uint32_t tot = block_sum_1024(cnt, wsum);
     if (tid == 0) block_cnt[blockIdx.x] = tot;
 }
 
@@ -66,139 +66,13 @@ __global__ void __launch_bounds__(1024) part_count_kernel(const void* values, bo
 __global__ void __launch_bounds__(1024) part_compact_kernel(const void* values, bool is_u64, uint64_t n, const uint32_t* tomb,
                                                             const uint64_t* block_off, uint64_t* keys, uint32_t* rows) {
     __shared__ uint32_t wsum[16];
-    const uint32_t tid = threadIdx.x;
-    uint64_t base = block_off[blockIdx.x];
     const uint64_t r0 = (uint64_t)blockIdx.x * kPartBlockRows;
-    for (uint32_t t0 = 0; t0 < kPartBlockRows; t0 += 1024u) {
-        if (r0 + t0 >= n) break;  // block-uniform
-        const uint64_t r = r0 + t0 + tid;
-        const bool keep = r < n && row_live(tomb, r);
-        uint32_t rank;
-        const uint32_t tot = block_rank_1024(keep, wsum, &rank);
-        if (keep) {
-            keys[base + rank] = key_at(values, is_u64, r);
-            rows[base + rank] = (uint32_t)r;
-        }
-        base += tot;
-        __syncthreads();
-    }
-}
-
-// ---- B1: one 8-bit pass of the stable LSD radix sort of (key, row) pairs (sort_topk.hip's rs_* kernels for pairs)
-__device__ __forceinline__ uint32_t digit_of(uint64_t key, int shift) { return (uint32_t)(key >> shift) & 255u; }
-
-// grid (tiles), block 256: bh[d * NB + tile] = entries of the tile with digit d
-__global__ void __launch_bounds__(256) part_hist_kernel(const uint64_t* keys, uint64_t m, int shift, uint32_t* bh, uint32_t NB) {
-    __shared__ uint32_t lh[256];
-    lh[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t t0 = (uint64_t)blockIdx.x * kPartSortTile;
-#pragma unroll
-    for (int r = 0; r < kPartSortItems; r++) {
-        const uint64_t i = t0 + (uint64_t)r * 256 + threadIdx.x;
-        if (i < m) atomicAdd(&lh[digit_of(keys[i], shift)], 1u);
-    }
-    __syncthreads();
-    bh[(size_t)threadIdx.x * NB + blockIdx.x] = lh[threadIdx.x];
-}
-
-// grid (256), block 256; block d: exclusive scan of digit d's per-tile counts in place, the digit's total to tot[d]
-__global__ void __launch_bounds__(256) part_digit_scan_kernel(uint32_t* bh, uint32_t NB, uint32_t* tot) {
-    __shared__ uint32_t part[256];
-    uint32_t* row = bh + (size_t)blockIdx.x * NB;
-    const uint32_t per = (NB + 255) / 256, lo = threadIdx.x * per;
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < lo + per && i < NB; i++) s += row[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int t = 0; t < 256; t++) {
-            const uint32_t v = part[t];
-            part[t] = run;
-            run += v;
-        }
-        tot[blockIdx.x] = run;
-    }
-    __syncthreads();
-    uint32_t run = part[threadIdx.x];
-    for (uint32_t i = lo; i < lo + per && i < NB; i++) {
-        const uint32_t v = row[i];
-        row[i] = run;
-        run += v;
-    }
-}
-
-// grid (tiles), block 256.  Wave w owns the tile's entries [w TW, (w + 1) TW) and walks them in rounds of 64: a lane's rank
-// among the entries of its digit = the wave's running count of the digit (LDS) + its rank among the round's lanes with that
-// digit (one ballot per digit bit).  Waves in order, rounds in order, lanes in order: stable.
-__global__ void __launch_bounds__(256) part_scatter_pairs_kernel(const uint64_t* keys_in, const uint32_t* rows_in, uint64_t* keys_out,
-                                                                  uint32_t* rows_out, uint64_t m, int shift, const uint32_t* bh,
-                                                                  const uint32_t* tot, uint32_t NB) {
-    __shared__ uint32_t dbase[256];  // digit d's first output slot + what the tiles in front of this one hold of it
-    __shared__ uint32_t cw[4][256];  // per wave: running count per digit, then the wave's offset inside the tile's share
-    __shared__ uint32_t part[256];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    {
-        const uint32_t total = tot[tid];
-        part[tid] = total;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t run = 0;
-            for (int t = 0; t < 256; t++) {
-                const uint32_t v = part[t];
-                part[t] = run;
-                run += v;
-            }
-        }
-        __syncthreads();
-        dbase[tid] = part[tid] + bh[(size_t)tid * NB + blockIdx.x];
-        for (int w = 0; w < 4; w++) cw[w][tid] = 0;
-        __syncthreads();
-    }
-    constexpr int TW = kPartSortTile / 4, ROUNDS = TW / 64;
-    const uint64_t w0 = (uint64_t)blockIdx.x * kPartSortTile + (uint64_t)wave * TW;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    uint64_t el[ROUNDS];
-    uint32_t er[ROUNDS], lr[ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ROUNDS; r++) {
-        const uint64_t i = w0 + (uint64_t)r * 64 + lane;
-        const bool valid = i < m;
-        el[r] = valid ? keys_in[i] : 0ull;
-        er[r] = valid ? rows_in[i] : 0u;
-        const uint32_t d = digit_of(el[r], shift);
-        unsigned long long peers = __builtin_amdgcn_ballot_w64(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const unsigned long long bm = __builtin_amdgcn_ballot_w64((d >> b) & 1u);
-            peers &= ((d >> b) & 1u) ? bm : ~bm;
-        }
-        const uint32_t rank = (uint32_t)__builtin_popcountll(peers & lt);
-        const uint32_t base = valid ? cw[wave][d] : 0u;  // a wave's LDS operations execute in order: every peer reads before the leader writes
-        if (valid && rank == 0) cw[wave][d] = base + (uint32_t)__builtin_popcountll(peers);
-        lr[r] = base + rank;
-    }
-    __syncthreads();
-    {
-        uint32_t run = 0;  // the waves' offsets inside the tile's share of the thread's digit
-        for (int w = 0; w < 4; w++) {
-            const uint32_t v = cw[w][tid];
-            cw[w][tid] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ROUNDS; r++) {
-        const uint64_t i = w0 + (uint64_t)r * 64 + lane;
-        if (i < m) {
-            const uint32_t d = digit_of(el[r], shift);
-            const size_t o = (size_t)dbase[d] + cw[wave][d] + lr[r];
-            keys_out[o] = el[r];
-            rows_out[o] = er[r];
-        }
-    }
+    block_compact_1024(
+        r0, min(r0 + kPartBlockRows, n), block_off[blockIdx.x], wsum, [&](uint64_t r) { return row_live(tomb, r); },
+        [&](uint64_t r, uint64_t slot) {
+            keys[slot] = key_at(values, is_u64, r);
+            rows[slot] = (uint32_t)r;
+        });
 }
 
 // ---- B2: the key table.  grid (part_blocks(m)), block 1024
@@ -210,33 +84,21 @@ __global__ void __launch_bounds__(1024) part_heads_count_kernel(const uint64_t* 
     const uint64_t i0 = (uint64_t)blockIdx.x * kPartBlockRows;
     uint32_t cnt = 0;
     for (uint32_t t0 = 0; t0 < kPartBlockRows; t0 += 1024u) cnt += is_head(keys, m, i0 + t0 + tid) ? 1u : 0u;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    uint32_t before;
-    const uint32_t tot = block_counts_1024(cnt, wsum, &before);
+    const uint32_t tot = block_sum_1024(cnt, wsum);
     if (tid == 0) block_cnt[blockIdx.x] = tot;
 }
 
 __global__ void __launch_bounds__(1024) part_heads_write_kernel(const uint64_t* keys, uint64_t m, const uint64_t* block_off, uint64_t* table_keys,
                                                                 uint64_t* table_off) {
     __shared__ uint32_t wsum[16];
-    const uint32_t tid = threadIdx.x;
-    uint64_t base = block_off[blockIdx.x];
-    const uint64_t i0 = (uint64_t)blockIdx.x * kPartBlockRows;
-    for (uint32_t t0 = 0; t0 < kPartBlockRows; t0 += 1024u) {
-        if (i0 + t0 >= m) break;  // block-uniform
-        const uint64_t i = i0 + t0 + tid;
-        const bool head = is_head(keys, m, i);
-        uint32_t rank;
-        const uint32_t tot = block_rank_1024(head, wsum, &rank);
-        if (head) {
-            table_keys[base + rank] = keys[i];
-            table_off[base + rank] = i;
-        }
-        base += tot;
-        if (i == m - 1) table_off[base] = m;  // the thread of the last entry: `base` now counts every head, n_keys
-        __syncthreads();
-    }
+    const uint64_t i0 = (uint64_t)blockIdx.x * kPartBlockRows, i1 = min(i0 + kPartBlockRows, m);
+    const uint64_t heads = block_compact_1024(
+        i0, i1, block_off[blockIdx.x], wsum, [&](uint64_t i) { return is_head(keys, m, i); },
+        [&](uint64_t i, uint64_t slot) {
+            table_keys[slot] = keys[i];
+            table_off[slot] = i;
+        });
+    if (i1 == m && threadIdx.x == 0) table_off[heads] = m;  // the block of the last entry: `heads` counts every head, n_keys
 }
 
 // ---- S1.  grid (n small-tier queries), block 256; dynamic LDS kGatherChunk * 8 (composites) + kGatherChunk * 4 (rows) + 16
@@ -411,10 +273,12 @@ hipError_t part_compact_launch(const void* values, bool is_u64, uint64_t n, cons
 hipError_t part_sort_pass_launch(const uint64_t* keys_in, const uint32_t* rows_in, uint64_t* keys_out, uint32_t* rows_out, uint64_t m, int shift,
                                  uint32_t* bh, uint32_t* tot, hipStream_t s) {
     if (m == 0) return hipSuccess;
-    const uint32_t NB = part_sort_tiles(m);
-    hipLaunchKernelGGL(part_hist_kernel, dim3(NB), dim3(256), 0, s, keys_in, m, shift, bh, NB);
-    hipLaunchKernelGGL(part_digit_scan_kernel, dim3(256), dim3(256), 0, s, bh, NB, tot);
-    hipLaunchKernelGGL(part_scatter_pairs_kernel, dim3(NB), dim3(256), 0, s, keys_in, rows_in, keys_out, rows_out, m, shift, bh, tot, NB);
+    static_assert(kPartSortTile == kRsTile, "part_sort_tiles() counts the shared pass's tiles");
+    const uint32_t NB = part_sort_tiles(m);  // one list: no batch, strides 0
+    hipLaunchKernelGGL((rs_hist_kernel<8, RsKeyDigit>), dim3(NB), dim3(256), 0, s, keys_in, m, shift, bh, NB, 0, 0);
+    hipLaunchKernelGGL(rs_scan_kernel, dim3(256), dim3(256), 0, s, bh, NB, tot, 0);
+    hipLaunchKernelGGL((rs_scatter_kernel<8, true, RsKeyDigit, true>), dim3(NB), dim3(256), 0, s, keys_in, keys_out, rows_in, rows_out, m, shift, bh,
+                       tot, NB, 0, 0);
     return hipGetLastError();
 }
 

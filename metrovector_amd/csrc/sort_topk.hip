@@ -23,13 +23,13 @@
 // Measured (profiles/r05_any_k.txt): 10M x 768 f32, one query, k = 16384: 5.21 ms (library sort of all 10M entries) -> 4.9-5.0.
 #include "aux_kernels.h"
 #include "bitonic.h"
+#include "radix_pass.h"
 
 namespace mvf {
 namespace {
 
 constexpr int kSelBins = 2048;                  // bins of a select pass (passes 0 / 1: 11 bits, pass 2: 10)
 constexpr uint32_t kSmallSort = 2048;           // entries one block sorts in LDS (bitonic network; 16384 took 0.12 ms, the radix passes 0.06)
-constexpr int kRsItems = 8, kRsTile = 256 * kRsItems;  // radix sort: entries per thread / per block tile
 constexpr uint32_t kRsFewBlocks = 64;           // up to this many tiles (131072 entries: L2-resident) the digits are 11 bits wide, three passes
 constexpr uint32_t kRsSelfSum = 16;             // up to this many tiles a scatter block sums the tiles in front of it itself (no scan launch)
 constexpr uint32_t kSelWavesMax = 4096;         // waves of the count / write passes (one contiguous run of entries each)
@@ -171,173 +171,26 @@ __global__ void __launch_bounds__(1024) sort_small_kernel(const uint64_t* in, ui
         buf[i] = i < m ? (ent << 32) | (ent >> 32) : ~0ull;  // rank entry -> (key' << 32 | position): distinct, their order is the result's
     }
     __syncthreads();
-    if (P <= 1024) bitonic_sort_u64_reg<1024, 1>(buf, P, threadIdx.x);
-    else if (P <= 2048) bitonic_sort_u64_reg<1024, 2>(buf, P, threadIdx.x);
-    else if (P <= 4096) bitonic_sort_u64_reg<1024, 4>(buf, P, threadIdx.x);
-    else bitonic_sort_u64<1024>(buf, P, threadIdx.x);
+    bitonic_sort_u64_1024(buf, P, threadIdx.x);
     for (uint32_t i = threadIdx.x; i < m; i += 1024) out[i] = (buf[i] << 32) | (buf[i] >> 32);
 }
 
-// ---- stable LSD radix sort on the key half: 8-bit digits (four passes) for long lists, 11-bit digits (three passes: 11 + 11 +
-// 10) for lists that stay in L2, where 2048 output streams per tile cost nothing ---------------------------------------------
-template <int BITS>
-__global__ void __launch_bounds__(256) rs_hist_kernel(const uint64_t* in, size_t m, int shift, uint32_t* bh, uint32_t NB, size_t stride,
-                                                       size_t bh_stride) {
-    constexpr int NBIN = 1 << BITS;
-    __shared__ uint32_t lh[NBIN];
-    in += (size_t)blockIdx.y * stride, bh += (size_t)blockIdx.y * bh_stride;
-    for (int i = threadIdx.x; i < NBIN; i += 256) lh[i] = 0;
-    __syncthreads();
-    const size_t t0 = (size_t)blockIdx.x * kRsTile;
-#pragma unroll
-    for (int r = 0; r < kRsItems; r++) {
-        const size_t i = t0 + (size_t)r * 256 + threadIdx.x;
-        if (i < m) atomicAdd(&lh[((uint32_t)in[i] >> shift) & (NBIN - 1)], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NBIN; i += 256) bh[(size_t)i * NB + blockIdx.x] = lh[i];
-}
-
-// block d: exclusive scan of digit d's per-block counts in place, the digit's total to tot[d]
-__global__ void __launch_bounds__(256) rs_scan_kernel(uint32_t* bh, uint32_t NB, uint32_t* tot, size_t bh_stride) {
-    __shared__ uint32_t part[256];
-    bh += (size_t)blockIdx.y * bh_stride, tot += (size_t)blockIdx.y * 2048;
-    uint32_t* row = bh + (size_t)blockIdx.x * NB;
-    const uint32_t per = (NB + 255) / 256, lo = threadIdx.x * per;
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < lo + per && i < NB; i++) s += row[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int t = 0; t < 256; t++) {
-            const uint32_t v = part[t];
-            part[t] = run;
-            run += v;
-        }
-        tot[blockIdx.x] = run;
-    }
-    __syncthreads();
-    uint32_t run = part[threadIdx.x];
-    for (uint32_t i = lo; i < lo + per && i < NB; i++) {
-        const uint32_t v = row[i];
-        row[i] = run;
-        run += v;
-    }
-}
-
-// Block b scatters its tile in order.  Wave w owns the tile's entries [w TW, (w + 1) TW) and walks them in rounds of 64: a
-// lane's rank among the entries of its digit = the wave's running count of the digit (LDS) + its rank among the round's lanes
-// with that digit (one ballot per digit bit).  Waves in order, rounds in order, lanes in order: stable.
-// SCANNED: bh holds the tiles' counts already scanned per digit and tot the digits' totals (rs_scan_kernel); otherwise (few
-// tiles) the block sums the raw counts of the tiles in front of it, and of all tiles, itself.
-template <int BITS, bool SCANNED>
-__global__ void __launch_bounds__(256) rs_scatter_kernel(const uint64_t* in, uint64_t* out, size_t m, int shift, const uint32_t* bh,
-                                                          const uint32_t* tot, uint32_t NB, size_t stride, size_t bh_stride) {
-    constexpr int NBIN = 1 << BITS, PER = NBIN / 256;
-    in += (size_t)blockIdx.y * stride, out += (size_t)blockIdx.y * stride, bh += (size_t)blockIdx.y * bh_stride, tot += (size_t)blockIdx.y * 2048;
-    __shared__ uint32_t dbase[NBIN];     // digit d's first output slot + what the tiles in front of this one hold of it
-    __shared__ uint32_t cw[4][NBIN];     // per wave: running count per digit, then the wave's offset inside the block's share
-    __shared__ uint32_t part[256];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    {
-        // digit totals and this tile's share: thread t owns digits [t PER, (t + 1) PER)
-        uint32_t mine = 0;
-        for (int x = 0; x < PER; x++) {
-            const int d = tid * PER + x;
-            uint32_t total, before;
-            if (SCANNED) {
-                total = tot[d];
-                before = bh[(size_t)d * NB + blockIdx.x];
-            } else {
-                total = before = 0;
-                for (uint32_t b = 0; b < NB; b++) {
-                    const uint32_t v = bh[(size_t)d * NB + b];
-                    total += v;
-                    before += b < blockIdx.x ? v : 0u;
-                }
-            }
-            cw[0][d] = total;
-            dbase[d] = before;
-            mine += total;
-        }
-        part[tid] = mine;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t run = 0;
-            for (int t = 0; t < 256; t++) {
-                const uint32_t v = part[t];
-                part[t] = run;
-                run += v;
-            }
-        }
-        __syncthreads();
-        uint32_t run = part[tid];
-        for (int x = 0; x < PER; x++) {
-            const int d = tid * PER + x;
-            const uint32_t total = cw[0][d];
-            dbase[d] += run;
-            run += total;
-        }
-        __syncthreads();
-        for (int w = 0; w < 4; w++)
-            for (int x = 0; x < PER; x++) cw[w][tid * PER + x] = 0;
-        __syncthreads();
-    }
-    constexpr int TW = kRsTile / 4, ROUNDS = TW / 64;
-    const size_t w0 = (size_t)blockIdx.x * kRsTile + (size_t)wave * TW;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    uint64_t el[ROUNDS];
-    uint32_t lr[ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ROUNDS; r++) {
-        const size_t i = w0 + (size_t)r * 64 + lane;
-        const bool valid = i < m;
-        el[r] = valid ? in[i] : 0ull;
-        const uint32_t d = ((uint32_t)el[r] >> shift) & (NBIN - 1);
-        unsigned long long peers = __builtin_amdgcn_ballot_w64(valid);
-#pragma unroll
-        for (int b = 0; b < BITS; b++) {
-            const unsigned long long bm = __builtin_amdgcn_ballot_w64((d >> b) & 1u);
-            peers &= ((d >> b) & 1u) ? bm : ~bm;
-        }
-        const uint32_t rank = (uint32_t)__builtin_popcountll(peers & lt);
-        const uint32_t base = valid ? cw[wave][d] : 0u;  // a wave's LDS operations execute in order: every peer reads before the leader writes
-        if (valid && rank == 0) cw[wave][d] = base + (uint32_t)__builtin_popcountll(peers);
-        lr[r] = base + rank;
-    }
-    __syncthreads();
-    for (int x = 0; x < PER; x++) {  // the waves' offsets inside the block's share of the thread's digits
-        const int d = tid * PER + x;
-        uint32_t run = 0;
-        for (int w = 0; w < 4; w++) {
-            const uint32_t v = cw[w][d];
-            cw[w][d] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ROUNDS; r++) {
-        const size_t i = w0 + (size_t)r * 64 + lane;
-        if (i < m) {
-            const uint32_t d = ((uint32_t)el[r] >> shift) & (NBIN - 1);
-            out[(size_t)dbase[d] + cw[wave][d] + lr[r]] = el[r];
-        }
-    }
-}
-
+// ---- stable LSD radix sort on the key half (radix_pass.h, the digit from the entry's low word): 8-bit digits (four passes) for
+// long lists, 11-bit digits (three passes: 11 + 11 + 10) for lists that stay in L2, where 2048 output streams per tile cost
+// nothing.  Up to kRsSelfSum tiles the scatter sums the tiles' counts itself: two launches a pass.
 template <int BITS>
 void radix_sort_entries(uint64_t*& cur, uint64_t*& oth, size_t m, uint32_t* bh, uint32_t* tot, size_t stride, uint32_t nb, size_t bh_stride,
                         hipStream_t s) {
     const uint32_t NB = (uint32_t)((m + kRsTile - 1) / kRsTile);
     for (int shift = 0; shift < 32; shift += BITS) {
-        hipLaunchKernelGGL(rs_hist_kernel<BITS>, dim3(NB, nb), dim3(256), 0, s, cur, m, shift, bh, NB, stride, bh_stride);
-        if (NB <= kRsSelfSum) {
-            hipLaunchKernelGGL((rs_scatter_kernel<BITS, false>), dim3(NB, nb), dim3(256), 0, s, cur, oth, m, shift, bh, tot, NB, stride, bh_stride);
+        hipLaunchKernelGGL((rs_hist_kernel<BITS, RsEntryDigit>), dim3(NB, nb), dim3(256), 0, s, cur, m, shift, bh, NB, stride, bh_stride);
+        if (NB <= kRsSelfSum) {  // (no payload: the entries carry their position themselves)
+            hipLaunchKernelGGL((rs_scatter_kernel<BITS, false, RsEntryDigit, false>), dim3(NB, nb), dim3(256), 0, s, cur, oth, nullptr, nullptr, m,
+                               shift, bh, tot, NB, stride, bh_stride);
         } else {
             hipLaunchKernelGGL(rs_scan_kernel, dim3(1 << BITS, nb), dim3(256), 0, s, bh, NB, tot, bh_stride);
-            hipLaunchKernelGGL((rs_scatter_kernel<BITS, true>), dim3(NB, nb), dim3(256), 0, s, cur, oth, m, shift, bh, tot, NB, stride, bh_stride);
+            hipLaunchKernelGGL((rs_scatter_kernel<BITS, true, RsEntryDigit, false>), dim3(NB, nb), dim3(256), 0, s, cur, oth, nullptr, nullptr, m,
+                               shift, bh, tot, NB, stride, bh_stride);
         }
         std::swap(cur, oth);
     }

@@ -79,6 +79,68 @@ def group_by(lay):
     return k, c.astype(np.uint64)
 
 
+# ---- layouts whose pair sort covers many tiles (scan_partition.h: kPartSortTile = 2048 pairs per block)
+WIDE_N, WIDE_KEYS, SORT_TILE = 40_000, 300, 2048
+WIDE_MID = 0x00A5C30F5A3C9600  # bits 8..55 of every key of "u64_two_digits"
+WIDE_KINDS = ("u64_two_digits", "u32_random", "one_key", "distinct")
+
+
+def wide_layout(kind, n=WIDE_N, live=None):
+    """-> dict(col, dead, big: the key that holds most live rows or None).  `live` None: every 10th position is dead (36 000
+    live rows of 40 000: 18 tiles); a number: exactly that many live rows, the dead ones drawn by a seeded permutation.
+      u64_two_digits  300 keys that differ only in bits 0..7 and 56..63 (two of the eight digits), one of them on about 70 %
+                      of the live rows, the others spread evenly: every key lies scattered over all positions
+      u32_random      the same shares over 300 random u32 values: all four digits differ
+      one_key         every live row carries one key (no digit differs); the dead rows carry others
+      distinct        every live row carries a key of its own
+    Dead rows carry values no live row has in bits 8..55 (u64) or at all (u32), and some carry live keys."""
+    rng = np.random.default_rng(_seed("wide", kind, n, live))
+    dead = np.zeros(n, bool)
+    if live is None:
+        dead[::10] = True
+    else:
+        dead[rng.permutation(n)[:n - live]] = True
+    m = int((~dead).sum())
+    u64 = kind != "u32_random"
+    if kind == "u64_two_digits":
+        cells = rng.choice(1 << 16, WIDE_KEYS, replace=False).astype(np.uint64)
+        values = np.uint64(WIDE_MID) | ((cells >> np.uint64(8)) << np.uint64(56)) | (cells & np.uint64(255))
+    elif kind == "u32_random":
+        values = np.unique(rng.integers(0, 1 << 32, 2 * WIDE_KEYS, dtype=np.uint64))[:WIDE_KEYS]
+        values = values[rng.permutation(values.size)]
+    elif kind == "one_key":
+        values = np.array([0x0123456789ABCDEF], np.uint64)
+    else:
+        values = np.unique(rng.integers(0, 1 << 63, 2 * m, dtype=np.uint64))[:m]
+        values = values[rng.permutation(m)]
+    if kind == "distinct":
+        which = np.arange(m)
+    elif values.size == 1:
+        which = np.zeros(m, np.int64)
+    else:
+        which = np.where(rng.random(m) < 0.7, 0, rng.integers(1, values.size, m))
+    col = np.zeros(n, np.uint64)
+    col[~dead] = values[which]
+    dead_pos = np.nonzero(dead)[0]
+    col[dead_pos] = (rng.integers(0, 1 << 63, dead_pos.size, dtype=np.uint64) | np.uint64(1 << 40)) if u64 else np.uint64(0xFFFFFFFF)
+    col[dead_pos[::3]] = values[rng.integers(0, values.size, dead_pos[::3].size)]  # dead rows inside live partitions
+    if not u64:
+        assert 0xFFFFFFFF not in values.tolist()
+    return dict(col=col.astype(np.uint64 if u64 else np.uint32), dead=dead, big=None if kind == "distinct" else int(values[0]))
+
+
+def sample_keys(lay, count=16):
+    """keys to search a wide layout by: the largest, the smallest, six whose run of the sorted pairs crosses, begins at or
+    ends at a tile edge (a multiple of SORT_TILE), then others evenly up to `count`"""
+    keys, counts = group_by(lay)
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    end = first + counts.astype(np.int64)
+    pick = [int(np.argmax(counts)), int(np.argmin(counts))]
+    pick += np.nonzero((first // SORT_TILE != (end - 1) // SORT_TILE) | (first % SORT_TILE == 0) | (end % SORT_TILE == 0))[0][1:7].tolist()
+    pick += np.linspace(0, keys.size - 1, count).astype(np.int64).tolist()
+    return [int(keys[i]) for i in list(dict.fromkeys(pick))[:count]]
+
+
 def mixed_keys(lay, nq=64):
     """one key per query: every sized partition, an absent key, the fully deleted key, further keys and repeats"""
     base = list(lay["keys"]) + [lay["absent_key"], lay["dead_key"]] + list(lay["all_keys"][len(lay["keys"]):len(lay["keys"]) + 8])

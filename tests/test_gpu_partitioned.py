@@ -174,6 +174,46 @@ def test_the_index_is_the_columns_group_by_over_the_live_rows(worlds, flavour):
         _lib.gpu_check(_lib.gpu().mvfgpu_partition_keys(w.part._h, inf.n_keys, 1, one.ctypes.data, one.ctypes.data))
 
 
+# The pair sort over many tiles: 18 (36 000 live rows of 40 000) for every kind of tests/_partitioned.py's wide layouts, and
+# the u64 keys of two differing digits with exactly 18 full tiles and one pair more
+WIDE = [(kind, None) for kind in P.WIDE_KINDS] + [("u64_two_digits", 18 * P.SORT_TILE), ("u64_two_digits", 18 * P.SORT_TILE + 1)]
+
+
+@pytest.mark.parametrize("kind,live", WIDE, ids=[f"{kind}-{live or 'tenth_dead'}" for kind, live in WIDE])
+def test_an_index_over_many_sort_tiles_is_the_group_by_and_serves_the_candidate_searchs_bytes(kind, live):
+    lay = P.wide_layout(kind, live=live)
+    keys, counts = P.group_by(lay)
+    n_live = int((~lay["dead"]).sum())
+    assert n_live == (live or 36_000) and -(-n_live // P.SORT_TILE) >= 18
+    if kind in ("u64_two_digits", "u32_random"):
+        assert keys.size == P.WIDE_KEYS and 0.68 < counts.max() / n_live < 0.72
+        differ = int(np.bitwise_or.reduce(keys) ^ np.bitwise_and.reduce(keys))
+        digits = [d for d in range(8) if (differ >> (8 * d)) & 255]
+        assert digits == ([0, 7] if kind == "u64_two_digits" else [0, 1, 2, 3]), "the digits the build sorts by"
+    else:
+        assert keys.size == (1 if kind == "one_key" else n_live)
+    w = World("i8", 16, None, n=P.WIDE_N, lay=lay)
+    try:
+        inf = w.part.info()
+        assert (inf.rows, inf.live_rows, inf.n_keys, inf.largest) == (P.WIDE_N, n_live, keys.size, int(counts.max()))
+        gk, gc = w.part.keys()
+        assert (gk == keys).all() and (gc == counts).all()
+        ask = np.concatenate([keys[:2000], lay["col"][lay["dead"]][:200].astype(np.uint64), np.array([(1 << 64) - 2], np.uint64)])
+        want = np.array([counts[i] if i < keys.size and keys[i] == a else 0 for a, i in zip(ask, np.searchsorted(keys, ask))], np.uint64)
+        assert (w.part.lookup(ask) == want).all()
+        picked = P.sample_keys(lay)
+        assert lay["big"] is None or lay["big"] in picked
+        q = P.make_queries(len(picked), 16, "i8")
+        for j, key in enumerate(picked):
+            r = w.ref(key)
+            k = min(r.size, 1024)
+            res = w.c.search_partitioned(q[j:j + 1], [key], k, L2, w.part)
+            same_bytes(res, w.c.search_candidates(q[j:j + 1], w.entries(r)[None, :], k, L2), f"{kind}, key {key:#x} ({r.size} rows)")
+            assert (res.indices[0] != PAD).all()
+    finally:
+        w.close()
+
+
 @pytest.mark.parametrize("case", range(len(CASES)), ids=[f"{dt}d{dim}m{m}" for dt, dim, m in CASES])
 def test_every_batch_equals_the_candidate_search_the_filtered_search_and_the_oracle(oracle, worlds, case):
     dt, dim, metric = CASES[case]
