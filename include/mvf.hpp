@@ -528,6 +528,44 @@ public:
             }
         return out;
     }
+    // The k best values of `column` -- documents of a corpus of token or passage vectors -- for ONE query of n_tokens vectors
+    // (mvfgpu_search_maxsim; DESIGN.md section 3, "Multi-vector search"): late interaction, a document's score being the sum
+    // over the query's vectors, in their order, of that vector's best score among the document's vectors.  query_vectors holds
+    // n_tokens x dimension floats; the column as in find_top_k_per_key.  -> (column value, score), best first, ties by
+    // ascending value; fewer than k where the column has fewer values among the live vectors.  The column and the index live
+    // for this call.
+    std::vector<std::pair<uint64_t, float>> find_top_k_documents(const std::vector<float>& query_vectors, size_t k,
+                                                                 const MetadataColumn& column) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "find_top_k_documents takes f32 queries: Float32 / Float16 spaces");
+        if (dim_ == 0 || query_vectors.empty() || query_vectors.size() % (size_t)dim_)
+            throw MvfError(MVF_ERR_DIMENSION_MISMATCH, "find_top_k_documents takes whole query vectors of the space's dimension");
+        const size_t n_tokens = query_vectors.size() / (size_t)dim_;
+        std::vector<std::pair<uint64_t, float>> out;
+        if (k == 0) return out;
+        mvfgpu_corpus_info inf;
+        MVFGPU_INIT(inf);
+        detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+        const uint64_t es = column.data_type == MVF_DTYPE_UINT32 ? 4 : column.data_type == MVF_DTYPE_UINT64 ? 8 : 0;
+        if (!es || column.size / es < inf.rows)
+            throw MvfError(MVF_ERR_BUILD, es ? "metadata column '" + column.name + "' holds fewer values than the space has vectors"
+                                             : "Unsupported metadata column data type");
+        mvfgpu_column* col = nullptr;
+        mvfgpu_partition* part = nullptr;
+        std::vector<float> scores(k);
+        std::vector<uint64_t> keys(k);
+        uint32_t count = 0;
+        int rc = mvfgpu_column_create(c_, column.data, column.data_type, 0, column.size / es, &col);
+        if (rc == MVF_OK) rc = mvfgpu_partition_create(c_, col, &part);
+        if (rc == MVF_OK)
+            rc = mvfgpu_search_maxsim(c_, part, (uint8_t)metric_, query_vectors.data(), MVF_DTYPE_FLOAT32, dim_, 1,
+                                      (uint32_t)std::min<size_t>(n_tokens, UINT32_MAX), (uint32_t)k, scores.data(), keys.data(), &count);
+        mvfgpu_partition_destroy(part);
+        mvfgpu_column_destroy(col);
+        detail::check_gpu(rc);
+        for (uint32_t i = 0; i < count; i++) out.emplace_back(keys[i], scores[i]);
+        return out;
+    }
     // The k-NN graph (mvfgpu_knn_join; DESIGN.md section 3, "Join"): for each of the rows [first, first + count) -- count
     // UINT64_MAX: to the end of the space -- its k nearest OTHER rows under the space's metric, best first.  A row is never its
     // own neighbour (decided by position: its exact duplicates are); a deleted row gets an empty list; fewer than k live

@@ -684,6 +684,65 @@ int mvfgpu_selftest_grouped_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_p
                                      const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t k,
                                      uint32_t per_key, float* d_scores, uint64_t* d_indices, void* hip_stream, float* out_ms);
 
+/* ---- multi-vector search: top-k keys by summed per-token best (MaxSim) --------- */
+
+/*
+ * mvfgpu_search_maxsim / mvfgpu_search_maxsim_device answer SETS of query vectors with KEYS of a partition index (DESIGN.md
+ * section 3, "Multi-vector search"): late interaction, as in ColBERT / ColPali-style retrieval.  The rows are the tokens or
+ * passages of documents, the column holds the document, a query is a set of T = n_tokens vectors, and a document's score is the
+ * sum over the query's vectors of that vector's best score among the document's rows.
+ *   queries     : [nq][n_tokens][query_dim], row-major; type and dimension rules are mvfgpu_search's.  n_tokens is
+ *                 1 .. MVFGPU_MAXSIM_MAX_TOKENS and the same for every set of a call (ragged sets: one call per length).
+ *   per-token best: for token t of set q and key g, b(t, g) is the score of the first row in mvfgpu_search's order for that
+ *                 token -- best first, NaN last, -0.0 == +0.0 -- among the rows the partition holds for g; NaN only when every
+ *                 row of g scores NaN.  Every row score is the one a one-query mvfgpu_search on the stored rows reports for
+ *                 (token, row): the candidate search's rule.  Int8 / UInt8 rows choose the best on the exact i32 order key.  The
+ *                 value is the score reconstructed from the order key, as in every result the library writes (+0.0 for +-0.0).
+ *   key score   : S(g) = ((b(0,g) + b(1,g)) + ...) + b(T-1,g): plain f32 additions in token order, not fused, not reassociated.
+ *                 Under L2 a sum of smallest distances.
+ *   result row  : the k best keys by key_from_score(S, metric) -- ascending S under L2, descending otherwise --, ties by ascending
+ *                 key value (the order of mvfgpu_partition_keys), NaN last.  out_scores[q][i] = S, out_keys[q][i] = the column
+ *                 value zero-extended to 64 bits.  Entries from min(k, n_keys) on are padding: key UINT64_MAX, score +inf (L2) or
+ *                 -inf.  out_counts[q] (nullable) = min(k, n_keys): it tells a real key UINT64_MAX from padding.  k is
+ *                 1 .. MVFGPU_MAX_K.  There is no out_raw: a sum of i32 scores can leave i32.
+ * Refusals, in this order, all before any device call and leaving no device error: mvfgpu_search's metric, nq, k and NULL-buffer
+ * checks; n_tokens 0 or above the maximum (MVF_ERR_INVALID_ARGUMENT, "n_tokens must be in 1..1024, got N"); a NULL partition; the
+ * handle checks; a partition of another handle or of an older tombstone generation, with the partitioned search's messages.
+ * No rows, no held rows or no keys give rows of padding and counts of 0.  The device call makes no host wait and is asynchronous on
+ * the caller's stream.  No repair feedback is read or posted (mvfgpu_corpus_info::selection_state stays).
+ * So, byte for byte: with R_t = mvfgpu_search_grouped(per_key = 1, k = n_keys) of token t and the hits' keys from
+ * mvfgpu_column_gather, summing R_t's scores per key in f32 in token order and ordering by (order key of the sum, key value)
+ * gives this call's score bits, keys and counts.
+ * Cost: the held rows leave HBM once per chunk of up to 32 tokens (fewer where the padded tokens exceed 40 KiB of LDS or the
+ * scratch, chunk x n_keys x 4 + n_keys x 20 bytes per query set, would exceed its budget) and query set.
+ * Not built: the arg-best rows per token; ragged token counts; per-token weights; a route over the selection shadows or the
+ * batched (MFMA) kernels; shard sets; a filter on top of the partition.
+ */
+#define MVFGPU_MAXSIM_MAX_TOKENS 1024u
+int mvfgpu_search_maxsim(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                         const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens,
+                         uint32_t k, float* out_scores, uint64_t* out_keys, uint32_t* out_counts);
+int mvfgpu_search_maxsim_device(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens,
+                                uint32_t k, float* d_scores, uint64_t* d_keys, uint32_t* d_counts, void* hip_stream);
+/*
+ * Self-test of the multi-vector search's scratch plan (no GPU needed): for n_keys keys, n_tokens tokens per set, nq sets, padded
+ * tokens of token_bytes in LDS and a scratch budget, the tokens per chunk and the query sets per window.  A chunk holds at most 32
+ * tokens, at most what 40 KiB of LDS take (a larger token is read through the cache) and at least one group of four tokens (all
+ * where there are fewer); chunk x n_keys x 4 + n_keys x 20 bytes per set of a window stay inside the budget wherever such a
+ * one-group chunk does.  The budget of a search is MVF_MAXSIM_SCRATCH_BYTES (default 512 MiB), read when the handle is created.
+ */
+int mvfgpu_selftest_maxsim_plan(uint64_t n_keys, uint32_t n_tokens, uint32_t nq, uint64_t token_bytes, uint64_t budget_bytes,
+                                uint32_t* tokens_per_chunk, uint32_t* sets_per_window);
+/*
+ * Stage timer of a multi-vector search (scripts/probe_maxsim.py): mvfgpu_search_maxsim_device without d_counts, with events between
+ * its stages; waits for the stream.  out_ms[0..3] = the key ordinals (once per call), M0 (scoring and per-key best), M1 (the sums),
+ * the tail (select, sort, format), each summed over the call's chunks and windows.
+ */
+int mvfgpu_selftest_maxsim_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                    const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens,
+                                    uint32_t k, float* d_scores, uint64_t* d_keys, void* hip_stream, float* out_ms);
+
 /*
  * Self-test of the host-side normalisation (no GPU needed): every operator but IN / NOT_IN (MVF_ERR_INVALID_ARGUMENT) becomes
  * one range test *out_lo <= v <= *out_hi on a column of `data_type`, negated where *out_negate is 1 (NE only).  The range is
@@ -898,7 +957,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * mvfgpu_filter_create_where, mvfgpu_selftest_predicate_range and mvfgpu_selftest_where_kernel_ms, nor did mvfgpu_selftest_poison, nor did the partitioned search, which only
  * adds mvfgpu_partition_*, mvfgpu_search_partitioned, mvfgpu_search_partitioned_device and mvfgpu_selftest_partition_plan, nor did
  * the grouped search, which only adds mvfgpu_search_grouped, mvfgpu_search_grouped_device, mvfgpu_column_gather,
- * mvfgpu_selftest_group_plan and mvfgpu_selftest_grouped_stage_ms).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * mvfgpu_selftest_group_plan and mvfgpu_selftest_grouped_stage_ms, nor did the multi-vector search, which only adds
+ * mvfgpu_search_maxsim, mvfgpu_search_maxsim_device, mvfgpu_selftest_maxsim_plan and mvfgpu_selftest_maxsim_stage_ms).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

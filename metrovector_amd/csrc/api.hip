@@ -149,6 +149,7 @@ Tuning read_tuning() {
     t.large_k = (int)std::min(2l, std::max(0l, num("MVF_LARGE_K", 0)));
     t.host_flag_wait = flag("MVF_HOST_FLAG_WAIT", true);
     t.filter_route = (int)std::min(2l, std::max(0l, num("MVF_FILTER_ROUTE", 0)));
+    t.maxsim_scratch = (size_t)std::max(1l, num("MVF_MAXSIM_SCRATCH_BYTES", 512l << 20));
     return t;
 }
 }  // namespace mvf
@@ -2250,6 +2251,7 @@ CorpusView corpus_view(const mvfgpu_corpus* c) {
     v.tomb = static_cast<const uint32_t*>(c->tomb.p);
     v.tomb_gen = c->tomb_gen;
     v.filter_route = c->tune.filter_route;
+    v.maxsim_scratch = c->tune.maxsim_scratch;
     v.ids = static_cast<const uint64_t*>(c->ids.p);
     v.stream = c->own_stream;
     v.scan_path = c->scan_path;

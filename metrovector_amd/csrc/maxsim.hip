@@ -1,0 +1,215 @@
+// maxsim.hip — mvfgpu_search_maxsim / mvfgpu_search_maxsim_device: the k best keys of a partition index for every SET of query
+// vectors, a key's score being the sum over the set's vectors of that vector's best score among the key's rows (late
+// interaction; include/mvf_gpu.h; DESIGN.md §3 "Multi-vector search", §5 "M0 / M1 — multi-vector search").
+//
+// Per window of query sets and chunk of tokens: M0 (scan_maxsim.hip) scores every row the index holds, in the index's key
+// order, against the chunk's tokens with K1's one-query bits and keeps the smallest order key per (token, key); M1 adds the
+// chunk's scores to every key's running sum in token order.  Behind the last chunk the keys' rank entries are ranked by the
+// whole-list select and sort (sort_topk.hip) and a writer maps ordinals to key values.  No host wait, no plan on the host but
+// the chunk and window sizes (maxsim_plan).  The host call runs the same device work per host window (host_staging.h).
+
+#include "../../include/mvf_gpu.h"
+
+#include "aux_kernels.h"
+#include "host_staging.h"
+#include "internal.h"
+#include "mvf_common.h"
+#include "scan_gather.h"
+#include "scan_maxsim.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+using namespace mvf;
+
+namespace {
+
+// the checks of both searches, none of which touches the device: the grouped search's, with n_tokens in per_key's place
+int check_maxsim_args(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries, uint8_t query_dtype,
+                      uint32_t query_dim, uint32_t nq, uint32_t n_tokens, uint32_t k, const void* out_scores, const void* out_keys) {
+    if (const int rc = check_search_scalars(metric, nq, k, queries, out_scores, out_keys)) return rc;
+    if (n_tokens == 0 || n_tokens > MVFGPU_MAXSIM_MAX_TOKENS)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT,
+                        "n_tokens must be in 1.." + std::to_string(MVFGPU_MAXSIM_MAX_TOKENS) + ", got " + std::to_string(n_tokens));
+    if (!part) return set_fail(MVF_ERR_INVALID_ARGUMENT, "partition is NULL");
+    if (const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_keys)) return rc;
+    return check_partition_use(c, part);
+}
+
+// the stage timer's events: one behind every stage of every chunk and window, with the stage it closes
+struct StageMarks {
+    std::vector<std::pair<int, hipEvent_t>> ev;
+    hipError_t mark(int stage, hipStream_t s) {
+        hipEvent_t e = nullptr;
+        hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) return rc;
+        ev.emplace_back(stage, e);
+        return hipEventRecord(e, s);
+    }
+    ~StageMarks() {
+        for (auto& m : ev) (void)hipEventDestroy(m.second);
+    }
+};
+
+// The device work of both calls: query sets and results in device memory; everything on `s`.  Runs under corpus_device_call.
+// marks (the stage timer only): stage 0 the ordinals, 1 M0, 2 M1, 3 the tail.
+int maxsim_core(const CorpusView& v, const PartitionView& pv, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t n_tokens,
+                uint32_t k, float* d_scores, uint64_t* d_keys, uint32_t* d_counts, hipStream_t s, StageMarks* marks = nullptr) {
+    if (v.n == 0 || pv.live == 0 || pv.n_keys == 0) {
+        if (d_counts) MVF_HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)nq * 4, s));
+        return fill_padding(metric, nq, k, d_scores, d_keys, nullptr, s);
+    }
+    const OneQueryGroup g1 = one_query_group(v);
+    const size_t set_bytes = query_row_bytes(v) * n_tokens;
+    const uint32_t live = (uint32_t)pv.live, nk = (uint32_t)pv.n_keys;  // n_keys <= live rows < 2^32
+    const MaxsimPlan pl = maxsim_plan(nk, n_tokens, nq, g1.qbytes, v.maxsim_scratch);
+    const uint32_t W = pl.window;
+    const size_t kk = std::min<size_t>(k, nk);
+    size_t tmp_bytes = 0;
+    MVF_HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, nk, kk, nullptr, s, W, nk));
+
+    AsyncBuf dord, dbest, dsum, da, db, dtmp;
+    MVF_HIP_TRY(dord.alloc((size_t)live * 4, s));
+    MVF_HIP_TRY(dbest.alloc((size_t)W * pl.chunk * nk * 4, s));
+    MVF_HIP_TRY(dsum.alloc((size_t)W * nk * 4, s));
+    MVF_HIP_TRY(da.alloc((size_t)W * nk * 8, s));
+    MVF_HIP_TRY(db.alloc((size_t)W * nk * 8, s));
+    MVF_HIP_TRY(dtmp.alloc(tmp_bytes, s));
+    if (marks) MVF_HIP_TRY(marks->mark(-1, s));
+    MVF_HIP_TRY(maxsim_ordinals_launch(pv.table + pv.n_keys, pv.n_keys, live, static_cast<uint32_t*>(dord.p), s));
+    if (marks) MVF_HIP_TRY(marks->mark(0, s));
+
+    for (uint32_t w0 = 0; w0 < nq; w0 += W) {
+        const uint32_t wn = std::min(W, nq - w0);
+        for (uint32_t t0 = 0; t0 < n_tokens; t0 += pl.chunk) {
+            const uint32_t tc = std::min(pl.chunk, n_tokens - t0);
+            // M0: the smallest order key of every (token of the chunk, key) to best[set][t][key], dead on entry
+            MVF_HIP_TRY(hipMemsetAsync(dbest.p, 0xFF, (size_t)wn * tc * nk * 4, s));
+            MaxsimScoreParams sp{};
+            sp.rows = v.rows;
+            sp.queries = static_cast<const unsigned char*>(d_queries) + (size_t)w0 * set_bytes;
+            sp.list = pv.rows_by_key;
+            sp.ord = static_cast<const uint32_t*>(dord.p);
+            sp.best = static_cast<uint32_t*>(dbest.p);
+            sp.m = live;
+            sp.n_keys = nk;
+            sp.sets = wn;
+            sp.n_tokens = n_tokens;
+            sp.t0 = t0;
+            sp.tc = tc;
+            sp.dim = v.dim;
+            sp.pitch = v.pitch;
+            sp.V = v.V;
+            sp.J = g1.J;
+            MVF_HIP_TRY(maxsim_score_launch(v.dtype, metric, g1.G, sp, s));
+            if (marks) MVF_HIP_TRY(marks->mark(1, s));
+            // M1: S[set][key] advances by the chunk's scores in token order; behind the last chunk the rank entries
+            MaxsimSumParams mp{};
+            mp.best = sp.best;
+            mp.sum = static_cast<float*>(dsum.p);
+            mp.rank = static_cast<uint64_t*>(da.p);
+            mp.n_keys = nk;
+            mp.sets = wn;
+            mp.tc = tc;
+            mp.metric = metric;
+            mp.dtype = v.dtype;
+            mp.first = t0 == 0;
+            mp.last = t0 + tc == n_tokens;
+            MVF_HIP_TRY(maxsim_sum_launch(mp, s));
+            if (marks) MVF_HIP_TRY(marks->mark(2, s));
+        }
+        // the tail: entries in ascending ordinal -- ascending key value --, as the sort takes them
+        size_t tb = tmp_bytes;
+        uint64_t* sorted = nullptr;
+        MVF_HIP_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), nk, kk, &sorted, s, wn, nk));
+        MaxsimWriteParams wp{};
+        wp.sorted = sorted;
+        wp.sum = static_cast<const float*>(dsum.p);
+        wp.keys = pv.table;
+        wp.out_scores = d_scores + (size_t)w0 * k;
+        wp.out_keys = d_keys + (size_t)w0 * k;
+        wp.out_counts = d_counts ? d_counts + w0 : nullptr;
+        wp.n_keys = nk;
+        wp.sets = wn;
+        wp.k = k;
+        wp.metric = metric;
+        MVF_HIP_TRY(maxsim_write_launch(wp, s));
+        if (marks) MVF_HIP_TRY(marks->mark(3, s));
+    }
+    return MVF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvfgpu_search_maxsim_device(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,
+                                uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens, uint32_t k, float* d_scores,
+                                uint64_t* d_keys, uint32_t* d_counts, void* hip_stream) {
+    const int rc = check_maxsim_args(c, part, metric, d_queries, query_dtype, query_dim, nq, n_tokens, k, d_scores, d_keys);
+    if (rc != MVF_OK) return rc;
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    return corpus_device_call(c, s, [&]() {
+        return maxsim_core(corpus_view(c), partition_view(part), metric, d_queries, nq, n_tokens, k, d_scores, d_keys, d_counts, s);
+    });
+}
+
+int mvfgpu_search_maxsim(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries, uint8_t query_dtype,
+                         uint32_t query_dim, uint32_t nq, uint32_t n_tokens, uint32_t k, float* out_scores, uint64_t* out_keys,
+                         uint32_t* out_counts) {
+    const int rc0 = check_maxsim_args(c, part, metric, queries, query_dtype, query_dim, nq, n_tokens, k, out_scores, out_keys);
+    if (rc0 != MVF_OK) return rc0;
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    std::lock_guard<std::mutex> host_lk(corpus_host_mutex(c));
+    const CorpusView v = corpus_view(c);
+    const PartitionView pv = partition_view(part);
+    hipStream_t s = static_cast<hipStream_t>(v.stream);
+    const HostIn in[] = {{queries, query_row_bytes(v) * n_tokens}};
+    const HostOut out[] = {{out_keys, (size_t)k * 8}, {out_scores, (size_t)k * 4}, {out_counts, 4}};
+    return stage_host_windows(c, s, nq, in, out, stage_as_given, [&](uint32_t, uint32_t wn, void* const* d_in, void* const* d_out) {
+        return maxsim_core(v, pv, metric, d_in[0], wn, n_tokens, k, static_cast<float*>(d_out[1]), static_cast<uint64_t*>(d_out[0]),
+                           static_cast<uint32_t*>(d_out[2]), s);
+    });
+}
+
+int mvfgpu_selftest_maxsim_stage_ms(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,
+                                    uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens, uint32_t k, float* d_scores,
+                                    uint64_t* d_keys, void* hip_stream, float* out_ms) {
+    if (!out_ms) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    const int rc0 = check_maxsim_args(c, part, metric, d_queries, query_dtype, query_dim, nq, n_tokens, k, d_scores, d_keys);
+    if (rc0 != MVF_OK) return rc0;
+    const PartitionView pv = partition_view(part);
+    if (corpus_view(c).n == 0 || pv.live == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "the stage timer needs held rows");
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    StageMarks marks;
+    int rc = corpus_device_call(c, s, [&]() { return maxsim_core(corpus_view(c), pv, metric, d_queries, nq, n_tokens, k, d_scores, d_keys, nullptr, s, &marks); });
+    if (rc == MVF_OK && hipStreamSynchronize(s) != hipSuccess) rc = set_fail(MVF_ERR_DEVICE, "hipStreamSynchronize failed");
+    for (int i = 0; i < 4; i++) out_ms[i] = 0.0f;
+    for (size_t i = 1; i < marks.ev.size() && rc == MVF_OK; i++) {  // every stage's time: from the event in front of it
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, marks.ev[i - 1].second, marks.ev[i].second) != hipSuccess) rc = set_fail(MVF_ERR_DEVICE, "hipEventElapsedTime failed");
+        else out_ms[marks.ev[i].first] += ms;
+    }
+    return rc;
+}
+
+int mvfgpu_selftest_maxsim_plan(uint64_t n_keys, uint32_t n_tokens, uint32_t nq, uint64_t token_bytes, uint64_t budget_bytes,
+                                uint32_t* tokens_per_chunk, uint32_t* sets_per_window) {
+    if (!tokens_per_chunk || !sets_per_window) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (n_tokens == 0 || n_tokens > MVFGPU_MAXSIM_MAX_TOKENS)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT,
+                        "n_tokens must be in 1.." + std::to_string(MVFGPU_MAXSIM_MAX_TOKENS) + ", got " + std::to_string(n_tokens));
+    if (nq == 0 || budget_bytes == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "empty batch or budget");
+    const MaxsimPlan pl = maxsim_plan(n_keys, n_tokens, nq, token_bytes, budget_bytes);
+    *tokens_per_chunk = pl.chunk;
+    *sets_per_window = pl.window;
+    return MVF_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,317 @@
+// scan_maxsim.hip — the kernels of the multi-vector search (DESIGN.md §3 "Multi-vector search", §5 "M0 / M1 — multi-vector
+// search"; maxsim.hip is the host side).
+//
+// M0 walks the partition's key-ordered row list in blocks of kMaxsimRows positions.  The chunk's tokens are staged as K1
+// stages one query (zero padded to J G vectors; sums of squares in K1's order), each G-lane group of K1's one-query shape
+// scores a row against the tokens, kMaxsimTokenGroup at a time, with K1's per-row arithmetic (k1_rowscore.h): for every
+// (token, row) the vectors advance j = 0 .. J-1, so the bits are K1's whatever the chunk.  Rows of up to kMaxsimRegSteps steps
+// are loaded ONCE (non-temporal 16-byte loads) and stay in registers over the whole chunk; longer rows are read again per token
+// group, through the cache.  The G partial sums of a step's (token, row) pairs meet in k1::group_sum's pairs and order, scattered
+// over the group's lanes (scatter_sum): one lane per pair makes the key.  What is kept is the smallest u32 order key per (token,
+// key): an LDS minimum per (token, key of the block) first, then one atomicMin per (token, run of the block) into
+// best[token][key ordinal].  A minimum does not depend on the order of its operands: the result is deterministic.
+// M1 adds the chunk's reconstructed scores to the running f32 sum of every key, in token order.
+//
+// Algorithmic HBM bytes of M0: the held rows' pitch once per chunk of tokens and query set (+ 8 bytes per held row and block).
+
+#include "scan_maxsim.h"
+#include "k1_rowscore.h"
+
+#include <algorithm>
+
+namespace mvf {
+namespace {
+
+__global__ void __launch_bounds__(256) maxsim_ordinals_kernel(const uint64_t* offsets, uint64_t n_keys, uint32_t live, uint32_t* ord) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= live) return;
+    uint64_t lo = 0, hi = n_keys;  // the last j with offsets[j] <= i; offsets[0] = 0
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (offsets[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    ord[i] = (uint32_t)lo;
+}
+
+// k1::group_sum over N values per lane at once: the G lanes' partial sums of every value meet in group_sum's pairs, in its
+// order (offsets G/2, G/4, .., 1) -- a + b is b + a, so every total has group_sum's bits -- but while a lane holds more than
+// one value, each step leaves it HALF of them: the lane whose `sub` has the offset's bit clear keeps the lower half, its
+// partner the upper half, and each sends the other half.  Behind it v[0 .. max(N / G, 1)) are the totals of the values
+// first, first + 1, ..; the G / N lanes that differ only in the low bits of `sub` hold the same ones (N <= G).  log2(N) +
+// N - 1 shuffles where N group_sums take N log2(G).
+template <int OFF, int N, int NV, typename T>
+__device__ __forceinline__ void scatter_sum(T (&v)[NV], int sub, int& first) {
+    if constexpr (OFF > 0) {
+        if constexpr (N > 1) {
+            constexpr int H = N / 2;
+            const bool upper = (sub & OFF) != 0;
+#pragma unroll
+            for (int i = 0; i < H; i++) {
+                const T keep = upper ? v[i + H] : v[i], send = upper ? v[i] : v[i + H];
+                v[i] = keep + __shfl_xor(send, OFF, 64);
+            }
+            first += upper ? H : 0;
+            scatter_sum<OFF / 2, H, NV>(v, sub, first);
+        } else {
+            v[0] += __shfl_xor(v[0], OFF, 64);
+            scatter_sum<OFF / 2, 1, NV>(v, sub, first);
+        }
+    }
+}
+
+// the bytes of M0's dynamic LDS in front of the tokens: minima [tc][kMaxsimRows], rows and local ordinals [kMaxsimRows] each,
+// qq partials [tc][4] and sums [tc]
+__host__ __device__ constexpr uint32_t maxsim_lds_head(uint32_t tc) { return tc * kMaxsimRows * 4u + kMaxsimRows * 8u + tc * 20u; }
+
+// grid (ceil(m / kMaxsimRows), sets), block 256; dynamic LDS maxsim_lds_head(tc) rounded up to 16 (+ tc padded tokens when QLDS)
+template <int DT, int METRIC, int G, bool REG, bool QLDS>
+__global__ void __launch_bounds__(256) maxsim_score_kernel(MaxsimScoreParams p) {
+    using Tr = k1::Traits<DT>;
+    using Acc = typename Tr::Acc;
+    using QT = typename Tr::Q;
+    constexpr int EPV = 16 / Tr::ES;
+    constexpr int RPG = 64 / G;
+    constexpr int U = REG ? 2 : 4;
+    constexpr int JR = REG ? (int)kMaxsimRegSteps : 1;
+    constexpr int TG = (int)kMaxsimTokenGroup;
+    constexpr bool NEED_XX = k1::kNeedXX<DT, METRIC>;
+    constexpr int NV = TG * U;                     // sums per lane and step: (token of the group, row)
+    constexpr int KEPT = NV > G ? NV / G : 1;      // .. that a lane holds behind scatter_sum
+    constexpr int SAME = NV > G ? 1 : G / NV;      // .. and neighbouring lanes that hold the same ones
+    static_assert(QLDS || !Tr::INT, "only float tokens are ever read through the cache");
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t tc = p.tc;
+    uint32_t* lmin = reinterpret_cast<uint32_t*>(smem);                         // [tc][kMaxsimRows] the block's minima
+    uint32_t* rowbuf = lmin + tc * kMaxsimRows;                                 // [kMaxsimRows] the block's rows
+    uint32_t* ordbuf = rowbuf + kMaxsimRows;                                    // [kMaxsimRows] .. and key ordinals - the first's
+    Acc* red = reinterpret_cast<Acc*>(ordbuf + kMaxsimRows);                    // [tc][4] qq partials
+    Acc* qqs = red + tc * 4;                                                    // [tc] the tokens' sums of squares
+    unsigned char* qs = smem + ((maxsim_lds_head(tc) + 15u) & ~15u);            // [tc][J G vectors] the tokens (QLDS)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sub = lane % G, rsel = lane / G;
+    const uint32_t c0 = blockIdx.x * kMaxsimRows, set = blockIdx.y;
+    const uint32_t nr = min(kMaxsimRows, p.m - c0);  // >= 1: the grid covers m
+
+    // ---- the tokens: K1's staging loop and sums of squares, one token after the other (k1::stage_queries' lines)
+    const uint32_t VP = p.J * G;
+    const size_t qstride = (size_t)VP * (EPV * sizeof(QT));  // bytes of a padded token in LDS
+    const QT* src0 = reinterpret_cast<const QT*>(p.queries) + ((size_t)set * p.n_tokens + p.t0) * p.dim;
+    for (uint32_t t = 0; t < tc; t++) {
+        const QT* src = src0 + (size_t)t * p.dim;
+        Acc qq_part = 0;
+        for (uint32_t e = tid; e < VP * EPV; e += 256) {
+            const QT v = e < p.dim ? src[e] : (QT)0;
+            if constexpr (QLDS) reinterpret_cast<QT*>(qs + t * qstride)[e] = v;
+            if constexpr (Tr::INT) qq_part += (int32_t)v * (int32_t)v;
+            else qq_part = fmaf(v, v, qq_part);
+        }
+        const Acc s = k1::group_sum<64>(qq_part);
+        if (lane == 0) red[t * 4 + wave] = s;
+    }
+    const uint32_t ord0 = p.ord[c0];
+    for (uint32_t i = tid; i < nr; i += 256) {
+        rowbuf[i] = p.list[c0 + i];
+        ordbuf[i] = min(p.ord[c0 + i] - ord0, kMaxsimRows - 1u);  // every key holds a row: at most i
+    }
+    for (uint32_t i = tid; i < tc * kMaxsimRows; i += 256) lmin[i] = kNanKey;
+    __syncthreads();
+    for (uint32_t t = tid; t < tc; t += 256) qqs[t] = red[t * 4] + red[t * 4 + 1] + red[t * 4 + 2] + red[t * 4 + 3];
+    __syncthreads();
+
+    const uint32_t ngroups = (nr + RPG - 1) / RPG;
+    for (uint32_t g0 = (uint32_t)wave * U; g0 < ngroups; g0 += 4 * U) {  // wave-uniform: every lane reaches the shuffles
+        uint32_t idx[U];
+        bool rv[U];
+        const unsigned char* rp[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            idx[u] = (g0 + u) * RPG + rsel;
+            rv[u] = idx[u] < nr;
+            rp[u] = p.rows + (size_t)(rv[u] ? rowbuf[idx[u]] : 0u) * p.pitch;
+        }
+        k1::u32x4 xr[JR][U];
+        if constexpr (REG) {  // the rows, once
+#pragma unroll
+            for (int j = 0; j < JR; j++) {
+                const uint32_t v = (uint32_t)j * G + sub;
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    xr[j][u] = k1::u32x4{0, 0, 0, 0};
+                    if ((uint32_t)j < p.J && v < p.V && rv[u])
+                        xr[j][u] = __builtin_nontemporal_load(reinterpret_cast<const k1::u32x4*>(rp[u] + (size_t)v * 16));
+                }
+            }
+        }
+        for (uint32_t tg0 = 0; tg0 < tc; tg0 += TG) {
+            Acc acc[TG][U], xx[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                xx[u] = 0;
+#pragma unroll
+                for (int q = 0; q < TG; q++) acc[q][u] = 0;
+            }
+            auto step = [&](uint32_t j, const k1::u32x4(&x)[U]) __attribute__((always_inline)) {
+                const uint32_t v = j * G + sub;
+                k1::accumulate<DT, METRIC, U, TG>(acc, xx, x, [&](int q, int half) __attribute__((always_inline)) {
+                    const uint32_t t = min(tg0 + (uint32_t)q, tc - 1u);  // a short last group scores its last token again
+                    if constexpr (Tr::INT) {
+                        return *reinterpret_cast<const uint4*>(qs + t * qstride + (size_t)v * 16);
+                    } else if constexpr (QLDS) {
+                        return *reinterpret_cast<const float4*>(qs + t * qstride + (size_t)v * (EPV * 4) + half * 16);
+                    } else {
+                        return k1::query_global4(reinterpret_cast<const float*>(src0) + (size_t)t * p.dim, p.dim, v * EPV + half * 4);
+                    }
+                });
+            };
+            if constexpr (REG) {
+#pragma unroll
+                for (int j = 0; j < JR; j++)
+                    if ((uint32_t)j < p.J) step((uint32_t)j, xr[j]);
+            } else {
+                for (uint32_t j = 0; j < p.J; j++) {
+                    const uint32_t v = j * G + sub;
+                    k1::u32x4 x[U];
+#pragma unroll
+                    for (int u = 0; u < U; u++) {
+                        x[u] = k1::u32x4{0, 0, 0, 0};
+                        if (v < p.V && rv[u]) x[u] = *reinterpret_cast<const k1::u32x4*>(rp[u] + (size_t)v * 16);
+                    }
+                    step(j, x);
+                }
+            }
+            // the group's sums, scattered over its lanes: each (token, row) of the step gets its key and its LDS minimum from one lane
+            Acc flat[NV], xxs[U];
+#pragma unroll
+            for (int q = 0; q < TG; q++)
+#pragma unroll
+                for (int u = 0; u < U; u++) flat[q * U + u] = acc[q][u];
+            int first = 0;
+            scatter_sum<G / 2, NV>(flat, sub, first);
+#pragma unroll
+            for (int u = 0; u < U; u++) xxs[u] = NEED_XX ? k1::group_sum<G>(xx[u]) : (Acc)0;
+#pragma unroll
+            for (int i = 0; i < KEPT; i++) {
+                const uint32_t q = (uint32_t)(first + i) / U, u = (uint32_t)(first + i) % U;
+                Acc xsel = xxs[0];
+#pragma unroll
+                for (int uu = 1; uu < U; uu++) xsel = u == (uint32_t)uu ? xxs[uu] : xsel;
+                const uint32_t t = min(tg0 + q, tc - 1u), pos = (g0 + u) * RPG + rsel;
+                const uint32_t key = k1::make_key<DT, METRIC>(flat[i], xsel, qqs[t]);
+                if ((sub & (SAME - 1)) == 0 && pos < nr && tg0 + q < tc) atomicMin(&lmin[t * kMaxsimRows + ordbuf[pos]], key);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- one atomicMin per (token, run of the block)
+    const uint32_t nseg = ordbuf[nr - 1] + 1u;
+    uint32_t* best = p.best + (size_t)set * tc * p.n_keys;
+    for (uint32_t i = tid; i < tc * nseg; i += 256) {
+        const uint32_t t = i / nseg, sg = i % nseg;
+        if (ord0 + sg < p.n_keys) atomicMin(&best[(size_t)t * p.n_keys + ord0 + sg], lmin[t * kMaxsimRows + sg]);
+    }
+}
+
+// the score a result reports for an order key (write_result's lines)
+__device__ __forceinline__ float maxsim_score_of(uint32_t key, uint8_t metric, bool raw_key) {
+    if (raw_key) {
+        const int32_t raw = raw_from_key(key, metric);
+        return metric == MVF_METRIC_L2 ? sqrtf((float)raw) : (float)raw;
+    }
+    return score_from_key(key, metric);
+}
+
+// grid (ceil(n_keys / 256), sets), block 256
+__global__ void __launch_bounds__(256) maxsim_sum_kernel(MaxsimSumParams p) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x, set = blockIdx.y;
+    if (g >= p.n_keys) return;
+    const bool raw_key = key_is_raw(p.dtype, p.metric);
+    const uint32_t* best = p.best + (size_t)set * p.tc * p.n_keys + g;
+    float* sum = p.sum + (size_t)set * p.n_keys + g;
+    float S = p.first ? 0.0f : *sum;
+    for (uint32_t t = 0; t < p.tc; t++) {
+        const float b = maxsim_score_of(best[(size_t)t * p.n_keys], p.metric, raw_key);
+        S = (p.first && t == 0) ? b : __fadd_rn(S, b);
+    }
+    *sum = S;
+    if (p.last) p.rank[(size_t)set * p.n_keys + g] = rank_entry(key_from_score(S, p.metric), g, false);
+}
+
+// grid (blocks over k, sets), block 256
+__global__ void __launch_bounds__(256) maxsim_write_kernel(MaxsimWriteParams p) {
+    const uint32_t set = blockIdx.y;
+    if (p.out_counts && blockIdx.x == 0 && threadIdx.x == 0) p.out_counts[set] = min(p.k, p.n_keys);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < p.k; i += (size_t)gridDim.x * 256) {
+        const size_t o = (size_t)set * p.k + i;
+        if (i < p.n_keys) {
+            const uint32_t g = (uint32_t)(p.sorted[(size_t)set * p.n_keys + i] >> 32);
+            const float S = p.sum[(size_t)set * p.n_keys + g];
+            p.out_scores[o] = S != S ? unord_f32(kNanKey) : S;  // the NaN every result carries
+            p.out_keys[o] = p.keys[g];
+        } else {
+            p.out_scores[o] = pad_score(p.metric);
+            p.out_keys[o] = ~0ull;
+        }
+    }
+}
+
+template <int DT>
+const void* pick_kernel(int metric, int G, bool reg, bool qlds) {
+    return k1::for_metric(metric, [&](auto m) {
+        return k1::for_group(G, [&](auto g) -> const void* {
+            constexpr int M = decltype(m)::value, GG = decltype(g)::value;
+            if constexpr (!k1::Traits<DT>::INT) {
+                if (!qlds) return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, false, false>);
+            }
+            if (reg) return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, true, true>);
+            return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, false, true>);
+        });
+    });
+}
+
+}  // namespace
+
+hipError_t maxsim_ordinals_launch(const uint64_t* offsets, uint64_t n_keys, uint32_t live, uint32_t* ord, hipStream_t s) {
+    if (live == 0 || n_keys == 0) return hipSuccess;
+    hipLaunchKernelGGL(maxsim_ordinals_kernel, dim3((live + 255u) / 256u), dim3(256), 0, s, offsets, n_keys, live, ord);
+    return hipGetLastError();
+}
+
+hipError_t maxsim_score_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s) {
+    if (p.sets == 0 || p.m == 0 || p.tc == 0) return hipSuccess;
+    if (p.tc > kMaxsimChunkMax || p.t0 + p.tc > p.n_tokens || p.sets > 65535u) return hipErrorInvalidValue;
+    const uint32_t qbytes = cand_query_bytes(dtype, G, p.J);
+    const bool qlds = is_int_dtype(dtype) || qbytes <= kCandQueryLdsMax;
+    if (qlds && (size_t)p.tc * qbytes > kCandQueryLdsMax && p.tc > 1) return hipErrorInvalidValue;
+    const bool reg = qlds && p.J <= kMaxsimRegSteps;
+    const void* fn = nullptr;
+    switch (dtype) {
+        case MVF_DTYPE_FLOAT32: fn = pick_kernel<MVF_DTYPE_FLOAT32>(metric, G, reg, qlds); break;
+        case MVF_DTYPE_FLOAT16: fn = pick_kernel<MVF_DTYPE_FLOAT16>(metric, G, reg, qlds); break;
+        case MVF_DTYPE_INT8: fn = pick_kernel<MVF_DTYPE_INT8>(metric, G, reg, qlds); break;
+        case MVF_DTYPE_UINT8: fn = pick_kernel<MVF_DTYPE_UINT8>(metric, G, reg, qlds); break;
+        default: break;
+    }
+    if (!fn) return hipErrorInvalidValue;
+    const size_t lds = ((maxsim_lds_head(p.tc) + 15u) & ~15u) + (qlds ? (size_t)p.tc * qbytes : 0u);
+    const dim3 grid((p.m + kMaxsimRows - 1) / kMaxsimRows, p.sets);
+    MaxsimScoreParams arg = p;
+    void* args[] = {&arg};
+    return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+}
+
+hipError_t maxsim_sum_launch(const MaxsimSumParams& p, hipStream_t s) {
+    if (p.n_keys == 0 || p.sets == 0) return hipSuccess;
+    hipLaunchKernelGGL(maxsim_sum_kernel, dim3((p.n_keys + 255u) / 256u, p.sets), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t maxsim_write_launch(const MaxsimWriteParams& p, hipStream_t s) {
+    if (p.sets == 0 || p.k == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)p.k + 255u) / 256u, 1024u);
+    hipLaunchKernelGGL(maxsim_write_kernel, dim3(blocks, p.sets), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace mvf

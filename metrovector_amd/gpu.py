@@ -44,6 +44,13 @@ class SearchResult:
 
 
 @dataclass
+class MaxSimResult:
+    scores: np.ndarray   # f32 [nq, k]: a key's sum over the query's vectors of that vector's best score among the key's rows
+    keys: np.ndarray     # u64 [nq, k]: the column values, best first (UINT64_MAX pads -- `counts` tells it from a real key)
+    counts: np.ndarray   # u32 [nq]: min(k, keys of the partition), the entries of a row that are no padding
+
+
+@dataclass
 class RadiusResult:
     counts: np.ndarray   # u64 [nq]: exact number of matches per query (also beyond max_per_query)
     scores: np.ndarray   # f32 [nq, max_per_query]: the best min(count, max_per_query) matches, best first, then padding
@@ -311,6 +318,14 @@ def group_plan(run_lengths, crossing, per_key: int) -> np.ndarray:
     _lib.gpu_check(_lib.gpu().mvfgpu_selftest_group_plan(ll.ctypes.data_as(C.c_void_p), cr.ctypes.data_as(C.c_void_p), ll.size, per_key,
                                                          tier.ctypes.data_as(C.c_void_p)))
     return tier[:ll.size]
+
+
+def maxsim_plan(n_keys: int, n_tokens: int, nq: int, token_bytes: int, budget_bytes: int) -> tuple[int, int]:
+    """(tokens per chunk, query sets per window) of a multi-vector search over `n_keys` keys with `n_tokens` tokens per set,
+    `nq` sets, padded tokens of `token_bytes` and a scratch budget: `mvfgpu_selftest_maxsim_plan`; no GPU needed."""
+    chunk, window = C.c_uint32(0), C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_plan(n_keys, n_tokens, nq, token_bytes, budget_bytes, C.byref(chunk), C.byref(window)))
+    return chunk.value, window.value
 
 
 def _keys_u64(keys) -> np.ndarray:
@@ -736,6 +751,46 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_grouped_stage_ms(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                    nq, k, per_key, C.c_void_p(d_scores), C.c_void_p(d_indices),
                                                                    _opt(stream), out))
+        return tuple(float(x) for x in out)
+
+    # ---- multi-vector search: top-k keys by summed per-token best --------------------------
+    def search_maxsim(self, query_sets: np.ndarray, k: int, metric: int, part: GpuPartition) -> MaxSimResult:
+        """The k best keys of `part` for every SET of query vectors (`mvfgpu_search_maxsim`; late interaction): `query_sets` is
+        [nq, n_tokens, dim] (a 2-D array is one set), a key's score the sum over the set's vectors, in their order, of that
+        vector's best score among the key's rows; ties by ascending key."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        q = np.asarray(query_sets)
+        if q.ndim == 2:
+            q = q[None, :, :]
+        if q.ndim != 3:
+            raise InvalidArgument(f"query sets must be [nq, n_tokens, dim], got shape {q.shape}")
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, n_tokens, qdim = q.shape
+        sc, keys, cnt = np.empty((nq, k), np.float32), np.empty((nq, k), np.uint64), np.zeros(nq, np.uint32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_maxsim(self._h, hpart, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, n_tokens, k,
+                                                       sc.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p),
+                                                       cnt.ctypes.data_as(C.c_void_p)))
+        return MaxSimResult(sc, keys, cnt)
+
+    def search_maxsim_device(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int, k: int,
+                             metric: int, d_scores: int, d_keys: int, d_counts: int = 0, stream: int = 0) -> None:
+        """Device-pointer multi-vector search (`mvfgpu_search_maxsim_device`), asynchronous on `stream`."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_maxsim_device(self._h, hpart, metric, C.c_void_p(d_queries), query_dtype, query_dim,
+                                                              nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+                                                              _opt(d_counts), _opt(stream)))
+
+    def maxsim_stage_ms(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int, k: int,
+                        metric: int, d_scores: int, d_keys: int, stream: int = 0) -> tuple[float, float, float, float]:
+        """(key ordinals, M0, M1, tail) in ms of one multi-vector search, summed over its chunks and windows
+        (`mvfgpu_selftest_maxsim_stage_ms`); waits for the stream."""
+        out = (C.c_float * 4)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_stage_ms(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
+                                                                  nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+                                                                  _opt(stream), out))
         return tuple(float(x) for x in out)
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,

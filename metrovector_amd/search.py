@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .errors import BuildError, InvalidVectorType
-from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, SearchResult, pack_allow_mask, query_dtype_code
+from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, MaxSimResult, SearchResult, pack_allow_mask, query_dtype_code
 from .reader import VectorSpace
 
 _NP_OF = {0: np.float32, 1: np.float16, 2: np.int8, 3: np.uint8}
@@ -331,6 +331,40 @@ def find_top_k_grouped(space: VectorSpace, queries, k: int, column: str, per_key
             with corpus.make_partition(col) as part:
                 res = corpus.search_grouped(np.asarray(queries, dtype=_NP_OF[query_dtype_code(dt)]), k, per_key, metric, part)
             return res, col.gather(res.indices)
+    finally:
+        if own:
+            corpus.close()
+
+
+def find_top_k_documents(space: VectorSpace, query_vectors, k: int, column: str, metric: int | None = None,
+                         corpus: GpuCorpus | None = None, device: int = 0) -> MaxSimResult:
+    """The k best values of the file's metadata column `column` -- documents of a corpus of token or passage vectors -- for a
+    SET of query vectors (`mvfgpu_search_maxsim`; DESIGN.md §3 "Multi-vector search"): late interaction, a document's score
+    being the sum over the query's vectors of that vector's best score among the document's vectors.  `query_vectors` is
+    [n_tokens, dim] for one query or [nq, n_tokens, dim].  The column is read as `find_top_k_per_key` reads it, with the same
+    refusals.  Returns scores [nq, k], keys [nq, k] (UINT64_MAX pads) and counts [nq].  The column and the index live for this
+    call: a caller with many batches attaches the column and builds the index once (`GpuCorpus.attach_column`,
+    `make_partition`, `search_maxsim`)."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    total = space.total_vectors()
+    mc = space._reader.metadata_column(column)  # everything about the file's column is refused before anything is uploaded
+    es = {4: 4, 5: 8}.get(int(mc.data_type))
+    if es is None:
+        raise BuildError("Unsupported metadata column data type")
+    if mc.size // es < total:
+        raise BuildError(f"metadata column '{column}' holds {mc.size // es} values, the space has {total} vectors")
+    dt = int(space.data_type())
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        base = int(corpus.info().index_base)
+        with corpus.attach_column_pointer(mc.as_ptr(), int(mc.data_type), base, mc.size // es) as col:
+            with corpus.make_partition(col) as part:
+                return corpus.search_maxsim(np.asarray(query_vectors, dtype=_NP_OF[query_dtype_code(dt)]), k, metric, part)
     finally:
         if own:
             corpus.close()
