@@ -151,6 +151,16 @@ extern "C" {
                                     d_queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, k: u32, per_key: u32,
                                     d_scores: *mut f32, d_indices: *mut u64, d_raw: *mut i32,
                                     hip_stream: *mut c_void) -> c_int;
+    /// Candidate multi-vector search (include/mvf_gpu.h, "Candidate keys"): the k best of each query set's own candidate
+    /// keys by summed per-token best (MaxSim re-ranking).  `candidate_keys` is a HOST array `[nq][m]` in both calls.
+    fn mvfgpu_search_maxsim_candidates(corpus: *const MvfGpuCorpus, partition: *const MvfGpuPartition, metric: u8,
+                                       queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, n_tokens: u32,
+                                       candidate_keys: *const u64, m: u32, k: u32, out_scores: *mut f32, out_keys: *mut u64,
+                                       out_counts: *mut u32) -> c_int;
+    fn mvfgpu_search_maxsim_candidates_device(corpus: *const MvfGpuCorpus, partition: *const MvfGpuPartition, metric: u8,
+                                              d_queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, n_tokens: u32,
+                                              candidate_keys: *const u64, m: u32, k: u32, d_scores: *mut f32, d_keys: *mut u64,
+                                              d_counts: *mut u32, hip_stream: *mut c_void) -> c_int;
     /// The column's values (zero-extended) of the rows a search reported; padding gives 0.
     fn mvfgpu_column_gather(column: *const MvfGpuColumn, indices: *const u64, count: u64, out_values: *mut u64) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;

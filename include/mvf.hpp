@@ -566,6 +566,45 @@ public:
         for (uint32_t i = 0; i < count; i++) out.emplace_back(keys[i], scores[i]);
         return out;
     }
+    // find_top_k_documents among CANDIDATE documents (mvfgpu_search_maxsim_candidates; DESIGN.md section 3, "Candidate keys"):
+    // the exact late-interaction scores of the values of `column` a first stage proposed, the best k first.  Values no live
+    // vector carries (UINT64_MAX pads among them) are skipped and a value listed twice counts once, so fewer than k come back
+    // where fewer distinct candidates are found.  The column and the index live for this call.
+    std::vector<std::pair<uint64_t, float>> rerank_top_k_documents(const std::vector<float>& query_vectors,
+                                                                   const std::vector<uint64_t>& candidate_keys, size_t k,
+                                                                   const MetadataColumn& column) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "rerank_top_k_documents takes f32 queries: Float32 / Float16 spaces");
+        if (dim_ == 0 || query_vectors.empty() || query_vectors.size() % (size_t)dim_)
+            throw MvfError(MVF_ERR_DIMENSION_MISMATCH, "rerank_top_k_documents takes whole query vectors of the space's dimension");
+        if (candidate_keys.size() > UINT32_MAX) throw MvfError(MVF_ERR_INVALID_ARGUMENT, "more than 2^32 - 1 candidate keys");
+        const size_t n_tokens = query_vectors.size() / (size_t)dim_;
+        std::vector<std::pair<uint64_t, float>> out;
+        if (k == 0) return out;
+        mvfgpu_corpus_info inf;
+        MVFGPU_INIT(inf);
+        detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+        const uint64_t es = column.data_type == MVF_DTYPE_UINT32 ? 4 : column.data_type == MVF_DTYPE_UINT64 ? 8 : 0;
+        if (!es || column.size / es < inf.rows)
+            throw MvfError(MVF_ERR_BUILD, es ? "metadata column '" + column.name + "' holds fewer values than the space has vectors"
+                                             : "Unsupported metadata column data type");
+        mvfgpu_column* col = nullptr;
+        mvfgpu_partition* part = nullptr;
+        std::vector<float> scores(k);
+        std::vector<uint64_t> keys(k);
+        uint32_t count = 0;
+        int rc = mvfgpu_column_create(c_, column.data, column.data_type, 0, column.size / es, &col);
+        if (rc == MVF_OK) rc = mvfgpu_partition_create(c_, col, &part);
+        if (rc == MVF_OK)
+            rc = mvfgpu_search_maxsim_candidates(c_, part, (uint8_t)metric_, query_vectors.data(), MVF_DTYPE_FLOAT32, dim_, 1,
+                                                 (uint32_t)std::min<size_t>(n_tokens, UINT32_MAX), candidate_keys.data(),
+                                                 (uint32_t)candidate_keys.size(), (uint32_t)k, scores.data(), keys.data(), &count);
+        mvfgpu_partition_destroy(part);
+        mvfgpu_column_destroy(col);
+        detail::check_gpu(rc);
+        for (uint32_t i = 0; i < count; i++) out.emplace_back(keys[i], scores[i]);
+        return out;
+    }
     // The k-NN graph (mvfgpu_knn_join; DESIGN.md section 3, "Join"): for each of the rows [first, first + count) -- count
     // UINT64_MAX: to the end of the space -- its k nearest OTHER rows under the space's metric, best first.  A row is never its
     // own neighbour (decided by position: its exact duplicates are); a deleted row gets an empty list; fewer than k live

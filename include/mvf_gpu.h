@@ -744,6 +744,59 @@ int mvfgpu_selftest_maxsim_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_pa
                                     uint32_t k, float* d_scores, uint64_t* d_keys, void* hip_stream, float* out_ms);
 
 /*
+ * Candidate keys ("Candidate keys"): mvfgpu_search_maxsim restricted, per query set, to a list of keys --
+ * the re-ranking step of late-interaction retrieval, whose first stage hands every query a few hundred or thousand documents.
+ * queries, n_tokens, metric, k and the outputs are mvfgpu_search_maxsim's, with the same types, limits and padding.
+ *   candidate_keys : [nq][m] column values, one list per query set; a HOST array in both calls, read before the call returns (as
+ *                    mvfgpu_search_partitioned's keys).  An entry is a candidate of its set iff the partition holds the key
+ *                    (mvfgpu_partition_lookup gives a count > 0).  Every other entry is skipped, not refused: unknown keys, keys
+ *                    whose rows are all deleted, the conventional pad UINT64_MAX where the column does not hold it.  A key listed
+ *                    twice counts once.  m = 0 is allowed: every row is padding, counts are 0, candidate_keys may be NULL.
+ *   score          : S(g) is mvfgpu_search_maxsim's, bit for bit: the same b(t, g) and the same plain f32 sum in token order.
+ *   result row     : the k best of the set's distinct held candidates by (order key of S, ascending key value), NaN last, then
+ *                    mvfgpu_search_maxsim's padding.  out_counts[q] (nullable) = min(k, distinct held candidates of q).
+ * So, byte for byte (score bits, keys, counts): the result row of set q is the row of mvfgpu_search_maxsim with k = n_keys on the
+ * same partition with the entries whose key is no candidate of q removed, cut at k and padded; a list of every key of
+ * mvfgpu_partition_keys reproduces mvfgpu_search_maxsim; b(t, g) is the score mvfgpu_search_partitioned reports for (token t,
+ * key g, k = 1).
+ * Refusals, all before any device call and leaving no device error: mvfgpu_search_maxsim's up to n_tokens, in its order; then a
+ * NULL candidate_keys while nq * m > 0 (MVF_ERR_INVALID_ARGUMENT, "NULL buffer (candidate_keys)"); then mvfgpu_search_maxsim's
+ * remaining ones in its order and wording.
+ * The device call is asynchronous on the caller's stream and waits on the host only for the previous call's plan to have left the
+ * index's pinned buffer (the partitioned search's rule).  No repair feedback is read or posted.
+ * Cost: the CANDIDATES' rows leave HBM once per chunk of tokens and query set; scratch per window of query sets is
+ * mvfgpu_search_maxsim's with the window's largest distinct-candidate count in n_keys' place, plus 8 bytes per candidate row
+ * (each set's rows rounded up to a multiple of 128), inside MVF_MAXSIM_SCRATCH_BYTES wherever one set's fits.
+ * Not built: shard sets (a document's rows may span shards); candidate keys in device memory; ragged token counts; per-token
+ * weights; the arg-best rows.
+ */
+int mvfgpu_search_maxsim_candidates(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                    const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens,
+                                    const uint64_t* candidate_keys, uint32_t m, uint32_t k, float* out_scores, uint64_t* out_keys,
+                                    uint32_t* out_counts);
+int mvfgpu_search_maxsim_candidates_device(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                           const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                                           uint32_t n_tokens, const uint64_t* candidate_keys, uint32_t m, uint32_t k, float* d_scores,
+                                           uint64_t* d_keys, uint32_t* d_counts, void* hip_stream);
+/*
+ * Self-test of the candidate plan of ONE query set (no GPU needed): from a list and every entry's held row count
+ * (mvfgpu_partition_lookup's), out_slot[i] = the slot ordinal of entry i -- its key's rank among the set's distinct held keys in
+ * ascending key value -- or UINT32_MAX where the entry is skipped (held_counts[i] == 0) or repeats an earlier entry;
+ * *out_distinct = the distinct held candidates, *out_rows = the rows they hold.
+ */
+int mvfgpu_selftest_maxsim_candidates_plan(const uint64_t* candidate_keys, const uint64_t* held_counts, uint32_t m,
+                                           uint32_t* out_slot, uint32_t* out_distinct, uint64_t* out_rows);
+/*
+ * Stage timer of a candidate multi-vector search (scripts/probe_maxsim_candidates.py): the device call without d_counts, with
+ * events between its stages; waits for the stream.  out_ms[0..3] = the plan's upload and E0 (the expansion), M0, M1, the tail,
+ * each summed over the call's chunks and windows.
+ */
+int mvfgpu_selftest_maxsim_candidates_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                               const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                                               uint32_t n_tokens, const uint64_t* candidate_keys, uint32_t m, uint32_t k,
+                                               float* d_scores, uint64_t* d_keys, void* hip_stream, float* out_ms);
+
+/*
  * Self-test of the host-side normalisation (no GPU needed): every operator but IN / NOT_IN (MVF_ERR_INVALID_ARGUMENT) becomes
  * one range test *out_lo <= v <= *out_hi on a column of `data_type`, negated where *out_negate is 1 (NE only).  The range is
  * clamped to the type's values (hi <= 2^32 - 1 on UInt32); an empty range is reported as lo = 1, hi = 0.
@@ -958,7 +1011,9 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * adds mvfgpu_partition_*, mvfgpu_search_partitioned, mvfgpu_search_partitioned_device and mvfgpu_selftest_partition_plan, nor did
  * the grouped search, which only adds mvfgpu_search_grouped, mvfgpu_search_grouped_device, mvfgpu_column_gather,
  * mvfgpu_selftest_group_plan and mvfgpu_selftest_grouped_stage_ms, nor did the multi-vector search, which only adds
- * mvfgpu_search_maxsim, mvfgpu_search_maxsim_device, mvfgpu_selftest_maxsim_plan and mvfgpu_selftest_maxsim_stage_ms).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * mvfgpu_search_maxsim, mvfgpu_search_maxsim_device, mvfgpu_selftest_maxsim_plan and mvfgpu_selftest_maxsim_stage_ms, nor did
+ * its candidate form, which only adds mvfgpu_search_maxsim_candidates, mvfgpu_search_maxsim_candidates_device,
+ * mvfgpu_selftest_maxsim_candidates_plan and mvfgpu_selftest_maxsim_candidates_stage_ms).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

@@ -277,6 +277,13 @@ struct PartitionView {
 PartitionView partition_view(const mvfgpu_partition* part);
 // a search of `c` may use the index: it was created for this handle and holds the handle's current tombstones
 int check_partition_use(const mvfgpu_corpus* c, const mvfgpu_partition* part);
+// `bytes` of a host-made plan into the index's pinned buffer and from there to `dst` on `s` (the partitioned search's plan, the
+// candidate multi-vector search's).  The caller holds the owner's lock.  Waits only for the previous upload to have left the buffer.
+int partition_upload(const mvfgpu_partition* part, const void* src, size_t bytes, void* dst, hipStream_t s);
+// mvfgpu_partition_lookup for one key, from the host mirror: (offset, count) of its rows in rows_by_key; count 0 where no live
+// row carries it.  from (nullable): a caller that looks keys up in ASCENDING order passes one word, 0 at first, and every search
+// covers only the table behind the previous key's place
+void partition_find(const mvfgpu_partition* part, uint64_t key, uint64_t* offset, uint64_t* count, uint64_t* from = nullptr);
 // waits for the newest work enqueued on the handle
 int corpus_wait_newest(const mvfgpu_corpus* c);
 

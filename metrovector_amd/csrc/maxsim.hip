@@ -7,6 +7,11 @@
 // chunk's scores to every key's running sum in token order.  Behind the last chunk the keys' rank entries are ranked by the
 // whole-list select and sort (sort_topk.hip) and a writer maps ordinals to key values.  No host wait, no plan on the host but
 // the chunk and window sizes (maxsim_plan).  The host call runs the same device work per host window (host_staging.h).
+//
+// mvfgpu_search_maxsim_candidates / _device restrict every query set to its own list of keys.  The host plans from the index's
+// mirror -- per set the distinct held candidates in ascending key value, their segments of rows_by_key and the windows --, the
+// plan travels through the index's pinned buffer (partition_upload), E0 expands it into the list M0's candidate form scores,
+// and M1, the sort and the writer run per set over its candidates: the cost follows the candidates' rows.
 
 #include "../../include/mvf_gpu.h"
 
@@ -18,6 +23,7 @@
 #include "scan_maxsim.h"
 
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -140,6 +146,240 @@ int maxsim_core(const CorpusView& v, const PartitionView& pv, uint8_t metric, co
     return MVF_OK;
 }
 
+// ---- the candidate form: mvfgpu_search_maxsim_candidates (DESIGN.md §3 "Candidate keys", §5 "E0")
+
+int check_candidates_args(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries, uint8_t query_dtype,
+                          uint32_t query_dim, uint32_t nq, uint32_t n_tokens, const uint64_t* candidate_keys, uint32_t m, uint32_t k,
+                          const void* out_scores, const void* out_keys) {
+    if (const int rc = check_search_scalars(metric, nq, k, queries, out_scores, out_keys)) return rc;
+    if (n_tokens == 0 || n_tokens > MVFGPU_MAXSIM_MAX_TOKENS)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT,
+                        "n_tokens must be in 1.." + std::to_string(MVFGPU_MAXSIM_MAX_TOKENS) + ", got " + std::to_string(n_tokens));
+    if (!candidate_keys && (uint64_t)nq * m > 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer (candidate_keys)");
+    if (!part) return set_fail(MVF_ERR_INVALID_ARGUMENT, "partition is NULL");
+    if (const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_keys)) return rc;
+    return check_partition_use(c, part);
+}
+
+// One set's list, a pure function: of the entries `take` admits the first occurrence of every key as (key, entry), in ascending
+// key value.  With take = "the key is held" a pair's place is the candidate's slot ordinal.
+template <class Take>
+void distinct_entries(const uint64_t* keys, uint32_t m, Take take, std::vector<std::pair<uint64_t, uint32_t>>* out) {
+    out->clear();
+    for (uint32_t i = 0; i < m; i++)
+        if (take(i)) out->emplace_back(keys[i], i);
+    std::sort(out->begin(), out->end());  // equal keys in ascending entry: the first occurrence leads
+    out->erase(std::unique(out->begin(), out->end(), [](const auto& a, const auto& b) { return a.first == b.first; }), out->end());
+}
+
+// the plan of a call: what the device reads, in the order of its upload, and the windows
+struct CandWindow {
+    uint32_t w0, wn, chunk, n_keys, blk0, n_blocks;
+};
+struct CandPlan {
+    std::vector<uint64_t> keys;           // [segments] the candidates' key values, set after set
+    std::vector<MaxsimCandSeg> segs;      // [segments]
+    std::vector<MaxsimCandSet> sets;      // [nq]
+    std::vector<MaxsimCandBlock> blocks;  // window after window
+    std::vector<CandWindow> windows;
+};
+
+// Windows: as many sets as maxsim_plan allows for the window's largest candidate count inside what the budget leaves beside the
+// window's concatenated list (8 bytes per position), the list itself inside the budget and below 2^32 positions; one set whatever
+// the budget.
+int plan_candidates(const mvfgpu_partition* part, const uint64_t* cand, uint32_t nq, uint32_t m, uint32_t n_tokens, uint64_t token_bytes,
+                    uint64_t budget, CandPlan* plan) {
+    std::vector<std::pair<uint64_t, uint32_t>> distinct;
+    plan->sets.resize(nq);
+    for (uint32_t q = 0; q < nq; q++) {
+        // the distinct entries first, then one lookup each, in ascending key: held is a function of the key, so dropping the
+        // entries that are not held afterwards leaves what take = "held" gives
+        distinct_entries(cand + (size_t)q * m, m, [](uint32_t) { return true; }, &distinct);
+        if (plan->segs.size() + distinct.size() > 0xFFFFFFFFull)
+            return set_fail(MVF_ERR_INVALID_ARGUMENT, "the candidate lists hold more than 2^32 - 1 candidates in all");
+        MaxsimCandSet& st = plan->sets[q];
+        st.seg0 = (uint32_t)plan->segs.size();
+        uint64_t rows = 0, from = 0;  // distinct keys of one index: at most its live rows, < 2^32
+        for (const auto& e : distinct) {
+            uint64_t off = 0, cnt = 0;
+            partition_find(part, e.first, &off, &cnt, &from);
+            if (!cnt) continue;
+            plan->keys.push_back(e.first);
+            plan->segs.push_back(MaxsimCandSeg{(uint32_t)off, (uint32_t)rows});
+            rows += cnt;
+        }
+        st.count = (uint32_t)(plan->segs.size() - st.seg0);
+        st.rows = (uint32_t)rows;
+        st.list0 = 0;
+    }
+    for (uint32_t w0 = 0; w0 < nq;) {
+        uint32_t wn = std::min(kMaxsimWindow, nq - w0);
+        CandWindow w{};
+        for (;;) {
+            uint64_t pos = 0;
+            uint32_t nk = 0;
+            for (uint32_t q = w0; q < w0 + wn; q++) {
+                pos += maxsim_cand_positions(plan->sets[q].rows);
+                nk = std::max(nk, plan->sets[q].count);
+            }
+            const bool list_ok = pos <= 0xFFFFFFFFull && pos * 8 <= budget;
+            const MaxsimPlan pl = maxsim_plan(nk, n_tokens, wn, token_bytes, budget > pos * 8 ? budget - pos * 8 : 0);
+            if (wn == 1 || (list_ok && pl.window >= wn)) {
+                if (pos > 0xFFFFFFFFull) return set_fail(MVF_ERR_INVALID_ARGUMENT, "a candidate list's rows take 2^32 list positions or more");
+                w = CandWindow{w0, wn, pl.chunk, nk, (uint32_t)plan->blocks.size(), (uint32_t)(pos / kMaxsimRows)};
+                break;
+            }
+            wn = std::max(1u, std::min(wn - 1, list_ok ? pl.window : wn / 2));
+        }
+        uint32_t list0 = 0;
+        for (uint32_t q = w0; q < w0 + wn; q++) {
+            MaxsimCandSet& st = plan->sets[q];
+            st.list0 = list0;
+            for (uint32_t r = 0; r < st.rows; r += kMaxsimRows) plan->blocks.push_back(MaxsimCandBlock{q - w0, std::min(kMaxsimRows, st.rows - r)});
+            list0 += (uint32_t)maxsim_cand_positions(st.rows);
+        }
+        plan->windows.push_back(w);
+        w0 += wn;
+    }
+    return MVF_OK;
+}
+
+int pad_sets(uint8_t metric, uint32_t nq, uint32_t k, float* d_scores, uint64_t* d_keys, uint32_t* d_counts, hipStream_t s) {
+    if (d_counts) MVF_HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)nq * 4, s));
+    return fill_padding(metric, nq, k, d_scores, d_keys, nullptr, s);
+}
+
+// The device work of both candidate calls: query sets and results in device memory, the lists on the host; everything on `s`.
+// Runs under corpus_device_call.  marks (the stage timer only): stage 0 the plan's upload and E0, 1 M0, 2 M1, 3 the tail.
+int maxsim_candidates_core(const CorpusView& v, const mvfgpu_partition* part, uint8_t metric, const void* d_queries, uint32_t nq,
+                           uint32_t n_tokens, const uint64_t* cand, uint32_t m, uint32_t k, float* d_scores, uint64_t* d_keys,
+                           uint32_t* d_counts, hipStream_t s, StageMarks* marks = nullptr) {
+    const PartitionView pv = partition_view(part);
+    if (marks) MVF_HIP_TRY(marks->mark(-1, s));
+    if (v.n == 0 || pv.live == 0 || pv.n_keys == 0 || m == 0) return pad_sets(metric, nq, k, d_scores, d_keys, d_counts, s);
+    const OneQueryGroup g1 = one_query_group(v);
+    const size_t set_bytes = query_row_bytes(v) * n_tokens;
+    CandPlan plan;
+    if (const int rc = plan_candidates(part, cand, nq, m, n_tokens, g1.qbytes, v.maxsim_scratch, &plan)) return rc;
+    if (plan.segs.empty()) return pad_sets(metric, nq, k, d_scores, d_keys, d_counts, s);
+
+    // the plan, one upload: keys | segments | sets | blocks, 8-byte entries throughout
+    const size_t nseg = plan.segs.size(), keys_b = nseg * 8, segs_b = nseg * sizeof(MaxsimCandSeg), sets_b = (size_t)nq * sizeof(MaxsimCandSet),
+                 blocks_b = plan.blocks.size() * sizeof(MaxsimCandBlock);
+    std::vector<unsigned char> blob(keys_b + segs_b + sets_b + blocks_b);
+    std::memcpy(blob.data(), plan.keys.data(), keys_b);
+    std::memcpy(blob.data() + keys_b, plan.segs.data(), segs_b);
+    std::memcpy(blob.data() + keys_b + segs_b, plan.sets.data(), sets_b);
+    if (blocks_b) std::memcpy(blob.data() + keys_b + segs_b + sets_b, plan.blocks.data(), blocks_b);
+    AsyncBuf dplan;
+    MVF_HIP_TRY(dplan.alloc(blob.size(), s));
+    if (const int rc = partition_upload(part, blob.data(), blob.size(), dplan.p, s)) return rc;
+    const unsigned char* dp = static_cast<const unsigned char*>(dplan.p);
+    const uint64_t* p_keys = reinterpret_cast<const uint64_t*>(dp);
+    const MaxsimCandSeg* p_segs = reinterpret_cast<const MaxsimCandSeg*>(dp + keys_b);
+    const MaxsimCandSet* p_sets = reinterpret_cast<const MaxsimCandSet*>(dp + keys_b + segs_b);
+    const MaxsimCandBlock* p_blocks = reinterpret_cast<const MaxsimCandBlock*>(dp + keys_b + segs_b + sets_b);
+
+    for (const CandWindow& w : plan.windows) {
+        float* w_scores = d_scores + (size_t)w.w0 * k;
+        uint64_t* w_keys = d_keys + (size_t)w.w0 * k;
+        uint32_t* w_counts = d_counts ? d_counts + w.w0 : nullptr;
+        if (w.n_keys == 0) {  // no set of the window holds a candidate
+            if (const int rc = pad_sets(metric, w.wn, k, w_scores, w_keys, w_counts, s)) return rc;
+            continue;
+        }
+        const uint32_t nk = w.n_keys, wn = w.wn;
+        const size_t npos = (size_t)w.n_blocks * kMaxsimRows, kk = std::min<size_t>(k, nk);
+        size_t tmp_bytes = 0;
+        MVF_HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, nk, kk, nullptr, s, wn, nk));
+        AsyncBuf dlist, dbest, dsum, da, db, dtmp;
+        MVF_HIP_TRY(dlist.alloc(npos * 8, s));  // rows [npos], then slot ordinals [npos]
+        MVF_HIP_TRY(dbest.alloc((size_t)wn * w.chunk * nk * 4, s));
+        MVF_HIP_TRY(dsum.alloc((size_t)wn * nk * 4, s));
+        MVF_HIP_TRY(da.alloc((size_t)wn * nk * 8, s));
+        MVF_HIP_TRY(db.alloc((size_t)wn * nk * 8, s));
+        MVF_HIP_TRY(dtmp.alloc(tmp_bytes, s));
+        // E0: the window's concatenated list
+        MaxsimExpandParams ep{};
+        ep.rows_by_key = pv.rows_by_key;
+        ep.sets = p_sets + w.w0;
+        ep.segs = p_segs;
+        ep.blocks = p_blocks + w.blk0;
+        ep.n_blocks = w.n_blocks;
+        ep.list = static_cast<uint32_t*>(dlist.p);
+        ep.ord = ep.list + npos;
+        MVF_HIP_TRY(maxsim_expand_launch(ep, s));
+        if (marks) MVF_HIP_TRY(marks->mark(0, s));
+        for (uint32_t t0 = 0; t0 < n_tokens; t0 += w.chunk) {
+            const uint32_t tc = std::min(w.chunk, n_tokens - t0);
+            MVF_HIP_TRY(hipMemsetAsync(dbest.p, 0xFF, (size_t)wn * tc * nk * 4, s));
+            MaxsimScoreParams sp{};
+            sp.rows = v.rows;
+            sp.queries = static_cast<const unsigned char*>(d_queries) + (size_t)w.w0 * set_bytes;
+            sp.list = ep.list;
+            sp.ord = ep.ord;
+            sp.best = static_cast<uint32_t*>(dbest.p);
+            sp.m = (uint32_t)npos;
+            sp.n_keys = nk;
+            sp.sets = wn;
+            sp.n_tokens = n_tokens;
+            sp.t0 = t0;
+            sp.tc = tc;
+            sp.dim = v.dim;
+            sp.pitch = v.pitch;
+            sp.V = v.V;
+            sp.J = g1.J;
+            sp.blocks = ep.blocks;
+            MVF_HIP_TRY(maxsim_score_candidates_launch(v.dtype, metric, g1.G, sp, s));
+            if (marks) MVF_HIP_TRY(marks->mark(1, s));
+            MaxsimSumParams mp{};
+            mp.best = sp.best;
+            mp.sum = static_cast<float*>(dsum.p);
+            mp.rank = static_cast<uint64_t*>(da.p);
+            mp.n_keys = nk;
+            mp.sets = wn;
+            mp.tc = tc;
+            mp.metric = metric;
+            mp.dtype = v.dtype;
+            mp.first = t0 == 0;
+            mp.last = t0 + tc == n_tokens;
+            mp.cand = ep.sets;
+            MVF_HIP_TRY(maxsim_sum_launch(mp, s));
+            if (marks) MVF_HIP_TRY(marks->mark(2, s));
+        }
+        // the tail: entries in ascending slot ordinal -- ascending key value --, the sets' fillers behind them
+        size_t tb = tmp_bytes;
+        uint64_t* sorted = nullptr;
+        MVF_HIP_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), nk, kk, &sorted, s, wn, nk));
+        MaxsimWriteParams wp{};
+        wp.sorted = sorted;
+        wp.sum = static_cast<const float*>(dsum.p);
+        wp.keys = p_keys;
+        wp.out_scores = w_scores;
+        wp.out_keys = w_keys;
+        wp.out_counts = w_counts;
+        wp.n_keys = nk;
+        wp.sets = wn;
+        wp.k = k;
+        wp.metric = metric;
+        wp.cand = ep.sets;
+        MVF_HIP_TRY(maxsim_write_launch(wp, s));
+        if (marks) MVF_HIP_TRY(marks->mark(3, s));
+    }
+    return MVF_OK;
+}
+
+// the stage timer's sums: every stage's time from the event in front of it
+int stage_sums(const StageMarks& marks, float* out_ms) {
+    for (int i = 0; i < 4; i++) out_ms[i] = 0.0f;
+    for (size_t i = 1; i < marks.ev.size(); i++) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, marks.ev[i - 1].second, marks.ev[i].second) != hipSuccess) return set_fail(MVF_ERR_DEVICE, "hipEventElapsedTime failed");
+        if (marks.ev[i].first >= 0) out_ms[marks.ev[i].first] += ms;
+    }
+    return MVF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -191,12 +431,73 @@ int mvfgpu_selftest_maxsim_stage_ms(const mvfgpu_corpus* c, const mvfgpu_partiti
     int rc = corpus_device_call(c, s, [&]() { return maxsim_core(corpus_view(c), pv, metric, d_queries, nq, n_tokens, k, d_scores, d_keys, nullptr, s, &marks); });
     if (rc == MVF_OK && hipStreamSynchronize(s) != hipSuccess) rc = set_fail(MVF_ERR_DEVICE, "hipStreamSynchronize failed");
     for (int i = 0; i < 4; i++) out_ms[i] = 0.0f;
-    for (size_t i = 1; i < marks.ev.size() && rc == MVF_OK; i++) {  // every stage's time: from the event in front of it
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, marks.ev[i - 1].second, marks.ev[i].second) != hipSuccess) rc = set_fail(MVF_ERR_DEVICE, "hipEventElapsedTime failed");
-        else out_ms[marks.ev[i].first] += ms;
+    return rc == MVF_OK ? stage_sums(marks, out_ms) : rc;
+}
+
+int mvfgpu_search_maxsim_candidates_device(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,
+                                           uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens,
+                                           const uint64_t* candidate_keys, uint32_t m, uint32_t k, float* d_scores, uint64_t* d_keys,
+                                           uint32_t* d_counts, void* hip_stream) {
+    const int rc = check_candidates_args(c, part, metric, d_queries, query_dtype, query_dim, nq, n_tokens, candidate_keys, m, k, d_scores, d_keys);
+    if (rc != MVF_OK) return rc;
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    return corpus_device_call(c, s, [&]() {
+        return maxsim_candidates_core(corpus_view(c), part, metric, d_queries, nq, n_tokens, candidate_keys, m, k, d_scores, d_keys, d_counts, s);
+    });
+}
+
+int mvfgpu_search_maxsim_candidates(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries,
+                                    uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens, const uint64_t* candidate_keys,
+                                    uint32_t m, uint32_t k, float* out_scores, uint64_t* out_keys, uint32_t* out_counts) {
+    const int rc0 = check_candidates_args(c, part, metric, queries, query_dtype, query_dim, nq, n_tokens, candidate_keys, m, k, out_scores, out_keys);
+    if (rc0 != MVF_OK) return rc0;
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    std::lock_guard<std::mutex> host_lk(corpus_host_mutex(c));
+    const CorpusView v = corpus_view(c);
+    hipStream_t s = static_cast<hipStream_t>(v.stream);
+    const HostIn in[] = {{queries, query_row_bytes(v) * n_tokens}};
+    const HostOut out[] = {{out_keys, (size_t)k * 8}, {out_scores, (size_t)k * 4}, {out_counts, 4}};
+    return stage_host_windows(c, s, nq, in, out, stage_as_given, [&](uint32_t w0, uint32_t wn, void* const* d_in, void* const* d_out) {
+        return maxsim_candidates_core(v, part, metric, d_in[0], wn, n_tokens, candidate_keys ? candidate_keys + (size_t)w0 * m : nullptr, m, k,
+                                      static_cast<float*>(d_out[1]), static_cast<uint64_t*>(d_out[0]), static_cast<uint32_t*>(d_out[2]), s);
+    });
+}
+
+int mvfgpu_selftest_maxsim_candidates_stage_ms(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,
+                                               uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens,
+                                               const uint64_t* candidate_keys, uint32_t m, uint32_t k, float* d_scores, uint64_t* d_keys,
+                                               void* hip_stream, float* out_ms) {
+    if (!out_ms) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    const int rc0 = check_candidates_args(c, part, metric, d_queries, query_dtype, query_dim, nq, n_tokens, candidate_keys, m, k, d_scores, d_keys);
+    if (rc0 != MVF_OK) return rc0;
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    StageMarks marks;
+    int rc = corpus_device_call(c, s, [&]() {
+        return maxsim_candidates_core(corpus_view(c), part, metric, d_queries, nq, n_tokens, candidate_keys, m, k, d_scores, d_keys, nullptr, s, &marks);
+    });
+    if (rc == MVF_OK && hipStreamSynchronize(s) != hipSuccess) rc = set_fail(MVF_ERR_DEVICE, "hipStreamSynchronize failed");
+    for (int i = 0; i < 4; i++) out_ms[i] = 0.0f;
+    return rc == MVF_OK ? stage_sums(marks, out_ms) : rc;
+}
+
+int mvfgpu_selftest_maxsim_candidates_plan(const uint64_t* candidate_keys, const uint64_t* held_counts, uint32_t m, uint32_t* out_slot,
+                                           uint32_t* out_distinct, uint64_t* out_rows) {
+    if (!out_distinct || !out_rows || (m && (!candidate_keys || !held_counts || !out_slot))) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    std::vector<std::pair<uint64_t, uint32_t>> distinct;
+    distinct_entries(candidate_keys, m, [&](uint32_t i) { return held_counts[i] != 0; }, &distinct);
+    for (uint32_t i = 0; i < m; i++) out_slot[i] = UINT32_MAX;
+    *out_distinct = (uint32_t)distinct.size();
+    *out_rows = 0;
+    for (size_t j = 0; j < distinct.size(); j++) {
+        out_slot[distinct[j].second] = (uint32_t)j;
+        *out_rows += held_counts[distinct[j].second];
     }
-    return rc;
+    return MVF_OK;
 }
 
 int mvfgpu_selftest_maxsim_plan(uint64_t n_keys, uint32_t n_tokens, uint32_t nq, uint64_t token_bytes, uint64_t budget_bytes,

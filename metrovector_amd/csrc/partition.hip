@@ -50,10 +50,12 @@ struct mvfgpu_partition {
 
     const uint64_t* keys() const { return mirror.data(); }
     const uint64_t* offsets() const { return mirror.data() + n_keys; }
-    // (offset, count) of `key`'s rows; count 0 for a key no live row carries
-    void find(uint64_t key, uint64_t* offset, uint64_t* count) const {
+    // (offset, count) of `key`'s rows; count 0 for a key no live row carries.  from (nullable): keys looked up in ascending order
+    // search only the table behind the previous one's place, which *from carries (0 at first)
+    void find(uint64_t key, uint64_t* offset, uint64_t* count, uint64_t* from = nullptr) const {
         const uint64_t* k0 = keys();
-        const uint64_t* it = std::lower_bound(k0, k0 + n_keys, key);
+        const uint64_t* it = std::lower_bound(k0 + (from ? std::min(*from, n_keys) : 0), k0 + n_keys, key);
+        if (from) *from = (uint64_t)(it - k0);
         if (it == k0 + n_keys || *it != key) {
             *offset = 0, *count = 0;
             return;
@@ -198,9 +200,16 @@ int check_partitioned_args(const mvfgpu_corpus* c, const mvfgpu_partition* part,
     return check_partition_use(c, part);
 }
 
-// The plan of `nq` queries into the index's pinned buffer and from there to `dst` on `s`.  The caller holds the owner's lock.
+// The plan of `nq` queries to `dst` on `s`
 int upload_plan(const mvfgpu_partition* part, const PartPlan& plan, void* dst, hipStream_t s) {
-    const size_t bytes = plan.entries.size() * sizeof(PartQuery);
+    return partition_upload(part, plan.entries.data(), plan.entries.size() * sizeof(PartQuery), dst, s);
+}
+
+}  // namespace
+
+namespace mvf {
+int partition_upload(const mvfgpu_partition* part, const void* src, size_t bytes, void* dst, hipStream_t s) {
+    if (!bytes) return MVF_OK;
     if (part->pin_busy) {  // the previous search's upload still reads the buffer
         MVF_HIP_TRY(hipEventSynchronize(part->copied));
         part->pin_busy = false;
@@ -213,12 +222,18 @@ int upload_plan(const mvfgpu_partition* part, const PartPlan& plan, void* dst, h
         poison_fill_host(part->pin, want);
         part->pin_bytes = want;
     }
-    std::memcpy(part->pin, plan.entries.data(), bytes);
+    std::memcpy(part->pin, src, bytes);
     MVF_HIP_TRY(hipMemcpyAsync(dst, part->pin, bytes, hipMemcpyHostToDevice, s));
     MVF_HIP_TRY(hipEventRecord(part->copied, s));
     part->pin_busy = true;
     return MVF_OK;
 }
+void partition_find(const mvfgpu_partition* part, uint64_t key, uint64_t* offset, uint64_t* count, uint64_t* from) {
+    part->find(key, offset, count, from);
+}
+}  // namespace mvf
+
+namespace {
 
 // The device work of both calls: queries and results in device memory, `keys` on the host; everything on `s`.  Runs under
 // corpus_device_call.

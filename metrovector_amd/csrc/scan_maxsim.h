@@ -52,8 +52,46 @@ struct MaxsimScoreParams {
     const uint32_t* ord;   // [m] key ordinals
     uint32_t* best;
     uint32_t m, n_keys, sets, n_tokens, t0, tc, dim, pitch, V, J;
+    const struct MaxsimCandBlock* blocks;  // the candidate form's block table; not read by the full search's form
 };
 hipError_t maxsim_score_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s);
+
+// ---- the candidate form (mvfgpu_search_maxsim_candidates; DESIGN.md §3 "Candidate keys", §5 "E0")
+// The plan of a query set, made on the host: its distinct held candidates in ascending key value are the segments
+// [seg0, seg0 + count) of the call's segment arrays -- the slot ordinal of a candidate is its rank among them --, `rows` the rows
+// they hold, list0 the set's first position of its window's concatenated list, a multiple of kMaxsimRows.
+struct MaxsimCandSet {
+    uint32_t seg0, count, list0, rows;
+};
+// a candidate's segment of rows_by_key and the rows the set's candidates in front of it hold
+struct MaxsimCandSeg {
+    uint32_t offset, before;
+};
+// the kMaxsimRows list positions of a block: its query set of the window and the positions that hold a row (1 .. kMaxsimRows);
+// no block spans two sets
+struct MaxsimCandBlock {
+    uint32_t set, nr;
+};
+// list positions a set of `rows` candidate rows takes: padded to whole blocks
+inline uint64_t maxsim_cand_positions(uint64_t rows) { return (rows + kMaxsimRows - 1) / kMaxsimRows * kMaxsimRows; }
+
+// E0.  One thread per list position of the window's n_blocks blocks: list[pos] = the local row and ord[pos] = the slot ordinal
+// of the position's candidate row, from a binary search of the set's `before` values; a position behind the set's rows is dead
+// (row 0, the set's last ordinal), which no block of M0 reads.
+struct MaxsimExpandParams {
+    const uint32_t* rows_by_key;
+    const MaxsimCandSet* sets;      // the window's
+    const MaxsimCandSeg* segs;      // the call's
+    const MaxsimCandBlock* blocks;  // the window's
+    uint32_t n_blocks;
+    uint32_t *list, *ord;           // [n_blocks * kMaxsimRows]
+};
+hipError_t maxsim_expand_launch(const MaxsimExpandParams& p, hipStream_t s);
+
+// M0 over the concatenated list: grid (p.m / kMaxsimRows blocks, 1); a block takes its set, and with it its tokens and its
+// best[set][t][n_keys], from p.blocks, and scores the block's first nr positions.  p.n_keys is the window's largest candidate
+// count, p.ord the slot ordinals.  The arithmetic is maxsim_score_launch's.
+hipError_t maxsim_score_candidates_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s);
 
 // M1.  sum[set][g] (f32; not read when `first`) advances by the chunk's tc reconstructed scores in token order; `last`: the
 // rank entry (key_from_score(S), ordinal g) goes to rank[set][g].
@@ -64,11 +102,14 @@ struct MaxsimSumParams {
     uint32_t n_keys, sets, tc;
     uint8_t metric, dtype;
     bool first, last;
+    const MaxsimCandSet* cand;  // nullable; the candidate form: ordinals from cand[set].count on are no keys -- dead rank entries
 };
 hipError_t maxsim_sum_launch(const MaxsimSumParams& p, hipStream_t s);
 
 // The result rows of `sets` query sets from their sorted rank entries sorted[set][n_keys]: the first min(k, n_keys) ordinals'
 // sums and key values (keys[n_keys], the index's key table), padding beyond, counts[set] (nullable) = min(k, n_keys).
+// The candidate form (cand not NULL): cand[set].count takes n_keys' place in both minima -- sorted and sum keep the stride
+// n_keys --, and ordinal g's key value is keys[cand[set].seg0 + g], the plan's key array.
 struct MaxsimWriteParams {
     const uint64_t* sorted;
     const float* sum;
@@ -78,6 +119,7 @@ struct MaxsimWriteParams {
     uint32_t* out_counts;
     uint32_t n_keys, sets, k;
     uint8_t metric;
+    const MaxsimCandSet* cand;  // nullable
 };
 hipError_t maxsim_write_launch(const MaxsimWriteParams& p, hipStream_t s);
 

@@ -11,6 +11,9 @@
 // key): an LDS minimum per (token, key of the block) first, then one atomicMin per (token, run of the block) into
 // best[token][key ordinal].  A minimum does not depend on the order of its operands: the result is deterministic.
 // M1 adds the chunk's reconstructed scores to the running f32 sum of every key, in token order.
+// The candidate form (mvfgpu_search_maxsim_candidates; DESIGN.md §5 "E0"): E0 expands the host plan's segments into one
+// concatenated (row, slot ordinal) list per window of query sets, every set's part padded to whole blocks, and M0's CAND
+// instantiations walk it with the block's set taken from a block table; M1 and the writer take the sets' candidate counts.
 //
 // Algorithmic HBM bytes of M0: the held rows' pitch once per chunk of tokens and query set (+ 8 bytes per held row and block).
 
@@ -65,7 +68,8 @@ __device__ __forceinline__ void scatter_sum(T (&v)[NV], int sub, int& first) {
 __host__ __device__ constexpr uint32_t maxsim_lds_head(uint32_t tc) { return tc * kMaxsimRows * 4u + kMaxsimRows * 8u + tc * 20u; }
 
 // grid (ceil(m / kMaxsimRows), sets), block 256; dynamic LDS maxsim_lds_head(tc) rounded up to 16 (+ tc padded tokens when QLDS)
-template <int DT, int METRIC, int G, bool REG, bool QLDS>
+// CAND, the candidate form: grid (m / kMaxsimRows, 1); the block's set and its number of positions come from p.blocks
+template <int DT, int METRIC, int G, bool REG, bool QLDS, bool CAND = false>
 __global__ void __launch_bounds__(256) maxsim_score_kernel(MaxsimScoreParams p) {
     using Tr = k1::Traits<DT>;
     using Acc = typename Tr::Acc;
@@ -91,8 +95,15 @@ __global__ void __launch_bounds__(256) maxsim_score_kernel(MaxsimScoreParams p) 
     unsigned char* qs = smem + ((maxsim_lds_head(tc) + 15u) & ~15u);            // [tc][J G vectors] the tokens (QLDS)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int sub = lane % G, rsel = lane / G;
-    const uint32_t c0 = blockIdx.x * kMaxsimRows, set = blockIdx.y;
-    const uint32_t nr = min(kMaxsimRows, p.m - c0);  // >= 1: the grid covers m
+    const uint32_t c0 = blockIdx.x * kMaxsimRows;
+    uint32_t set, nr;
+    if constexpr (CAND) {
+        const MaxsimCandBlock b = p.blocks[blockIdx.x];  // the same for every lane: kept in scalar registers
+        set = __builtin_amdgcn_readfirstlane(b.set);
+        nr = __builtin_amdgcn_readfirstlane(min(max(b.nr, 1u), kMaxsimRows));  // the plan's: 1 .. kMaxsimRows
+    } else {
+        set = blockIdx.y, nr = min(kMaxsimRows, p.m - c0);  // >= 1: the grid covers m
+    }
 
     // ---- the tokens: K1's staging loop and sums of squares, one token after the other (k1::stage_queries' lines)
     const uint32_t VP = p.J * G;
@@ -226,6 +237,10 @@ __device__ __forceinline__ float maxsim_score_of(uint32_t key, uint8_t metric, b
 __global__ void __launch_bounds__(256) maxsim_sum_kernel(MaxsimSumParams p) {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x, set = blockIdx.y;
     if (g >= p.n_keys) return;
+    if (p.cand && g >= p.cand[set].count) {  // no candidate of this set: behind every key, a NaN sum's included
+        if (p.last) p.rank[(size_t)set * p.n_keys + g] = rank_entry(kNanKey, g, true);
+        return;
+    }
     const bool raw_key = key_is_raw(p.dtype, p.metric);
     const uint32_t* best = p.best + (size_t)set * p.tc * p.n_keys + g;
     float* sum = p.sum + (size_t)set * p.n_keys + g;
@@ -241,14 +256,16 @@ __global__ void __launch_bounds__(256) maxsim_sum_kernel(MaxsimSumParams p) {
 // grid (blocks over k, sets), block 256
 __global__ void __launch_bounds__(256) maxsim_write_kernel(MaxsimWriteParams p) {
     const uint32_t set = blockIdx.y;
-    if (p.out_counts && blockIdx.x == 0 && threadIdx.x == 0) p.out_counts[set] = min(p.k, p.n_keys);
+    const uint32_t held = p.cand ? p.cand[set].count : p.n_keys;
+    const uint64_t* keys = p.cand ? p.keys + p.cand[set].seg0 : p.keys;
+    if (p.out_counts && blockIdx.x == 0 && threadIdx.x == 0) p.out_counts[set] = min(p.k, held);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < p.k; i += (size_t)gridDim.x * 256) {
         const size_t o = (size_t)set * p.k + i;
-        if (i < p.n_keys) {
+        if (i < held) {
             const uint32_t g = (uint32_t)(p.sorted[(size_t)set * p.n_keys + i] >> 32);
             const float S = p.sum[(size_t)set * p.n_keys + g];
             p.out_scores[o] = S != S ? unord_f32(kNanKey) : S;  // the NaN every result carries
-            p.out_keys[o] = p.keys[g];
+            p.out_keys[o] = keys[g];
         } else {
             p.out_scores[o] = pad_score(p.metric);
             p.out_keys[o] = ~0ull;
@@ -256,18 +273,40 @@ __global__ void __launch_bounds__(256) maxsim_write_kernel(MaxsimWriteParams p) 
     }
 }
 
-template <int DT>
+template <int DT, bool CAND>
 const void* pick_kernel(int metric, int G, bool reg, bool qlds) {
     return k1::for_metric(metric, [&](auto m) {
         return k1::for_group(G, [&](auto g) -> const void* {
             constexpr int M = decltype(m)::value, GG = decltype(g)::value;
             if constexpr (!k1::Traits<DT>::INT) {
-                if (!qlds) return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, false, false>);
+                if (!qlds) return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, false, false, CAND>);
             }
-            if (reg) return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, true, true>);
-            return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, false, true>);
+            if (reg) return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, true, true, CAND>);
+            return reinterpret_cast<const void*>(&maxsim_score_kernel<DT, M, GG, false, true, CAND>);
         });
     });
+}
+
+// E0; grid (n_blocks), block kMaxsimRows
+__global__ void __launch_bounds__(kMaxsimRows) maxsim_expand_kernel(MaxsimExpandParams p) {
+    const MaxsimCandBlock b = p.blocks[blockIdx.x];
+    const MaxsimCandSet st = p.sets[b.set];
+    const uint32_t pos = blockIdx.x * kMaxsimRows + threadIdx.x;
+    const uint32_t i = pos - st.list0;  // the position among the set's rows
+    uint32_t row = 0, slot = st.count ? st.count - 1u : 0u;
+    if (i < st.rows) {
+        const MaxsimCandSeg* seg = p.segs + st.seg0;
+        uint32_t lo = 0, hi = st.count;  // the last j with before[j] <= i; before[0] = 0
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (seg[mid].before <= i) lo = mid;
+            else hi = mid;
+        }
+        row = p.rows_by_key[(size_t)seg[lo].offset + (i - seg[lo].before)];
+        slot = lo;
+    }
+    p.list[pos] = row;
+    p.ord[pos] = slot;
 }
 
 }  // namespace
@@ -278,27 +317,45 @@ hipError_t maxsim_ordinals_launch(const uint64_t* offsets, uint64_t n_keys, uint
     return hipGetLastError();
 }
 
-hipError_t maxsim_score_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s) {
+namespace {
+template <bool CAND>
+hipError_t score_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s) {
     if (p.sets == 0 || p.m == 0 || p.tc == 0) return hipSuccess;
     if (p.tc > kMaxsimChunkMax || p.t0 + p.tc > p.n_tokens || p.sets > 65535u) return hipErrorInvalidValue;
+    if (CAND && (!p.blocks || p.m % kMaxsimRows)) return hipErrorInvalidValue;
     const uint32_t qbytes = cand_query_bytes(dtype, G, p.J);
     const bool qlds = is_int_dtype(dtype) || qbytes <= kCandQueryLdsMax;
     if (qlds && (size_t)p.tc * qbytes > kCandQueryLdsMax && p.tc > 1) return hipErrorInvalidValue;
     const bool reg = qlds && p.J <= kMaxsimRegSteps;
     const void* fn = nullptr;
     switch (dtype) {
-        case MVF_DTYPE_FLOAT32: fn = pick_kernel<MVF_DTYPE_FLOAT32>(metric, G, reg, qlds); break;
-        case MVF_DTYPE_FLOAT16: fn = pick_kernel<MVF_DTYPE_FLOAT16>(metric, G, reg, qlds); break;
-        case MVF_DTYPE_INT8: fn = pick_kernel<MVF_DTYPE_INT8>(metric, G, reg, qlds); break;
-        case MVF_DTYPE_UINT8: fn = pick_kernel<MVF_DTYPE_UINT8>(metric, G, reg, qlds); break;
+        case MVF_DTYPE_FLOAT32: fn = pick_kernel<MVF_DTYPE_FLOAT32, CAND>(metric, G, reg, qlds); break;
+        case MVF_DTYPE_FLOAT16: fn = pick_kernel<MVF_DTYPE_FLOAT16, CAND>(metric, G, reg, qlds); break;
+        case MVF_DTYPE_INT8: fn = pick_kernel<MVF_DTYPE_INT8, CAND>(metric, G, reg, qlds); break;
+        case MVF_DTYPE_UINT8: fn = pick_kernel<MVF_DTYPE_UINT8, CAND>(metric, G, reg, qlds); break;
         default: break;
     }
     if (!fn) return hipErrorInvalidValue;
     const size_t lds = ((maxsim_lds_head(p.tc) + 15u) & ~15u) + (qlds ? (size_t)p.tc * qbytes : 0u);
-    const dim3 grid((p.m + kMaxsimRows - 1) / kMaxsimRows, p.sets);
+    const dim3 grid((p.m + kMaxsimRows - 1) / kMaxsimRows, CAND ? 1u : p.sets);
     MaxsimScoreParams arg = p;
     void* args[] = {&arg};
     return hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+}
+}  // namespace
+
+hipError_t maxsim_score_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s) {
+    return score_launch<false>(dtype, metric, G, p, s);
+}
+
+hipError_t maxsim_score_candidates_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s) {
+    return score_launch<true>(dtype, metric, G, p, s);
+}
+
+hipError_t maxsim_expand_launch(const MaxsimExpandParams& p, hipStream_t s) {
+    if (p.n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(maxsim_expand_kernel, dim3(p.n_blocks), dim3(kMaxsimRows), 0, s, p);
+    return hipGetLastError();
 }
 
 hipError_t maxsim_sum_launch(const MaxsimSumParams& p, hipStream_t s) {

@@ -328,6 +328,33 @@ def maxsim_plan(n_keys: int, n_tokens: int, nq: int, token_bytes: int, budget_by
     return chunk.value, window.value
 
 
+def maxsim_candidates_plan(candidate_keys, held_counts) -> tuple[np.ndarray, int, int]:
+    """(slot ordinals [m], distinct held candidates, the rows they hold) of ONE query set's candidate list, given every entry's
+    held row count (`GpuPartition.lookup`'s): `mvfgpu_selftest_maxsim_candidates_plan`; no GPU needed.  A slot of UINT32_MAX
+    marks an entry that is skipped (no held row) or repeats an earlier one."""
+    ck = _keys_u64(candidate_keys)
+    hc = np.ascontiguousarray(np.asarray(held_counts).reshape(-1), dtype=np.uint64)
+    if ck.size != hc.size:
+        raise InvalidArgument("candidate_keys and held_counts must have one entry per candidate")
+    slot = np.zeros(max(ck.size, 1), np.uint32)
+    distinct, rows = C.c_uint32(0), C.c_uint64(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_candidates_plan(ck.ctypes.data_as(C.c_void_p), hc.ctypes.data_as(C.c_void_p), ck.size,
+                                                                     slot.ctypes.data_as(C.c_void_p), C.byref(distinct), C.byref(rows)))
+    return slot[:ck.size], distinct.value, rows.value
+
+
+def _candidate_lists(candidate_keys, nq: int) -> np.ndarray:
+    """[nq, m] uint64 from one list [m] (shared by every set) or [nq, m]"""
+    if candidate_keys is None:
+        return np.zeros((nq, 0), np.uint64)
+    a = np.asarray(candidate_keys)
+    if a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[0] != nq):
+        raise InvalidArgument(f"candidate_keys must be [m] or [{nq}, m], got shape {a.shape}")
+    m = a.shape[-1]
+    flat = _keys_u64(a).reshape(-1, m) if m else np.zeros((a.shape[0] if a.ndim == 2 else 1, 0), np.uint64)
+    return np.ascontiguousarray(np.broadcast_to(flat, (nq, m)))
+
+
 def _keys_u64(keys) -> np.ndarray:
     if isinstance(keys, np.ndarray) and keys.dtype.kind == "u":
         return np.ascontiguousarray(keys.reshape(-1), dtype=np.uint64)
@@ -791,6 +818,55 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_stage_ms(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                   nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
                                                                   _opt(stream), out))
+        return tuple(float(x) for x in out)
+
+    def search_maxsim_candidates(self, query_sets: np.ndarray, candidate_keys, k: int, metric: int, part: GpuPartition) -> MaxSimResult:
+        """`search_maxsim` among every set's own candidate keys (`mvfgpu_search_maxsim_candidates`; re-ranking): `candidate_keys`
+        is [m] (one list for every set) or [nq, m]; entries the partition does not hold -- unknown keys, wholly deleted keys,
+        UINT64_MAX pads -- are skipped, repeats count once.  counts[q] = min(k, distinct held candidates of set q)."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        q = np.asarray(query_sets)
+        if q.ndim == 2:
+            q = q[None, :, :]
+        if q.ndim != 3:
+            raise InvalidArgument(f"query sets must be [nq, n_tokens, dim], got shape {q.shape}")
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, n_tokens, qdim = q.shape
+        cand = _candidate_lists(candidate_keys, nq)
+        m = cand.shape[1]
+        sc, keys, cnt = np.empty((nq, k), np.float32), np.empty((nq, k), np.uint64), np.zeros(nq, np.uint32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_maxsim_candidates(self._h, hpart, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
+                                                                  n_tokens, cand.ctypes.data_as(C.c_void_p) if cand.size else None, m, k,
+                                                                  sc.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p),
+                                                                  cnt.ctypes.data_as(C.c_void_p)))
+        return MaxSimResult(sc, keys, cnt)
+
+    def search_maxsim_candidates_device(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int,
+                                        candidate_keys, k: int, metric: int, d_scores: int, d_keys: int, d_counts: int = 0,
+                                        stream: int = 0) -> None:
+        """Device-pointer candidate multi-vector search (`mvfgpu_search_maxsim_candidates_device`), asynchronous on `stream`;
+        `candidate_keys` ([m] or [nq, m]) stays on the host and is read before the call returns."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        cand = _candidate_lists(candidate_keys, nq)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_maxsim_candidates_device(
+            self._h, hpart, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq, n_tokens,
+            cand.ctypes.data_as(C.c_void_p) if cand.size else None, cand.shape[1], k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+            _opt(d_counts), _opt(stream)))
+
+    def maxsim_candidates_stage_ms(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int,
+                                   candidate_keys, k: int, metric: int, d_scores: int, d_keys: int,
+                                   stream: int = 0) -> tuple[float, float, float, float]:
+        """(plan upload + E0, M0, M1, tail) in ms of one candidate multi-vector search, summed over its chunks and windows
+        (`mvfgpu_selftest_maxsim_candidates_stage_ms`); waits for the stream."""
+        out = (C.c_float * 4)()
+        cand = _candidate_lists(candidate_keys, nq)
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_candidates_stage_ms(
+            self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq, n_tokens,
+            cand.ctypes.data_as(C.c_void_p) if cand.size else None, cand.shape[1], k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+            _opt(stream), out))
         return tuple(float(x) for x in out)
 
     def search_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, metric: int,

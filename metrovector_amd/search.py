@@ -370,6 +370,39 @@ def find_top_k_documents(space: VectorSpace, query_vectors, k: int, column: str,
             corpus.close()
 
 
+def rerank_top_k_documents(space: VectorSpace, query_vectors, candidate_keys, k: int, column: str, metric: int | None = None,
+                           corpus: GpuCorpus | None = None, device: int = 0) -> MaxSimResult:
+    """`find_top_k_documents` among CANDIDATE documents (`mvfgpu_search_maxsim_candidates`; DESIGN.md §3 "Candidate keys"): the
+    exact late-interaction scores of the documents a first stage proposed, best k first.  `candidate_keys` holds values of the
+    column, [m] for every query or [nq, m]; values no live vector carries (UINT64_MAX pads among them) are skipped, repeats
+    count once, and counts[q] = min(k, the distinct candidates found).  The column is read as `find_top_k_per_key` reads it,
+    with the same refusals; it and the index live for this call (`GpuCorpus.search_maxsim_candidates` for many batches)."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    total = space.total_vectors()
+    mc = space._reader.metadata_column(column)  # everything about the file's column is refused before anything is uploaded
+    es = {4: 4, 5: 8}.get(int(mc.data_type))
+    if es is None:
+        raise BuildError("Unsupported metadata column data type")
+    if mc.size // es < total:
+        raise BuildError(f"metadata column '{column}' holds {mc.size // es} values, the space has {total} vectors")
+    dt = int(space.data_type())
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        base = int(corpus.info().index_base)
+        with corpus.attach_column_pointer(mc.as_ptr(), int(mc.data_type), base, mc.size // es) as col:
+            with corpus.make_partition(col) as part:
+                return corpus.search_maxsim_candidates(np.asarray(query_vectors, dtype=_NP_OF[query_dtype_code(dt)]), candidate_keys, k,
+                                                       metric, part)
+    finally:
+        if own:
+            corpus.close()
+
+
 def build_knn_graph(space: VectorSpace, k: int, metric: int | None = None, corpus: GpuCorpus | None = None, first: int = 0,
                     count: int | None = None, device: int = 0) -> SearchResult:
     """The k-NN graph of a space (`mvfgpu_knn_join`; DESIGN.md §3 "Join"): for rows [first, first + count) (local rows of
