@@ -161,6 +161,11 @@ extern "C" {
                                               d_queries: *const c_void, query_dtype: u8, query_dim: u32, nq: u32, n_tokens: u32,
                                               candidate_keys: *const u64, m: u32, k: u32, d_scores: *mut f32, d_keys: *mut u64,
                                               d_counts: *mut u32, hip_stream: *mut c_void) -> c_int;
+    /// Which instantiation of the multi-vector scoring kernel serves rows of `dimension` elements (include/mvf_gpu.h; no GPU,
+    /// no handle): lanes per row, 16-byte steps per lane, bytes of a padded token, the form (0 rows in registers, 1 rows read
+    /// again, 2 tokens through the cache) and the tokens per chunk LDS allows.  `forced_g`: 0, or the width `MVF_K1_G` forces.
+    fn mvfgpu_selftest_maxsim_form(data_type: u8, dimension: u32, forced_g: u32, out_g: *mut u32, out_j: *mut u32,
+                                   out_token_bytes: *mut u32, out_form: *mut u32, out_lds_chunk_cap: *mut u32) -> c_int;
     /// The column's values (zero-extended) of the rows a search reported; padding gives 0.
     fn mvfgpu_column_gather(column: *const MvfGpuColumn, indices: *const u64, count: u64, out_values: *mut u64) -> c_int;
     fn mvfgpu_last_error_message() -> *const c_char;

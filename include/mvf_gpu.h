@@ -735,6 +735,18 @@ int mvfgpu_search_maxsim_device(const mvfgpu_corpus* corpus, const mvfgpu_partit
 int mvfgpu_selftest_maxsim_plan(uint64_t n_keys, uint32_t n_tokens, uint32_t nq, uint64_t token_bytes, uint64_t budget_bytes,
                                 uint32_t* tokens_per_chunk, uint32_t* sets_per_window);
 /*
+ * Self-test of the scoring kernel's form (no GPU, no handle): which instantiation of M0 ("M0 / M1") scores
+ * rows of `dimension` elements of `data_type` -- the decision the launch itself takes.  forced_g = 0: the library's own lane-group
+ * rule; 1, 4, 8, 16, 32 or 64: the width MVF_K1_G forces on a handle.  *out_g = lanes per row, *out_j = 16-byte steps per lane,
+ * *out_token_bytes = a padded token (g x j vectors; Float16 rows keep their tokens widened: 32 bytes per vector),
+ * *out_form = 0 where the rows stay in registers over a chunk (j <= 4), 1 where they are read again per token group, 2 where in
+ * addition the float tokens exceed 40 KiB and are read through the cache; *out_lds_chunk_cap = tokens_per_chunk of
+ * mvfgpu_selftest_maxsim_plan for 1024 tokens and an unbounded budget.  Refused with MVF_ERR_INVALID_ARGUMENT: a NULL output, an
+ * unknown data type, dimension 0, an Int8 / UInt8 dimension above MVFGPU_MAX_INT_DIM, a row above 1 GiB, any other forced_g.
+ */
+int mvfgpu_selftest_maxsim_form(uint8_t data_type, uint32_t dimension, uint32_t forced_g, uint32_t* out_g, uint32_t* out_j,
+                                uint32_t* out_token_bytes, uint32_t* out_form, uint32_t* out_lds_chunk_cap);
+/*
  * Stage timer of a multi-vector search (scripts/probe_maxsim.py): mvfgpu_search_maxsim_device without d_counts, with events between
  * its stages; waits for the stream.  out_ms[0..3] = the key ordinals (once per call), M0 (scoring and per-key best), M1 (the sums),
  * the tail (select, sort, format), each summed over the call's chunks and windows.
@@ -1013,7 +1025,7 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * mvfgpu_selftest_group_plan and mvfgpu_selftest_grouped_stage_ms, nor did the multi-vector search, which only adds
  * mvfgpu_search_maxsim, mvfgpu_search_maxsim_device, mvfgpu_selftest_maxsim_plan and mvfgpu_selftest_maxsim_stage_ms, nor did
  * its candidate form, which only adds mvfgpu_search_maxsim_candidates, mvfgpu_search_maxsim_candidates_device,
- * mvfgpu_selftest_maxsim_candidates_plan and mvfgpu_selftest_maxsim_candidates_stage_ms).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * mvfgpu_selftest_maxsim_candidates_plan and mvfgpu_selftest_maxsim_candidates_stage_ms, nor did mvfgpu_selftest_maxsim_form).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

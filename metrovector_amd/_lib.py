@@ -237,6 +237,8 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_search_maxsim_device.restype = C.c_int
     lib.mvfgpu_selftest_maxsim_plan.argtypes = [u64, u32, u32, u64, u64, vp, vp]
     lib.mvfgpu_selftest_maxsim_plan.restype = C.c_int
+    lib.mvfgpu_selftest_maxsim_form.argtypes = [u8, u32, u32, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_maxsim_form.restype = C.c_int
     lib.mvfgpu_selftest_maxsim_stage_ms.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp]
     lib.mvfgpu_selftest_maxsim_stage_ms.restype = C.c_int
     lib.mvfgpu_search_maxsim_candidates.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, u32, vp, vp, vp]

@@ -513,4 +513,27 @@ int mvfgpu_selftest_maxsim_plan(uint64_t n_keys, uint32_t n_tokens, uint32_t nq,
     return MVF_OK;
 }
 
+int mvfgpu_selftest_maxsim_form(uint8_t data_type, uint32_t dimension, uint32_t forced_g, uint32_t* out_g, uint32_t* out_j,
+                                uint32_t* out_token_bytes, uint32_t* out_form, uint32_t* out_lds_chunk_cap) {
+    if (!out_g || !out_j || !out_token_bytes || !out_form || !out_lds_chunk_cap) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (elem_size(data_type) == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported vector data type code " + std::to_string(data_type));
+    if (dimension == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "dimension must be > 0");
+    if (is_int_dtype(data_type) && dimension > MVFGPU_MAX_INT_DIM)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "Int8/UInt8 dimension exceeds the exact-i32 bound (33025)");
+    if ((uint64_t)dimension * elem_size(data_type) > (1ull << 30)) return set_fail(MVF_ERR_INVALID_ARGUMENT, "a row holds at most 1 GiB");
+    if (forced_g != 0 && forced_g != 1 && forced_g != 4 && forced_g != 8 && forced_g != 16 && forced_g != 32 && forced_g != 64)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "forced_g must be 0, 1, 4, 8, 16, 32 or 64, got " + std::to_string(forced_g));
+    const uint32_t V = (uint32_t)(((uint64_t)dimension * elem_size(data_type) + 15u) / 16u);  // alloc_rows' pitch / 16
+    int G = 0;
+    uint32_t J = 0;
+    k1_group(V, 1, (int)forced_g, &G, &J);  // one_query_group's
+    const MaxsimForm f = maxsim_form(data_type, G, J);
+    *out_g = (uint32_t)G;
+    *out_j = J;
+    *out_token_bytes = f.token_bytes;
+    *out_form = f.reg ? 0u : f.qlds ? 1u : 2u;
+    *out_lds_chunk_cap = maxsim_plan(1, MVFGPU_MAXSIM_MAX_TOKENS, 1, f.token_bytes, ~0ull).chunk;
+    return MVF_OK;
+}
+
 }  // extern "C"

@@ -39,6 +39,22 @@ inline MaxsimPlan maxsim_plan(uint64_t n_keys, uint32_t n_tokens, uint32_t nq, u
     return pl;
 }
 
+// The form of M0 that scores rows of J steps per lane of a G-lane group, a pure function: the bytes of a padded token
+// (cand_query_bytes); qlds: the tokens live in LDS -- Int8 / UInt8 always, float tokens up to kCandQueryLdsMax bytes, beyond that
+// they are read through the cache --; reg: the rows stay in registers over a chunk (J <= kMaxsimRegSteps), else they are read
+// again per token group.  score_launch picks its instantiation from it and mvfgpu_selftest_maxsim_form reports it.
+struct MaxsimForm {
+    uint32_t token_bytes;
+    bool qlds, reg;
+};
+inline MaxsimForm maxsim_form(uint8_t dtype, int G, uint32_t J) {
+    MaxsimForm f;
+    f.token_bytes = cand_query_bytes(dtype, G, J);
+    f.qlds = is_int_dtype(dtype) || f.token_bytes <= kCandQueryLdsMax;
+    f.reg = f.qlds && J <= kMaxsimRegSteps;
+    return f;
+}
+
 // ord[i] = the ordinal, in the key table, of the key whose segment holds position i of the key-ordered list, from the table's
 // offsets [n_keys + 1]; once per call
 hipError_t maxsim_ordinals_launch(const uint64_t* offsets, uint64_t n_keys, uint32_t live, uint32_t* ord, hipStream_t s);

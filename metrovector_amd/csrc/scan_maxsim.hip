@@ -323,10 +323,10 @@ hipError_t score_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParam
     if (p.sets == 0 || p.m == 0 || p.tc == 0) return hipSuccess;
     if (p.tc > kMaxsimChunkMax || p.t0 + p.tc > p.n_tokens || p.sets > 65535u) return hipErrorInvalidValue;
     if (CAND && (!p.blocks || p.m % kMaxsimRows)) return hipErrorInvalidValue;
-    const uint32_t qbytes = cand_query_bytes(dtype, G, p.J);
-    const bool qlds = is_int_dtype(dtype) || qbytes <= kCandQueryLdsMax;
+    const MaxsimForm form = maxsim_form(dtype, G, p.J);
+    const uint32_t qbytes = form.token_bytes;
+    const bool qlds = form.qlds, reg = form.reg;
     if (qlds && (size_t)p.tc * qbytes > kCandQueryLdsMax && p.tc > 1) return hipErrorInvalidValue;
-    const bool reg = qlds && p.J <= kMaxsimRegSteps;
     const void* fn = nullptr;
     switch (dtype) {
         case MVF_DTYPE_FLOAT32: fn = pick_kernel<MVF_DTYPE_FLOAT32, CAND>(metric, G, reg, qlds); break;

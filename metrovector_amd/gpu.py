@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -326,6 +327,22 @@ def maxsim_plan(n_keys: int, n_tokens: int, nq: int, token_bytes: int, budget_by
     chunk, window = C.c_uint32(0), C.c_uint32(0)
     _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_plan(n_keys, n_tokens, nq, token_bytes, budget_bytes, C.byref(chunk), C.byref(window)))
     return chunk.value, window.value
+
+
+class MaxSimForm(NamedTuple):
+    G: int              # lanes per row
+    J: int              # 16-byte steps per lane
+    token_bytes: int    # a padded token
+    form: int           # 0 rows in registers, 1 rows read again per token group, 2 .. and float tokens read through the cache
+    lds_chunk_cap: int  # tokens per chunk for 1024 tokens and an unbounded budget
+
+
+def maxsim_form(dtype: int, dim: int, forced_g: int = 0) -> MaxSimForm:
+    """The instantiation of the multi-vector search's scoring kernel for rows of `dim` elements of `dtype` (a data type code),
+    under the library's lane-group rule or the width `MVF_K1_G` = `forced_g` forces: `mvfgpu_selftest_maxsim_form`; no GPU needed."""
+    out = [C.c_uint32(0) for _ in range(5)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_form(dtype, dim, forced_g, *[C.byref(o) for o in out]))
+    return MaxSimForm(*[o.value for o in out])
 
 
 def maxsim_candidates_plan(candidate_keys, held_counts) -> tuple[np.ndarray, int, int]:

@@ -7,6 +7,11 @@ first, NaN last, -0.0 == +0.0), reconstructed from its order key; the sum over t
 (order key of the sum, key value); padding.  It takes the row scores as given -- the library's (the identity tests) or float64
 ones rounded to f32 (the CPU tests) -- so it states the SELECTION and the SUM, not the arithmetic of a row score.
 
+Behind it, for the tests of the scoring kernel's forms (DESIGN.md §5 "M0 / M1"; tests/test_gpu_maxsim_forms.py): the table of
+(type, dimension) cases with the cell each holds, and two references that DO state a row score's arithmetic, independent of
+every kernel -- float64 sums with §3's tolerance per token, and exact integers for Int8 / UInt8 rows --, the saturated integer
+world and two wrong kernels as models.
+
 Imports numpy and the standard library only; as a child it keeps the binding from loading torch.
 """
 import ctypes as C
@@ -121,6 +126,223 @@ def plan(n_keys, n_tokens, nq, token_bytes, budget):
 
 def make_sets(nq, n_tokens, dim, dt):
     return P.make_queries(nq * n_tokens, dim, dt).reshape(nq, n_tokens, dim)
+
+
+# ---- the scoring kernel's forms (DESIGN.md §5 "M0 / M1"; tests/test_gpu_maxsim_forms.py, tests/test_maxsim_cpu.py)
+DTYPE = {"f32": 0, "f16": 1, "i8": 2, "u8": 3}
+REG, REREAD, CACHE = 0, 1, 2
+REG_STEPS = 4      # kMaxsimRegSteps: rows of up to this many steps per lane stay in registers
+FORM_LAYOUT = (300, 129, 128, 127, 64, 2, 1), 20   # P.layout's sizes and further keys, on 2048 or 1024 rows
+
+# (type, dimension) -> the cell it holds: (lanes per row G, steps per lane J, form), worked out by hand from the rules of
+# choose_group (api.hip) and maxsim_form (scan_maxsim.h); mvfgpu_selftest_maxsim_form is the authority the tests hold it to.
+FORM_CELLS = {
+    ("f32", 3): (1, 1, REG), ("f32", 16): (4, 1, REG), ("f32", 32): (8, 1, REG), ("f32", 64): (16, 1, REG), ("f32", 100): (32, 1, REG),
+    ("f32", 128): (16, 2, REG), ("f32", 256): (16, 4, REG), ("f32", 288): (16, 5, REREAD), ("f32", 384): (16, 6, REREAD),
+    ("f32", 736): (16, 12, REREAD), ("f32", 1024): (64, 4, REG), ("f32", 1028): (64, 5, REREAD), ("f32", 10240): (64, 40, REREAD),
+    ("f32", 10241): (64, 41, CACHE),
+    ("f16", 8): (1, 1, REG), ("f16", 20): (4, 1, REG), ("f16", 64): (8, 1, REG), ("f16", 128): (16, 1, REG), ("f16", 200): (32, 1, REG),
+    ("f16", 512): (16, 4, REG), ("f16", 768): (16, 6, REREAD), ("f16", 1024): (16, 8, REREAD), ("f16", 2048): (64, 4, REG),
+    ("f16", 2056): (64, 5, REREAD), ("f16", 10240): (64, 20, REREAD), ("f16", 10248): (64, 21, CACHE),
+    ("i8", 16): (1, 1, REG), ("i8", 64): (4, 1, REG), ("i8", 128): (8, 1, REG), ("i8", 400): (32, 1, REG), ("i8", 768): (16, 3, REG),
+    ("i8", 1000): (64, 1, REG), ("i8", 1536): (16, 6, REREAD), ("i8", 4096): (64, 4, REG), ("i8", 4112): (64, 5, REREAD),
+    ("i8", 33025): (64, 33, REREAD),
+    ("u8", 5): (1, 1, REG), ("u8", 64): (4, 1, REG), ("u8", 100): (8, 1, REG), ("u8", 256): (16, 1, REG), ("u8", 300): (32, 1, REG),
+    ("u8", 1024): (16, 4, REG), ("u8", 2048): (16, 8, REREAD), ("u8", 3000): (64, 3, REG), ("u8", 33025): (64, 33, REREAD),
+}
+FORM_CASES = list(FORM_CELLS)
+# the three switches, (type, last dimension on the near side, first on the far side): J 4 -> 5 at 16 lanes, at 64 lanes, LDS -> cache
+FORM_SWITCHES = {"reg to reread, G 16": [("f32", 256, 288)],
+                 "reg to reread, G 64": [("f32", 1024, 1028), ("f16", 2048, 2056), ("i8", 4096, 4112)],
+                 "LDS to cache": [("f32", 10240, 10241), ("f16", 10240, 10248)]}
+FORCED_WIDTHS = (1, 4, 8, 16, 32, 64)
+FORCED_SHAPES = [("f32", 200), ("f16", 400), ("i8", 800)]   # V = 50 vectors of 16 bytes
+
+
+def form_rows(dim):
+    """rows of a form case's world: 2048; 1024 for the widest rows (the layout keeps a key across a 128-position block edge)"""
+    return 1024 if dim >= 10240 else 2048
+
+
+def form_layout(n):
+    return P.layout("u32", n, *FORM_LAYOUT)
+
+
+def key_order(lay):
+    """(live rows in the index's order -- ascending key value, then position --, their keys, the first list position of every
+    key, the keys' values)"""
+    live = np.nonzero(~lay["dead"])[0]
+    keys = lay["col"][live].astype(np.uint64)
+    order = np.argsort(keys, kind="stable")
+    live, keys = live[order], keys[order]
+    starts = np.nonzero(np.concatenate([[True], keys[1:] != keys[:-1]]))[0]
+    return live, keys, starts, keys[starts]
+
+
+def spans_block_edge(lay, block=128):
+    """a key's rows lie on both sides of a multiple of `block` list positions"""
+    _, keys, starts, _ = key_order(lay)
+    ends = np.concatenate([starts[1:], [keys.size]])
+    return bool(((starts // block) != ((ends - 1) // block)).any())
+
+
+def token_pool(dt, dim, nq=3, T=33):
+    """[nq, T, dim]: the query sets of a form case are its leading [:nq, :T], so one reference serves every (nq, T)"""
+    return P.make_queries(nq * T, dim, dt).reshape(nq, T, dim)
+
+
+# -- floats: the float64 contract (DESIGN.md §3 "Tolerance")
+def f64_key_bests(rows, lay, tokens, tol_unit):
+    """{metric: (b [T, n_keys] float64 -- token t's best score among key g's live rows --, tol [T, n_keys]: §3's tolerance of
+    that row score: tol_unit relative under L2, absolute under Cosine, x |q| max|x| of the key under InnerProduct)},
+    independent of every kernel"""
+    import _wide as W
+    live, _, starts, _ = key_order(lay)
+    x = rows[live]
+    all64 = W.f64_scores_all(x, tokens)
+    xn = np.sqrt(np.einsum("ij,ij->i", x.astype(np.float64), x.astype(np.float64)))
+    qn = np.linalg.norm(tokens.astype(np.float64), axis=1)
+    out = {}
+    for metric in (0, 1, 2):
+        sign = 1.0 if metric == 0 else -1.0
+        b = sign * np.minimum.reduceat(sign * all64[metric], starts, axis=1)
+        if metric == 0:
+            tol = tol_unit * np.abs(b)
+        elif metric == 2:
+            tol = np.full(b.shape, tol_unit)
+        else:
+            tol = tol_unit * np.maximum.reduceat(xn, starts)[None, :] * qn[:, None]
+        out[metric] = (b, tol)
+    return out
+
+
+def assert_f64_contract(scores, keys, key_values, S, tol, metric, k):
+    """One result row against float64 sums S [n_keys] with their tolerances tol [n_keys] (each the sum over the tokens of a row
+    score's): k distinct keys of the partition, every returned sum within its tolerance, the list in (order key, key value)
+    order, and the set of keys right up to sums within two such tolerances of the k-th -- boundary ties only at the k-th rank."""
+    at = np.searchsorted(key_values, keys)
+    assert (key_values[at] == keys).all() and np.unique(at).size == k, "k distinct keys of the partition"
+    assert (np.abs(scores.astype(np.float64) - S[at]) <= tol[at]).all(), f"k {k}: a sum outside its tolerance"
+    okey = order_key(scores, metric).astype(np.int64)
+    assert ((okey[1:] > okey[:-1]) | ((okey[1:] == okey[:-1]) & (keys[1:] > keys[:-1]))).all(), "order"
+    key = (1.0 if metric == 0 else -1.0) * S
+    kth, band = np.partition(key, k - 1)[k - 1], 2 * tol.max()
+    assert set(np.nonzero(key < kth - band)[0].tolist()) <= set(at.tolist()), "a clear winner is missing"
+    assert set(at.tolist()) <= set(np.nonzero(key <= kth + band)[0].tolist()), "a clear loser was returned"
+
+
+def f64_fraction(scores, keys, key_values, S, tol):
+    """the largest |returned sum - float64 sum| of a result row in units of its tolerance"""
+    at = np.searchsorted(key_values, keys)
+    return float(np.max(np.abs(scores.astype(np.float64) - S[at]) / tol[at]))
+
+
+# -- Int8 / UInt8: exact
+def int_raw(rows, lay, tokens):
+    """the exact integers of every (token, live row): W.int_raw's (dot, qq, xx) over the live rows in the index's order"""
+    import _wide as W
+    return W.int_raw(rows[key_order(lay)[0]], tokens)
+
+
+def int_row_scores(rows, lay, tokens, metric, raw=None):
+    """(f32 scores [T, live] of the live rows in the index's order, their exact raw integers, their keys): W.int_raw ->
+    W.int_scores; raw: int_raw's result where a caller keeps it over the metrics"""
+    import _wide as W
+    sc, _, r = W.int_scores(metric, *(int_raw(rows, lay, tokens) if raw is None else raw))
+    return sc, r, key_order(lay)[1]
+
+
+def rank_sets(scores, keys, nq, T, metric, k, stride=None):
+    """(scores [nq, k], keys [nq, k], counts [nq]): `vectorised` over set j's token rows scores[j * stride : j * stride + T]"""
+    stride = T if stride is None else stride
+    res = [vectorised(scores[j * stride:j * stride + T], keys, metric, k) for j in range(nq)]
+    return np.stack([r[0] for r in res]), np.stack([r[1] for r in res]), np.array([r[2] for r in res], np.uint32)
+
+
+def int_reference(rows, lay, sets, metric, k):
+    """(scores [nq, k], keys [nq, k], counts [nq]) of search_maxsim over Int8 / UInt8 rows, exact: every byte must match"""
+    nq, T, dim = sets.shape
+    sc, _, keys = int_row_scores(rows, lay, sets.reshape(nq * T, dim), metric)
+    return rank_sets(sc, keys, nq, T, metric, k)
+
+
+# -- saturated integer rows: sums next to 2^31 (tests/_wide.py's saturated_rows, on this file's layout)
+INT_RANGE = {"i8": (-128, 127), "u8": (0, 255)}
+SAT_OWN_KEY0, SAT_TIE_KEY = 0x70000000, 0x70000100   # the planted rows' keys: values the layout does not draw
+
+
+def saturated_positions(n):
+    """13 live positions (none a multiple of 10): the first rows, both sides of 128, 256 and the middle, the tail"""
+    pos = [1, 2, 127, 128, 129, 255, 257, n // 2 - 1, n // 2 + 1, n - 1, n - 2, n - 3, n - 5]
+    assert len(set(pos)) == len(pos) and all(p % 10 for p in pos)
+    return pos
+
+
+def saturated_world(dt, dim, n=None):
+    """-> (rows [n, dim], layout, planted positions).  Random rows with saturated ones planted.  Planted rows 0..9 carry a key of
+    their own each -- their score is that key's best whatever the metric --: all-min, all-max, alternating min / max, all-max with
+    one element at min, then six all-max rows with one to three elements lowered by one, the second of them equal to the first
+    (two keys with equal rows: bit-equal sums).  Planted rows 10..12 share one further key: two equal near-max rows and a third
+    (a tie inside a key)."""
+    n = form_rows(dim) if n is None else n
+    lo, hi = INT_RANGE[dt]
+    lay = form_layout(n)
+    rows = P.make_rows(n, dim, dt)
+    pos = saturated_positions(n)
+    assert not lay["dead"][pos].any()
+    t = rows.dtype.type
+    rows[pos[0]] = t(lo)
+    rows[pos[1]] = t(hi)
+    rows[pos[2], 0::2] = t(lo)
+    rows[pos[2], 1::2] = t(hi)
+    rows[pos[3]] = t(hi)
+    rows[pos[3], dim // 2] = t(lo)
+    rng = np.random.default_rng(P._seed("saturated", dt, dim, n))
+    for i, p in enumerate(pos[4:]):
+        rows[p] = t(hi)
+        if i in (1, 7):                  # the same row as the one before it, elsewhere
+            rows[p] = rows[pos[4 + i - 1]]
+            continue
+        for j in rng.choice(dim, 1 + i % 3, replace=False):
+            rows[p, j] = t(hi - 1)
+    col = lay["col"].copy()
+    own = [SAT_OWN_KEY0 + i for i in range(10)]
+    assert not np.isin(col, np.array(own + [SAT_TIE_KEY], col.dtype)).any()
+    col[pos[:10]] = np.array(own, col.dtype)
+    col[pos[10:]] = SAT_TIE_KEY
+    return rows, dict(lay, col=col), pos
+
+
+def saturated_sets(dt, dim, nq=2, T=5):
+    """[nq, T, dim]: tests/_wide.py saturated_queries' four special tokens -- all-min, all-max, alternating, all-zero -- among
+    random ones, at other places in every set"""
+    lo, hi = INT_RANGE[dt]
+    sets = make_sets(nq, T, dim, dt)
+    special = [np.full(dim, lo), np.full(dim, hi), np.where(np.arange(dim) % 2 == 0, lo, hi), np.zeros(dim, np.int64)]
+    assert T > len(special)
+    for j in range(nq):
+        for i, s in enumerate(special):
+            sets[j, (i + j) % T if j % 2 == 0 else T - 1 - i] = s.astype(sets.dtype)
+    return sets
+
+
+# -- two wrong kernels the exact reference must tell from the right one
+def model_drops_last_step(rows, tokens, G, J, elems_per_vector=16):
+    """(rows, tokens) as a kernel sees them that never runs the row's last step j = J - 1: the vectors (J - 1) G .. are zero"""
+    cut = (J - 1) * G * elems_per_vector
+    r, q = rows.copy(), tokens.copy()
+    r[:, cut:], q[:, cut:] = 0, 0
+    return r, q
+
+
+def model_swaps_row_pairs(n_live, G, block=128):
+    """the list position whose score a kernel attributes to position i when it takes row u of a step for row u ^ 1: rows of a
+    step are neighbouring groups of 64 / G positions of the block; a partner behind the list's end leaves the position its own"""
+    rpg = 64 // G
+    i = np.arange(n_live)
+    inb, b0 = i % block, i - i % block
+    partner = b0 + ((inb // rpg) ^ 1) * rpg + inb % rpg
+    return np.where(partner < n_live, partner, i)
 
 
 # ---- the fresh-process scenario: Float32 8192 x 100, the stock layout, 3 sets of 5 tokens, host call and device call

@@ -16,6 +16,7 @@ import _grouped as GR
 import _maxsim as MS
 import _partitioned as P
 from _children import RUNNER
+from _maxsim_world import World, check_sets, expected, ks_of, same_bytes
 from _util import PAD, TOL
 from metrovector_amd import errors as E
 from metrovector_amd import gpu as G
@@ -31,26 +32,6 @@ NQS = (1, 3)
 LAYOUTS = {"stock": GR.stock, "caps": GR.caps, "dominant": GR.dominant, "own_keys": GR.own_keys, "one_key": GR.one_key}
 
 
-class World:
-    """one corpus with its column and partition index"""
-
-    def __init__(self, dt, dim, lay, rows=None):
-        self.dt, self.dim, self.lay = dt, dim, lay
-        self.rows = P.make_rows(len(lay["col"]), dim, dt) if rows is None else rows
-        self.c = G.GpuCorpus.from_array(self.rows)
-        self.c.set_tombstones(np.packbits(lay["dead"], bitorder="little"))
-        self.col = self.c.attach_column(lay["col"])
-        self.part = self.c.make_partition(self.col)
-        self.live = GR.live_rows(lay)
-        self.keys = self.part.keys()[0] if self.live.size else np.zeros(0, np.uint64)
-        self.nk = int(self.keys.size)
-
-    def close(self):
-        self.part.close()
-        self.col.close()
-        self.c.close()
-
-
 @pytest.fixture(scope="module")
 def worlds():
     made = {}
@@ -62,44 +43,6 @@ def worlds():
     yield get
     for w in made.values():
         w.close()
-
-
-def recipe(w, sets, metric):
-    """b(t, g) of every query set, f32 [T, n_keys] in ascending key order, from the existing API: one grouped search per token"""
-    nq, T, dim = sets.shape
-    res = w.c.search_grouped(np.ascontiguousarray(sets.reshape(nq * T, dim)), w.nk, 1, metric, w.part)
-    assert (res.indices != PAD).all(), "per_key = 1 and k = n_keys: every key's best row"
-    keys = w.col.gather(res.indices)
-    order = np.argsort(keys, axis=1, kind="stable")
-    assert (np.take_along_axis(keys, order, 1) == w.keys[None, :]).all()
-    return np.take_along_axis(res.scores, order, 1).reshape(nq, T, w.nk)
-
-
-def expected(w, best, metric, k):
-    """the result rows of the query sets from their b(t, g): the f32 sum in token order, (order key, key value), padding"""
-    rows = [MS.rank_keys(b, w.keys, metric, k) for b in best]
-    return G.MaxSimResult(np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows]), np.array([r[2] for r in rows], np.uint32))
-
-
-def same_bytes(got, want, what):
-    assert got.scores.shape == want.scores.shape and got.keys.shape == want.keys.shape, what
-    assert (got.keys == want.keys).all(), f"{what}: keys"
-    assert (got.scores.view(np.uint32) == want.scores.view(np.uint32)).all(), f"{what}: score bits"
-    assert (got.counts == want.counts).all(), f"{what}: counts"
-
-
-def ks_of(w):
-    return (1, 10, w.nk, w.nk + 3)
-
-
-def check_sets(w, sets, metric, what, ks=None):
-    """search_maxsim at every k against the recipe; -> the recipe's b(t, g)"""
-    best = recipe(w, sets, metric)
-    for k in ks or ks_of(w):
-        got = w.c.search_maxsim(sets, k, metric, w.part)
-        same_bytes(got, expected(w, best, metric, k), f"{what}, k {k}")
-        assert (got.counts == min(k, w.nk)).all()
-    return best
 
 
 @pytest.mark.parametrize("case", range(len(SHAPES)), ids=[f"{dt}d{dim}" for dt, dim in SHAPES])
@@ -210,30 +153,11 @@ def test_the_float64_contract_reference_within_the_tolerance_scaled_by_the_token
     w = worlds("f32", 100, "stock", "u32")
     T, nq = 5, 3
     sets = MS.make_sets(nq, T, 100, "f32")
-    x = w.rows[w.live]
-    xn = np.sqrt((x.astype(np.float64) ** 2).sum(1))
-    starts = np.nonzero(np.concatenate([[True], np.diff(np.sort(w.lay["col"][w.live].astype(np.uint64))) != 0]))[0]
-    by_key = np.argsort(w.lay["col"][w.live].astype(np.uint64), kind="stable")
-    sign = 1.0 if metric == L2 else -1.0
+    b, tol = MS.f64_key_bests(w.rows, w.lay, sets.reshape(nq * T, 100), TOL)[metric]
     for k in (1, 10, w.nk):
         got = w.c.search_maxsim(sets, k, metric, w.part)
         for j in range(nq):
-            S, tol = np.zeros(w.nk), np.zeros(w.nk)
-            for t in range(T):
-                s = _f64_row_scores(x, sets[j, t], metric)
-                b = sign * np.minimum.reduceat((sign * s)[by_key], starts)
-                S += b
-                qn = float(np.linalg.norm(sets[j, t].astype(np.float64)))
-                tol += TOL * np.abs(b) if metric == L2 else TOL if metric == COS else TOL * np.maximum.reduceat(xn[by_key], starts) * qn
-            at = np.searchsorted(w.keys, got.keys[j])
-            assert (w.keys[at] == got.keys[j]).all() and np.unique(at).size == k, "k distinct keys of the partition"
-            assert (np.abs(got.scores[j].astype(np.float64) - S[at]) <= tol[at]).all(), f"k {k}, set {j}: a sum outside its tolerance"
-            okey = MS.order_key(got.scores[j], metric).astype(np.int64)
-            assert ((okey[1:] > okey[:-1]) | ((okey[1:] == okey[:-1]) & (got.keys[j][1:] > got.keys[j][:-1]))).all(), "order"
-            key = sign * S
-            kth, band = np.partition(key, k - 1)[k - 1], 2 * tol.max()
-            assert set(np.nonzero(key < kth - band)[0].tolist()) <= set(at.tolist()), "a clear winner is missing"
-            assert set(at.tolist()) <= set(np.nonzero(key <= kth + band)[0].tolist()), "a clear loser was returned"
+            MS.assert_f64_contract(got.scores[j], got.keys[j], w.keys, b[j * T:(j + 1) * T].sum(0), tol[j * T:(j + 1) * T].sum(0), metric, k)
 
 
 def _library_row_scores(w, q, metric):

@@ -351,15 +351,7 @@ def test_the_float64_contract_reference_within_the_tolerance_scaled_by_the_token
         for k in (1, 10, cand.size):
             got = w.c.search_maxsim_candidates(sets[j], lists[j], k, metric, w.part)
             assert got.counts[0] == k
-            at = np.searchsorted(cand, got.keys[0])
-            assert (cand[at] == got.keys[0]).all() and np.unique(at).size == k, "k distinct candidates of the set"
-            assert (np.abs(got.scores[0].astype(np.float64) - S[at]) <= tol[at]).all(), f"k {k}, set {j}: a sum outside its tolerance"
-            okey = MS.order_key(got.scores[0], metric).astype(np.int64)
-            assert ((okey[1:] > okey[:-1]) | ((okey[1:] == okey[:-1]) & (got.keys[0][1:] > got.keys[0][:-1]))).all(), "order"
-            key = sign * S
-            kth, band = np.partition(key, k - 1)[k - 1], 2 * tol.max()
-            assert set(np.nonzero(key < kth - band)[0].tolist()) <= set(at.tolist()), "a clear winner is missing"
-            assert set(at.tolist()) <= set(np.nonzero(key <= kth + band)[0].tolist()), "a clear loser was returned"
+            MS.assert_f64_contract(got.scores[0], got.keys[0], cand, S, tol, metric, k)   # "keys of the partition": the set's candidates
 
 
 def test_device_call_equals_the_host_call_and_the_stage_timer_is_the_device_call(worlds):
