@@ -2258,7 +2258,6 @@ CorpusView corpus_view(const mvfgpu_corpus* c) {
     return v;
 }
 int corpus_row_norms(const mvfgpu_corpus* c, void* stream, const float** xnorm, const float** xx2, const float** xxmax) {
-    std::lock_guard<std::mutex> lk(c->mu);
     const int rc = ensure_norms(c, static_cast<hipStream_t>(stream));
     if (rc != MVF_OK) return rc;
     const float* xn = static_cast<const float*>(c->xnorm.p);

@@ -175,7 +175,8 @@ CorpusView corpus_view(const mvfgpu_corpus* c);
 inline size_t query_row_bytes(const CorpusView& v) { return (size_t)v.dim * (is_int_dtype(v.dtype) ? 1 : 4); }
 std::mutex& corpus_host_mutex(const mvfgpu_corpus* c);  // serialises the host-buffer calls of a handle
 // Float32 / Float16 corpora: the row norms the batched kernels read (built on first use, on `stream`): xnorm[n] = |x|,
-// xx2[n] = sum x^2, xxmax[1] = max of xx2
+// xx2[n] = sum x^2, xxmax[1] = max of xx2.  The caller runs under corpus_device_call(c, stream, ...): the handle's lock is held,
+// and `stream` is ordered behind a build that another stream's call enqueued.
 int corpus_row_norms(const mvfgpu_corpus* c, void* stream, const float** xnorm, const float** xx2, const float** xxmax);
 // K1's lane-group width for rows of V 16-byte vectors and nqv queries per pass (MVF_K1_G forces one: `forced`)
 void k1_group(uint32_t V, int nqv, int forced, int* G, uint32_t* J);

@@ -154,214 +154,219 @@ int mvfgpu_search_radius(const mvfgpu_corpus* c, uint8_t metric, const void* que
 
     {
         std::lock_guard<std::mutex> lk(corpus_host_mutex(c));
-        const CorpusView v = corpus_view(c);  // under the lock: mvfgpu_corpus_reload_tuning changes the tuning under it too
-        qbytes = query_row_bytes(v);
-        std::vector<uint32_t> bound(nq);
-        for (uint32_t q = 0; q < nq; q++) bound[q] = radius_bound_key(v.dtype, metric, radii[q], nullptr);
-        hipStream_t s = static_cast<hipStream_t>(v.stream);
-        // R1's shape for this batch: K1's rule with R1's LDS formula (it keeps no lists in LDS: k and pmax do not matter)
-        const K1Shape sh = k1_pass_shape(v.V, nq, 0, v.k1_g,
-                                         [&](int G, uint32_t J, int nqv, uint32_t) { return radius_scan_lds_bytes(v.dtype, G, J, nqv); });
-        const int nqv = sh.nqv, G = sh.G;
-        const uint32_t J = sh.J;
-        const size_t lds = sh.lds;
-        if (lds > 160 * 1024) return set_fail(MVF_ERR_BUILD, "dimension too large for the radius kernel's LDS query tile");
-        const void* fn = radius_scan_kernel_ptr(v.dtype, metric, G, nqv);
-        if (!fn) return set_fail(MVF_ERR_BUILD, "no radius kernel for this shape");
-        int occ = 1;
-        MVF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, lds));
-        occ = std::max(occ, 1);
-        const uint64_t rows_per_block_step = 16ull * 64u / (uint32_t)G;  // 4 waves x U = 4 groups x 64/G rows
-        const uint32_t nblk = (uint32_t)std::max<uint64_t>(
-            1, std::min<uint64_t>((v.n + rows_per_block_step - 1) / rows_per_block_step, (uint64_t)occ * v.num_cus));
+        const hipStream_t s = static_cast<hipStream_t>(corpus_view(c).stream);
+        // the handle's own stream, with mvfgpu_search_device's discipline: behind the handle's newest work on another stream (a
+        // lazy build enqueued there: the norms below), ev_done recorded on every way out
+        const int rc_call = corpus_device_call(c, s, [&]() -> int {
+            const CorpusView v = corpus_view(c);  // under the lock: mvfgpu_corpus_reload_tuning changes the tuning under it too
+            qbytes = query_row_bytes(v);
+            std::vector<uint32_t> bound(nq);
+            for (uint32_t q = 0; q < nq; q++) bound[q] = radius_bound_key(v.dtype, metric, radii[q], nullptr);
+            // R1's shape for this batch: K1's rule with R1's LDS formula (it keeps no lists in LDS: k and pmax do not matter)
+            const K1Shape sh = k1_pass_shape(v.V, nq, 0, v.k1_g,
+                                             [&](int G, uint32_t J, int nqv, uint32_t) { return radius_scan_lds_bytes(v.dtype, G, J, nqv); });
+            const int nqv = sh.nqv, G = sh.G;
+            const uint32_t J = sh.J;
+            const size_t lds = sh.lds;
+            if (lds > 160 * 1024) return set_fail(MVF_ERR_BUILD, "dimension too large for the radius kernel's LDS query tile");
+            const void* fn = radius_scan_kernel_ptr(v.dtype, metric, G, nqv);
+            if (!fn) return set_fail(MVF_ERR_BUILD, "no radius kernel for this shape");
+            int occ = 1;
+            MVF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, lds));
+            occ = std::max(occ, 1);
+            const uint64_t rows_per_block_step = 16ull * 64u / (uint32_t)G;  // 4 waves x U = 4 groups x 64/G rows
+            const uint32_t nblk = (uint32_t)std::max<uint64_t>(
+                1, std::min<uint64_t>((v.n + rows_per_block_step - 1) / rows_per_block_step, (uint64_t)occ * v.num_cus));
 
-        const uint32_t W = std::min(nq, kWindow);
-        AsyncBuf dq, dbound, dcnt, dlist, dsc, didx, draw;
-        MVF_HIP_TRY(dq.alloc((size_t)W * qbytes, s));
-        MVF_HIP_TRY(dbound.alloc((size_t)W * 4, s));
-        MVF_HIP_TRY(dcnt.alloc((size_t)W * 4, s));
-        if (maxq > 0) {
-            MVF_HIP_TRY(dlist.alloc((size_t)W * cap * 8, s));
-            MVF_HIP_TRY(dsc.alloc((size_t)W * kk * 4, s));
-            MVF_HIP_TRY(didx.alloc((size_t)W * kk * 8, s));
-            MVF_HIP_TRY(draw.alloc((size_t)W * kk * 4, s));
-        }
-        std::vector<uint32_t> hcnt(W), hccnt(W);
-        std::vector<float> hsc(maxq > 0 ? (size_t)W * kk : 0);
-        std::vector<uint64_t> hidx(hsc.size());
-        std::vector<int32_t> hraw(hsc.size());
-        std::vector<unsigned char> hq((size_t)W * qbytes);
-        std::vector<uint32_t> hb(W);
-
-        // a window of the queries `sel[w0 .. w0 + wn)`: queries and bounds to the device, packed contiguously
-        auto upload = [&](const std::vector<uint32_t>& sel, uint32_t w0, uint32_t wn) -> int {
-            for (uint32_t i = 0; i < wn; i++) {
-                std::memcpy(hq.data() + (size_t)i * qbytes, static_cast<const unsigned char*>(queries) + (size_t)sel[w0 + i] * qbytes, qbytes);
-                hb[i] = bound[sel[w0 + i]];
-            }
-            MVF_HIP_TRY(hipMemcpyAsync(dq.p, hq.data(), (size_t)wn * qbytes, hipMemcpyHostToDevice, s));
-            MVF_HIP_TRY(hipMemcpyAsync(dbound.p, hb.data(), (size_t)wn * 4, hipMemcpyHostToDevice, s));
-            MVF_HIP_TRY(hipMemsetAsync(dcnt.p, 0, (size_t)wn * 4, s));
-            return MVF_OK;
-        };
-        // R2 over the window's lists, results back, one wait; `repair` (nullable): the window's candidate counts, a query
-        // with more candidates than its list held is collected in *redo instead
-        auto finish = [&](const std::vector<uint32_t>& sel, uint32_t w0, uint32_t wn, const uint32_t* dccnt,
-                          std::vector<uint32_t>* redo) -> int {
+            const uint32_t W = std::min(nq, kWindow);
+            AsyncBuf dq, dbound, dcnt, dlist, dsc, didx, draw;
+            MVF_HIP_TRY(dq.alloc((size_t)W * qbytes, s));
+            MVF_HIP_TRY(dbound.alloc((size_t)W * 4, s));
+            MVF_HIP_TRY(dcnt.alloc((size_t)W * 4, s));
             if (maxq > 0) {
-                RadiusPackParams pp{};
-                pp.lists = static_cast<const uint64_t*>(dlist.p);
-                pp.counts = static_cast<const uint32_t*>(dcnt.p);
-                pp.cap = cap;
-                pp.kout = kk;
-                pp.metric = metric;
-                pp.dtype = v.dtype;
-                pp.index_base = v.index_base;
-                pp.ids = v.ids;
-                pp.out_scores = static_cast<float*>(dsc.p);
-                pp.out_indices = static_cast<uint64_t*>(didx.p);
-                pp.out_raw = static_cast<int32_t*>(draw.p);
-                MVF_HIP_TRY(radius_pack_launch(pp, wn, s));
-                MVF_HIP_TRY(hipMemcpyAsync(hsc.data(), dsc.p, (size_t)wn * kk * 4, hipMemcpyDeviceToHost, s));
-                MVF_HIP_TRY(hipMemcpyAsync(hidx.data(), didx.p, (size_t)wn * kk * 8, hipMemcpyDeviceToHost, s));
-                MVF_HIP_TRY(hipMemcpyAsync(hraw.data(), draw.p, (size_t)wn * kk * 4, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(dlist.alloc((size_t)W * cap * 8, s));
+                MVF_HIP_TRY(dsc.alloc((size_t)W * kk * 4, s));
+                MVF_HIP_TRY(didx.alloc((size_t)W * kk * 8, s));
+                MVF_HIP_TRY(draw.alloc((size_t)W * kk * 4, s));
             }
-            MVF_HIP_TRY(hipMemcpyAsync(hcnt.data(), dcnt.p, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
-            if (dccnt) MVF_HIP_TRY(hipMemcpyAsync(hccnt.data(), dccnt, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
-            MVF_HIP_TRY(hipStreamSynchronize(s));
-            for (uint32_t i = 0; i < wn; i++) {
-                const uint32_t q = sel[w0 + i];
-                if (dccnt && hccnt[i] > kBatchCap) {
-                    redo->push_back(q);
-                    continue;
-                }
-                out_counts[q] = hcnt[i];
-                if (maxq == 0) continue;
-                if (hcnt[i] > cap) {
-                    over.push_back(q);
-                    continue;
-                }
-                const uint64_t m = std::min<uint64_t>(hcnt[i], maxq);  // <= kk
-                const size_t src = (size_t)i * kk, dst = (size_t)q * maxq;
-                std::copy(hsc.begin() + src, hsc.begin() + src + m, out_scores + dst);
-                std::copy(hidx.begin() + src, hidx.begin() + src + m, out_indices + dst);
-                if (out_raw) std::copy(hraw.begin() + src, hraw.begin() + src + m, out_raw + dst);
-                pad_entries(dst + m, dst + maxq, metric, out_scores, out_indices, out_raw);
-            }
-            return MVF_OK;
-        };
-        // R1 over the rows for the queries `sel`, in windows
-        auto stream = [&](const std::vector<uint32_t>& sel) -> int {
-            for (uint32_t w0 = 0; w0 < (uint32_t)sel.size(); w0 += W) {
-                const uint32_t wn = std::min<uint32_t>(W, (uint32_t)sel.size() - w0);
-                int rc = upload(sel, w0, wn);
-                if (rc != MVF_OK) return rc;
-                if (v.n > 0) {
-                    RadiusParams rp{};
-                    rp.rows = v.rows;
-                    rp.queries = dq.p;
-                    rp.tomb = v.tomb;
-                    rp.bound = static_cast<const uint32_t*>(dbound.p);
-                    rp.counts = static_cast<uint32_t*>(dcnt.p);
-                    rp.lists = maxq > 0 ? static_cast<uint64_t*>(dlist.p) : nullptr;
-                    rp.cap = cap;
-                    rp.n = (uint32_t)v.n;
-                    rp.pitch = v.pitch;
-                    rp.dim = v.dim;
-                    rp.V = v.V;
-                    rp.J = J;
-                    rp.q0 = 0;
-                    rp.nq_total = wn;
-                    MVF_HIP_TRY(radius_scan_launch(v.dtype, metric, G, nqv, rp, dim3(nblk, (wn + nqv - 1) / nqv), lds, s));
-                }
-                rc = finish(sel, w0, wn, nullptr, nullptr);
-                if (rc != MVF_OK) return rc;
-            }
-            return MVF_OK;
-        };
+            std::vector<uint32_t> hcnt(W), hccnt(W);
+            std::vector<float> hsc(maxq > 0 ? (size_t)W * kk : 0);
+            std::vector<uint64_t> hidx(hsc.size());
+            std::vector<int32_t> hraw(hsc.size());
+            std::vector<unsigned char> hq((size_t)W * qbytes);
+            std::vector<uint32_t> hb(W);
 
-        std::vector<uint32_t> all(nq);
-        for (uint32_t q = 0; q < nq; q++) all[q] = q;
-        int rc = MVF_OK;
-        if (radius_route(v.dtype, nq, v.scan_path) == 0 || v.n == 0) {
-            rc = stream(all);
-        } else {
-            // ---- the batched route (Float32 rows): ONE pass of the f32 MFMA selection kernel over all rows with tau[q] = the
-            // radius loosened by the kernel's proven error bound, R3 re-scores the candidates exactly, R2 packs; a query whose
-            // candidates overflowed the kernel's list is redone by R1 (the repair)
-            const float *xnorm = nullptr, *xx2 = nullptr, *xxmax = nullptr;
-            rc = corpus_row_norms(c, s, &xnorm, &xx2, &xxmax);
-            if (rc != MVF_OK) return rc;
-            float hxxmax = 0.0f;
-            MVF_HIP_TRY(hipMemcpyAsync(&hxxmax, xxmax, 4, hipMemcpyDeviceToHost, s));
-            MVF_HIP_TRY(hipStreamSynchronize(s));
-            const uint32_t nq_pad = (W + 127u) & ~127u, KT = (v.dim + 31u) / 32u, KP = KT * 32u;
-            AsyncBuf dqmat, dqn, dtau, dccnt, dcand;
-            MVF_HIP_TRY(dqmat.alloc((size_t)nq_pad * KP * 4, s));
-            MVF_HIP_TRY(dqn.alloc((size_t)nq_pad * 4, s));
-            MVF_HIP_TRY(dtau.alloc((size_t)nq_pad * 4, s));
-            MVF_HIP_TRY(dccnt.alloc((size_t)nq_pad * 4, s));
-            MVF_HIP_TRY(dcand.alloc((size_t)nq_pad * kBatchCap * 8, s));
-            std::vector<uint32_t> htau(nq_pad), redo;
-            const double eps = (double)(std::max<uint32_t>(v.dim, 64) + 16) * 1.1920929e-7;  // the f32 kernel's bound (api.hip)
-            for (uint32_t w0 = 0; w0 < nq && rc == MVF_OK; w0 += W) {
-                const uint32_t wn = std::min(W, nq - w0), wpad = (wn + 127u) & ~127u;
-                rc = upload(all, w0, wn);
-                if (rc != MVF_OK) break;
-                std::fill(htau.begin(), htau.end(), 0u);
+            // a window of the queries `sel[w0 .. w0 + wn)`: queries and bounds to the device, packed contiguously
+            auto upload = [&](const std::vector<uint32_t>& sel, uint32_t w0, uint32_t wn) -> int {
                 for (uint32_t i = 0; i < wn; i++) {
-                    const float* qv = reinterpret_cast<const float*>(hq.data() + (size_t)i * qbytes);
-                    double qq = 0.0;
-                    for (uint32_t e = 0; e < v.dim; e++) qq += (double)qv[e] * qv[e];
-                    htau[i] = batched_tau(metric, radii[w0 + i], qq, hxxmax, eps);
+                    std::memcpy(hq.data() + (size_t)i * qbytes, static_cast<const unsigned char*>(queries) + (size_t)sel[w0 + i] * qbytes, qbytes);
+                    hb[i] = bound[sel[w0 + i]];
                 }
-                MVF_HIP_TRY(hipMemcpyAsync(dtau.p, htau.data(), (size_t)wpad * 4, hipMemcpyHostToDevice, s));
-                MVF_HIP_TRY(hipMemsetAsync(dccnt.p, 0, (size_t)wpad * 4, s));
-                MVF_HIP_TRY(launch_prep_queries(static_cast<const float*>(dq.p), wn, wpad, v.dim, KP, static_cast<float*>(dqmat.p),
-                                            static_cast<float*>(dqn.p), s));
-                BatchParams bp{};
-                bp.qmat = static_cast<const float*>(dqmat.p);
-                bp.qnorm = static_cast<const float*>(dqn.p);
-                bp.rows = v.rows;
-                bp.xnorm = xnorm;
-                bp.xx2 = xx2;
-                bp.xxmax = xxmax;
-                bp.tomb = v.tomb;
-                bp.tau = static_cast<const uint32_t*>(dtau.p);
-                bp.cand = static_cast<uint64_t*>(dcand.p);
-                bp.cnt = static_cast<uint32_t*>(dccnt.p);
-                bp.pitch = v.pitch;
-                bp.V = v.V;
-                bp.KP = KP;
-                bp.KT = KT;
-                bp.nq = wn;
-                bp.row_begin = 0;
-                bp.row_end = (uint32_t)v.n;
-                bp.ntiles = (uint32_t)((v.n + 127u) / 128u);
-                bp.mtiles = wpad / 128u;
-                bp.cap = kBatchCap;
-                bp.direct = 0;  // every candidate passes the threshold test
-                MVF_HIP_TRY(launch_scan_mfma_f32(bp, metric, s));
-                RadiusRescoreParams rr{};
-                rr.cand = static_cast<const uint64_t*>(dcand.p);
-                rr.ccnt = static_cast<const uint32_t*>(dccnt.p);
-                rr.ccap = kBatchCap;
-                rr.rows = v.rows;
-                rr.queries = static_cast<const float*>(dq.p);
-                rr.dim = v.dim;
-                rr.pitch = v.pitch;
-                rr.V = v.V;
-                rr.J = J;
-                rr.bound = static_cast<const uint32_t*>(dbound.p);
-                rr.counts = static_cast<uint32_t*>(dcnt.p);
-                rr.lists = maxq > 0 ? static_cast<uint64_t*>(dlist.p) : nullptr;
-                rr.cap = cap;
-                MVF_HIP_TRY(radius_rescore_launch(metric, G, rr, wn, radius_scan_lds_bytes(MVF_DTYPE_FLOAT32, G, J, 1), s));
-                rc = finish(all, w0, wn, static_cast<const uint32_t*>(dccnt.p), &redo);
+                MVF_HIP_TRY(hipMemcpyAsync(dq.p, hq.data(), (size_t)wn * qbytes, hipMemcpyHostToDevice, s));
+                MVF_HIP_TRY(hipMemcpyAsync(dbound.p, hb.data(), (size_t)wn * 4, hipMemcpyHostToDevice, s));
+                MVF_HIP_TRY(hipMemsetAsync(dcnt.p, 0, (size_t)wn * 4, s));
+                return MVF_OK;
+            };
+            // R2 over the window's lists, results back, one wait; `repair` (nullable): the window's candidate counts, a query
+            // with more candidates than its list held is collected in *redo instead
+            auto finish = [&](const std::vector<uint32_t>& sel, uint32_t w0, uint32_t wn, const uint32_t* dccnt,
+                              std::vector<uint32_t>* redo) -> int {
+                if (maxq > 0) {
+                    RadiusPackParams pp{};
+                    pp.lists = static_cast<const uint64_t*>(dlist.p);
+                    pp.counts = static_cast<const uint32_t*>(dcnt.p);
+                    pp.cap = cap;
+                    pp.kout = kk;
+                    pp.metric = metric;
+                    pp.dtype = v.dtype;
+                    pp.index_base = v.index_base;
+                    pp.ids = v.ids;
+                    pp.out_scores = static_cast<float*>(dsc.p);
+                    pp.out_indices = static_cast<uint64_t*>(didx.p);
+                    pp.out_raw = static_cast<int32_t*>(draw.p);
+                    MVF_HIP_TRY(radius_pack_launch(pp, wn, s));
+                    MVF_HIP_TRY(hipMemcpyAsync(hsc.data(), dsc.p, (size_t)wn * kk * 4, hipMemcpyDeviceToHost, s));
+                    MVF_HIP_TRY(hipMemcpyAsync(hidx.data(), didx.p, (size_t)wn * kk * 8, hipMemcpyDeviceToHost, s));
+                    MVF_HIP_TRY(hipMemcpyAsync(hraw.data(), draw.p, (size_t)wn * kk * 4, hipMemcpyDeviceToHost, s));
+                }
+                MVF_HIP_TRY(hipMemcpyAsync(hcnt.data(), dcnt.p, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
+                if (dccnt) MVF_HIP_TRY(hipMemcpyAsync(hccnt.data(), dccnt, (size_t)wn * 4, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipStreamSynchronize(s));
+                for (uint32_t i = 0; i < wn; i++) {
+                    const uint32_t q = sel[w0 + i];
+                    if (dccnt && hccnt[i] > kBatchCap) {
+                        redo->push_back(q);
+                        continue;
+                    }
+                    out_counts[q] = hcnt[i];
+                    if (maxq == 0) continue;
+                    if (hcnt[i] > cap) {
+                        over.push_back(q);
+                        continue;
+                    }
+                    const uint64_t m = std::min<uint64_t>(hcnt[i], maxq);  // <= kk
+                    const size_t src = (size_t)i * kk, dst = (size_t)q * maxq;
+                    std::copy(hsc.begin() + src, hsc.begin() + src + m, out_scores + dst);
+                    std::copy(hidx.begin() + src, hidx.begin() + src + m, out_indices + dst);
+                    if (out_raw) std::copy(hraw.begin() + src, hraw.begin() + src + m, out_raw + dst);
+                    pad_entries(dst + m, dst + maxq, metric, out_scores, out_indices, out_raw);
+                }
+                return MVF_OK;
+            };
+            // R1 over the rows for the queries `sel`, in windows
+            auto stream = [&](const std::vector<uint32_t>& sel) -> int {
+                for (uint32_t w0 = 0; w0 < (uint32_t)sel.size(); w0 += W) {
+                    const uint32_t wn = std::min<uint32_t>(W, (uint32_t)sel.size() - w0);
+                    int rc = upload(sel, w0, wn);
+                    if (rc != MVF_OK) return rc;
+                    if (v.n > 0) {
+                        RadiusParams rp{};
+                        rp.rows = v.rows;
+                        rp.queries = dq.p;
+                        rp.tomb = v.tomb;
+                        rp.bound = static_cast<const uint32_t*>(dbound.p);
+                        rp.counts = static_cast<uint32_t*>(dcnt.p);
+                        rp.lists = maxq > 0 ? static_cast<uint64_t*>(dlist.p) : nullptr;
+                        rp.cap = cap;
+                        rp.n = (uint32_t)v.n;
+                        rp.pitch = v.pitch;
+                        rp.dim = v.dim;
+                        rp.V = v.V;
+                        rp.J = J;
+                        rp.q0 = 0;
+                        rp.nq_total = wn;
+                        MVF_HIP_TRY(radius_scan_launch(v.dtype, metric, G, nqv, rp, dim3(nblk, (wn + nqv - 1) / nqv), lds, s));
+                    }
+                    rc = finish(sel, w0, wn, nullptr, nullptr);
+                    if (rc != MVF_OK) return rc;
+                }
+                return MVF_OK;
+            };
+
+            std::vector<uint32_t> all(nq);
+            for (uint32_t q = 0; q < nq; q++) all[q] = q;
+            int rc = MVF_OK;
+            if (radius_route(v.dtype, nq, v.scan_path) == 0 || v.n == 0) {
+                rc = stream(all);
+            } else {
+                // ---- the batched route (Float32 rows): ONE pass of the f32 MFMA selection kernel over all rows with tau[q] = the
+                // radius loosened by the kernel's proven error bound, R3 re-scores the candidates exactly, R2 packs; a query whose
+                // candidates overflowed the kernel's list is redone by R1 (the repair)
+                const float *xnorm = nullptr, *xx2 = nullptr, *xxmax = nullptr;
+                rc = corpus_row_norms(c, s, &xnorm, &xx2, &xxmax);
+                if (rc != MVF_OK) return rc;
+                float hxxmax = 0.0f;
+                MVF_HIP_TRY(hipMemcpyAsync(&hxxmax, xxmax, 4, hipMemcpyDeviceToHost, s));
+                MVF_HIP_TRY(hipStreamSynchronize(s));
+                const uint32_t nq_pad = (W + 127u) & ~127u, KT = (v.dim + 31u) / 32u, KP = KT * 32u;
+                AsyncBuf dqmat, dqn, dtau, dccnt, dcand;
+                MVF_HIP_TRY(dqmat.alloc((size_t)nq_pad * KP * 4, s));
+                MVF_HIP_TRY(dqn.alloc((size_t)nq_pad * 4, s));
+                MVF_HIP_TRY(dtau.alloc((size_t)nq_pad * 4, s));
+                MVF_HIP_TRY(dccnt.alloc((size_t)nq_pad * 4, s));
+                MVF_HIP_TRY(dcand.alloc((size_t)nq_pad * kBatchCap * 8, s));
+                std::vector<uint32_t> htau(nq_pad), redo;
+                const double eps = (double)(std::max<uint32_t>(v.dim, 64) + 16) * 1.1920929e-7;  // the f32 kernel's bound (api.hip)
+                for (uint32_t w0 = 0; w0 < nq && rc == MVF_OK; w0 += W) {
+                    const uint32_t wn = std::min(W, nq - w0), wpad = (wn + 127u) & ~127u;
+                    rc = upload(all, w0, wn);
+                    if (rc != MVF_OK) break;
+                    std::fill(htau.begin(), htau.end(), 0u);
+                    for (uint32_t i = 0; i < wn; i++) {
+                        const float* qv = reinterpret_cast<const float*>(hq.data() + (size_t)i * qbytes);
+                        double qq = 0.0;
+                        for (uint32_t e = 0; e < v.dim; e++) qq += (double)qv[e] * qv[e];
+                        htau[i] = batched_tau(metric, radii[w0 + i], qq, hxxmax, eps);
+                    }
+                    MVF_HIP_TRY(hipMemcpyAsync(dtau.p, htau.data(), (size_t)wpad * 4, hipMemcpyHostToDevice, s));
+                    MVF_HIP_TRY(hipMemsetAsync(dccnt.p, 0, (size_t)wpad * 4, s));
+                    MVF_HIP_TRY(launch_prep_queries(static_cast<const float*>(dq.p), wn, wpad, v.dim, KP, static_cast<float*>(dqmat.p),
+                                                static_cast<float*>(dqn.p), s));
+                    BatchParams bp{};
+                    bp.qmat = static_cast<const float*>(dqmat.p);
+                    bp.qnorm = static_cast<const float*>(dqn.p);
+                    bp.rows = v.rows;
+                    bp.xnorm = xnorm;
+                    bp.xx2 = xx2;
+                    bp.xxmax = xxmax;
+                    bp.tomb = v.tomb;
+                    bp.tau = static_cast<const uint32_t*>(dtau.p);
+                    bp.cand = static_cast<uint64_t*>(dcand.p);
+                    bp.cnt = static_cast<uint32_t*>(dccnt.p);
+                    bp.pitch = v.pitch;
+                    bp.V = v.V;
+                    bp.KP = KP;
+                    bp.KT = KT;
+                    bp.nq = wn;
+                    bp.row_begin = 0;
+                    bp.row_end = (uint32_t)v.n;
+                    bp.ntiles = (uint32_t)((v.n + 127u) / 128u);
+                    bp.mtiles = wpad / 128u;
+                    bp.cap = kBatchCap;
+                    bp.direct = 0;  // every candidate passes the threshold test
+                    MVF_HIP_TRY(launch_scan_mfma_f32(bp, metric, s));
+                    RadiusRescoreParams rr{};
+                    rr.cand = static_cast<const uint64_t*>(dcand.p);
+                    rr.ccnt = static_cast<const uint32_t*>(dccnt.p);
+                    rr.ccap = kBatchCap;
+                    rr.rows = v.rows;
+                    rr.queries = static_cast<const float*>(dq.p);
+                    rr.dim = v.dim;
+                    rr.pitch = v.pitch;
+                    rr.V = v.V;
+                    rr.J = J;
+                    rr.bound = static_cast<const uint32_t*>(dbound.p);
+                    rr.counts = static_cast<uint32_t*>(dcnt.p);
+                    rr.lists = maxq > 0 ? static_cast<uint64_t*>(dlist.p) : nullptr;
+                    rr.cap = cap;
+                    MVF_HIP_TRY(radius_rescore_launch(metric, G, rr, wn, radius_scan_lds_bytes(MVF_DTYPE_FLOAT32, G, J, 1), s));
+                    rc = finish(all, w0, wn, static_cast<const uint32_t*>(dccnt.p), &redo);
+                }
+                if (rc == MVF_OK && !redo.empty()) rc = stream(redo);
             }
-            if (rc == MVF_OK && !redo.empty()) rc = stream(redo);
-        }
-        if (rc != MVF_OK) return rc;
+            return rc;
+        });
+        if (rc_call != MVF_OK) return rc_call;
     }
 
     if (!over.empty()) {
