@@ -36,6 +36,7 @@
 
 #include "mvf_file.h"
 #include "mvf_gpu.h"
+#include "mvf_gpu_maxsim_route.h"
 #include "mvf_status.h"
 
 namespace mvf {
@@ -528,6 +529,9 @@ public:
             }
         return out;
     }
+    // The route of find_top_k_documents (mvfgpu_set_maxsim_route): 0 the library's rule, 1 always the one-pass route, 2 the MFMA
+    // selection route where it is eligible (Float32 / Float16 spaces, InnerProduct / Cosine).  The answers are the same bytes.
+    void set_maxsim_route(int route) { detail::check_gpu(mvfgpu_set_maxsim_route(c_, route)); }
     // The k best values of `column` -- documents of a corpus of token or passage vectors -- for ONE query of n_tokens vectors
     // (mvfgpu_search_maxsim; DESIGN.md section 3, "Multi-vector search"): late interaction, a document's score being the sum
     // over the query's vectors, in their order, of that vector's best score among the document's vectors.  query_vectors holds

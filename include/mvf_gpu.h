@@ -713,10 +713,10 @@ int mvfgpu_selftest_grouped_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_p
  * So, byte for byte: with R_t = mvfgpu_search_grouped(per_key = 1, k = n_keys) of token t and the hits' keys from
  * mvfgpu_column_gather, summing R_t's scores per key in f32 in token order and ordering by (order key of the sum, key value)
  * gives this call's score bits, keys and counts.
- * Cost: the held rows leave HBM once per chunk of up to 32 tokens (fewer where the padded tokens exceed 40 KiB of LDS or the
+ * Cost (route 1; include/mvf_gpu_maxsim_route.h): the held rows leave HBM once per chunk of up to 32 tokens (fewer where the padded tokens exceed 40 KiB of LDS or the
  * scratch, chunk x n_keys x 4 + n_keys x 20 bytes per query set, would exceed its budget) and query set.
- * Not built: the arg-best rows per token; ragged token counts; per-token weights; a route over the selection shadows or the
- * batched (MFMA) kernels; shard sets; a filter on top of the partition.
+ * Not built: the arg-best rows per token; ragged token counts; per-token weights; a route over the selection shadows (the
+ * batched MFMA kernels: include/mvf_gpu_maxsim_route.h); shard sets; a filter on top of the partition.
  */
 #define MVFGPU_MAXSIM_MAX_TOKENS 1024u
 int mvfgpu_search_maxsim(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
@@ -754,6 +754,11 @@ int mvfgpu_selftest_maxsim_form(uint8_t data_type, uint32_t dimension, uint32_t 
 int mvfgpu_selftest_maxsim_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
                                     const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens,
                                     uint32_t k, float* d_scores, uint64_t* d_keys, void* hip_stream, float* out_ms);
+
+/*
+ * The MFMA selection route of the multi-vector search -- mvfgpu_set_maxsim_route, MVF_MAXSIM_ROUTE and the route's self-tests -- is
+ * declared in include/mvf_gpu_maxsim_route.h: the same bytes as this call's, from a selection on the matrix unit.
+ */
 
 /*
  * Candidate keys ("Candidate keys"): mvfgpu_search_maxsim restricted, per query set, to a list of keys --
@@ -1004,7 +1009,7 @@ int mvfgpu_set_scan_path(mvfgpu_corpus* corpus, int path);
 
 /*
  * The tuning switches of the environment (MVF_K1_G, MVF_K2_*, MVF_I8_SHADOW, MVF_F16_SHADOW, MVF_QS_REFINE,
- * MVF_STREAM_I8, MVF_STREAM_6B, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_FILTER_ROUTE, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
+ * MVF_STREAM_I8, MVF_STREAM_6B, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_FILTER_ROUTE, MVF_MAXSIM_ROUTE, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
  * handle, when it is created: a search never calls getenv.  An A/B script that changes the environment of a live handle
  * calls this to have it read again.  A development aid: it waits for the handle's host-buffer searches, but
  * mvfgpu_search_device reads the switches unlocked -- do not call it beside device-pointer searches of the same handle.
@@ -1025,7 +1030,8 @@ int mvfgpu_corpus_reload_tuning(mvfgpu_corpus* corpus);
  * mvfgpu_selftest_group_plan and mvfgpu_selftest_grouped_stage_ms, nor did the multi-vector search, which only adds
  * mvfgpu_search_maxsim, mvfgpu_search_maxsim_device, mvfgpu_selftest_maxsim_plan and mvfgpu_selftest_maxsim_stage_ms, nor did
  * its candidate form, which only adds mvfgpu_search_maxsim_candidates, mvfgpu_search_maxsim_candidates_device,
- * mvfgpu_selftest_maxsim_candidates_plan and mvfgpu_selftest_maxsim_candidates_stage_ms, nor did mvfgpu_selftest_maxsim_form).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
+ * mvfgpu_selftest_maxsim_candidates_plan and mvfgpu_selftest_maxsim_candidates_stage_ms, nor did mvfgpu_selftest_maxsim_form, nor did
+ * the multi-vector search's MFMA route, whose functions include/mvf_gpu_maxsim_route.h declares).  A binding compares it with the MVFGPU_ABI_VERSION it was built against
  * at load time.
  */
 #define MVFGPU_ABI_VERSION 3u

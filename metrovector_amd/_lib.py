@@ -241,6 +241,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_maxsim_form.restype = C.c_int
     lib.mvfgpu_selftest_maxsim_stage_ms.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp]
     lib.mvfgpu_selftest_maxsim_stage_ms.restype = C.c_int
+    lib.mvfgpu_set_maxsim_route.argtypes = [vp, i32]
+    lib.mvfgpu_set_maxsim_route.restype = C.c_int
+    lib.mvfgpu_selftest_maxsim_route.argtypes = [u64, u64, u32, u8, u8, u32, u32, u32, i32, vp]
+    lib.mvfgpu_selftest_maxsim_route.restype = C.c_int
+    lib.mvfgpu_selftest_maxsim_margin.argtypes = [u8, u8, u32, vp, u32, C.c_float, vp]
+    lib.mvfgpu_selftest_maxsim_margin.restype = C.c_int
+    lib.mvfgpu_selftest_maxsim_mfma_stage_ms.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_maxsim_mfma_stage_ms.restype = C.c_int
     lib.mvfgpu_search_maxsim_candidates.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, u32, vp, vp, vp]
     lib.mvfgpu_search_maxsim_candidates.restype = C.c_int
     lib.mvfgpu_search_maxsim_candidates_device.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp]

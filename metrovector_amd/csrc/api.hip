@@ -6,6 +6,7 @@
 // here: without a device every compute entry point fails with MVF_ERR_DEVICE.
 
 #include "../../include/mvf_gpu.h"
+#include "../../include/mvf_gpu_maxsim_route.h"
 
 #include "aux_kernels.h"
 #include "internal.h"
@@ -150,6 +151,7 @@ Tuning read_tuning() {
     t.host_flag_wait = flag("MVF_HOST_FLAG_WAIT", true);
     t.filter_route = (int)std::min(2l, std::max(0l, num("MVF_FILTER_ROUTE", 0)));
     t.maxsim_scratch = (size_t)std::max(1l, num("MVF_MAXSIM_SCRATCH_BYTES", 512l << 20));
+    t.maxsim_route = (int)std::min(2l, std::max(0l, num("MVF_MAXSIM_ROUTE", 0)));
     return t;
 }
 }  // namespace mvf
@@ -263,6 +265,7 @@ struct mvfgpu_corpus {
 
     bool profiling = false;
     int scan_path = 0;
+    int maxsim_route = 0;  // mvfgpu_set_maxsim_route; 0: tune.maxsim_route
     mvf::Tuning tune;  // the environment's tuning switches as they were when the handle was created
     struct ProfSlot {
         hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // [0,1] the timed scan launch, [2] end of its select; [3,4] the whole search
@@ -2252,6 +2255,7 @@ CorpusView corpus_view(const mvfgpu_corpus* c) {
     v.tomb_gen = c->tomb_gen;
     v.filter_route = c->tune.filter_route;
     v.maxsim_scratch = c->tune.maxsim_scratch;
+    v.maxsim_route = c->maxsim_route ? c->maxsim_route : c->tune.maxsim_route;
     v.ids = static_cast<const uint64_t*>(c->ids.p);
     v.stream = c->own_stream;
     v.scan_path = c->scan_path;
@@ -3176,6 +3180,14 @@ int mvfgpu_set_scan_path(mvfgpu_corpus* c, int path) {
     if (path < 0 || path > 7) return fail(MVF_ERR_INVALID_ARGUMENT, "path must be 0..7");
     std::lock_guard<std::mutex> lk(c->mu);
     c->scan_path = path;
+    return MVF_OK;
+}
+
+int mvfgpu_set_maxsim_route(mvfgpu_corpus* c, int route) {
+    if (!c) return fail(MVF_ERR_INVALID_ARGUMENT, "corpus is NULL");
+    if (route < 0 || route > 2) return fail(MVF_ERR_INVALID_ARGUMENT, "route must be 0, 1 or 2");
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->maxsim_route = route;
     return MVF_OK;
 }
 

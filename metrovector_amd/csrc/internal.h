@@ -149,6 +149,7 @@ struct Tuning {
     bool host_flag_wait = true; // MVF_HOST_FLAG_WAIT=0: the blocking host call always waits on its stream (not on the flag the final select writes)
     int filter_route = 0;       // MVF_FILTER_ROUTE=1|2: a filtered search always by the mask route (1) / always by the list route (2; the list is then built whatever the count); 0: the rule (filter_route_rule)
     size_t maxsim_scratch = 512ull << 20;  // MVF_MAXSIM_SCRATCH_BYTES: the multi-vector search's scratch per window (tests: several token chunks and windows at a small shape)
+    int maxsim_route = 0;       // MVF_MAXSIM_ROUTE=1|2: a multi-vector search always by the one-pass route (1) / by the MFMA selection route where it is eligible (2); 0: the rule (maxsim_route, scan_maxsim.h)
     int large_k = 0;            // MVF_LARGE_K=1|2: k beyond one pass always by passes (1; k <= 16384) / always by the whole-shard sort (2); 0: the cheaper one
 };
 Tuning read_tuning();
@@ -169,6 +170,7 @@ struct CorpusView {
     uint64_t tomb_gen = 0;           // the generation of `tomb`: every mvfgpu_corpus_set_tombstones starts a new one
     int filter_route = 0;            // Tuning::filter_route
     size_t maxsim_scratch = 0;       // Tuning::maxsim_scratch
+    int maxsim_route = 0;            // mvfgpu_set_maxsim_route, else Tuning::maxsim_route
 };
 CorpusView corpus_view(const mvfgpu_corpus* c);
 // bytes of one query of the handle's space: Float32, or the space's own type for Int8 / UInt8

@@ -14,6 +14,7 @@
 // and M1, the sort and the writer run per set over its candidates: the cost follows the candidates' rows.
 
 #include "../../include/mvf_gpu.h"
+#include "../../include/mvf_gpu_maxsim_route.h"
 
 #include "aux_kernels.h"
 #include "host_staging.h"
@@ -21,6 +22,7 @@
 #include "mvf_common.h"
 #include "scan_gather.h"
 #include "scan_maxsim.h"
+#include "scan_mfma.h"
 
 #include <algorithm>
 #include <cstring>
@@ -58,10 +60,21 @@ struct StageMarks {
     }
 };
 
+// what the stage timer of route 2 asks for beside the marks: per set of the CALL the candidate keys and the blocks re-scored
+struct MfmaStats {
+    uint32_t* d_stats;  // device [2][nq], zero on entry
+    uint32_t nq;
+};
+
 // The device work of both calls: query sets and results in device memory; everything on `s`.  Runs under corpus_device_call.
-// marks (the stage timer only): stage 0 the ordinals, 1 M0, 2 M1, 3 the tail.
-int maxsim_core(const CorpusView& v, const PartitionView& pv, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t n_tokens,
-                uint32_t k, float* d_scores, uint64_t* d_keys, uint32_t* d_counts, hipStream_t s, StageMarks* marks = nullptr) {
+// Route 1 (maxsim_route): M0 over every held row.  Route 2: per window A0's approximate scores go through M1 and the sort to the
+// kth best approximate sum, P0 makes the candidates' block table, and M0's candidate form, M1, the sort and the writer give the
+// answer -- route 1's, byte for byte.
+// marks (the stage timers only): route 1: stage 0 the ordinals, 1 M0, 2 M1, 3 the tail; route 2: 0 the preparation, 1 A0, 2 the
+// approximate sums, their kth best and P0, 3 M0 over the candidates' blocks, 4 M1 and the mask, 5 the tail.
+int maxsim_core(const mvfgpu_corpus* c, const CorpusView& v, const PartitionView& pv, uint8_t metric, const void* d_queries, uint32_t nq,
+                uint32_t n_tokens, uint32_t k, float* d_scores, uint64_t* d_keys, uint32_t* d_counts, hipStream_t s,
+                StageMarks* marks = nullptr, const MfmaStats* stats = nullptr) {
     if (v.n == 0 || pv.live == 0 || pv.n_keys == 0) {
         if (d_counts) MVF_HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)nq * 4, s));
         return fill_padding(metric, nq, k, d_scores, d_keys, nullptr, s);
@@ -69,32 +82,68 @@ int maxsim_core(const CorpusView& v, const PartitionView& pv, uint8_t metric, co
     const OneQueryGroup g1 = one_query_group(v);
     const size_t set_bytes = query_row_bytes(v) * n_tokens;
     const uint32_t live = (uint32_t)pv.live, nk = (uint32_t)pv.n_keys;  // n_keys <= live rows < 2^32
-    const MaxsimPlan pl = maxsim_plan(nk, n_tokens, nq, g1.qbytes, v.maxsim_scratch);
-    const uint32_t W = pl.window;
+    // the timers time one route each: route 1's (marks alone) and route 2's (with stats) whatever the handle would take
+    const int forced = stats ? 2 : marks ? 1 : v.maxsim_route;
+    const bool mfma = maxsim_route(pv.live, pv.n_keys, v.dim, v.dtype, metric, nq, n_tokens, k, forced) == 2;
+    const bool f16 = v.dtype == MVF_DTYPE_FLOAT16;
+    const uint32_t kp_bytes = (v.V + 1u) / 2u * 32u;  // a prepared token of route 2: whole 32-byte steps of A0
+    MaxsimPlan pl = maxsim_plan(nk, n_tokens, nq, g1.qbytes, v.maxsim_scratch);
+    uint32_t achunk = 0;  // route 2: A0's own tokens per chunk
+    if (mfma) {
+        const MaxsimMfmaPlan mp = maxsim_mfma_plan(nk, live, n_tokens, nq, g1.qbytes, kp_bytes, v.maxsim_scratch);
+        pl.chunk = mp.chunk, pl.window = mp.window, achunk = mp.achunk;
+    }
+    const uint32_t W = pl.window, n_blocks = (live + kMaxsimRows - 1) / kMaxsimRows;
     const size_t kk = std::min<size_t>(k, nk);
     size_t tmp_bytes = 0;
     MVF_HIP_TRY(sort_composites(nullptr, &tmp_bytes, nullptr, nullptr, nk, kk, nullptr, s, W, nk));
 
     AsyncBuf dord, dbest, dsum, da, db, dtmp;
     MVF_HIP_TRY(dord.alloc((size_t)live * 4, s));
-    MVF_HIP_TRY(dbest.alloc((size_t)W * pl.chunk * nk * 4, s));
+    MVF_HIP_TRY(dbest.alloc((size_t)W * std::max(pl.chunk, achunk) * nk * 4, s));
     MVF_HIP_TRY(dsum.alloc((size_t)W * nk * 4, s));
     MVF_HIP_TRY(da.alloc((size_t)W * nk * 8, s));
     MVF_HIP_TRY(db.alloc((size_t)W * nk * 8, s));
     MVF_HIP_TRY(dtmp.alloc(tmp_bytes, s));
+    AsyncBuf dprep, daux, dflag, dblocks, ddelta;  // route 2
+    const float *xnorm = nullptr, *xx2 = nullptr, *xxmax = nullptr;
+    if (mfma) {
+        MVF_HIP_TRY(dprep.alloc((size_t)W * n_tokens * kp_bytes, s));
+        MVF_HIP_TRY(daux.alloc((size_t)W * n_tokens * 8, s));  // the undo scales [W * n_tokens], then |q|
+        MVF_HIP_TRY(dflag.alloc((size_t)W * nk, s));
+        MVF_HIP_TRY(dblocks.alloc((size_t)W * n_blocks * sizeof(MaxsimCandBlock), s));
+        MVF_HIP_TRY(ddelta.alloc((size_t)W * 8, s));
+    }
     if (marks) MVF_HIP_TRY(marks->mark(-1, s));
+    if (mfma)
+        if (const int rc = corpus_row_norms(c, s, &xnorm, &xx2, &xxmax)) return rc;
     MVF_HIP_TRY(maxsim_ordinals_launch(pv.table + pv.n_keys, pv.n_keys, live, static_cast<uint32_t*>(dord.p), s));
     if (marks) MVF_HIP_TRY(marks->mark(0, s));
 
     for (uint32_t w0 = 0; w0 < nq; w0 += W) {
         const uint32_t wn = std::min(W, nq - w0);
-        for (uint32_t t0 = 0; t0 < n_tokens; t0 += pl.chunk) {
-            const uint32_t tc = std::min(pl.chunk, n_tokens - t0);
-            // M0: the smallest order key of every (token of the chunk, key) to best[set][t][key], dead on entry
-            MVF_HIP_TRY(hipMemsetAsync(dbest.p, 0xFF, (size_t)wn * tc * nk * 4, s));
+        const unsigned char* w_queries = static_cast<const unsigned char*>(d_queries) + (size_t)w0 * set_bytes;
+        // M1: S[set][key] advances by the chunk's scores in token order; behind the last chunk the rank entries
+        auto sums = [&](uint32_t t0, uint32_t tc) -> int {
+            MaxsimSumParams mp{};
+            mp.best = static_cast<const uint32_t*>(dbest.p);
+            mp.sum = static_cast<float*>(dsum.p);
+            mp.rank = static_cast<uint64_t*>(da.p);
+            mp.n_keys = nk;
+            mp.sets = wn;
+            mp.tc = tc;
+            mp.metric = metric;
+            mp.dtype = v.dtype;
+            mp.first = t0 == 0;
+            mp.last = t0 + tc == n_tokens;
+            MVF_HIP_TRY(maxsim_sum_launch(mp, s));
+            return MVF_OK;
+        };
+        // M0's parameters of a chunk: the smallest order key of every (token of the chunk, key) to best[set][t][key], dead on entry
+        auto score_params = [&](uint32_t t0, uint32_t tc) {
             MaxsimScoreParams sp{};
             sp.rows = v.rows;
-            sp.queries = static_cast<const unsigned char*>(d_queries) + (size_t)w0 * set_bytes;
+            sp.queries = w_queries;
             sp.list = pv.rows_by_key;
             sp.ord = static_cast<const uint32_t*>(dord.p);
             sp.best = static_cast<uint32_t*>(dbest.p);
@@ -108,22 +157,115 @@ int maxsim_core(const CorpusView& v, const PartitionView& pv, uint8_t metric, co
             sp.pitch = v.pitch;
             sp.V = v.V;
             sp.J = g1.J;
-            MVF_HIP_TRY(maxsim_score_launch(v.dtype, metric, g1.G, sp, s));
-            if (marks) MVF_HIP_TRY(marks->mark(1, s));
-            // M1: S[set][key] advances by the chunk's scores in token order; behind the last chunk the rank entries
-            MaxsimSumParams mp{};
-            mp.best = sp.best;
-            mp.sum = static_cast<float*>(dsum.p);
-            mp.rank = static_cast<uint64_t*>(da.p);
-            mp.n_keys = nk;
-            mp.sets = wn;
-            mp.tc = tc;
-            mp.metric = metric;
-            mp.dtype = v.dtype;
-            mp.first = t0 == 0;
-            mp.last = t0 + tc == n_tokens;
-            MVF_HIP_TRY(maxsim_sum_launch(mp, s));
+            return sp;
+        };
+        if (mfma) {
+            // the window's tokens as (set, token) query rows; no key is forced yet
+            const uint32_t qrows = wn * n_tokens;
+            float *undo = static_cast<float*>(daux.p), *qnorm = undo + (size_t)W * n_tokens;
+            if (f16)
+                MVF_HIP_TRY(launch_prep_queries16(w_queries, MVF_DTYPE_FLOAT16, qrows, qrows, v.dim, kp_bytes, static_cast<unsigned char*>(dprep.p), undo, qnorm, s));
+            else
+                MVF_HIP_TRY(launch_prep_queries(reinterpret_cast<const float*>(w_queries), qrows, qrows, v.dim, kp_bytes / 4, static_cast<float*>(dprep.p), qnorm, s));
+            MVF_HIP_TRY(hipMemsetAsync(dflag.p, 0, (size_t)wn * nk, s));
+            if (marks) MVF_HIP_TRY(marks->mark(0, s));
+            for (uint32_t t0 = 0; t0 < n_tokens; t0 += achunk) {
+                const uint32_t tc = std::min(achunk, n_tokens - t0);
+                MVF_HIP_TRY(hipMemsetAsync(dbest.p, 0xFF, (size_t)wn * tc * nk * 4, s));
+                MaxsimMfmaParams ap{};
+                ap.rows = v.rows;
+                ap.qprep = static_cast<const unsigned char*>(dprep.p);
+                ap.undo = f16 ? undo : nullptr;
+                ap.qnorm = qnorm;
+                ap.xnorm = xnorm;
+                ap.list = pv.rows_by_key;
+                ap.ord = static_cast<const uint32_t*>(dord.p);
+                ap.best = static_cast<uint32_t*>(dbest.p);
+                ap.force = static_cast<unsigned char*>(dflag.p);
+                ap.m = live;
+                ap.n_keys = nk;
+                ap.sets = wn;
+                ap.n_tokens = n_tokens;
+                ap.t0 = t0;
+                ap.tc = tc;
+                ap.pitch = v.pitch;
+                ap.V = v.V;
+                ap.kp_bytes = kp_bytes;
+                MVF_HIP_TRY(maxsim_mfma_score_launch(v.dtype, metric, ap, s));
+                if (marks) MVF_HIP_TRY(marks->mark(1, s));
+                if (const int rc = sums(t0, tc)) return rc;
+                if (marks) MVF_HIP_TRY(marks->mark(2, s));
+            }
+            // theta: the kth best approximate sum among the keys whose sum the bound covers; the others rank behind them
+            MaxsimMaskParams kp{};
+            kp.rank = static_cast<uint64_t*>(da.p);
+            kp.sum = static_cast<const float*>(dsum.p);
+            kp.flag = static_cast<const unsigned char*>(dflag.p);
+            kp.n_keys = nk;
+            kp.sets = wn;
+            kp.dead = false;
+            MVF_HIP_TRY(maxsim_mask_launch(kp, s));
+            size_t tb = tmp_bytes;
+            uint64_t* approx = nullptr;
+            MVF_HIP_TRY(sort_composites(dtmp.p, &tb, static_cast<uint64_t*>(da.p), static_cast<uint64_t*>(db.p), nk, kk, &approx, s, wn, nk));
+            MaxsimPickParams pp{};
+            pp.sorted = approx;
+            pp.sum = static_cast<const float*>(dsum.p);
+            pp.qnorm = qnorm;
+            pp.xxmax = xxmax;
+            pp.ord = static_cast<const uint32_t*>(dord.p);
+            pp.flag = static_cast<unsigned char*>(dflag.p);
+            pp.blocks = static_cast<MaxsimCandBlock*>(dblocks.p);
+            pp.stats = nullptr;
+            pp.delta = static_cast<double*>(ddelta.p);
+            pp.m = live;
+            pp.n_keys = nk;
+            pp.sets = wn;
+            pp.n_tokens = n_tokens;
+            pp.kth = (uint32_t)kk - 1u;
+            pp.dim = v.dim;
+            pp.metric = metric;
+            pp.dtype = v.dtype;
+            AsyncBuf dwstats;  // the window's counts [2][wn], filed under the call's sets behind P0
+            if (stats) {
+                MVF_HIP_TRY(dwstats.alloc((size_t)wn * 8, s));
+                MVF_HIP_TRY(hipMemsetAsync(dwstats.p, 0, (size_t)wn * 8, s));
+                pp.stats = static_cast<uint32_t*>(dwstats.p);
+            }
+            MVF_HIP_TRY(maxsim_pick_launch(pp, s));
+            if (stats) {
+                MVF_HIP_TRY(hipMemcpyAsync(stats->d_stats + w0, pp.stats, (size_t)wn * 4, hipMemcpyDeviceToDevice, s));
+                MVF_HIP_TRY(hipMemcpyAsync(stats->d_stats + stats->nq + w0, pp.stats + wn, (size_t)wn * 4, hipMemcpyDeviceToDevice, s));
+            }
             if (marks) MVF_HIP_TRY(marks->mark(2, s));
+        }
+        for (uint32_t t0 = 0; t0 < n_tokens; t0 += pl.chunk) {
+            const uint32_t tc = std::min(pl.chunk, n_tokens - t0);
+            MVF_HIP_TRY(hipMemsetAsync(dbest.p, 0xFF, (size_t)wn * tc * nk * 4, s));
+            MaxsimScoreParams sp = score_params(t0, tc);
+            if (mfma) {  // M0's candidate form over the full list, set after set with the set's slice of P0's table
+                sp.m = n_blocks * kMaxsimRows;
+                for (uint32_t q = 0; q < wn; q++) {
+                    sp.blocks = static_cast<const MaxsimCandBlock*>(dblocks.p) + (size_t)q * n_blocks;
+                    MVF_HIP_TRY(maxsim_score_candidates_launch(v.dtype, metric, g1.G, sp, s));
+                }
+            } else {
+                MVF_HIP_TRY(maxsim_score_launch(v.dtype, metric, g1.G, sp, s));
+            }
+            if (marks) MVF_HIP_TRY(marks->mark(mfma ? 3 : 1, s));
+            if (const int rc = sums(t0, tc)) return rc;
+            if (marks && !mfma) MVF_HIP_TRY(marks->mark(2, s));
+        }
+        if (mfma) {  // a key that is no candidate may be scored in part: behind every candidate
+            MaxsimMaskParams kp{};
+            kp.rank = static_cast<uint64_t*>(da.p);
+            kp.sum = static_cast<const float*>(dsum.p);
+            kp.flag = static_cast<const unsigned char*>(dflag.p);
+            kp.n_keys = nk;
+            kp.sets = wn;
+            kp.dead = true;
+            MVF_HIP_TRY(maxsim_mask_launch(kp, s));
+            if (marks) MVF_HIP_TRY(marks->mark(4, s));
         }
         // the tail: entries in ascending ordinal -- ascending key value --, as the sort takes them
         size_t tb = tmp_bytes;
@@ -141,7 +283,7 @@ int maxsim_core(const CorpusView& v, const PartitionView& pv, uint8_t metric, co
         wp.k = k;
         wp.metric = metric;
         MVF_HIP_TRY(maxsim_write_launch(wp, s));
-        if (marks) MVF_HIP_TRY(marks->mark(3, s));
+        if (marks) MVF_HIP_TRY(marks->mark(mfma ? 5 : 3, s));
     }
     return MVF_OK;
 }
@@ -370,12 +512,12 @@ int maxsim_candidates_core(const CorpusView& v, const mvfgpu_partition* part, ui
 }
 
 // the stage timer's sums: every stage's time from the event in front of it
-int stage_sums(const StageMarks& marks, float* out_ms) {
-    for (int i = 0; i < 4; i++) out_ms[i] = 0.0f;
+int stage_sums(const StageMarks& marks, float* out_ms, int stages = 4) {
+    for (int i = 0; i < stages; i++) out_ms[i] = 0.0f;
     for (size_t i = 1; i < marks.ev.size(); i++) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, marks.ev[i - 1].second, marks.ev[i].second) != hipSuccess) return set_fail(MVF_ERR_DEVICE, "hipEventElapsedTime failed");
-        if (marks.ev[i].first >= 0) out_ms[marks.ev[i].first] += ms;
+        if (marks.ev[i].first >= 0 && marks.ev[i].first < stages) out_ms[marks.ev[i].first] += ms;
     }
     return MVF_OK;
 }
@@ -393,7 +535,7 @@ int mvfgpu_search_maxsim_device(const mvfgpu_corpus* c, const mvfgpu_partition* 
     if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     return corpus_device_call(c, s, [&]() {
-        return maxsim_core(corpus_view(c), partition_view(part), metric, d_queries, nq, n_tokens, k, d_scores, d_keys, d_counts, s);
+        return maxsim_core(c, corpus_view(c), partition_view(part), metric, d_queries, nq, n_tokens, k, d_scores, d_keys, d_counts, s);
     });
 }
 
@@ -411,7 +553,7 @@ int mvfgpu_search_maxsim(const mvfgpu_corpus* c, const mvfgpu_partition* part, u
     const HostIn in[] = {{queries, query_row_bytes(v) * n_tokens}};
     const HostOut out[] = {{out_keys, (size_t)k * 8}, {out_scores, (size_t)k * 4}, {out_counts, 4}};
     return stage_host_windows(c, s, nq, in, out, stage_as_given, [&](uint32_t, uint32_t wn, void* const* d_in, void* const* d_out) {
-        return maxsim_core(v, pv, metric, d_in[0], wn, n_tokens, k, static_cast<float*>(d_out[1]), static_cast<uint64_t*>(d_out[0]),
+        return maxsim_core(c, v, pv, metric, d_in[0], wn, n_tokens, k, static_cast<float*>(d_out[1]), static_cast<uint64_t*>(d_out[0]),
                            static_cast<uint32_t*>(d_out[2]), s);
     });
 }
@@ -428,10 +570,74 @@ int mvfgpu_selftest_maxsim_stage_ms(const mvfgpu_corpus* c, const mvfgpu_partiti
     if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     StageMarks marks;
-    int rc = corpus_device_call(c, s, [&]() { return maxsim_core(corpus_view(c), pv, metric, d_queries, nq, n_tokens, k, d_scores, d_keys, nullptr, s, &marks); });
+    int rc = corpus_device_call(c, s, [&]() { return maxsim_core(c, corpus_view(c), pv, metric, d_queries, nq, n_tokens, k, d_scores, d_keys, nullptr, s, &marks); });
     if (rc == MVF_OK && hipStreamSynchronize(s) != hipSuccess) rc = set_fail(MVF_ERR_DEVICE, "hipStreamSynchronize failed");
     for (int i = 0; i < 4; i++) out_ms[i] = 0.0f;
     return rc == MVF_OK ? stage_sums(marks, out_ms) : rc;
+}
+
+int mvfgpu_selftest_maxsim_mfma_stage_ms(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,
+                                         uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens, uint32_t k,
+                                         float* d_scores, uint64_t* d_keys, void* hip_stream, float* out_ms, uint32_t* out_candidates,
+                                         uint32_t* out_blocks) {
+    if (!out_ms || !out_candidates || !out_blocks) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    const int rc0 = check_maxsim_args(c, part, metric, d_queries, query_dtype, query_dim, nq, n_tokens, k, d_scores, d_keys);
+    if (rc0 != MVF_OK) return rc0;
+    const PartitionView pv = partition_view(part);
+    if (corpus_view(c).n == 0 || pv.live == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "the stage timer needs held rows");
+    if (!maxsim_mfma_eligible(corpus_view(c).dtype, metric))
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "the MFMA route takes Float32 / Float16 rows under InnerProduct / Cosine");
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    StageMarks marks;
+    std::vector<uint32_t> host((size_t)nq * 2, 0u);
+    int rc;
+    {
+        AsyncBuf dstats;
+        rc = corpus_device_call(c, s, [&]() -> int {
+            MVF_HIP_TRY(dstats.alloc((size_t)nq * 8, s));
+            MVF_HIP_TRY(hipMemsetAsync(dstats.p, 0, (size_t)nq * 8, s));
+            const MfmaStats st{static_cast<uint32_t*>(dstats.p), nq};
+            const int rc1 = maxsim_core(c, corpus_view(c), pv, metric, d_queries, nq, n_tokens, k, d_scores, d_keys, nullptr, s, &marks, &st);
+            if (rc1 != MVF_OK) return rc1;
+            MVF_HIP_TRY(hipMemcpyAsync(host.data(), dstats.p, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
+            return MVF_OK;
+        });
+        if (hipStreamSynchronize(s) != hipSuccess && rc == MVF_OK) rc = set_fail(MVF_ERR_DEVICE, "hipStreamSynchronize failed");
+    }
+    for (int i = 0; i < 6; i++) out_ms[i] = 0.0f;
+    if (rc != MVF_OK) return rc;
+    std::memcpy(out_candidates, host.data(), (size_t)nq * 4);
+    std::memcpy(out_blocks, host.data() + nq, (size_t)nq * 4);
+    return stage_sums(marks, out_ms, 6);
+}
+
+int mvfgpu_selftest_maxsim_route(uint64_t held_rows, uint64_t n_keys, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq,
+                                 uint32_t n_tokens, uint32_t k, int forced, uint32_t* out_route) {
+    if (!out_route) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (elem_size(data_type) == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported vector data type code " + std::to_string(data_type));
+    if (const int rc = check_metric(metric)) return rc;
+    if (dimension == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "dimension must be > 0");
+    if (n_tokens == 0 || n_tokens > MVFGPU_MAXSIM_MAX_TOKENS)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT,
+                        "n_tokens must be in 1.." + std::to_string(MVFGPU_MAXSIM_MAX_TOKENS) + ", got " + std::to_string(n_tokens));
+    if (forced < 0 || forced > 2) return set_fail(MVF_ERR_INVALID_ARGUMENT, "route must be 0, 1 or 2, got " + std::to_string(forced));
+    *out_route = maxsim_route(held_rows, n_keys, dimension, data_type, metric, nq, n_tokens, k, forced);
+    return MVF_OK;
+}
+
+int mvfgpu_selftest_maxsim_margin(uint8_t data_type, uint8_t metric, uint32_t dimension, const float* token_norms, uint32_t n_tokens,
+                                  float xxmax, double* out_delta) {
+    if (!token_norms || !out_delta) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!maxsim_mfma_eligible(data_type, metric))
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "the MFMA route takes Float32 / Float16 rows under InnerProduct / Cosine");
+    if (dimension == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "dimension must be > 0");
+    if (n_tokens == 0 || n_tokens > MVFGPU_MAXSIM_MAX_TOKENS)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT,
+                        "n_tokens must be in 1.." + std::to_string(MVFGPU_MAXSIM_MAX_TOKENS) + ", got " + std::to_string(n_tokens));
+    *out_delta = maxsim_margin(data_type, metric, dimension, token_norms, n_tokens, xxmax);
+    return MVF_OK;
 }
 
 int mvfgpu_search_maxsim_candidates_device(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,

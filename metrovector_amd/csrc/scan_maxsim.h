@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -138,5 +139,116 @@ struct MaxsimWriteParams {
     const MaxsimCandSet* cand;  // nullable
 };
 hipError_t maxsim_write_launch(const MaxsimWriteParams& p, hipStream_t s);
+
+// ---- the MFMA selection route (scan_maxsim_mfma.hip; DESIGN.md §3 "Multi-vector search: the MFMA route", §5 "A0 / P0")
+// The route of a full multi-vector search, a pure function (mvfgpu_selftest_maxsim_route; the launch calls it): 1 = the one-pass
+// route (M0 over every row), 2 = select on MFMA scores inside a proven bound, then M0 over the candidates' blocks.  forced:
+// mvfgpu_set_maxsim_route / MVF_MAXSIM_ROUTE (0 = automatic).  Eligible: Float32 / Float16 rows under InnerProduct / Cosine;
+// everything else takes route 1 whatever is forced.  Automatic takes route 2 where it is eligible, k <= n_keys / 2 (beyond that
+// most keys are candidates), the call fills a tile of A0 (nq x n_tokens >= 32 query rows: A0 costs whole tiles) and held rows x
+// n_tokens reaches the crossover of profiles/r18_maxsim_mfma.txt: 2M rows x 32 tokens is the smallest measured shape where
+// route 2 wins on both README shapes with one query set (0.52 and 0.63 of route 1; at 500k x 32 the Float16 shape still loses).
+constexpr uint64_t kMaxsimMfmaCrossover = 64000000ull;  // held rows x n_tokens
+constexpr uint32_t kMaxsimMfmaTile = 32;                // query rows of an accumulator of A0
+inline bool maxsim_mfma_eligible(uint8_t dtype, uint8_t metric) {
+    return (dtype == MVF_DTYPE_FLOAT32 || dtype == MVF_DTYPE_FLOAT16) && (metric == MVF_METRIC_INNER_PRODUCT || metric == MVF_METRIC_COSINE);
+}
+inline uint32_t maxsim_route(uint64_t held_rows, uint64_t n_keys, uint32_t dim, uint8_t dtype, uint8_t metric, uint32_t nq,
+                             uint32_t n_tokens, uint32_t k, int forced) {
+    (void)dim;
+    if (forced == 1 || !maxsim_mfma_eligible(dtype, metric)) return 1u;
+    if (forced == 2) return 2u;
+    const bool pays = (uint64_t)k <= n_keys / 2 && (uint64_t)nq * n_tokens >= kMaxsimMfmaTile &&
+                      held_rows >= (kMaxsimMfmaCrossover + n_tokens - 1) / (n_tokens ? n_tokens : 1);  // no overflow
+    return pays ? 2u : 1u;
+}
+
+// The bound of |S~ - S| of a query set, S~ the sum of the per-token bests of A0's scores, S the exact route's: as the device
+// computes it (P0) and as mvfgpu_selftest_maxsim_margin states it.  eps is the batched search's own: (max(dim, 64) + 16) 2^-23 for
+// the f32 accumulation and the norms, plus 2^-11 1.001 on Float16 rows for the query's rounding to f16; in units u_t = 1 (Cosine)
+// or |q_t| sqrt(xxmax) (InnerProduct).  Delta = 1.001 (eps + (T - 1) 2^-23) sum u_t: the second term is the two f32 sums' own
+// rounding, |b| <= u_t.  A unit that is NaN, or neither 0 nor in [1e-24, 1e37), leaves the premises (partial sums that overflow
+// in one order and not in another; products the matrix unit may flush): Delta is +inf and every key a candidate.
+MVF_HD double maxsim_margin(uint8_t dtype, uint8_t metric, uint32_t dim, const float* token_norms, uint32_t n_tokens, float xxmax) {
+    double eps = (double)((dim > 64u ? dim : 64u) + 16u) * 1.1920928955078125e-7;
+    if (dtype == MVF_DTYPE_FLOAT16) eps += 4.8828125e-4 * 1.001;
+    const double xm = sqrt((double)xxmax), inf = (double)bits_f32(0x7F800000u);
+    double sum = 0.0;
+    for (uint32_t t = 0; t < n_tokens; t++) {
+        const double u = metric == MVF_METRIC_COSINE ? 1.0 : (double)token_norms[t] * xm;
+        if (!(u == 0.0 || (u >= 1e-24 && u < 1e37))) return inf;
+        sum += u;
+    }
+    if (!(sum < 1e37)) return inf;
+    return 1.001 * (eps + (double)(n_tokens - 1u) * 1.1920928955078125e-7) * sum;
+}
+
+// The plan of route 2: maxsim_plan's chunk for M0 over the candidates, a chunk of its own for A0 -- A0 keeps no tokens in LDS,
+// so only kMaxsimChunkMax and the budget bound it: whole tiles of 32 query rows and fewer passes over the rows where M0's
+// tokens are large --, and a window that also holds what the route adds per query set inside the budget: the prepared tokens
+// (n_tokens rows of kp_bytes, two floats each), one flag byte per key and one MaxsimCandBlock per block of the list.  One set
+// whatever the budget.
+struct MaxsimMfmaPlan {
+    uint32_t chunk, achunk, window;
+};
+inline MaxsimMfmaPlan maxsim_mfma_plan(uint64_t n_keys, uint64_t held_rows, uint32_t n_tokens, uint32_t nq, uint64_t token_bytes,
+                                       uint64_t kp_bytes, uint64_t budget_bytes) {
+    const MaxsimPlan m0 = maxsim_plan(n_keys, n_tokens, nq, token_bytes, budget_bytes), a0 = maxsim_plan(n_keys, n_tokens, nq, 0, budget_bytes);
+    const uint64_t nk = n_keys ? n_keys : 1, blocks = (held_rows + kMaxsimRows - 1) / kMaxsimRows;
+    const uint64_t per_set = nk * ((uint64_t)std::max(m0.chunk, a0.chunk) * 4 + kMaxsimKeyBytes + 1) + (uint64_t)n_tokens * (kp_bytes + 8) + blocks * 8;
+    MaxsimMfmaPlan pl;
+    pl.chunk = m0.chunk, pl.achunk = a0.chunk;
+    pl.window = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min(m0.window, a0.window), budget_bytes / per_set));
+    return pl;
+}
+
+// A0.  Grid (blocks of kMaxsimRows list positions), block 256: wave w scores positions 32 w .. 32 w + 31 of its block against
+// the window's (set, token of the chunk) query rows, 32 per accumulator, and ends as M0 does: best[set][t][n_keys] receives the
+// smallest order key of the APPROXIMATE score; force[set][n_keys] (bytes, zero on entry) is raised for a key where the bound's
+// premises fail.
+struct MaxsimMfmaParams {
+    const unsigned char* rows;
+    const unsigned char* qprep;  // [sets * n_tokens][kp_bytes]: f32 rows: the zero-padded f32 tokens; f16 rows: the plane f16(q 2^e)
+    const float* undo;           // [sets * n_tokens] f16 rows: 2^-e; NULL on f32 rows
+    const float* qnorm;          // [sets * n_tokens] |q|
+    const float* xnorm;          // [n] |x| per local row
+    const uint32_t* list;        // the key-ordered list [m]
+    const uint32_t* ord;         // [m] key ordinals
+    uint32_t* best;
+    unsigned char* force;
+    uint32_t m, n_keys, sets, n_tokens, t0, tc, pitch, V, kp_bytes;
+};
+hipError_t maxsim_mfma_score_launch(uint8_t dtype, int metric, const MaxsimMfmaParams& p, hipStream_t s);
+
+// rank[set][g] = the live NaN entry where flag[set][g] != 0 or (also_nonfinite and sum[set][g] is not finite) -- behind every
+// finite sum, in front of the dead entries --; dead: the dead entry where flag[set][g] == 0 instead (the keys that are no
+// candidates of the set).
+struct MaxsimMaskParams {
+    uint64_t* rank;
+    const float* sum;
+    const unsigned char* flag;
+    uint32_t n_keys, sets;
+    bool dead;
+};
+hipError_t maxsim_mask_launch(const MaxsimMaskParams& p, hipStream_t s);
+
+// P0.  flag[set][g] (A0's force on entry) becomes "g is a candidate of the set": forced, or S~(g), theta or Delta not finite, or
+// S~(g) >= theta - 2 Delta (in double, rounded down), theta the score of the kth entry of sorted[set][n_keys] (kth < n_keys)
+// and Delta = maxsim_margin of the set's token norms.  Then blocks[set][n_blocks] = {set, the block's positions where it holds a
+// row of a candidate, else 0}.  stats (nullable): [2][sets] candidates and flagged blocks per set, zero on entry.
+struct MaxsimPickParams {
+    const uint64_t* sorted;
+    const float* sum;
+    const float* qnorm;   // [sets * n_tokens]
+    const float* xxmax;   // [1]
+    const uint32_t* ord;  // [m]
+    unsigned char* flag;
+    MaxsimCandBlock* blocks;
+    uint32_t* stats;
+    double* delta;        // [sets] scratch: the sets' bounds
+    uint32_t m, n_keys, sets, n_tokens, kth, dim;
+    uint8_t metric, dtype;
+};
+hipError_t maxsim_pick_launch(const MaxsimPickParams& p, hipStream_t s);
 
 }  // namespace mvf

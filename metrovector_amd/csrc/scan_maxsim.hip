@@ -100,7 +100,8 @@ __global__ void __launch_bounds__(256) maxsim_score_kernel(MaxsimScoreParams p) 
     if constexpr (CAND) {
         const MaxsimCandBlock b = p.blocks[blockIdx.x];  // the same for every lane: kept in scalar registers
         set = __builtin_amdgcn_readfirstlane(b.set);
-        nr = __builtin_amdgcn_readfirstlane(min(max(b.nr, 1u), kMaxsimRows));  // the plan's: 1 .. kMaxsimRows
+        nr = __builtin_amdgcn_readfirstlane(min(b.nr, kMaxsimRows));  // a host plan's: 1 .. kMaxsimRows
+        if (nr == 0) return;  // P0's table (scan_maxsim_mfma.hip): the block holds no row of a candidate of its set
     } else {
         set = blockIdx.y, nr = min(kMaxsimRows, p.m - c0);  // >= 1: the grid covers m
     }

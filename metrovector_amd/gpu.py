@@ -345,6 +345,24 @@ def maxsim_form(dtype: int, dim: int, forced_g: int = 0) -> MaxSimForm:
     return MaxSimForm(*[o.value for o in out])
 
 
+def maxsim_route(held_rows: int, n_keys: int, dim: int, dtype: int, metric: int, nq: int, n_tokens: int, k: int, forced: int = 0) -> int:
+    """The route of a full multi-vector search -- 1: the one-pass route, 2: the MFMA selection route -- for `forced` = 0 (automatic),
+    1 or 2 (`GpuCorpus.set_maxsim_route`, `MVF_MAXSIM_ROUTE`): `mvfgpu_selftest_maxsim_route`; no GPU needed."""
+    out = C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_route(held_rows, n_keys, dim, dtype, metric, nq, n_tokens, k, forced, C.byref(out)))
+    return out.value
+
+
+def maxsim_margin(dtype: int, metric: int, dim: int, token_norms, xxmax: float) -> float:
+    """The bound of |approximate sum - exact sum| the MFMA selection route holds for one query set whose tokens have the f32
+    norms `token_norms`, over rows whose largest sum of squares is `xxmax`: `mvfgpu_selftest_maxsim_margin`; no GPU needed."""
+    tn = np.ascontiguousarray(np.asarray(token_norms).reshape(-1), dtype=np.float32)
+    out = C.c_double(0.0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_margin(dtype, metric, dim, tn.ctypes.data_as(C.c_void_p) if tn.size else None, tn.size,
+                                                            float(np.float32(xxmax)), C.byref(out)))
+    return out.value
+
+
 def maxsim_candidates_plan(candidate_keys, held_counts) -> tuple[np.ndarray, int, int]:
     """(slot ordinals [m], distinct held candidates, the rows they hold) of ONE query set's candidate list, given every entry's
     held row count (`GpuPartition.lookup`'s): `mvfgpu_selftest_maxsim_candidates_plan`; no GPU needed.  A slot of UINT32_MAX
@@ -836,6 +854,23 @@ class GpuCorpus:
                                                                   nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
                                                                   _opt(stream), out))
         return tuple(float(x) for x in out)
+
+    def set_maxsim_route(self, route: int) -> None:
+        """0: the library's rule, 1: multi-vector searches always by the one-pass route, 2: by the MFMA selection route where it
+        is eligible (Float32 / Float16 rows, InnerProduct / Cosine); the answers are the same bytes (`mvfgpu_set_maxsim_route`)."""
+        _lib.gpu_check(_lib.gpu().mvfgpu_set_maxsim_route(self._h, route))
+
+    def maxsim_mfma_stage_ms(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int, k: int,
+                             metric: int, d_scores: int, d_keys: int, stream: int = 0) -> tuple[tuple[float, ...], np.ndarray, np.ndarray]:
+        """((preparation, A0, approximate sums + kth best + P0, M0 over the candidates' blocks, M1 + mask, tail) in ms, candidate
+        keys per set, blocks scored again per set) of one multi-vector search by the MFMA selection route
+        (`mvfgpu_selftest_maxsim_mfma_stage_ms`); waits for the stream."""
+        out = (C.c_float * 6)()
+        cand, blocks = np.zeros(max(nq, 1), np.uint32), np.zeros(max(nq, 1), np.uint32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_mfma_stage_ms(
+            self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+            _opt(stream), out, cand.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p)))
+        return tuple(float(x) for x in out), cand[:nq], blocks[:nq]
 
     def search_maxsim_candidates(self, query_sets: np.ndarray, candidate_keys, k: int, metric: int, part: GpuPartition) -> MaxSimResult:
         """`search_maxsim` among every set's own candidate keys (`mvfgpu_search_maxsim_candidates`; re-ranking): `candidate_keys`
