@@ -61,6 +61,26 @@ int mvfgpu_selftest_maxsim_mfma_stage_ms(const mvfgpu_corpus* corpus, const mvfg
                                          const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
                                          uint32_t n_tokens, uint32_t k, float* d_scores, uint64_t* d_keys, void* hip_stream,
                                          float* out_ms, uint32_t* out_candidates, uint32_t* out_blocks);
+/*
+ * Read-out of route 2's selection (tests/test_gpu_maxsim_mfma_bound.py): mvfgpu_search_maxsim_device without d_counts by route 2
+ * whatever the handle's route, as the stage timer runs it; waits for the stream.  Beside the search's result it fills caller-owned
+ * HOST arrays with what the selection held on the device, per query set of the call and per key in ascending key value (the order
+ * of mvfgpu_partition_keys):
+ *   out_sums[nq][n_keys]        the approximate sums as P0 read them;
+ *   out_forced[nq][n_keys]      bytes: A0's forced keys, before P0;
+ *   out_candidates[nq][n_keys]  bytes: the candidates, behind P0;
+ *   out_delta[nq]               the bound Delta the device computed;
+ *   out_theta[nq], out_theta_nan[nq] (bytes)  the min(k, n_keys)-th best approximate sum P0 compared with, and whether that entry
+ *                               was the live NaN entry (fewer keys than that with a sum the bound covers; out_theta is NaN then);
+ *   out_xxmax[1]                the largest sum of squares of a stored row, as P0 read it.
+ * The production path enqueues nothing for it.  Refused with MVF_ERR_INVALID_ARGUMENT: what the stage timer refuses, and every
+ * NULL output.
+ */
+int mvfgpu_selftest_maxsim_mfma_selection(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
+                                          const void* d_queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
+                                          uint32_t n_tokens, uint32_t k, float* d_scores, uint64_t* d_keys, void* hip_stream,
+                                          float* out_sums, uint8_t* out_forced, uint8_t* out_candidates, double* out_delta,
+                                          float* out_theta, uint8_t* out_theta_nan, float* out_xxmax);
 
 #ifdef __cplusplus
 }

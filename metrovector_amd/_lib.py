@@ -249,6 +249,8 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_maxsim_margin.restype = C.c_int
     lib.mvfgpu_selftest_maxsim_mfma_stage_ms.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_maxsim_mfma_stage_ms.restype = C.c_int
+    lib.mvfgpu_selftest_maxsim_mfma_selection.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_maxsim_mfma_selection.restype = C.c_int
     lib.mvfgpu_search_maxsim_candidates.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, u32, vp, vp, vp]
     lib.mvfgpu_search_maxsim_candidates.restype = C.c_int
     lib.mvfgpu_search_maxsim_candidates_device.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp]

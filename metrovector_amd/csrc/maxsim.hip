@@ -64,6 +64,15 @@ struct StageMarks {
 struct MfmaStats {
     uint32_t* d_stats;  // device [2][nq], zero on entry
     uint32_t nq;
+    // the selection's read-out (mvfgpu_selftest_maxsim_mfma_selection), all device memory; d_sums is the switch: where it is set
+    // the other five are set too.  What the selection holds around P0, filed under the call's sets while it is valid -- M0 / M1
+    // reuse the sums behind P0
+    float* d_sums = nullptr;            // [nq][n_keys] the approximate sums P0 reads
+    unsigned char* d_forced = nullptr;  // [nq][n_keys] A0's force, in front of P0
+    unsigned char* d_cands = nullptr;   // [nq][n_keys] the candidates, behind P0
+    double* d_delta = nullptr;          // [nq]
+    uint64_t* d_kth = nullptr;          // [nq] the sorted entry P0 takes theta from
+    float* d_xxmax = nullptr;           // [1]
 };
 
 // The device work of both calls: query sets and results in device memory; everything on `s`.  Runs under corpus_device_call.
@@ -232,7 +241,17 @@ int maxsim_core(const mvfgpu_corpus* c, const CorpusView& v, const PartitionView
                 MVF_HIP_TRY(hipMemsetAsync(dwstats.p, 0, (size_t)wn * 8, s));
                 pp.stats = static_cast<uint32_t*>(dwstats.p);
             }
+            const bool readout = stats && stats->d_sums;
+            if (readout) MVF_HIP_TRY(hipMemcpyAsync(stats->d_forced + (size_t)w0 * nk, dflag.p, (size_t)wn * nk, hipMemcpyDeviceToDevice, s));
             MVF_HIP_TRY(maxsim_pick_launch(pp, s));
+            if (readout) {
+                MVF_HIP_TRY(hipMemcpyAsync(stats->d_sums + (size_t)w0 * nk, dsum.p, (size_t)wn * nk * 4, hipMemcpyDeviceToDevice, s));
+                MVF_HIP_TRY(hipMemcpyAsync(stats->d_cands + (size_t)w0 * nk, dflag.p, (size_t)wn * nk, hipMemcpyDeviceToDevice, s));
+                MVF_HIP_TRY(hipMemcpyAsync(stats->d_delta + w0, ddelta.p, (size_t)wn * 8, hipMemcpyDeviceToDevice, s));
+                for (uint32_t q = 0; q < wn; q++)
+                    MVF_HIP_TRY(hipMemcpyAsync(stats->d_kth + w0 + q, approx + (size_t)q * nk + pp.kth, 8, hipMemcpyDeviceToDevice, s));
+                MVF_HIP_TRY(hipMemcpyAsync(stats->d_xxmax, xxmax, 4, hipMemcpyDeviceToDevice, s));
+            }
             if (stats) {
                 MVF_HIP_TRY(hipMemcpyAsync(stats->d_stats + w0, pp.stats, (size_t)wn * 4, hipMemcpyDeviceToDevice, s));
                 MVF_HIP_TRY(hipMemcpyAsync(stats->d_stats + stats->nq + w0, pp.stats + wn, (size_t)wn * 4, hipMemcpyDeviceToDevice, s));
@@ -611,6 +630,73 @@ int mvfgpu_selftest_maxsim_mfma_stage_ms(const mvfgpu_corpus* c, const mvfgpu_pa
     std::memcpy(out_candidates, host.data(), (size_t)nq * 4);
     std::memcpy(out_blocks, host.data() + nq, (size_t)nq * 4);
     return stage_sums(marks, out_ms, 6);
+}
+
+int mvfgpu_selftest_maxsim_mfma_selection(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,
+                                          uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens, uint32_t k,
+                                          float* d_scores, uint64_t* d_keys, void* hip_stream, float* out_sums, uint8_t* out_forced,
+                                          uint8_t* out_candidates, double* out_delta, float* out_theta, uint8_t* out_theta_nan,
+                                          float* out_xxmax) {
+    if (!out_sums || !out_forced || !out_candidates || !out_delta || !out_theta || !out_theta_nan || !out_xxmax)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    const int rc0 = check_maxsim_args(c, part, metric, d_queries, query_dtype, query_dim, nq, n_tokens, k, d_scores, d_keys);
+    if (rc0 != MVF_OK) return rc0;
+    const PartitionView pv = partition_view(part);
+    if (corpus_view(c).n == 0 || pv.live == 0 || pv.n_keys == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "the read-out needs held rows");
+    if (!maxsim_mfma_eligible(corpus_view(c).dtype, metric))
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "the MFMA route takes Float32 / Float16 rows under InnerProduct / Cosine");
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const size_t cells = (size_t)nq * pv.n_keys;
+    std::vector<float> sums(cells);
+    std::vector<unsigned char> forced(cells), cands(cells);
+    std::vector<double> delta(nq);
+    std::vector<uint64_t> kth(nq);
+    float xxmax = 0.0f;
+    int rc;
+    {
+        AsyncBuf dstats, dsums, dforced, dcands, ddelta, dkth, dxxmax;
+        rc = corpus_device_call(c, s, [&]() -> int {
+            MVF_HIP_TRY(dstats.alloc((size_t)nq * 8, s));
+            MVF_HIP_TRY(hipMemsetAsync(dstats.p, 0, (size_t)nq * 8, s));
+            MVF_HIP_TRY(dsums.alloc(cells * 4, s));
+            MVF_HIP_TRY(dforced.alloc(cells, s));
+            MVF_HIP_TRY(dcands.alloc(cells, s));
+            MVF_HIP_TRY(ddelta.alloc((size_t)nq * 8, s));
+            MVF_HIP_TRY(dkth.alloc((size_t)nq * 8, s));
+            MVF_HIP_TRY(dxxmax.alloc(4, s));
+            MfmaStats st{static_cast<uint32_t*>(dstats.p), nq};
+            st.d_sums = static_cast<float*>(dsums.p);
+            st.d_forced = static_cast<unsigned char*>(dforced.p);
+            st.d_cands = static_cast<unsigned char*>(dcands.p);
+            st.d_delta = static_cast<double*>(ddelta.p);
+            st.d_kth = static_cast<uint64_t*>(dkth.p);
+            st.d_xxmax = static_cast<float*>(dxxmax.p);
+            const int rc1 = maxsim_core(c, corpus_view(c), pv, metric, d_queries, nq, n_tokens, k, d_scores, d_keys, nullptr, s, nullptr, &st);
+            if (rc1 != MVF_OK) return rc1;
+            MVF_HIP_TRY(hipMemcpyAsync(sums.data(), dsums.p, cells * 4, hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipMemcpyAsync(forced.data(), dforced.p, cells, hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipMemcpyAsync(cands.data(), dcands.p, cells, hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipMemcpyAsync(delta.data(), ddelta.p, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipMemcpyAsync(kth.data(), dkth.p, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
+            MVF_HIP_TRY(hipMemcpyAsync(&xxmax, dxxmax.p, 4, hipMemcpyDeviceToHost, s));
+            return MVF_OK;
+        });
+        if (hipStreamSynchronize(s) != hipSuccess && rc == MVF_OK) rc = set_fail(MVF_ERR_DEVICE, "hipStreamSynchronize failed");
+    }
+    if (rc != MVF_OK) return rc;
+    std::memcpy(out_sums, sums.data(), cells * 4);
+    std::memcpy(out_forced, forced.data(), cells);
+    std::memcpy(out_candidates, cands.data(), cells);
+    std::memcpy(out_delta, delta.data(), (size_t)nq * 8);
+    for (uint32_t q = 0; q < nq; q++) {  // as P0 reads the entry: the key half, 0xFFFFFFFE a live NaN entry
+        const uint32_t te = (uint32_t)kth[q];
+        out_theta[q] = score_from_key(te, metric);
+        out_theta_nan[q] = te >= 0xFFFFFFFEu ? 1 : 0;
+    }
+    *out_xxmax = xxmax;
+    return MVF_OK;
 }
 
 int mvfgpu_selftest_maxsim_route(uint64_t held_rows, uint64_t n_keys, uint32_t dimension, uint8_t data_type, uint8_t metric, uint32_t nq,

@@ -52,6 +52,18 @@ class MaxSimResult:
 
 
 @dataclass
+class MaxSimSelection:
+    """What the MFMA selection route held on the device for one call (`GpuCorpus.maxsim_mfma_selection`); keys in ascending value."""
+    sums: np.ndarray        # f32 [nq, n_keys]: the approximate sums as the candidate rule read them
+    forced: np.ndarray      # bool [nq, n_keys]: keys the scoring kernel forced, before the rule
+    candidates: np.ndarray  # bool [nq, n_keys]: the candidates, behind the rule
+    delta: np.ndarray       # f64 [nq]: the bound the device computed
+    theta: np.ndarray       # f32 [nq]: the min(k, n_keys)-th best approximate sum the rule compared with
+    theta_nan: np.ndarray   # bool [nq]: that entry was the live NaN entry
+    xxmax: float            # the largest sum of squares of a stored row, as the rule read it
+
+
+@dataclass
 class RadiusResult:
     counts: np.ndarray   # u64 [nq]: exact number of matches per query (also beyond max_per_query)
     scores: np.ndarray   # f32 [nq, max_per_query]: the best min(count, max_per_query) matches, best first, then padding
@@ -871,6 +883,22 @@ class GpuCorpus:
             self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
             _opt(stream), out, cand.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p)))
         return tuple(float(x) for x in out), cand[:nq], blocks[:nq]
+
+    def maxsim_mfma_selection(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int, k: int,
+                              metric: int, d_scores: int, d_keys: int, stream: int = 0) -> MaxSimSelection:
+        """The selection of one multi-vector search by the MFMA selection route, read out of the device: approximate sums, forced
+        keys, candidates, the bound, the kth best approximate sum (`mvfgpu_selftest_maxsim_mfma_selection`); waits for the stream."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        nk = int(part.info().n_keys)
+        shape = (max(nq, 1), max(nk, 1))  # never an empty buffer: the library refuses nq 0 and a partition without keys itself
+        sums, forced, cands = np.zeros(shape, np.float32), np.zeros(shape, np.uint8), np.zeros(shape, np.uint8)
+        delta, theta, tnan = np.zeros(shape[0], np.float64), np.zeros(shape[0], np.float32), np.zeros(shape[0], np.uint8)
+        xxmax = C.c_float(0.0)
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_mfma_selection(
+            self._h, hpart, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+            _opt(stream), *(a.ctypes.data_as(C.c_void_p) for a in (sums, forced, cands, delta, theta, tnan)), C.byref(xxmax)))
+        return MaxSimSelection(sums[:nq], forced[:nq].astype(bool), cands[:nq].astype(bool), delta[:nq], theta[:nq], tnan[:nq].astype(bool),
+                               float(xxmax.value))
 
     def search_maxsim_candidates(self, query_sets: np.ndarray, candidate_keys, k: int, metric: int, part: GpuPartition) -> MaxSimResult:
         """`search_maxsim` among every set's own candidate keys (`mvfgpu_search_maxsim_candidates`; re-ranking): `candidate_keys`

@@ -1,8 +1,10 @@
 """No-GPU tests of the multi-vector search's MFMA selection route (DESIGN.md §3 "Multi-vector search: the MFMA route", §5
 "A0 / P0"): the route rule, the bound Delta against a restatement of its formula, the formula against the arithmetic by
 emulation -- the selection's scores as a sequential f32 chain (the tokens rounded to f16 on Float16 rows) against a blocked f32
-product and float64 --, adversarial rows and tokens, and the refusals of the new entry points.
-Run time: 15 s together on one core; the slowest case (768 dimensions) takes 4 s."""
+product and float64 --, adversarial rows and tokens, the yardsticks tests/test_gpu_maxsim_mfma_bound.py holds the selection's
+read-out to (P0's rule restated, the float64 sums; the distance of its finite worlds from the bound's premises), and the
+refusals of the new entry points.
+Run time: 16 s together on one core, of which the yardsticks' tests take 1 s; the slowest case (768 dimensions) takes 4 s."""
 import ctypes as C
 
 import numpy as np
@@ -233,6 +235,76 @@ def test_the_reference_alone_selects_on_the_gpu_tests_world(dt, dim):
             assert values.size >= 1000 and 10 <= n <= values.size // 4, f"{dt}, metric {metric}: {n} candidates of {values.size} keys"
 
 
+# ---- the yardsticks of tests/test_gpu_maxsim_mfma_bound.py, themselves tested
+@pytest.mark.parametrize("dtype", [F32, F16], ids=["f32", "f16"])
+def test_the_restated_rule_is_the_emulations_on_the_emulations_worlds(dtype):
+    """tests/_maxsim_mfma.py p0_rule / theta_of -- what the GPU tests recompute P0 with -- against candidates() on the worlds of
+    test_the_formula_holds_the_arithmetic and the one-signed world, then the clauses the emulation's worlds never reach"""
+    import _maxsim_mfma as MM
+    dim = 128
+    rng = np.random.default_rng(P._seed("mfma rule", dtype))
+    rt = np.float16 if dtype == F16 else np.float32
+    q = rng.standard_normal((33, dim)).astype(np.float32)
+    worlds = [(q, rng.standard_normal((16000, dim)).astype(rt)), (np.abs(q), np.abs(rng.standard_normal((1600, dim))).astype(rt))]
+    for qs, x in worlds:
+        for T in (5, 33):
+            for metric in (IP, COS):
+                approx, exact, s64, delta = emulate(qs[:T], x, dtype, metric, 8)
+                for k in (1, 10, approx.size):
+                    theta, nan = MM.theta_of(approx[None], np.zeros((1, approx.size), bool), k)
+                    assert not nan[0] and theta[0] == np.sort(approx)[::-1][k - 1]
+                    got = MM.p0_rule(approx[None], np.zeros((1, approx.size), bool), np.array([delta]), theta, nan)[0]
+                    want = candidates(approx, delta, k)
+                    assert (got == want).all() and want.sum() >= k, (T, metric, k)
+    # the other clauses: a forced key and a sum that is not finite are candidates and do not count towards theta; theta the NaN
+    # entry, theta or Delta not finite: every key; a sum exactly on the threshold is inside (the threshold rounds downwards)
+    S = np.array([[5.0, 4.0, np.nan, 3.0, np.inf, 1.0]], np.float32)
+    forced = np.array([[True, False, False, False, False, False]])
+    theta, nan = MM.theta_of(S, forced, 2)
+    assert theta[0] == 3.0 and not nan[0]
+    assert MM.p0_rule(S, forced, np.array([0.25]), theta, nan)[0].tolist() == [True, True, True, True, True, False]
+    assert MM.p0_rule(S, forced, np.array([1.0]), theta, nan)[0].tolist() == [True, True, True, True, True, True], "1.0 >= 3 - 2 x 1"
+    theta, nan = MM.theta_of(S, forced, 4)
+    assert nan[0] and np.isnan(theta[0]) and MM.p0_rule(S, forced, np.array([0.25]), theta, nan).all()
+    for delta, th in ((np.inf, 3.0), (np.nan, 3.0), (0.25, np.inf), (0.25, -np.inf)):
+        assert MM.p0_rule(S, forced, np.array([delta]), np.array([th], np.float32), np.array([False])).all(), (delta, th)
+    edge = np.array([[1.0, np.float32(1.0) - np.float32(2.0 ** -10), 0.5]], np.float32)
+    got = MM.p0_rule(edge, np.zeros((1, 3), bool), np.array([2.0 ** -11]), np.array([1.0], np.float32), np.array([False]))
+    assert got[0].tolist() == [True, True, False]
+
+
+def test_the_float64_yardstick_and_the_finite_worlds_distance_from_the_premises():
+    """tests/_maxsim_mfma.py f64_sums on a world small enough to state by hand, and the condition under which
+    tests/test_gpu_maxsim_mfma_bound.py asserts that NO key is forced: on its finite worlds (World A's rows at every shape with
+    the token pool, their absolute values at 768 dimensions) every dot product stays below 1e30 and every Cosine denominator
+    inside (1e-20, 1e30) -- seven decades and more from the premises' edges 1e37 and 1e-30, from the float64 reference alone"""
+    import _maxsim as MS
+    import _maxsim_mfma as MM
+    x = np.array([[1, 0], [0, 2], [3, 4], [0, 0], [np.nan, 1]], np.float32)
+    starts = np.array([0, 2, 3, 4])
+    sets = np.array([[[1, 1], [1, -1]], [[0, 0], [2, 0]]], np.float32)
+    S, fails = MM.key_sums(MM.f64_sums(x, starts, sets, IP), 2, 2)
+    assert S[:, :3].tolist() == [[2 + 1, 7 - 1, 0], [0 + 2, 0 + 6, 0]] and np.isnan(S[:, 3]).all()
+    assert fails.tolist() == [[False, False, False, True]] * 2
+    S, fails = MM.key_sums(MM.f64_sums(x, starts, sets, COS), 2, 2)
+    r = np.sqrt(0.5)
+    assert S[0, :3] == pytest.approx([r + r, 7 / 5 * r - 1 / 5 * r, 0]) and S[1, :3] == pytest.approx([1.0, 0.6, 0.0])
+    assert fails.tolist() == [[False, False, False, True]] * 2, "a zero row and a zero token score 0: no premise fails"
+    tiny = MM.f64_sums(x[:3], starts[:2], np.full((1, 1, 2), 1e-30, np.float32), COS)
+    assert (tiny["best"] == 0).all() and not tiny["bad"].any(), "a token whose f32 sum of squares is 0 has norm 0: K1's rule"
+    huge = MM.f64_sums(x[:3], starts[:2], np.full((1, 1, 2), 1e30, np.float32), COS)
+    assert huge["bad"].all(), "a token whose f32 sum of squares is not finite: the denominator leaves the premises"
+    lay = MS.form_layout(2048)
+    live, _, starts, _ = MS.key_order(lay)
+    for dt, dim in [("f32", 3), ("f32", 100), ("f32", 129), ("f32", 768), ("f16", 8), ("f16", 20), ("f16", 200), ("f16", 768)]:
+        rows, pool = P.make_rows(2048, dim, dt), MS.token_pool(dt, dim, 3, 70)
+        worlds = [(rows, pool)] + ([(np.abs(rows), np.abs(MS.make_sets(3, 33, dim, dt)))] if dim == 768 else [])
+        for r, sets in worlds:
+            ref = MM.f64_sums(r[live], starts, sets, COS)
+            assert ref["dot_max"] < 1e30 and 1e-20 < ref["den_min"] and ref["den_max"] < 1e30 and not ref["bad"].any(), (dt, dim)
+            assert not MM.f64_sums(r[live], starts, sets, IP)["bad"].any()
+
+
 # ---- the route's header
 def test_the_routes_header_is_classed_exported_and_plain_c(tmp_path):
     """include/mvf_gpu_maxsim_route.h: every function it declares has a stream class in tests/_maxsim_mfma.py in the words of
@@ -250,7 +322,7 @@ def test_the_routes_header_is_classed_exported_and_plain_c(tmp_path):
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"^\s*#[^\n]*", " ", text, flags=re.M)
     fns = set(re.findall(r"\b(mvfgpu_\w+)\s*\(", text))
-    assert fns == set(MM.ENTRY_CLASS) and len(fns) == 4
+    assert fns == set(MM.ENTRY_CLASS) and len(fns) == 5
     assert set(MM.ENTRY_CLASS.values()) <= {S.NO_HANDLE, S.NO_DEVICE_WORK, S.DEVICE_CALL}
     assert not fns & set(S.ENTRY_CLASS), "declared once"
     for aid, form in MM.TIMED_FORM_OF.items():
@@ -292,6 +364,13 @@ def test_refusals_of_the_new_entry_points():
                 lambda: lib.mvfgpu_selftest_maxsim_mfma_stage_ms(None, None, IP, None, 0, 8, 1, 4, 1, None, None, None, None, None, None)):
         assert bad() == E.InvalidArgument.status
     assert out.value == 7 and d.value == 7.0, "a refused call writes nothing"
+    # the selection's read-out: NULL outputs, each alone and all together, and -- every output given -- the search's own refusal of
+    # a NULL handle (an ineligible type or metric needs a handle: tests/test_gpu_maxsim_mfma_bound.py)
+    bufs = [np.full(4, 7, t) for t in (np.float32, np.uint8, np.uint8, np.float64, np.float32, np.uint8, np.float32)]
+    given = [b.ctypes.data_as(C.c_void_p) for b in bufs]
+    for outs in [[None] * 7, given] + [[None if i == j else g for i, g in enumerate(given)] for j in range(7)]:
+        assert lib.mvfgpu_selftest_maxsim_mfma_selection(None, None, IP, None, 0, 8, 1, 4, 1, None, None, None, *outs) == E.InvalidArgument.status
+    assert all((b == 7).all() for b in bufs), "a refused call writes nothing"
     with pytest.raises(E.InvalidArgument, match="route must be 0, 1 or 2, got 3"):
         G.maxsim_route(10, 2, 8, F32, IP, 1, 4, 1, 3)
     with pytest.raises(E.InvalidArgument, match="Float32 / Float16 rows under InnerProduct / Cosine"):
