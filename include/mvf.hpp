@@ -37,6 +37,7 @@
 #include "mvf_file.h"
 #include "mvf_gpu.h"
 #include "mvf_gpu_maxsim_route.h"
+#include "mvf_gpu_mmr.h"
 #include "mvf_status.h"
 
 namespace mvf {
@@ -388,6 +389,32 @@ public:
         std::vector<ScoredVector> out;
         for (size_t i = 0; i < k && i < count; i++) out.push_back({idx[i], scores[i], {}});
         return out;
+    }
+    // Diversified re-ranking by maximal marginal relevance (mvfgpu_search_mmr, mvf_gpu_mmr.h): of the rows
+    // `candidates` names (as rerank_top_k takes them, at most MVFGPU_MMR_MAX_CANDIDATES) k that are relevant and not near-copies
+    // of each other, in pick order; lambda in [0, 1] -- 1 ranks by relevance alone.  Each hit's score is the query's score of
+    // the row, as rerank_top_k reports it.
+    std::vector<ScoredVector> diversify_top_k(const std::vector<float>& query, const std::vector<uint64_t>& candidates, size_t k,
+                                              float lambda = 0.5f) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "diversify_top_k takes f32 queries: Float32 / Float16 spaces");
+        if (k == 0) return {};
+        uint64_t count = 0;
+        std::vector<float> scores(k);
+        std::vector<uint64_t> idx(k);
+        detail::check_gpu(mvfgpu_search_mmr(c_, (uint8_t)metric_, query.data(), MVF_DTYPE_FLOAT32, (uint32_t)query.size(), 1,
+                                            candidates.empty() ? nullptr : candidates.data(), (uint32_t)candidates.size(), (uint32_t)k,
+                                            lambda, scores.data(), idx.data(), nullptr, nullptr, &count));
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < k && i < count; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
+    // The usual one-call form: find_top_k_similar with fetch_k (at most MVFGPU_MMR_MAX_CANDIDATES), then diversify_top_k over
+    // the rows it found.
+    std::vector<ScoredVector> find_top_k_diverse(const std::vector<float>& query, size_t k, size_t fetch_k, float lambda = 0.5f) const {
+        std::vector<uint64_t> candidates;
+        for (const auto& h : find_top_k_similar(query, fetch_k, false)) candidates.push_back(h.index);
+        return diversify_top_k(query, candidates, k, lambda);
     }
     // find_top_k_similar among the rows a predicate admits (mvfgpu_search_filtered; DESIGN.md section 3, "Filtered search"):
     // bit r of allow_bits (byte r >> 3, bit r & 7; at least one bit per row) admits row r.  Deleted rows are never returned;

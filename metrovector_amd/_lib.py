@@ -173,6 +173,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_search_candidates.restype = C.c_int
     lib.mvfgpu_search_candidates_device.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp]
     lib.mvfgpu_search_candidates_device.restype = C.c_int
+    lib.mvfgpu_search_mmr.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp]
+    lib.mvfgpu_search_mmr.restype = C.c_int
+    lib.mvfgpu_search_mmr_device.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_search_mmr_device.restype = C.c_int
+    lib.mvfgpu_selftest_mmr_walk.argtypes = [vp, vp, u32, u8, C.c_float, u32, vp, vp]
+    lib.mvfgpu_selftest_mmr_walk.restype = C.c_int
+    lib.mvfgpu_selftest_mmr_stage_ms.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_mmr_stage_ms.restype = C.c_int
     lib.mvfgpu_knn_join.argtypes = [vp, vp, u8, u64, u64, u32, u32, vp, vp, vp]
     lib.mvfgpu_knn_join.restype = C.c_int
     lib.mvfgpu_knn_join_device.argtypes = [vp, vp, u8, u64, u64, u32, u32, vp, vp, vp, vp]

@@ -87,6 +87,37 @@ class CandidateResult(SearchResult):
     counts: np.ndarray   # u64 [nq]: distinct live in-shard candidates per query; the first min(count, k) entries are real
 
 
+MMR_MAX_CANDIDATES = 1024  # include/mvf_gpu_mmr.h MVFGPU_MMR_MAX_CANDIDATES
+
+
+@dataclass
+class MmrResult(CandidateResult):
+    objective: np.ndarray  # f32 [nq, k]: lambda * rel of pick 0, the objective of the later picks, the padding score behind them
+
+
+def mmr_walk(rel_scores, sim_scores, metric: int, lambda_mult: float, k: int) -> tuple[np.ndarray, np.ndarray, int]:
+    """The greedy walk of the diversified re-ranking on the host, with the device's arithmetic
+    (`mvfgpu_selftest_mmr_walk`, include/mvf_gpu_mmr.h; no GPU needed): `rel_scores` [m] and `sim_scores` [m, m]
+    (`sim_scores[s, d]`: row s as the query) in score form -> (the picks' positions [k], UINT32_MAX behind them; the
+    objective [k]; the number of picks)."""
+    rel = np.ascontiguousarray(rel_scores, np.float32).reshape(-1)
+    m = rel.size
+    sim = np.ascontiguousarray(sim_scores, np.float32)
+    if sim.size != m * m:
+        raise InvalidArgument(f"sim_scores must hold {m} x {m} scores, got shape {sim.shape}")
+    k = int(k)
+    if k < 0:
+        raise InvalidArgument("k must be >= 0")
+    order = np.empty(max(k, 1), np.uint32)
+    obj = np.empty(max(k, 1), np.float32)
+    n = _lib.gpu().mvfgpu_selftest_mmr_walk(rel.ctypes.data_as(C.c_void_p) if m else None, sim.ctypes.data_as(C.c_void_p) if m else None,
+                                            m, metric, float(lambda_mult), k, order.ctypes.data_as(C.c_void_p),
+                                            obj.ctypes.data_as(C.c_void_p))
+    if n < 0:
+        _lib.gpu_check(-n)
+    return order[:k], obj[:k], int(n)
+
+
 def radius_bound(data_type: int, metric: int, radius: float) -> tuple[int, int]:
     """(largest matching order key, exact i32 bound of Int8/UInt8 L2/InnerProduct spaces) of a radius --
     `mvfgpu_selftest_radius_bound`; no GPU needed."""
@@ -631,6 +662,57 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_search_candidates_device(self._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                   nq, _opt(d_candidates), m, k, C.c_void_p(d_scores),
                                                                   C.c_void_p(d_indices), _opt(d_raw), _opt(d_counts), _opt(stream)))
+
+    def search_mmr(self, queries: np.ndarray, candidates: np.ndarray, k: int, lambda_mult: float = 0.5, metric: int = L2) -> MmrResult:
+        """Diversified re-ranking (`mvfgpu_search_mmr`, include/mvf_gpu_mmr.h): of each query's candidate rows -- `candidates`
+        as `search_candidates` takes them, at most MMR_MAX_CANDIDATES per query -- the k picks of the greedy maximal-marginal-
+        relevance walk, in pick order; `lambda_mult` in [0, 1] weighs relevance against the similarity to the rows already
+        picked (1: the candidate search's order)."""
+        q, qcode, nq, qdim = _query_args(queries)
+        cand = candidates if isinstance(candidates, np.ndarray) else np.asarray(candidates)
+        if cand.ndim != 2 or cand.dtype != np.uint64:
+            raise InvalidArgument(f"candidates must be a 2-D uint64 array [nq, m], got {cand.dtype} of shape {cand.shape}")
+        if cand.shape[0] != nq:
+            raise InvalidArgument(f"candidates holds {cand.shape[0]} lists for {nq} queries")
+        if cand.shape[1] > 0xFFFFFFFF:
+            raise InvalidArgument("at most 2^32 - 1 candidates per query")
+        cand = np.ascontiguousarray(cand)
+        m = cand.shape[1]
+        sc, idx, raw = _result_arrays(nq, k)
+        obj = np.empty((nq, k), np.float32)
+        counts = np.zeros(nq, np.uint64)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_mmr(self._h, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
+                                                    cand.ctypes.data_as(C.c_void_p) if m else None, m, k, float(lambda_mult),
+                                                    sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                    raw.ctypes.data_as(C.c_void_p), obj.ctypes.data_as(C.c_void_p),
+                                                    counts.ctypes.data_as(C.c_void_p)))
+        return MmrResult(sc, idx, raw, counts, obj)
+
+    def search_mmr_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, d_candidates: int, m: int, k: int,
+                          lambda_mult: float, metric: int, d_scores: int, d_indices: int, d_raw: int = 0, d_objective: int = 0,
+                          d_counts: int = 0, stream: int = 0) -> None:
+        """Device-pointer diversified re-ranking (`mvfgpu_search_mmr_device`), asynchronous on `stream`; the lists are
+        global positions."""
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_mmr_device(self._h, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq,
+                                                           _opt(d_candidates), m, k, float(lambda_mult), C.c_void_p(d_scores),
+                                                           C.c_void_p(d_indices), _opt(d_raw), _opt(d_objective), _opt(d_counts),
+                                                           _opt(stream)))
+
+    def mmr_stage_ms(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, d_candidates: int, m: int, k: int,
+                     lambda_mult: float, metric: int, d_scores: int, d_indices: int, stream: int = 0) -> tuple[float, float]:
+        """(C0 + relevance, D0) milliseconds of one device call (`mvfgpu_selftest_mmr_stage_ms`); waits for the stream."""
+        ms = (C.c_float * 2)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_mmr_stage_ms(self._h, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq,
+                                                               _opt(d_candidates), m, k, float(lambda_mult), C.c_void_p(d_scores),
+                                                               C.c_void_p(d_indices), None, None, None, _opt(stream), ms))
+        return float(ms[0]), float(ms[1])
+
+    @staticmethod
+    def mmr_walk(rel_scores, sim_scores, metric: int, lambda_mult: float, k: int) -> tuple[np.ndarray, np.ndarray, int]:
+        """The walk of `search_mmr` on the host (`mvfgpu_selftest_mmr_walk`; no GPU needed): `rel_scores` [m] and
+        `sim_scores` [m, m] (row s as the query) in score form -> (the picks' positions [k], UINT32_MAX behind them; the
+        objective [k]; the number of picks)."""
+        return mmr_walk(rel_scores, sim_scores, metric, lambda_mult, k)
 
     def knn_join(self, k: int, metric: int = L2, first: int = 0, count: int | None = None,
                  queries_from: "GpuCorpus | None" = None, exclude_self: bool = True) -> SearchResult:

@@ -187,6 +187,64 @@ def rerank_top_k(space: VectorSpace, queries, candidates, k: int, metric: int | 
     return out
 
 
+def diversify_top_k(space: VectorSpace, queries, candidates, k: int, lambda_mult: float = 0.5, metric: int | None = None,
+                    corpus: GpuCorpus | None = None, device: int = 0, with_vectors: bool = False) -> list[list[ScoredVector]]:
+    """Diversified re-ranking by maximal marginal relevance (`mvfgpu_search_mmr`; DESIGN.md §3 "Diversified re-ranking"): of
+    each query's candidate rows -- `candidates` [nq, m] uint64 as `rerank_top_k` takes them, at most 1024 per query -- k that
+    are relevant and not near-copies of each other, in pick order.  `lambda_mult` in [0, 1]: 1 ranks by relevance alone
+    (`rerank_top_k`'s order), 0 by dissimilarity to the rows already picked.  Each hit's score is the query's score of the
+    row, as `rerank_top_k` reports it.  The row payloads are fetched only when `with_vectors` is set."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    dt = int(space.data_type())
+    q = np.asarray(queries, dtype=_NP_OF[query_dtype_code(dt)])
+    if q.ndim != 2:
+        raise BuildError("queries must be a 2-D array [nq, dimension]")
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        res = corpus.search_mmr(q, candidates, k, lambda_mult, metric)
+        n = np.minimum(res.counts, np.uint64(k)).astype(np.int64)
+        rows = None
+        if with_vectors and int(n.sum()):
+            rows = corpus.gather_rows(np.concatenate([res.indices[i][:n[i]] for i in range(q.shape[0])]))
+    finally:
+        if own:
+            corpus.close()
+    out, r = [], 0
+    for i in range(q.shape[0]):
+        hits = []
+        for j in range(int(n[i])):
+            payload = None
+            if rows is not None:
+                payload = rows[r].astype(np.float32) if dt in (0, 1) else rows[r].copy()
+                r += 1
+            hits.append(ScoredVector(int(res.indices[i][j]), float(res.scores[i][j]), payload))
+        out.append(hits)
+    return out
+
+
+def find_top_k_diverse(space: VectorSpace, queries, k: int, fetch_k: int, lambda_mult: float = 0.5, metric: int | None = None,
+                       corpus: GpuCorpus | None = None, device: int = 0, with_vectors: bool = False) -> list[list[ScoredVector]]:
+    """The usual one-call form ("max marginal relevance search"): `find_top_k_similar_batch` with `fetch_k` (at most 1024),
+    then `diversify_top_k` over the rows it found."""
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        top = find_top_k_similar_batch(space, queries, fetch_k, metric, corpus=corpus)
+        cand = np.full((len(top), max(fetch_k, 1)), 0xFFFFFFFFFFFFFFFF, np.uint64)
+        for i, hits in enumerate(top):
+            cand[i, :len(hits)] = [h.index for h in hits]
+        return diversify_top_k(space, queries, cand, k, lambda_mult, metric, corpus=corpus, with_vectors=with_vectors)
+    finally:
+        if own:
+            corpus.close()
+
+
 def find_top_k_filtered(space: VectorSpace, query, k: int, allow, metric: int | None = None, corpus: GpuCorpus | None = None,
                         device: int = 0) -> list[ScoredVector]:
     """`find_top_k_similar` among the rows a predicate admits (`mvfgpu_search_filtered`; DESIGN.md §3 "Filtered search"):
