@@ -87,6 +87,7 @@ int set_fail(int status, const std::string& msg) { return fail(status, msg); }
 
 hipError_t scratch_pool(hipMemPool_t* out) {
     constexpr int kMaxDevices = 64;
+    constexpr size_t kScratchAnchorBytes = 4096;
     static std::mutex mu;
     static hipMemPool_t pools[kMaxDevices] = {};
     int dev = 0;
@@ -106,6 +107,17 @@ hipError_t scratch_pool(hipMemPool_t* out) {
         uint64_t keep = ~0ull;  // never trimmed at a synchronisation
         e = hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
         if (e != hipSuccess) {
+            (void)hipMemPoolDestroy(pool);
+            return e;
+        }
+        // One block stays in use for the life of the process.  While the pool holds no block in use, a synchronous hipFree
+        // elsewhere in the process (a column, a partition index, a filter) leaves the pool's memory zero again, and the zeros
+        // land DURING the next call: its first copy or its last store is lost (profiles/r20_fresh_index_routes.txt).
+        void* anchor = nullptr;
+        e = hipMallocFromPoolAsync(&anchor, kScratchAnchorBytes, pool, nullptr);
+        if (e == hipSuccess) e = poison_fill(anchor, kScratchAnchorBytes, nullptr);
+        if (e != hipSuccess) {
+            if (anchor) (void)hipFreeAsync(anchor, nullptr);
             (void)hipMemPoolDestroy(pool);
             return e;
         }

@@ -15,11 +15,16 @@ import numpy as np
 import pytest
 
 import _fresh_process as F
+import _grouped as GR
+import _maxsim as MS
+import _maxsim_candidates as MC
+import _mmr as MM
+import _partitioned as P
 from _candidates import candidate_rows
 from _children import RUNNER
 from _filtered import assert_float_filtered, oracle_filtered
 from _radius import assert_float_radius, oracle_radius
-from _util import PAD
+from _util import PAD, TOL
 from metrovector_amd import gpu as G
 
 pytestmark = pytest.mark.gpu
@@ -215,12 +220,311 @@ def expect_s10(oracle, name):
     return check
 
 
+# ---- S11 .. S17: the routes over a partition index ------------------------------------------------------------------------------
+def _same_call(out, key, fields):
+    """the device call left the host call's bytes"""
+    for f in fields:
+        a, b = out[f"{key}.{f}"], out[f"{key}@device.{f}"]
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"{key}: the device call's {f} differ from the host call's"
+
+
+def _row(got, j):
+    return Got({"x.scores": got.scores[j:j + 1], "x.indices": got.indices[j:j + 1], "x.raw": got.raw[j:j + 1]}, "x")
+
+
+def expect_s11(oracle, name):
+    dt, dim = F.any_shape(name.split("_")[1])
+    inp = F.s11_inputs(dt, dim)
+    lay = inp["lay"]
+    admits = [np.zeros(F.FI_N, bool) for _ in inp["keys"]]
+    for a, key in zip(admits, inp["keys"]):
+        a[P.reference_rows(lay, key)] = True
+    held = [int(a.sum()) for a in admits]
+    assert held == [300, 1, 0, 0, 2] and min(F.S11_KS) < 300 < max(F.S11_KS)
+
+    def check(out):
+        for key, metric, nq, k in F.s11_calls():
+            got = Got(out, key)
+            _same_call(out, key, ("scores", "indices", "raw"))
+            for j in range(nq):
+                _check_topk(oracle, inp["rows"], dt, metric, inp["queries"][j:j + 1], k, admits[j], _row(got, j), what=f"{key} query {j}")
+                assert (got.indices[j, min(k, held[j]):] == PAD).all(), f"{key} query {j}: padding behind the key's {held[j]} rows"
+    return check
+
+
+def expect_s12(oracle, name):
+    dt, dim = F.any_shape(name.split("_")[1])
+    code = F.DT[dt][1]
+    inp = F.s12_inputs(dt, dim)
+    lay, rows, q = inp["lay"], inp["rows"], inp["queries"]
+    live = GR.live_rows(lay)
+    admit = ~lay["dead"]
+    ranked = {}
+    if dt in INT:  # the oracle's ranking of every held row
+        for metric in F.METRICS:
+            sc, idx, raw = oracle.search(rows[live], code, metric, q, live.size)
+            ranked[metric] = (sc, live[idx.astype(np.int64)].astype(np.uint64), raw)
+
+    def check(out):
+        for metric in F.METRICS:
+            rk = Got(out, f"rank_m{metric}")
+            # the candidate search over every held row is the exact ranking (the oracle's bytes, or its scores within the tolerance)
+            _check_topk(oracle, rows, dt, metric, q, live.size, admit, rk, what=f"ranking, metric {metric}")
+        for key, metric, per_key, k, nq in F.s12_calls():
+            got = Got(out, key)
+            _same_call(out, key, ("scores", "indices", "raw"))
+            assert got.scores.shape == got.indices.shape == got.raw.shape == (nq, k), key
+            rk = ranked[metric] if dt in INT else (out[f"rank_m{metric}.scores"], out[f"rank_m{metric}.indices"], out[f"rank_m{metric}.raw"])
+            for j in range(nq):
+                places = GR.grouped_walk(rk[1][j].astype(np.int64), lay["col"], per_key, k)
+                s, i, r = GR.expected(rk[0][j], rk[1][j], rk[2][j], places, k, metric)
+                assert (got.indices[j] == i).all() and (got.raw[j] == r).all(), f"{key} query {j}: the walk's rows"
+                assert (got.scores[j].view(np.uint32) == s.view(np.uint32)).all(), f"{key} query {j}: score bits"
+    return check
+
+
+def _float_sets_reference(inp):
+    """{metric: (b, tol)} of every token of the pool, float64 (tests/_maxsim.py f64_key_bests; DESIGN.md §3's tolerance)"""
+    nq, T, dim = inp["pool"].shape
+    return MS.f64_key_bests(inp["rows"], inp["lay"], inp["pool"].reshape(nq * T, dim), TOL)
+
+
+def _check_maxsim_float(got, f64, key_values, metric, nq, T, k, pool_T, what):
+    nk = key_values.size
+    kk = min(k, nk)
+    b, tol = f64[metric]
+    assert got.counts.tolist() == [kk] * nq, f"{what}: counts"
+    assert (got.keys[:, kk:] == PAD).all() and (got.scores[:, kk:] == (np.inf if metric == F.L2 else -np.inf)).all(), f"{what}: padding"
+    for j in range(nq):
+        sl = slice(j * pool_T, j * pool_T + T)
+        MS.assert_f64_contract(got.scores[j, :kk], got.keys[j, :kk], key_values, b[sl].sum(0), tol[sl].sum(0), metric, kk)
+
+
+class GotMs:
+    def __init__(self, out, key):
+        self.scores, self.keys, self.counts = out[key + ".scores"], out[key + ".keys"], out[key + ".counts"]
+
+
+def _maxsim_expect(inp, dt, dim, calls):
+    """check(out) of a multi-vector scenario: Int8 the exact reference byte for byte, floats the float64 contract; the device
+    call the host call's bytes"""
+    lay = inp["lay"]
+    key_values = MS.key_order(lay)[3]
+    pool_T = inp["pool"].shape[1]
+    assert min(F.MS_KS) < key_values.size < max(F.MS_KS), "k below and above the keys that hold rows"
+    f64 = None if dt in INT else _float_sets_reference(inp)
+    want = {}
+    if dt in INT:
+        for key, metric, T, nq, k in calls:
+            want[key] = MS.int_reference(inp["rows"], lay, F.ms_sets(inp, nq, T), metric, k)
+
+    def check(out):
+        for key, metric, T, nq, k in calls:
+            got = GotMs(out, key)
+            _same_call(out, key, ("scores", "keys", "counts"))
+            assert got.scores.shape == got.keys.shape == (nq, k) and got.counts.shape == (nq,), key
+            if dt in INT:
+                sc, ky, cnt = want[key]
+                assert (got.keys == ky).all() and (got.counts == cnt).all(), f"{key}: keys"
+                assert (got.scores.view(np.uint32) == sc.view(np.uint32)).all(), f"{key}: score bits"
+            else:
+                _check_maxsim_float(got, f64, key_values, metric, nq, T, k, pool_T, key)
+    return check
+
+
+def expect_s13(oracle, name):
+    dt, dim = F.any_shape(name.split("_")[1])
+    return _maxsim_expect(F.ms_inputs("s13", dt, dim), dt, dim, list(F.ms_calls()))
+
+
+def expect_s14(oracle, name):
+    dt, dim, metric = F.S14_CASES[name.split("_")[1]]
+    inp = F.ms_inputs("s14", dt, dim)
+    calls = list(F.ms_calls((metric,)))
+    contract = _maxsim_expect(inp, dt, dim, calls)
+    route1 = {}  # DESIGN.md §3: route 2's answer is route 1's bytes -- route 1 on a handle of this process
+    with G.GpuCorpus.from_array(inp["rows"]) as c:
+        c.set_tombstones(np.packbits(inp["lay"]["dead"], bitorder="little"))
+        with c.attach_column(inp["lay"]["col"]) as col, c.make_partition(col) as part:
+            c.set_maxsim_route(1)
+            for key, m, T, nq, k in calls:
+                route1[key] = c.search_maxsim(F.ms_sets(inp, nq, T), k, m, part)
+
+    def check(out):
+        contract(out)
+        assert (out["candidates"] >= F.MS_KS[0]).all() and (out["blocks"] >= 1).all(), "the child's handle selected by the MFMA route"
+        for key, *_ in calls:
+            got, want = GotMs(out, key), route1[key]
+            assert (got.keys == want.keys).all() and (got.counts == want.counts).all(), f"{key}: route 1's keys"
+            assert (got.scores.view(np.uint32) == want.scores.view(np.uint32)).all(), f"{key}: route 1's score bits"
+    return check
+
+
+def s15_held(inp):
+    """per list the distinct candidates that hold rows, from the layout alone"""
+    held = P.group_by(inp["lay"])[0]
+    return held, [MC.held_distinct(l, held) for l in inp["lists"]]
+
+
+def expect_s15(oracle, name):
+    dt, dim = F.any_shape(name.split("_")[1])
+    inp = F.s15_inputs(dt, dim)
+    lay, sets, lists = inp["lay"], inp["sets"], inp["lists"]
+    nq, T = sets.shape[:2]
+    held, mine = s15_held(inp)
+    nk = held.size
+    assert all(1 <= m.size < F.S15_M for m in mine) and max(F.S15_KS) > F.S15_M
+    if dt in INT:
+        full_ref = {metric: MS.int_reference(inp["rows"], lay, sets, metric, nk) for metric in F.METRICS}
+    else:
+        f64 = MS.f64_key_bests(inp["rows"], lay, sets.reshape(nq * T, dim), TOL)
+
+    def check(out):
+        for metric in F.METRICS:
+            full = GotMs(out, f"full_m{metric}")
+            if dt in INT:
+                sc, ky, cnt = full_ref[metric]
+                assert (full.keys == ky).all() and (full.scores.view(np.uint32) == sc.view(np.uint32)).all(), f"metric {metric}: the full search"
+            for k in F.S15_KS:
+                key = f"m{metric}_k{k}"
+                got = GotMs(out, key)
+                _same_call(out, key, ("scores", "keys", "counts"))
+                sc, ky, cnt = MC.filter_full(full.scores, full.keys, nk, lists, held, k, metric)
+                assert (got.counts == cnt).all() and got.counts.tolist() == [min(k, m.size) for m in mine], f"{key}: counts"
+                assert (got.keys == ky).all(), f"{key}: the full search's keys, filtered"
+                assert (got.scores.view(np.uint32) == sc.view(np.uint32)).all(), f"{key}: the full search's score bits, filtered"
+                if dt not in INT:  # and the float64 contract among the list's own keys
+                    b, tol = f64[metric]
+                    for j in range(nq):
+                        at = np.searchsorted(held, mine[j])
+                        kk = min(k, mine[j].size)
+                        sl = slice(j * T, (j + 1) * T)
+                        MS.assert_f64_contract(got.scores[j, :kk], got.keys[j, :kk], mine[j], b[sl].sum(0)[at], tol[sl].sum(0)[at], metric, kk)
+    return check
+
+
+class _Replay:
+    """tests/_mmr.py `recipe` asks a corpus for three things; this one answers from what the child saved"""
+
+    def __init__(self, out, metric, j, rows):
+        self.out, self.metric, self.j, self.rows, self.asked = out, metric, j, rows, 0
+
+    def search_candidates(self, q, entries, m, metric):
+        assert metric == self.metric
+        key = ("rel" if self.asked == 0 else "sim") + f"_m{metric}_q{self.j}"
+        self.asked += 1
+        return G.CandidateResult(self.out[key + ".scores"], self.out[key + ".indices"], self.out[key + ".raw"], self.out[key + ".counts"])
+
+    def gather_rows(self, pos):
+        return self.rows[np.asarray(pos).astype(np.int64)]
+
+
+def expect_s16(oracle, name):
+    inp = F.s16_inputs()
+    rows, q, lists = inp["rows"], inp["queries"], inp["lists"]
+    nq = q.shape[0]
+    sels = [candidate_rows(lists[j], F.S16_N) for j in range(nq)]
+    assert sels[0].size == F.S16_M and 1 <= sels[1].size < F.S16_M
+
+    def check(out):
+        for metric in (F.COS, F.L2):
+            for j in range(nq):  # the recipe's ingredients are the exact candidate searches
+                rel = Got(out, f"rel_m{metric}_q{j}")
+                admit = np.zeros(F.S16_N, bool)
+                admit[sels[j]] = True
+                assert rel.counts.tolist() == [sels[j].size]
+                _check_topk(oracle, rows, "f32", metric, q[j:j + 1], F.S16_M, admit, rel, what=f"relevance, metric {metric}, query {j}")
+                sim = Got(out, f"sim_m{metric}_q{j}")
+                for s in (0, sels[j].size - 1):
+                    _check_topk(oracle, rows, "f32", metric, rows[sels[j][s]][None, :], F.S16_M, admit, _row(sim, s),
+                                what=f"similarity, metric {metric}, query {j}, row {s}")
+            for lam in F.S16_LAMBDAS:
+                key = f"l{lam}_m{metric}"
+                _same_call(out, key, ("scores", "indices", "raw", "objective", "counts"))
+                got = G.MmrResult(out[key + ".scores"], out[key + ".indices"], out[key + ".raw"], out[key + ".counts"], out[key + ".objective"])
+                for j in range(nq):
+                    MM.assert_rows_equal(got, MM.recipe(_Replay(out, metric, j, rows), metric, q[j], lists[j], F.S16_K, lam), j, key)
+                if metric == F.COS:  # the planted world: relevance alone takes the eight copies first, lambda 0.5 takes one
+                    picked = np.isin(got.indices[0][:8], inp["copies"])
+                    assert picked.all() if lam == 1.0 else picked.sum() == 1, f"{key}: the copies among the first eight picks"
+    return check
+
+
+def s17_reference():
+    """(documents ascending, float64 sums, tolerances, the candidate documents that hold rows): the float64 contract of the
+    documents example, in numpy"""
+    inp = F.s17_inputs()
+    rows, doc, q = inp["rows"].astype(np.float64), inp["doc"], inp["query"].astype(np.float64)
+    d = np.sqrt(((rows[None, :, :] - q[:, None, :]) ** 2).sum(2))   # [T, n] L2
+    docs = np.unique(doc)
+    b = np.stack([d[:, doc == g].min(1) for g in docs], axis=1)      # [T, documents]
+    return docs, b.sum(0), (TOL * np.abs(b)).sum(0), MC.held_distinct(inp["cand"], docs)
+
+
+def check_s17_answer(full_scores, full_keys, cand_scores, cand_keys, ref=None):
+    """the documents line (k = S17_K) and the re-ranked line of one process against the float64 contract"""
+    docs, S, tol, held = ref or s17_reference()
+    MS.assert_f64_contract(full_scores, full_keys, docs, S, tol, F.L2, F.S17_K)
+    at = np.searchsorted(docs, held)
+    assert len(cand_keys) == min(F.S17_K, held.size), "the candidates that hold rows"
+    MS.assert_f64_contract(cand_scores, cand_keys, held, S[at], tol[at], F.L2, len(cand_keys))
+
+
+def expect_s17(oracle, name):
+    steps = F.S17_STEPS[name.split("_")[1]]
+    inp = F.s17_inputs()
+    ref = s17_reference()
+    docs, S, tol, held = ref
+    assert docs.size == F.S17_DOCS and held.size == 5, "4, 9, 0, 13, 21: the repeats, 77 and the pad are skipped"
+
+    def check(out):
+        tags = [f"step{i}_{s}" for i, s in enumerate(steps)]
+        full = GotMs(out, next(t for t, s in zip(tags, steps) if s == "full"))
+        assert full.counts.tolist() == [F.S17_DOCS] and (np.sort(full.keys[0, :F.S17_DOCS]) == docs).all()
+        MS.assert_f64_contract(full.scores[0, :F.S17_DOCS], full.keys[0, :F.S17_DOCS], docs, S, tol, F.L2, F.S17_DOCS)
+        want = MC.filter_full(full.scores, full.keys, F.S17_DOCS, inp["cand"][None, :], docs, F.S17_K, F.L2)
+        cands = []
+        for tag, step in zip(tags, steps):
+            if step == "full":
+                top = GotMs(out, tag + "_k")
+                assert top.counts.tolist() == [F.S17_K] and (top.keys[0] == full.keys[0, :F.S17_K]).all()
+                assert (top.scores[0].view(np.uint32) == full.scores[0, :F.S17_K].view(np.uint32)).all(), f"{tag}: k = {F.S17_K} is the head of the full list"
+            elif step == "cand":
+                got = GotMs(out, tag)
+                cands.append(got)
+                check_s17_answer(full.scores[0, :F.S17_K], full.keys[0, :F.S17_K], got.scores[0, :5], got.keys[0, :5], ref)
+                assert got.counts.tolist() == [5] and (got.keys == want[1]).all(), f"{tag}: the same child's full answer, filtered"
+                assert (got.scores.view(np.uint32) == want[0].view(np.uint32)).all(), f"{tag}: the same child's full answer's score bits, filtered"
+            elif step == "empty":
+                got = GotMs(out, tag)
+                assert got.counts.tolist() == [0] and (got.keys == PAD).all() and np.isposinf(got.scores).all(), f"{tag}: no candidates"
+            elif step == "perkey":
+                got = Got(out, tag)
+                for j, key in enumerate(inp["cand"][[0, 3, 4]]):
+                    _check_topk(oracle, inp["rows"], "f32", F.L2, inp["query"][j:j + 1], F.S17_K, inp["doc"] == key, _row(got, j), what=f"{tag} query {j}")
+            elif step == "grouped":
+                got = Got(out, tag)
+                for j in range(F.S17_T):  # one row per document: every hit the best row of its document, documents in the order of those
+                    hit = got.indices[j].astype(np.int64)
+                    assert np.unique(inp["doc"][hit]).size == F.S17_K, f"{tag} query {j}: one row per document"
+                    d = np.sqrt(((inp["rows"].astype(np.float64) - inp["query"][j].astype(np.float64)) ** 2).sum(1))
+                    best = np.array([d[inp["doc"] == g].min() for g in docs])
+                    assert np.allclose(got.scores[j], np.sort(best)[:F.S17_K], rtol=TOL, atol=0), f"{tag} query {j}: the documents' best rows"
+                    assert np.allclose(got.scores[j], d[hit], rtol=TOL, atol=0), f"{tag} query {j}: the hits' own distances"
+        for later in cands[1:]:
+            for f in ("scores", "keys", "counts"):
+                assert getattr(later, f).tobytes() == getattr(cands[0], f).tobytes(), f"the second candidate call's {f} differ from the first's"
+    return check
+
+
 EXPECT = dict(s1=expect_s1, s2=expect_s2, s3=expect_s3, s4=expect_s4, s5=expect_s5, s6=expect_s6, s7=expect_s7, s8=expect_s8,
-              s9=expect_s9, s10=expect_s10)
+              s9=expect_s9, s10=expect_s10, s11=expect_s11, s12=expect_s12, s13=expect_s13, s14=expect_s14, s15=expect_s15,
+              s16=expect_s16, s17=expect_s17)
 
 
 def _child(name, tag, poison, tmp_path):
-    env = {k: v for k, v in os.environ.items() if k not in ("MVF_DEBUG_POISON", "MVF_FILTER_ROUTE", "MVF_LARGE_K")}
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("MVF_DEBUG_POISON", "MVF_FILTER_ROUTE", "MVF_LARGE_K", "MVF_MAXSIM_ROUTE", "MVF_MAXSIM_SCRATCH_BYTES")}
     if poison is not None:
         env["MVF_DEBUG_POISON"] = str(poison)
     path = str(tmp_path / f"{tag}.npz")
