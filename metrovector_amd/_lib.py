@@ -281,6 +281,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_shadow6_pack.restype = C.c_int
     lib.mvfgpu_selftest_shadow6_unpack.argtypes = [vp, u64, u64, u32, vp]
     lib.mvfgpu_selftest_shadow6_unpack.restype = C.c_int
+    lib.mvfgpu_selftest_shadow51_bytes.argtypes = [u64, u32]
+    lib.mvfgpu_selftest_shadow51_bytes.restype = u64
+    lib.mvfgpu_selftest_shadow51_pack.argtypes = [vp, u64, u32, vp, u64]
+    lib.mvfgpu_selftest_shadow51_pack.restype = C.c_int
+    lib.mvfgpu_selftest_shadow51_unpack.argtypes = [vp, u64, u64, u32, vp]
+    lib.mvfgpu_selftest_shadow51_unpack.restype = C.c_int
+    lib.mvfgpu_debug_stream_lo_lines.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    lib.mvfgpu_debug_stream_lo_lines.restype = C.c_int
     poison = getattr(lib, "mvfgpu_selftest_poison", None)  # added within ABI 3 as well: a diagnostic entry point
     if poison is not None:
         poison.argtypes = []

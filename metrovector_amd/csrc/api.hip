@@ -16,6 +16,8 @@
 #include "scan_mfma.h"
 #include "scan_stream.h"
 #include "shadow_6b.h"
+#include "shadow_5p1.h"
+#include "../../include/mvf_gpu_stream_5p1.h"
 
 #include <algorithm>
 #include <cmath>
@@ -156,6 +158,7 @@ Tuning read_tuning() {
     if (const char* e = getenv("MVF_K2_REGION_RECORDS")) t.region_records = strtoull(e, nullptr, 10);
     t.stream_i8 = getenv("MVF_STREAM_I8") ? (flag("MVF_STREAM_I8", false) ? 1 : 0) : -1;
     t.stream_6b = flag("MVF_STREAM_6B", true);
+    t.stream_5p1 = getenv("MVF_STREAM_5P1") ? (flag("MVF_STREAM_5P1", false) ? 1 : 0) : -1;
     t.upload_threads = (unsigned)std::max(0l, num("MVF_UPLOAD_THREADS", 0));
     t.host_zc_query = (size_t)std::max(0l, num("MVF_HOST_ZC_QUERY", 64l << 10));
     t.host_zc_results = (size_t)std::max(0l, num("MVF_HOST_ZC_RESULTS", 256l << 10));
@@ -218,6 +221,11 @@ struct mvfgpu_corpus {
     mutable DevBuf shadow6, xscale6, qs6_stats;  // Float32 corpora: the 6-bit shadow in 64-row tiles (shadow_6b.h), s_r per row, its 4 bound maxima
     mutable int shadow6_state = 0;               // 0 not tried, 1 all rows, -1 no room (whole or none: no prefix shadows on this route)
     mutable int shadow6_finite = -1;             // as shadow8_finite
+    mutable bool shadow6_p51 = false;            // the shadow is held in the 5+1 layout (shadow_5p1.h; stream_5p1_layout): one of the two formats, whole or none
+    // the 5+1 scan's per-block words (ScanParams::pub / lo_stats): kPub51Blocks x 8 bytes of published bests, then kPub51Blocks x
+    // 16 bytes of low-plane counters; zeroed once, told apart between searches by pub51_seq
+    mutable DevBuf pub51;
+    mutable uint32_t pub51_seq = 0, pub51_blocks = 0;  // the newest 5+1 search's sequence number and blocks (0: the newest 6-bit-route search was not one)
     // feedback for the automatic choice: after a search that selected on the int8 shadow the number of queries the
     // repair launches had to redo is copied to pinned host memory (no wait); a later search that finds it large
     // (the data defeats the int8 bound: near-duplicates everywhere, heavy-tailed rows) switches this corpus back to the
@@ -454,16 +462,18 @@ K1Shape k1_shape(const mvfgpu_corpus* c, uint32_t queries, uint32_t k, uint32_t 
 }
 K1Shape k1_shape(const mvfgpu_corpus* c, uint32_t queries, uint32_t k) { return k1_shape(c, queries, k, c->V, c->dtype); }
 // ... of the pass over the 6-bit shadow (scan_stream.inc, S6): one query, one lane per row, a step per 64-element unit
-K1Shape k1_shape_6b(uint32_t units, uint32_t k) {
+// (p51: the 5+1 unit -- `units` of 128 elements; the chunks are those of the 6-bit unit over the same rows)
+K1Shape k1_shape_6b(uint32_t units, uint32_t k, bool p51 = false) {
     K1Shape sh;
     sh.nqv = 1;
     sh.G = 1;
     sh.J = units;
-    sh.chunk_rows = scan_chunk_rows(1, units, 1);
+    sh.chunk_rows = scan_chunk_rows(1, p51 ? 2u * units : units, 1);
     sh.pmax = next_pow2(k + scan_chunk_safe(1));
-    sh.lds = scan_lds_bytes_6b(units, sh.pmax);
+    sh.lds = p51 ? scan_lds_bytes_51(units, sh.pmax) : scan_lds_bytes_6b(units, sh.pmax);
     return sh;
 }
+constexpr uint32_t kPub51Blocks = 4096;  // blocks of a 5+1 scan the handle keeps words for (8 resident blocks on each of 512 CUs)
 int k1_shape_fits(const K1Shape& sh) {
     if (sh.lds > 160 * 1024) return fail(MVF_ERR_BUILD, "dimension too large for the streaming kernel's LDS query tile");
     return MVF_OK;
@@ -530,6 +540,7 @@ struct ShadowStream {
     // qaux0 / qaux1 / delta (qstats, xxmax: what the bound is made of); xrow: the rows' norm array
     bool i8;
     bool s6;  // ... in 6-bit tiles (dt2y unit: pitch = a tile's bytes, V = the units per row)
+    bool p51; // ... held in the 5+1 layout (dt2z unit: 128-element units)
     float *qaux0, *qaux1;
     const float *qstats, *xxmax, *xrow;
     // ... and select_final's margin mode instead of the k best: every row within 2 delta[q] of the rank_k-th best
@@ -590,7 +601,7 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
     hipStream_t s = sc.stream;
     const uint32_t kcap = next_pow2(k);
     const uint32_t ostride = out_stride ? out_stride : k;
-    const bool alt8 = alt && alt->i8, alt6 = alt8 && alt->s6;
+    const bool alt8 = alt && alt->i8, alt6 = alt8 && alt->s6, alt51 = alt6 && alt->p51;
     const uint8_t kdtype = alt8 ? (uint8_t)MVF_DTYPE_INT8 : alt ? (uint8_t)MVF_DTYPE_FLOAT16 : c->dtype;
     const uint32_t kV = alt ? alt->V : c->V;
 
@@ -615,7 +626,7 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
 
     for (uint32_t q0 = 0; q0 < nq;) {
         // (the f16 shadow's unit and a one-query dump take one query per pass)
-        K1Shape sh = alt6 ? k1_shape_6b(kV, k) : k1_shape(c, (!alt || alt8) && !(rank && rank->nqv == 1) ? nq - q0 : 1u, k, kV, kdtype);
+        K1Shape sh = alt6 ? k1_shape_6b(kV, k, alt51) : k1_shape(c, (!alt || alt8) && !(rank && rank->nqv == 1) ? nq - q0 : 1u, k, kV, kdtype);
         const int G = sh.G, nqv = sh.nqv;
         const size_t lds = sh.lds;
         uint32_t& chunk_rows = sh.chunk_rows;  // (the small-corpus rule below may shorten it)
@@ -626,7 +637,8 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
 
         uint32_t nblocks = 0;
         if (nchunks > 0) {
-            const void* kfn = alt6  ? scan_stream_kernel_ptr_dt2y(metric, G, nqv)
+            const void* kfn = alt51 ? scan_stream_kernel_ptr_dt2z(metric, G, nqv)
+                              : alt6  ? scan_stream_kernel_ptr_dt2y(metric, G, nqv)
                               : alt8  ? scan_stream_kernel_ptr_dt2x(metric, G, nqv)
                               : alt ? scan_stream_kernel_ptr_dt1x(metric, G, nqv)
                                     : scan_kernel(c->dtype, metric, G, nqv, /*redo=*/false, floor1 != nullptr || rank != nullptr);
@@ -692,7 +704,25 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
             sp.dump = rank ? rank->a : nullptr;
             if (ps && first && ts_work) sp.ts = ts_work;
             else if (ps && first) MVF_HIP_TRY(hipEventRecord(ps->e[0], s));
-            if (alt6) MVF_HIP_TRY(scan_stream_launch_dt2y(sp, metric, G, nqv, dim3(nblocks), lds, s));
+            if (alt6) c->pub51_blocks = 0;
+            if (alt51) {  // the blocks' published bests and low-plane counters, under a sequence number of this search's own
+                if (nblocks > kPub51Blocks) return fail(MVF_ERR_BUILD, "more scan blocks than the 5+1 stream's per-block words");
+                if (!c->pub51.p) {
+                    MVF_HIP_TRY(c->pub51.reserve((size_t)kPub51Blocks * 24));
+                    MVF_HIP_TRY(hipMemsetAsync(c->pub51.p, 0, (size_t)kPub51Blocks * 24, s));
+                    c->pub51_seq = 0;
+                }
+                if (++c->pub51_seq == 0) c->pub51_seq = 1;  // (0 is what the zeroed words carry)
+                sp.pub = static_cast<uint64_t*>(c->pub51.p);
+                sp.lo_stats = reinterpret_cast<uint32_t*>(sp.pub + kPub51Blocks);
+                sp.pub_seq = c->pub51_seq;
+                sp.skip_rank = alt->rank_k;
+                // half a safe piece (one iteration of the block's four waves) while a block has neither threshold: its best is
+                // published, and the others' are read, 512 rows sooner (>= the longest list of the route, 204 entries)
+                sp.first_piece = std::min(sp.first_piece, 512u);
+                c->pub51_blocks = nblocks;
+                MVF_HIP_TRY(scan_stream_launch_dt2z(sp, metric, G, nqv, dim3(nblocks), lds, s));
+            } else if (alt6) MVF_HIP_TRY(scan_stream_launch_dt2y(sp, metric, G, nqv, dim3(nblocks), lds, s));
             else if (alt8) MVF_HIP_TRY(scan_stream_launch_dt2x(sp, metric, G, nqv, dim3(nblocks), lds, s));
             else if (alt) MVF_HIP_TRY(scan_stream_launch_dt1x(sp, metric, G, nqv, dim3(nblocks), lds, s));
             else MVF_HIP_TRY(scan_launch(c->dtype, sp, metric, G, nqv, dim3(nblocks, npass), lds, s));
@@ -700,7 +730,9 @@ int search_stream_path(const mvfgpu_corpus* c, SearchCall& sc, bool profile = tr
                 if (!ts_work) MVF_HIP_TRY(hipEventRecord(ps->e[1], s));
                 ps->scanned = true;
                 ps->ts_scan = ts_work != nullptr;
-                tm.scan_bytes = alt6 ? (uint64_t)s6_bytes(c->n, c->dim) : (uint64_t)c->n * c->dim * elem_size(kdtype);
+                // (5+1: the layout's bytes, hi and lo planes -- the 6-bit layout's figure; what the scan fetched of the lo planes:
+                // mvfgpu_debug_stream_lo_lines)
+                tm.scan_bytes = alt51 ? (uint64_t)s51_bytes(c->n, c->dim) : alt6 ? (uint64_t)s6_bytes(c->n, c->dim) : (uint64_t)c->n * c->dim * elem_size(kdtype);
                 tm.scan_flops = 2ull * nq_here * c->n * c->dim;
                 if (npass > 1) tm.scan_bytes *= npass;
             }
@@ -1082,13 +1114,27 @@ hipError_t ensure_shadow8(const mvfgpu_corpus* c, hipStream_t s, bool insist, bo
     return e;
 }
 
+// The layout the 6-bit shadow of a handle is held in: 5+1 (shadow_5p1.h) where that is no larger than the 6-bit layout -- the
+// dimension modulo 128 is 0 or above 64 -- and the corpus is large enough for the skipped low bits to outweigh what the scan
+// pays for them (two tiles in flight instead of four, a short first piece, a second round trip per tile that holds a needing
+// row, the skip key's refresh per chunk, and ~0.9M low-plane lines read before the published bests are good -- whatever the size).
+// Measured, 768-dim cosine, top-100, device ms per search, 6-bit layout | 5+1 (profiles/r21_stream_5p1.txt): 4 GiB 0.187 |
+// 0.210; 8 GiB 0.327 | 0.338; 12 GiB 0.419 | 0.423; 16 GiB 0.554 | 0.519; 20 GiB 0.682 | 0.622; 28.6 GiB 0.944 | 0.845.
+// MVF_STREAM_5P1=0 never, =1 wherever it is no larger; a handle on scan path 7 (tests) takes it at any size too.
+constexpr uint64_t kStream51MinBytes = 16ull << 30;
+bool stream_5p1_layout(const Tuning& t, uint64_t rows, uint32_t dim, bool forced) {
+    if (t.stream_5p1 == 0 || !s51_eligible(dim)) return false;
+    return t.stream_5p1 == 1 || forced || rows * (uint64_t)dim * 4u >= kStream51MinBytes;
+}
+
 // The 6-bit shadow (shadow_6b.hip), built straight from the stored rows beside whatever int8 shadow exists: ensure_shadow8's
 // free-memory rule (its bytes + 2 GiB must be free unless the caller insists), all rows or none.
 hipError_t ensure_shadow6(const mvfgpu_corpus* c, hipStream_t s, bool insist) {
     if (c->shadow6_state == -1 && insist) c->shadow6_state = 0;
     if (c->shadow6_state != 0) return hipSuccess;
     const uint64_t rows = std::max<uint64_t>(c->n, 1);
-    const size_t need = s6_bytes(rows, c->dim);
+    const bool p51 = stream_5p1_layout(c->tune, c->n, c->dim, c->scan_path == 7);
+    const size_t need = p51 ? s51_bytes(rows, c->dim) : s6_bytes(rows, c->dim);
     if (!insist) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)2 << 30)) {
@@ -1108,8 +1154,9 @@ hipError_t ensure_shadow6(const mvfgpu_corpus* c, hipStream_t s, bool insist) {
     hipError_t e = hipMemsetAsync(c->qs6_stats.p, 0, 16, s);
     if (e == hipSuccess)
         e = launch_shadow_6b(c->d_rows, (uint32_t)c->n, c->pitch, c->dim, static_cast<unsigned char*>(c->shadow6.p),
-                             static_cast<float*>(c->xscale6.p), static_cast<float*>(c->qs6_stats.p), s);
+                             static_cast<float*>(c->xscale6.p), static_cast<float*>(c->qs6_stats.p), s, p51);
     if (e == hipSuccess) {
+        c->shadow6_p51 = p51;
         c->shadow6_state = 1;
         c->shadow6_finite = -1;
     }
@@ -1750,6 +1797,11 @@ int search_stream_qs_path(const mvfgpu_corpus* c, SearchCall& sc, bool s6 = fals
         alt.qstats = static_cast<const float*>(c->qs6_stats.p);
         alt.pitch = (uint32_t)s6_tile_bytes(c->dim);
         alt.V = s6_units(c->dim);
+        if (c->shadow6_p51) {
+            alt.p51 = true;
+            alt.pitch = (uint32_t)s51_tile_bytes(c->dim);
+            alt.V = s51_units(c->dim);
+        }
     }
     alt.cand = static_cast<uint64_t*>(c->bcand.p);
     alt.cnt = bs.cnt;
@@ -2475,6 +2527,7 @@ void mvfgpu_corpus_destroy(mvfgpu_corpus* c) {
         c->shadow6.release();
         c->xscale6.release();
         c->qs6_stats.release();
+        c->pub51.release();
         c->h_q.release();
         c->h_s.release();
         c->h_i.release();
@@ -2516,7 +2569,7 @@ int mvfgpu_corpus_get_info(const mvfgpu_corpus* c, mvfgpu_corpus_info* out) {
         inf.shadows = (uint8_t)((c->shadow8_state == 1 ? 1 : 0) | (c->shadow_state == 1 ? 2 : 0) | (c->shadow8_state == 2 ? 4 : 0) | (c->shadow6_state == 1 ? 8 : 0));
         inf.selection_state = (uint8_t)((c->qs_disabled ? 1 : 0) | (c->bias_disabled ? 2 : 0) | (c->s6_disabled ? 4 : 0));
         inf.device_bytes = c->tomb.bytes + c->ids.bytes + c->rows_bytes + c->cand.bytes + c->bq.bytes + c->bstate.bytes + c->bcand.bytes +
-                           c->xnorm.bytes + c->repair.bytes + c->floor1.bytes + c->rank_a.bytes + c->rank_b.bytes + c->rank_tmp.bytes + c->blk.bytes + c->shadow8.bytes + c->xscale8.bytes + c->qs_stats.bytes + c->split_out.bytes + c->shadow6.bytes + c->xscale6.bytes + c->qs6_stats.bytes +
+                           c->xnorm.bytes + c->repair.bytes + c->floor1.bytes + c->rank_a.bytes + c->rank_b.bytes + c->rank_tmp.bytes + c->blk.bytes + c->shadow8.bytes + c->xscale8.bytes + c->qs_stats.bytes + c->split_out.bytes + c->shadow6.bytes + c->xscale6.bytes + c->qs6_stats.bytes + c->pub51.bytes +
                            c->shadow.bytes + c->xscale.bytes + c->h_q.bytes + c->h_s.bytes + c->h_i.bytes + c->h_r.bytes + c->h_v.bytes;
     }
     return copy_out_struct(out, inf);
@@ -3185,6 +3238,20 @@ int mvfgpu_last_timing(const mvfgpu_corpus* c, mvfgpu_timing* out) {
         tm.search_ms_avg = wcnt ? (float)(wsum / wcnt) : 0.f;
     }
     return copy_out_struct(out, tm);
+}
+
+int mvfgpu_debug_stream_lo_lines(const mvfgpu_corpus* c, uint64_t* out_fetched, uint64_t* out_total) {
+    if (!c || !out_fetched || !out_total) return fail(MVF_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out_fetched = *out_total = 0;
+    if (!c->pub51.p || c->pub51_blocks == 0) return MVF_OK;  // the newest 6-bit-route search did not read the 5+1 layout
+    DevScope guard(c->device);
+    if (c->has_done) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
+    std::vector<uint32_t> st((size_t)c->pub51_blocks * 4);
+    MVF_HIP_TRY(hipMemcpy(st.data(), static_cast<const unsigned char*>(c->pub51.p) + (size_t)kPub51Blocks * 8, st.size() * 4, hipMemcpyDeviceToHost));
+    for (uint32_t b = 0; b < c->pub51_blocks; b++)
+        if (st[(size_t)b * 4] == c->pub51_seq) *out_fetched += st[(size_t)b * 4 + 1], *out_total += st[(size_t)b * 4 + 2];
+    return MVF_OK;
 }
 
 int mvfgpu_set_scan_path(mvfgpu_corpus* c, int path) {

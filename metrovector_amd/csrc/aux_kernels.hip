@@ -8,6 +8,7 @@
 #include "aux_kernels.h"
 #include "bitonic.h"
 #include "mvf_common.h"
+#include "margin_key.h"
 #include "repair_flags.h"
 
 #include <hip/hip_fp16.h>
@@ -192,10 +193,7 @@ __global__ void __launch_bounds__(1024) select_final_kernel(SelectParams p) {
     if (p.delta) {  // margin mode: everything within 2 delta of the k-th best, from every list
         __shared__ uint32_t cut_s;
         uint32_t tkey = kNanKey;  // fewer than k rows in all: everything is a candidate
-        if (m >= p.margin_rank) {
-            const float vk = score_from_key((uint32_t)(buf[p.margin_rank - 1] >> 32), p.metric), d = 2.0f * p.delta[q];
-            tkey = key_from_score(p.metric == MVF_METRIC_L2 ? vk + d : vk - d, p.metric);
-        }
+        if (m >= p.margin_rank) tkey = margin_key((uint32_t)(buf[p.margin_rank - 1] >> 32), p.delta[q], p.metric);
         __syncthreads();
         if (tid == 0) *cnt = 0, cut_s = 0;
         __syncthreads();

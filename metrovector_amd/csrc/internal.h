@@ -143,6 +143,7 @@ struct Tuning {
     uint64_t region_records = 0;  // MVF_K2_REGION_RECORDS: size of the candidate regions (tests: force overflows)
     int stream_i8 = -1;         // MVF_STREAM_I8: unset -1 (the automatic rule), 0 off, 1 on (any size once a shadow exists)
     bool stream_6b = true;      // MVF_STREAM_6B=0: ONE Float32 query never streams the 6-bit shadow (it stays on the int8 shadow / the stored rows)
+    int stream_5p1 = -1;        // MVF_STREAM_5P1: unset -1 (the 5+1 layout of the 6-bit shadow from kStream51MinBytes of rows on, shadow_5p1.h), 0 never, 1 wherever it is no larger than the 6-bit layout
     unsigned upload_threads = 0;  // MVF_UPLOAD_THREADS
     size_t host_zc_query = 64u << 10;     // MVF_HOST_ZC_QUERY: mvfgpu_search reads queries up to this size in place (pinned host)
     size_t host_zc_results = 256u << 10;  // MVF_HOST_ZC_RESULTS: ... and writes results up to this size in place

@@ -13,6 +13,8 @@ constexpr float kQ16Max = 16256.0f;  // 127 * 128: the largest |Q| whose high pl
 // LDS or global, natural element order).  Thread t takes the elements t, t + 256, ... in both passes; the sums meet as in
 // query_i8s.h (xor butterfly, then red[]).  red: 16 words of LDS.  Three block barriers.
 //   *sq_out = s_q, *qn_out = |q| (f32 norm of the ORIGINAL query), *qsum_out = sum Q (exact), in every thread;
+//   *qpos_out (where asked for: the 5+1 unit) = P = sum max(Q, 0) (exact), in every thread: the most the low bits of a row's
+//   codes can add to Q.y (shadow_5p1.h: y = 2 hi + lo, 0 <= Q.lo <= P);
 //   *delta_out (thread 0 only, where want_delta) = the proven bound of |approximate score - exact score| over ALL rows,
 //   query_i8s.h's three forms with the 6-bit shadow's maxima in stats[0..3], the 16-bit query's MEASURED |eq| and |Q|, and
 //   6e-7 where the int8 route has 4e-7: the approximate dot product is float(128 hi.y + lo.y - 32 sum Q), an exact integer
@@ -21,7 +23,7 @@ constexpr float kQ16Max = 16256.0f;  // 127 * 128: the largest |Q| whose high pl
 // A non-finite query gets s_q = 0 and delta = +inf: every row is kept, the query overflows its budget and K1 repairs it.
 __device__ __forceinline__ void prep_query_16s(const float* q, uint32_t dim, uint32_t nelem, int metric, const float* stats,
                                                const float* xxmax, int8_t* dst_lo, int8_t* dst_hi, float* red, bool want_delta,
-                                               float* sq_out, float* qn_out, int32_t* qsum_out, float* delta_out) {
+                                               float* sq_out, float* qn_out, int32_t* qsum_out, float* delta_out, int32_t* qpos_out = nullptr) {
     const uint32_t tid = threadIdx.x;
     float mx = 0.f, ss = 0.f;
     bool bad = false;
@@ -48,7 +50,7 @@ __device__ __forceinline__ void prep_query_16s(const float* q, uint32_t dim, uin
     __syncthreads();
     const float sq = (bad || !(mx > 0.f)) ? 0.f : mx / kQ16Max;
     float q2 = 0.f, e2 = 0.f;
-    int32_t qsum = 0;
+    int32_t qsum = 0, qpos = 0;
     for (uint32_t c = tid; c < nelem; c += 256) {
         const float v = c < dim ? q[c] : 0.f;
         const float t = sq > 0.f ? v / sq : 0.f;
@@ -59,6 +61,7 @@ __device__ __forceinline__ void prep_query_16s(const float* q, uint32_t dim, uin
         e2 = fmaf(e, e, e2);
         const int Q = (int)r16, lo = ((Q + 64) & 127) - 64;
         qsum += Q;
+        if (qpos_out) qpos += Q > 0 ? Q : 0;
         dst_lo[c] = (int8_t)lo;
         dst_hi[c] = (int8_t)((Q - lo) >> 7);
     }
@@ -66,17 +69,20 @@ __device__ __forceinline__ void prep_query_16s(const float* q, uint32_t dim, uin
         q2 += __shfl_xor(q2, off, 64);
         e2 += __shfl_xor(e2, off, 64);
         qsum += __shfl_xor(qsum, off, 64);
+        if (qpos_out) qpos += __shfl_xor(qpos, off, 64);
     }
     if ((tid & 63) == 0) {
         red[tid >> 6] = q2;
         red[4 + (tid >> 6)] = e2;
         reinterpret_cast<int32_t*>(red)[12 + (tid >> 6)] = qsum;
+        if (qpos_out) reinterpret_cast<int32_t*>(red)[8 + (tid >> 6)] = qpos;
     }
     __syncthreads();
     const int32_t* rsum = reinterpret_cast<const int32_t*>(red) + 12;
     *sq_out = sq;
     *qn_out = sqrtf(ss);
     *qsum_out = rsum[0] + rsum[1] + rsum[2] + rsum[3];
+    if (qpos_out) *qpos_out = rsum[-4] + rsum[-3] + rsum[-2] + rsum[-1];
     if (want_delta && tid == 0) {
         const float qn = sqrtf(ss);
         q2 = red[0] + red[1] + red[2] + red[3];

@@ -184,9 +184,9 @@ hipError_t launch_shadow_f16(const unsigned char* rows32, uint32_t n, uint32_t p
 hipError_t launch_shadow_i8(const unsigned char* rows, int src_dtype, uint32_t n, uint32_t pitch, uint32_t dim, unsigned char* rows8,
                             uint32_t pitch8, float* xscale8, float* stats, hipStream_t s);
 // 6-bit shadow of a Float32 corpus in the tiled layout of shadow_6b.h (shadow_6b.hip): rows6 holds s6_bytes(n, dim) bytes;
-// stats: 4 floats, zeroed by the caller
+// stats: 4 floats, zeroed by the caller.  p51: the same codes in the 5+1 layout of shadow_5p1.h, s51_bytes(n, dim) bytes
 hipError_t launch_shadow_6b(const unsigned char* rows, uint32_t n, uint32_t pitch, uint32_t dim, unsigned char* rows6, float* xscale6,
-                            float* stats, hipStream_t s);
+                            float* stats, hipStream_t s, bool p51 = false);
 hipError_t launch_prep_queries_i8s(const float* q, uint32_t nq, uint32_t nq_pad, uint32_t dim, uint32_t KPB, int metric,
                                    const float* stats, const float* xxmax, unsigned char* qprep, float* qaux0, float* qaux1,
                                    float* delta, hipStream_t s);

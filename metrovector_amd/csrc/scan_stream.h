@@ -57,6 +57,15 @@ struct ScanParams {
     // wall clock at its start to ts[0], thread 0 of every block folds it at its end into ts[1] (a vector atomic maximum); the select behind the
     // launch publishes and re-arms the pair (SelectParams::ts_work).  NULL = not profiled: one scalar compare.
     uint64_t* ts;
+    // The 5+1 unit (dt2z; shadow_5p1.h) only.  pub[block] = {pub_seq : 32 | the best key of the block's list : 32}, stored by
+    // the block whenever a merge changes the head of its list; words of another sequence number are ignored, so nothing resets
+    // them between searches.  The skip_rank-th best of the published keys is a proven bound of the search's skip_rank-th best
+    // 6-bit key; 2 delta behind it (margin_key.h) lies the key beyond which a row's low bit is never fetched.
+    // lo_stats[block] = {pub_seq, low-plane lines fetched, low-plane lines in the rows scanned, 0}, stored once at the block's end.
+    uint64_t* pub;
+    uint32_t* lo_stats;
+    uint32_t pub_seq;
+    uint32_t skip_rank;
 };
 
 // nqv: queries per pass, 1 or 4; p.redo_list != NULL selects the repair variant of the kernel, p.floor1 != NULL the
@@ -71,6 +80,7 @@ MVF_DECL_SCAN(2)
 MVF_DECL_SCAN(3)
 MVF_DECL_SCAN(1x)  // Float16 rows of an f32 corpus' shadow, scaled back by ScanParams::xscale; nqv = 1 only
 MVF_DECL_SCAN(2x)  // Int8 shadow rows of a float corpus: exact i32 dot, float keys dot * xscale[r] * qaux0[q]; nqv = 1 or 4
+MVF_DECL_SCAN(2z)  // the same shadow in the 5+1 layout (shadow_5p1.h): as 2y with 128-element units; pitch = a tile's bytes (hi and lo planes), V = J = units per row
 MVF_DECL_SCAN(2y)  // the 6-bit shadow of a Float32 corpus in 64-row tiles (shadow_6b.h): G = 1, nqv = 1 only; pitch = a tile's bytes, V = J = units per row
 #undef MVF_DECL_SCAN
 
@@ -101,5 +111,9 @@ inline size_t scan_lds_bytes(int dtype, int G, uint32_t J, int nqv, uint32_t pma
 
 // ... of the 6-bit-shadow unit: both int8 planes of the 16-bit query, 64 bytes per unit each
 inline size_t scan_lds_bytes_6b(uint32_t units, uint32_t pmax) { return (size_t)units * 128u + (size_t)pmax * 8u + 32u; }
+
+// ... of the 5+1 unit: 128 bytes per unit and query plane, and four words behind the thresholds (the low-plane counters, the
+// skip key, the query's bound)
+inline size_t scan_lds_bytes_51(uint32_t units, uint32_t pmax) { return (size_t)units * 256u + (size_t)pmax * 8u + 32u + 16u; }
 
 }  // namespace mvf

@@ -28,6 +28,8 @@
 #include "query_i8s.h"
 #include "query_16s.h"
 #include "shadow_6b.h"
+#include "shadow_5p1.h"
+#include "margin_key.h"
 
 #include <hip/hip_fp16.h>
 
@@ -73,7 +75,49 @@ constexpr bool QSK = XS && MVF_SCAN_DT == MVF_DTYPE_INT8;
 // plane p of unit j of the tile's 64 rows -- ScanParams::pitch is the TILE's size and V = J the units per row.  The query is
 // quantised to sixteen bits in the prologue (query_16s.h) and sits in LDS as two int8 planes in natural element order, 64
 // bytes per unit each: per row two exact i32 sums, combined exactly with the per-query constant 32 sum Q, then QSK's keys.
-constexpr bool S6 = QSK && MVF_SCAN_XS == 2;
+constexpr bool S6 = QSK && (MVF_SCAN_XS == 2 || MVF_SCAN_XS == 3);
+// S51: the S6 unit over the same codes in the 5+1 LAYOUT (MVF_SCAN_XS == 3; shadow_5p1.h): a step is a 128-element unit, five
+// wave-loads of hi planes.  Two phases per wave iteration:
+//   1. the hi planes of every row: 2 Q.hi exactly, and with P = sum max(Q, 0) (query_16s.h) the integer
+//      D_best = 2 Q.hi + P - 32 sum Q >= Q.x6 -- the most the row's dot product can be whatever its low bits are.  key_best is
+//      make_key of D_best: every float operation behind the integer is monotone in it (one int64 -> f32 rounding, products
+//      with the non-negative s_r and s_q, Cosine: a division by a positive number or the constant 0, L2: a subtraction from a
+//      value that does not depend on it), so key_best is never worse than the row's 6-bit key.
+//   2. only for the rows whose key_best reaches the SKIP KEY: the lo plane (lane-masked 16-byte loads of the 8-lane groups holding such a row: only touched 128-byte lines
+//      are requested), Q.lo exactly, and from there S6's integer, rounding and key.  The other rows are no candidates.
+//      (The block's own running threshold does not enter the decision: it is the 128-th best of ~13 000 rows, 2.2 sigma on
+//      the benchmark's corpus, where every 128-byte line holds a row that beats it -- it only filters the candidates, as on S6.)
+// The skip key is margin_key (2 delta behind) of a bound of the search's k-th best 6-bit key: the k-th best of the bests the
+// blocks PUBLISH (ScanParams::pub) -- k distinct live rows scored with all six bits.  Select_final's margin threshold is the
+// same expression of the true k-th best, so no row it keeps is ever skipped, and the k-th best itself is unchanged.
+constexpr bool S51 = QSK && MVF_SCAN_XS == 3;
+
+// The skip key of the 5+1 unit, by ONE wave (the same value in every lane): the rank-th best of the keys published under `seq`
+// among the first min(nb, 1024) blocks, rounded to the worse end of its 4096-key bucket, moved by the margin.  0xFFFFFFFF
+// (every row needs its low bit) while fewer than `rank` blocks have published.  Stale words only weaken the bound.
+__device__ __forceinline__ uint32_t skip_key_51(const uint64_t* pub, uint32_t nb, uint32_t seq, uint32_t rank, float delta, uint8_t metric, uint32_t lane) {
+    uint32_t keys[16];
+    uint32_t valid = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const uint32_t b = (uint32_t)i * 64u + lane;
+        uint64_t w = 0;
+        if (b < nb) w = __hip_atomic_load(pub + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        keys[i] = (b < nb && (uint32_t)(w >> 32) == seq) ? (uint32_t)w : 0xFFFFFFFFu;
+        valid += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(keys[i] != 0xFFFFFFFFu));
+    }
+    if (valid < rank || !(delta < 3.0e38f)) return 0xFFFFFFFFu;  // (a non-finite query: every row is kept, as on the 6-bit unit)
+    uint32_t lo = 0, hi = 0xFFFFFu;  // the smallest 20-bit prefix with at least `rank` keys at or in front of it
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        uint32_t c = 0;
+#pragma unroll
+        for (int i = 0; i < 16; i++) c += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64((keys[i] >> 12) <= mid));
+        if (c >= rank) hi = mid;
+        else lo = mid + 1;
+    }
+    return margin_key((lo << 12) | 0xFFFu, delta, metric);
+}
 
 // Short rows (G <= 8: one step per row) are latency-bound -- a wave has 4 KiB in flight and its iteration is load -> wait ->
 // sums -> keys in sequence -- so those instantiations of the narrow types ask for more waves per SIMD than the 3-4 the
@@ -88,16 +132,18 @@ constexpr bool S6 = QSK && MVF_SCAN_XS == 2;
 #define MVF_K1_SHORT_ROW_WAVES 5  // A/B builds: -DMVF_K1_SHORT_ROW_WAVES=8|7|6|1
 #endif
 template <int DT, int METRIC, int G, int NQ, bool REDO = false, bool FLOOR = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((G <= 8 && NQ == 1 && DT != MVF_DTYPE_FLOAT32 && !S6) ? MVF_K1_SHORT_ROW_WAVES : 1, 8)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S51 ? 3 : (G <= 8 && NQ == 1 && DT != MVF_DTYPE_FLOAT32 && !S6) ? MVF_K1_SHORT_ROW_WAVES : 1, 8)))
 scan_stream_kernel(ScanParams p) {
     using Tr = DtTraits<DT>;
     using Acc = typename Tr::Acc;
     constexpr int ES = Tr::ES;
     static_assert(!S6 || (G == 1 && NQ == 1 && !REDO && !FLOOR), "the 6-bit unit: one lane per row, one query");
-    constexpr int EPV = S6 ? 64 : 16 / ES;  // corpus elements per 16-B vector (S6: per unit)
+    constexpr int EPV = S51 ? 128 : S6 ? 64 : 16 / ES;  // corpus elements per 16-B vector (S6: per unit)
     constexpr int RPG = 64 / G;   // rows per wave-load
-    constexpr int U = 4;          // row groups in flight per wave (8 for one-step rows measured SLOWER: 128-B rows 4.4 vs 5.3 TB/s)
-    constexpr int QB = S6 ? 128 : Tr::INT ? 16 : EPV * 4;  // query bytes per corpus vector in LDS (S6: per unit, both planes)
+    // row groups in flight per wave (8 for one-step rows measured SLOWER: 128-B rows 4.4 vs 5.3 TB/s).  S51: TWO tiles -- five
+    // planes of a unit each, 10 KiB in flight per wave -- beside the 64 registers of a unit's query planes
+    constexpr int U = S51 ? 2 : 4;
+    constexpr int QB = S51 ? 256 : S6 ? 128 : Tr::INT ? 16 : EPV * 4;  // query bytes per corpus vector in LDS (S6: per unit, both planes)
     constexpr bool NEED_XX = !QSK && ((METRIC == MVF_METRIC_COSINE) || (Tr::INT && METRIC == MVF_METRIC_L2));
     constexpr bool NEED_QQ = NEED_XX;
 
@@ -115,6 +161,7 @@ scan_stream_kernel(ScanParams p) {
     uint32_t* kprev = cnt + NQ;                                                            // [NQ]
     float* red = reinterpret_cast<float*>(kprev + NQ);                                     // [NQ][4] qq partials
     uint64_t* tau = reinterpret_cast<uint64_t*>(red + NQ * 4);                             // [NQ] (8-B aligned by layout)
+    [[maybe_unused]] uint32_t* s51w = reinterpret_cast<uint32_t*>(tau + NQ);  // S51: lo lines fetched, lo lines scanned, the skip key, delta's bits
 
     // Repair launches walk their flagged queries in groups of NQ, one pass over the rows per group; an ordinary launch
     // is the single group of its NQ queries.
@@ -136,6 +183,8 @@ scan_stream_kernel(ScanParams p) {
     Acc qq_part[NQ];
     float qsf[NQ], qnf[NQ];  // QSK: query scale and |q|
     [[maybe_unused]] int64_t qbias6 = 0;  // S6: 32 sum Q
+    [[maybe_unused]] int64_t qpos51 = 0;  // S51: P = sum max(Q, 0)
+    [[maybe_unused]] uint32_t pub_last = 0xFFFFFFFFu;  // S51, thread 0: the key this block published last
     // composites at or in front of the query's floor are not candidates (passes of a k > 1024 search); as ONE unsigned
     // compare: (comp - fl1) < (tau - fl1) with fl1 = floor + 1, which is comp < tau without a floor (fl1 = 0) and rejects
     // comp <= floor by wrapping (tau > floor always: the k-th best of the rows behind the floor, or the padding value)
@@ -155,6 +204,13 @@ scan_stream_kernel(ScanParams p) {
             float d = 0.f;
             if constexpr (S6) {  // both planes: lo at qs, hi behind it (VP * 64 bytes each)
                 int32_t qsum = 0;
+                if constexpr (S51) {  // every block moves its skip key by the query's bound: thread 0 of each computes it
+                    int32_t qpos = 0;
+                    prep_query_16s(reinterpret_cast<const float*>(p.queries) + (size_t)qi * p.dim, p.dim, VP * EPV, METRIC, p.qstats, p.xxmax,
+                                   reinterpret_cast<int8_t*>(qs), reinterpret_cast<int8_t*>(qs) + VP * EPV, prep_red, true, &qsf[q], &qnf[q], &qsum, &d, &qpos);
+                    qpos51 = qpos;
+                    if (tid == 0) s51w[0] = 0, s51w[1] = 0, s51w[2] = 0xFFFFFFFFu, s51w[3] = __float_as_uint(d);
+                } else
                 prep_query_16s(reinterpret_cast<const float*>(p.queries) + (size_t)qi * p.dim, p.dim, VP * EPV, METRIC, p.qstats, p.xxmax,
                                reinterpret_cast<int8_t*>(qs), reinterpret_cast<int8_t*>(qs) + VP * EPV, prep_red, owner, &qsf[q], &qnf[q], &qsum, &d);
                 qbias6 = (int64_t)kS6Bias * qsum;
@@ -230,7 +286,24 @@ scan_stream_kernel(ScanParams p) {
     for (uint32_t chunk = blockIdx.x; chunk < p.nchunks; chunk += gridDim.x) {
       const uint32_t cend = (chunk + 1) * p.chunk_rows;
       bool safe_only = false;
+      [[maybe_unused]] bool skip_fresh = false;  // S51: the skip key was read for this chunk
       for (uint32_t c0 = chunk * p.chunk_rows; c0 < cend && c0 < p.n;) {
+        [[maybe_unused]] uint32_t kskip = 0xFFFFFFFFu;
+        [[maybe_unused]] uint32_t lo_fetched = 0, lo_total = 0;  // S51, wave-uniform: this piece's low-plane lines
+        if constexpr (S51) {
+            // the published bests are read at the start of a chunk, and in front of every piece while there is no skip key yet
+            // (block-uniform: s51w[2] was last written in front of a barrier)
+            if (!skip_fresh || s51w[2] == 0xFFFFFFFFu) {
+                __syncthreads();  // (every wave has read the old key)
+                if (wave == 0) {
+                    const uint32_t kk = skip_key_51(p.pub, gridDim.x, p.pub_seq, p.skip_rank, __uint_as_float(s51w[3]), (uint8_t)METRIC, (uint32_t)lane);
+                    if (lane == 0) s51w[2] = kk;
+                }
+                __syncthreads();
+                skip_fresh = true;
+            }
+            kskip = s51w[2];
+        }
         uint64_t tau_r[NQ];
         uint32_t kprev_r[NQ];
         bool all_set = true;
@@ -241,6 +314,7 @@ scan_stream_kernel(ScanParams p) {
             all_set = all_set && tau_r[q] != kPadComposite;
             if constexpr (FLOOR) tau_r[q] -= fl1[q];  // from here on the threshold is relative to the floor, as the composites tested against it
         }
+        if constexpr (S51) all_set = all_set || kskip != 0xFFFFFFFFu;  // with a skip key few rows survive whatever the block's own threshold: long guarded pieces
         const uint32_t piece_rows = (all_set && !safe_only) ? cend - c0 : min((all_set || p.first_piece == 0) ? p.chunk_safe : p.first_piece, cend - c0);
         const uint32_t groups_per_chunk = piece_rows / RPG;
 
@@ -271,7 +345,48 @@ scan_stream_kernel(ScanParams p) {
                 for (int q = 0; q < NQ; q++) acc[u][q] = 0;
             }
 
-            if constexpr (S6) {
+            if constexpr (S51) {
+                for (uint32_t j = 0; j < p.J; j++) {
+                    u32x4 x[U][5];
+#pragma unroll
+                    for (int u = 0; u < U; u++)
+#pragma unroll
+                        for (int pl = 0; pl < 5; pl++) {
+                            x[u][pl] = u32x4{0, 0, 0, 0};
+                            if (rv[u]) x[u][pl] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rp[u] + ((size_t)j * 5 + pl) * 1024));
+                        }
+                    // the unit's 128 query elements in two halves of 64 (32 registers of query at a time): [g] = elements 16 g .. 16 g + 15
+#pragma unroll
+                    for (int gh = 0; gh < 2; gh++) {
+                        u32x4 ql[4], qh[4];
+#pragma unroll
+                        for (int g = 0; g < 4; g++) {
+                            ql[g] = *reinterpret_cast<const u32x4*>(qs + j * 128 + (gh * 4 + g) * 16);
+                            qh[g] = *reinterpret_cast<const u32x4*>(qs + VP * 128 + j * 128 + (gh * 4 + g) * 16);
+                        }
+#pragma unroll
+                        for (int u = 0; u < U; u++)
+#pragma unroll
+                            for (int i = 0; i < 4; i++) {
+                                const uint32_t p0 = x[u][0][i], p1 = x[u][1][i], p2 = x[u][2][i], p3 = x[u][3][i], p4 = x[u][4][i];
+                                uint32_t y[4];  // hi of the elements 16 (4 gh + g) + 4 i .. + 3 (shadow_5p1.h)
+                                if (gh == 0) {
+                                    y[0] = p0 & 0x1F1F1F1Fu, y[1] = p1 & 0x1F1F1F1Fu, y[2] = p2 & 0x1F1F1F1Fu, y[3] = p3 & 0x1F1F1F1Fu;
+                                } else {
+                                    y[0] = p4 & 0x1F1F1F1Fu;
+                                    y[1] = ((p0 >> 5) & 0x07070707u) | ((p1 >> 2) & 0x18181818u);
+                                    y[2] = ((p1 >> 7) & 0x01010101u) | ((p2 >> 4) & 0x0E0E0E0Eu) | ((p3 >> 1) & 0x10101010u);
+                                    y[3] = ((p3 >> 6) & 0x03030303u) | ((p4 >> 3) & 0x1C1C1C1Cu);
+                                }
+#pragma unroll
+                                for (int g = 0; g < 4; g++) {
+                                    acc[u][0] = dot4_i8(ql[g][i], y[g], acc[u][0]);
+                                    acch[u] = dot4_i8(qh[g][i], y[g], acch[u]);
+                                }
+                            }
+                    }
+                }
+            } else if constexpr (S6) {
                 for (uint32_t j = 0; j < p.J; j++) {
                     u32x4 x[U][3];
 #pragma unroll
@@ -466,7 +581,66 @@ scan_stream_kernel(ScanParams p) {
                 const bool dead = p.tomb && ((p.tomb[rl >> 5] >> (rl & 31)) & 1u);
                 p.dump[(size_t)ql * p.n + rl] = rank_entry((uint32_t)(comp >> 32), rl, dead);
             };
-            if constexpr (NQ == 4 && U == 4 && G >= 16) {
+            if constexpr (S51) {
+                // phase 1's verdict: which rows can still matter (the comment at S51)
+                bool need[U];
+                unsigned long long bal[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const int64_t dbest = 2ll * (128ll * (int64_t)acch[u] + (int64_t)acc[u][0]) + qpos51 - qbias6;
+                    const uint32_t kbest = make_key((Acc)__float_as_int((float)dbest), 0, qq[0], rs[u], rn[u], qsf[0], qnf[0]);
+                    need[u] = rv[u] && kbest <= kskip;
+                    bal[u] = __builtin_amdgcn_ballot_w64(need[u]);
+                    const unsigned long long live = __builtin_amdgcn_ballot_w64(rv[u]);  // (the last tile: only the lines that hold rows)
+#pragma unroll
+                    for (int g = 0; g < 8; g++) lo_total += ((live >> (8 * g)) & 0xFFull) != 0 ? p.J : 0u;
+                }
+                // phase 2, per tile that holds such a row
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    if (bal[u] == 0) continue;  // wave-uniform
+                    const bool grp = ((bal[u] >> (lane & 56)) & 0xFFull) != 0;  // a row of this lane's 128-byte line needs its bit
+                    uint32_t lines = 0;
+#pragma unroll
+                    for (int g = 0; g < 8; g++) lines += ((bal[u] >> (8 * g)) & 0xFFull) != 0 ? 1u : 0u;
+                    lo_fetched += lines * p.J;
+                    int32_t bl = 0, bh = 0;
+                    const unsigned char* lop = rp[u] + (size_t)p.J * 5u * 1024u;  // the tile's lo planes, this row's 16 bytes
+                    constexpr int LB = 6;  // lo planes per round trip (768 dimensions: all of them)
+                    for (uint32_t j0 = 0; j0 < p.J; j0 += LB) {
+                        u32x4 lo[LB];
+#pragma unroll
+                        for (int jj = 0; jj < LB; jj++) {
+                            lo[jj] = u32x4{0, 0, 0, 0};
+                            if (grp && j0 + jj < p.J) lo[jj] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(lop + (size_t)(j0 + jj) * 1024));
+                        }
+#pragma unroll
+                        for (int jj = 0; jj < LB; jj++) {
+                            if (j0 + jj >= p.J) break;  // wave-uniform
+                            if (!need[u]) continue;
+                            const uint32_t j = j0 + jj;
+#pragma unroll
+                            for (int g = 0; g < 8; g++) {
+                                const u32x4 qlg = *reinterpret_cast<const u32x4*>(qs + j * 128 + g * 16);
+                                const u32x4 qhg = *reinterpret_cast<const u32x4*>(qs + VP * 128 + j * 128 + g * 16);
+#pragma unroll
+                                for (int i = 0; i < 4; i++) {  // elements 16 g + 4 i .. + 3: bits m, m + 8, m + 16, m + 24 of dword g / 2, m = 4 (g & 1) + i
+                                    const uint32_t yl = (lo[jj][g >> 1] >> (4 * (g & 1) + i)) & 0x01010101u;
+                                    bl = dot4_i8(qlg[i], yl, bl);
+                                    bh = dot4_i8(qhg[i], yl, bh);
+                                }
+                            }
+                        }
+                    }
+                    // Q.y = 2 Q.hi + Q.lo, exact: from here S6's integer, its one rounding and its key
+                    const Acc s = (Acc)__float_as_int((float)(128ll * (2ll * (int64_t)acch[u] + (int64_t)bh) + 2ll * (int64_t)acc[u][0] + (int64_t)bl - qbias6));
+                    const uint64_t comp = ((uint64_t)make_key(s, 0, qq[0], rs[u], rn[u], qsf[0], qnf[0]) << 32) | r[u];
+                    if (need[u] && comp < tau_r[0] && !(p.tomb && ((p.tomb[r[u] >> 5] >> (r[u] & 31)) & 1u))) {
+                        const uint32_t slot = atomicAdd(&cnt[0], 1u);
+                        if (kprev_r[0] + slot < p.pmax) bufs[kprev_r[0] + slot] = comp;
+                    }
+                }
+            } else if constexpr (NQ == 4 && U == 4 && G >= 16) {
                 // Sixteen (row u, query q) sums per group.  A butterfly would leave all of them in every lane and the
                 // key arithmetic (two sqrt and a divide for cosine) would run 16 times per lane -- that made this
                 // variant VALU-bound at half the HBM rate.  REDUCE-SCATTER instead: each of the first four steps
@@ -644,6 +818,9 @@ scan_stream_kernel(ScanParams p) {
                 }
             }
         }
+        if constexpr (S51) {
+            if (lane == 0 && lo_total != 0) atomicAdd(&s51w[0], lo_fetched), atomicAdd(&s51w[1], lo_total);
+        }
         __syncthreads();
 
         if (piece_rows > p.chunk_safe) {  // block-uniform
@@ -702,6 +879,13 @@ scan_stream_kernel(ScanParams p) {
                     kprev[q] = kp;
                     cnt[q] = 0;
                     if (kp == p.k) tau[q] = b[p.k - 1];
+                    if constexpr (S51) {  // a new head of the list: publish it (a plain vector store, device scope)
+                        const uint32_t head = (uint32_t)(b[0] >> 32);
+                        if (head != pub_last) {
+                            __hip_atomic_store(p.pub + blockIdx.x, ((uint64_t)p.pub_seq << 32) | head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            pub_last = head;
+                        }
+                    }
                 }
             }
         }
@@ -722,6 +906,13 @@ scan_stream_kernel(ScanParams p) {
     }
 
     }  // groups
+    if constexpr (S51) {  // (behind the last piece's barriers)
+        if (tid == 0) {
+            uint32_t* st = p.lo_stats + (size_t)blockIdx.x * 4;
+            st[1] = s51w[0], st[2] = s51w[1], st[3] = 0;
+            st[0] = p.pub_seq;
+        }
+    }
     if (p.ts) {  // launch-uniform
         __syncthreads();
         if (tid == 0) atomicMax(reinterpret_cast<unsigned long long*>(p.ts) + 1, (unsigned long long)wall_clock64());
@@ -795,7 +986,9 @@ const void* kernel_g(int G, int nqv, bool redo, bool floor) {
 
 }  // namespace
 
-#if MVF_SCAN_XS == 2
+#if MVF_SCAN_XS == 3
+#define MVF_SCAN_FN2(name, dt) name##dt##z
+#elif MVF_SCAN_XS == 2
 #define MVF_SCAN_FN2(name, dt) name##dt##y
 #elif MVF_SCAN_XS
 #define MVF_SCAN_FN2(name, dt) name##dt##x

@@ -23,11 +23,13 @@
 // A row holding Inf / NaN makes the maxima +inf, as in shadow_i8.hip: the route then leaves such a corpus to the stored rows.
 
 #include "../../include/mvf_gpu.h"
+#include "../../include/mvf_gpu_stream_5p1.h"
 
 #include "internal.h"
 #include "mvf_common.h"
 #include "scan_mfma.h"
 #include "shadow_6b.h"
+#include "shadow_5p1.h"
 
 namespace mvf {
 namespace {
@@ -42,6 +44,9 @@ __device__ __forceinline__ void atomic_max_nonneg6(float* dst, float v) {  // v 
 // One wave per row, lane l taking element 64 u + l of unit u.  rows: Float32 at `pitch`; out: the tiled shadow (shadow_6b.h),
 // xscale6[r] = s_r, stats[0..3] = max s_r(|x6|+|ex|), max s_r|ex|, the same two over |x| -- shadow_i8_kernel's four, from the
 // measured |x6| and |ex|.  Every byte of the rows [0, n) is written (padding elements as the code of zero).
+// P51: the same codes in the 5+1 layout (shadow_5p1.h) -- a lane quantises the elements 128 U + l and 128 U + 64 + l of unit U
+// in the 6-bit kernel's order (the sums behind the bound maxima see the same operands in the same sequence: identical maxima).
+template <bool P51>
 __global__ void __launch_bounds__(256) shadow_6b_kernel(const unsigned char* rows, uint32_t n, uint32_t pitch, uint32_t dim,
                                                          unsigned char* rows6, float* xscale6, float* stats) {
     const uint32_t lane = threadIdx.x & 63;
@@ -65,8 +70,8 @@ __global__ void __launch_bounds__(256) shadow_6b_kernel(const unsigned char* row
         bad = __builtin_amdgcn_ballot_w64(bad) != 0 || !(ss < 3.0e38f);
         const float sr = bad ? 0.f : mx / (float)kS6Max;
         float x2 = 0.f, e2 = 0.f;
-        for (uint32_t u = 0; u < units; u++) {
-            const uint32_t c = u * 64 + lane;
+        // the code of element c (padding: the code of zero); x2 / e2 take its terms
+        auto quantise = [&](uint32_t c) __attribute__((always_inline)) -> uint32_t {
             const float x = c < dim ? rp[c] : 0.f;
             float t = sr > 0.f ? x / sr : 0.f;       // IEEE division: x = sr (t / (1 + eps)), |eps| <= 2^-24
             float q = rintf(t);
@@ -74,12 +79,37 @@ __global__ void __launch_bounds__(256) shadow_6b_kernel(const unsigned char* row
             const float e = t - q;
             x2 = fmaf(q, q, x2);
             e2 = fmaf(e, e, e2);
-            const uint32_t y = (uint32_t)((int)q + kS6Bias);
+            return (uint32_t)((int)q + kS6Bias);
+        };
+        auto word_of = [&](uint32_t byte) __attribute__((always_inline)) -> uint32_t {  // the bytes of lanes l .. l + 3
+            return byte | ((uint32_t)__shfl_down((int)byte, 1, 64) << 8) | ((uint32_t)__shfl_down((int)byte, 2, 64) << 16) |
+                   ((uint32_t)__shfl_down((int)byte, 3, 64) << 24);
+        };
+        if constexpr (P51) {
+            for (uint32_t u = 0; u < s51_units(dim); u++) {
+                const uint32_t y0 = quantise(u * 128 + lane), y1 = quantise(u * 128 + 64 + lane);
+                const uint32_t hi0 = y0 >> 1, hi1 = y1 >> 1, b = lane & 15u, pl = lane >> 4;
+                // the 15 spare bits of byte b of the five planes: hi of the elements 80 + b, 96 + b, 112 + b (lanes 16 + b, 32 + b, 48 + b)
+                const uint32_t sp = (uint32_t)__shfl((int)hi1, 16 + (int)b, 64) | ((uint32_t)__shfl((int)hi1, 32 + (int)b, 64) << 5) |
+                                    ((uint32_t)__shfl((int)hi1, 48 + (int)b, 64) << 10);
+                const uint32_t w = word_of(hi0 | (((sp >> (3u * pl)) & 7u) << 5));     // planes 0..3: element 16 pl + b
+                const uint32_t w4 = word_of(hi1 | (((sp >> 12) & 7u) << 5));            // plane 4 (lanes 0..15): element 64 + b
+                if ((lane & 3u) == 0) *reinterpret_cast<uint32_t*>(rows6 + s51_hi_offset(r, dim, u, pl) + b) = w;
+                if (lane < 16 && (lane & 3u) == 0) *reinterpret_cast<uint32_t*>(rows6 + s51_hi_offset(r, dim, u, 4) + b) = w4;
+                const unsigned long long l0 = __builtin_amdgcn_ballot_w64((y0 & 1u) != 0), l1 = __builtin_amdgcn_ballot_w64((y1 & 1u) != 0);
+#pragma unroll
+                for (uint32_t ph = 0; ph < 2; ph++) {  // lane l makes bit 64 ph + l of the lo plane
+                    const uint32_t B = 64u * ph + lane, d = B >> 5, beta = B & 31u, i = 32u * d + 4u * (beta & 7u) + (beta >> 3);
+                    const unsigned long long bits = __builtin_amdgcn_ballot_w64((((i < 64 ? l0 : l1) >> (i & 63u)) & 1ull) != 0);
+                    if (lane == 0) *reinterpret_cast<unsigned long long*>(rows6 + s51_lo_offset(r, dim, u) + 8u * ph) = bits;
+                }
+            }
+        } else
+        for (uint32_t u = 0; u < units; u++) {
+            const uint32_t y = quantise(u * 64 + lane);
             // lanes 0..47 hold the low six bits of byte (lane & 15) of plane lane / 16; its top two come from lane 48 + (lane & 15)
             const uint32_t yd = (uint32_t)__shfl((int)y, 48 + (int)(lane & 15u), 64);
-            const uint32_t byte = y | (((yd >> (2u * (lane >> 4))) & 3u) << 6);
-            const uint32_t w = byte | ((uint32_t)__shfl_down((int)byte, 1, 64) << 8) | ((uint32_t)__shfl_down((int)byte, 2, 64) << 16) |
-                               ((uint32_t)__shfl_down((int)byte, 3, 64) << 24);
+            const uint32_t w = word_of(y | (((yd >> (2u * (lane >> 4))) & 3u) << 6));
             if (lane < 48 && (lane & 3u) == 0)
                 *reinterpret_cast<uint32_t*>(rows6 + s6_offset(r, dim, u, lane >> 4) + (lane & 15u)) = w;
         }
@@ -113,16 +143,19 @@ __global__ void __launch_bounds__(256) shadow_6b_kernel(const unsigned char* row
 
 }  // namespace
 
-// rows6: s6_bytes(n, dim) bytes; the rows of the last tile behind row n - 1 are zeroed here, in front of the kernel
+// rows6: s6_bytes(n, dim) bytes (p51: s51_bytes(n, dim), the 5+1 layout); the rows of the last tile behind row n - 1 are
+// zeroed here, in front of the kernel
 hipError_t launch_shadow_6b(const unsigned char* rows, uint32_t n, uint32_t pitch, uint32_t dim, unsigned char* rows6, float* xscale6,
-                            float* stats, hipStream_t s) {
+                            float* stats, hipStream_t s, bool p51) {
     if (n == 0) return hipSuccess;
+    const size_t tile = p51 ? s51_tile_bytes(dim) : s6_tile_bytes(dim);
     if (n % kS6TileRows) {
-        hipError_t e = hipMemsetAsync(rows6 + (size_t)(n / kS6TileRows) * s6_tile_bytes(dim), 0, s6_tile_bytes(dim), s);
+        hipError_t e = hipMemsetAsync(rows6 + (size_t)(n / kS6TileRows) * tile, 0, tile, s);
         if (e != hipSuccess) return e;
     }
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3) / 4, 256u * 8u);
-    hipLaunchKernelGGL(shadow_6b_kernel, dim3(blocks), dim3(256), 0, s, rows, n, pitch, dim, rows6, xscale6, stats);
+    if (p51) hipLaunchKernelGGL(shadow_6b_kernel<true>, dim3(blocks), dim3(256), 0, s, rows, n, pitch, dim, rows6, xscale6, stats);
+    else hipLaunchKernelGGL(shadow_6b_kernel<false>, dim3(blocks), dim3(256), 0, s, rows, n, pitch, dim, rows6, xscale6, stats);
     return hipGetLastError();
 }
 
@@ -146,6 +179,25 @@ int mvfgpu_selftest_shadow6_unpack(const uint8_t* shadow, uint64_t shadow_bytes,
     if (!shadow || !out_codes || dimension == 0) return mvf::set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer or empty dimension");
     if (shadow_bytes < mvf::s6_bytes(rows, dimension)) return mvf::set_fail(MVF_ERR_INVALID_ARGUMENT, "fewer bytes than the shadow of these rows");
     for (uint64_t r = 0; r < rows; r++) mvf::s6_unpack_row(shadow, dimension, r, out_codes + r * dimension);
+    return MVF_OK;
+}
+
+uint64_t mvfgpu_selftest_shadow51_bytes(uint64_t rows, uint32_t dimension) { return dimension ? (uint64_t)mvf::s51_bytes(rows, dimension) : 0; }
+
+int mvfgpu_selftest_shadow51_pack(const int8_t* codes, uint64_t rows, uint32_t dimension, uint8_t* out, uint64_t out_bytes) {
+    if (!codes || !out || dimension == 0) return mvf::set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer or empty dimension");
+    if (out_bytes < mvf::s51_bytes(rows, dimension)) return mvf::set_fail(MVF_ERR_INVALID_ARGUMENT, "the output holds fewer bytes than the shadow of these rows");
+    for (uint64_t i = 0; i < rows * (uint64_t)dimension; i++)
+        if (codes[i] < -mvf::kS6Max || codes[i] > mvf::kS6Max) return mvf::set_fail(MVF_ERR_INVALID_ARGUMENT, "a 6-bit code lies in [-31, 31]");
+    memset(out, 0, mvf::s51_bytes(rows, dimension));
+    for (uint64_t r = 0; r < rows; r++) mvf::s51_pack_row(codes + r * dimension, dimension, r, out);
+    return MVF_OK;
+}
+
+int mvfgpu_selftest_shadow51_unpack(const uint8_t* shadow, uint64_t shadow_bytes, uint64_t rows, uint32_t dimension, int8_t* out_codes) {
+    if (!shadow || !out_codes || dimension == 0) return mvf::set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer or empty dimension");
+    if (shadow_bytes < mvf::s51_bytes(rows, dimension)) return mvf::set_fail(MVF_ERR_INVALID_ARGUMENT, "fewer bytes than the shadow of these rows");
+    for (uint64_t r = 0; r < rows; r++) mvf::s51_unpack_row(shadow, dimension, r, out_codes + r * dimension);
     return MVF_OK;
 }
 

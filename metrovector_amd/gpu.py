@@ -162,6 +162,29 @@ def shadow6_bytes(rows: int, dim: int) -> int:
     return int(_lib.gpu().mvfgpu_selftest_shadow6_bytes(rows, dim))
 
 
+def shadow51_bytes(rows: int, dim: int) -> int:
+    """Bytes of the 5+1 layout of the 6-bit shadow of `rows` x `dim` (64-row tiles of 128-element units: csrc/shadow_5p1.h); no
+    GPU needed."""
+    return int(_lib.gpu().mvfgpu_selftest_shadow51_bytes(rows, dim))
+
+
+def shadow51_pack(codes: np.ndarray) -> np.ndarray:
+    """`codes` (rows x dim int8 in [-31, 31]) in the 5+1 layout, as the build kernel packs them; no GPU needed."""
+    codes = np.ascontiguousarray(codes, dtype=np.int8)
+    rows, dim = codes.shape
+    out = np.empty(shadow51_bytes(rows, dim), np.uint8)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_shadow51_pack(codes.ctypes.data, rows, dim, out.ctypes.data, out.size))
+    return out
+
+
+def shadow51_unpack(shadow: np.ndarray, rows: int, dim: int) -> np.ndarray:
+    """The codes (rows x dim int8) held by a shadow in the 5+1 layout; no GPU needed."""
+    shadow = np.ascontiguousarray(shadow, dtype=np.uint8)
+    out = np.empty((rows, dim), np.int8)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_shadow51_unpack(shadow.ctypes.data, shadow.size, rows, dim, out.ctypes.data))
+    return out
+
+
 def shadow6_pack(codes: np.ndarray) -> np.ndarray:
     """`codes` (rows x dim int8 in [-31, 31]) in the 6-bit shadow's layout, as the build kernel packs them; no GPU needed."""
     codes = np.ascontiguousarray(codes, dtype=np.int8)
@@ -1046,6 +1069,13 @@ class GpuCorpus:
         t = _lib.Timing()
         _lib.gpu_check(_lib.gpu().mvfgpu_last_timing(self._h, C.byref(t)))
         return t
+
+    def stream_lo_lines(self):
+        """(fetched, total) 128-byte lines of the low-bit planes the newest one-query search over the 6-bit shadow requested / held
+        in the rows it scanned; (0, 0) where it read the 6-bit layout -- `mvfgpu_debug_stream_lo_lines`."""
+        f, t = C.c_uint64(0), C.c_uint64(0)
+        _lib.gpu_check(_lib.gpu().mvfgpu_debug_stream_lo_lines(self._h, C.byref(f), C.byref(t)))
+        return int(f.value), int(t.value)
 
     def set_scan_path(self, path: int) -> None:
         _lib.gpu_check(_lib.gpu().mvfgpu_set_scan_path(self._h, path))
