@@ -74,6 +74,17 @@ pub struct MvfGpuPartitionInfo {
     pub host_bytes: u64,
 }
 
+/// `mvfgpu_write_report` (include/mvf_gpu_update.h, "row writes"): what a write enqueued and refreshed.
+#[repr(C)]
+pub struct MvfGpuWriteReport {
+    pub struct_size: u32,
+    pub launches: u32,
+    pub rows_written: u64,
+    pub bytes_written: u64,
+    pub refreshed: u32, // bit 0 norms, 1 scaled-f16 shadow, 2 int8 shadow, 3 6-bit shadow
+    pub reserved: u32,
+}
+
 #[link(name = "mvf_gpu")]
 extern "C" {
     fn mvfgpu_corpus_create(rows: *const c_void, n: u64, dimension: u32, data_type: u8, stride_bytes: u64,
@@ -85,6 +96,13 @@ extern "C" {
     fn mvfgpu_search_fetch(corpus: *const MvfGpuCorpus, metric: u8, queries: *const c_void, query_dtype: u8,
                            query_dim: u32, nq: u32, k: u32, out_scores: *mut f32, out_indices: *mut u64,
                            out_raw: *mut i32, out_vectors: *mut c_void) -> c_int;
+    /// Row writes (include/mvf_gpu_update.h, DESIGN.md section 3 "Row writes"): `count` rows of the stored type, `stride_bytes`
+    /// apart, into `indices` (positions, or vector ids where attached; the device call: HOST positions, rows in device memory).
+    /// A row named twice is refused; `out_report` is nullable.
+    fn mvfgpu_corpus_write_rows(corpus: *mut MvfGpuCorpus, indices: *const u64, count: u64, rows: *const c_void,
+                                stride_bytes: u64, out_report: *mut MvfGpuWriteReport) -> c_int;
+    fn mvfgpu_corpus_write_rows_device(corpus: *mut MvfGpuCorpus, positions: *const u64, count: u64, d_rows: *const c_void,
+                                       stride_bytes: u64, hip_stream: *mut c_void, out_report: *mut MvfGpuWriteReport) -> c_int;
     /// Every row within a radius of each query (include/mvf_gpu.h): exact counts, the best `max_per_query` entries.
     fn mvfgpu_search_radius(corpus: *const MvfGpuCorpus, metric: u8, queries: *const c_void, query_dtype: u8,
                             query_dim: u32, nq: u32, radii: *const f32, max_per_query: u64, out_counts: *mut u64,

@@ -38,6 +38,7 @@
 #include "mvf_gpu.h"
 #include "mvf_gpu_maxsim_route.h"
 #include "mvf_gpu_mmr.h"
+#include "mvf_gpu_update.h"
 #include "mvf_status.h"
 
 namespace mvf {
@@ -331,6 +332,28 @@ public:
     GpuVectorSpace& operator=(const GpuVectorSpace&) = delete;
     ~GpuVectorSpace() {
         if (c_) mvfgpu_corpus_destroy(c_);
+    }
+    // Row writes (mvfgpu_corpus_write_rows, mvf_gpu_update.h; DESIGN.md section 3, "Row writes"): rows.size() / (dimension x
+    // element size) rows of the space's STORED type, back to back, into `indices` -- global positions, or vector ids when the
+    // space carries them; a row named twice is refused.  Every later search answers as a space uploaded from the changed rows
+    // would; the file behind the space is not changed.  With spare rows kept deleted this is the fixed-capacity upsert: write
+    // into a free slot, then clear its bit (mvfgpu_corpus_set_tombstones on raw()).
+    mvfgpu_write_report write_rows(const std::vector<uint64_t>& indices, const std::vector<uint8_t>& rows) {
+        const size_t es = dt_ == DataType::Float32 ? 4 : dt_ == DataType::Float16 ? 2 : 1, row_bytes = (size_t)dim_ * es;
+        if (rows.size() != indices.size() * row_bytes)
+            throw MvfError(MVF_ERR_INVALID_ARGUMENT, "write_rows takes " + std::to_string(row_bytes) + " bytes per index, got " +
+                                                         std::to_string(rows.size()) + " for " + std::to_string(indices.size()));
+        mvfgpu_write_report rep{};
+        rep.struct_size = sizeof rep;
+        detail::check_gpu(mvfgpu_corpus_write_rows(c_, indices.empty() ? nullptr : indices.data(), indices.size(),
+                                                   rows.empty() ? nullptr : rows.data(), row_bytes, &rep));
+        return rep;
+    }
+    // a Float32 space's rows as floats
+    mvfgpu_write_report write_rows(const std::vector<uint64_t>& indices, const std::vector<float>& rows) {
+        if (dt_ != DataType::Float32) throw MvfError(MVF_ERR_BUILD, "write_rows(float) writes Float32 spaces: pass the stored bytes");
+        const uint8_t* b = reinterpret_cast<const uint8_t*>(rows.data());
+        return write_rows(indices, std::vector<uint8_t>(b, b + rows.size() * 4));
     }
     // examples/similarity_search.rs:140-176 with the metric the space declares; DimensionMismatch for a query of another
     // length (the reference's zip would truncate silently); the payload of every hit is fetched from HBM

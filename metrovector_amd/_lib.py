@@ -51,6 +51,11 @@ class PartitionInfo(_OutStruct):
                 ("host_bytes", C.c_uint64)]
 
 
+class WriteReport(_OutStruct):  # include/mvf_gpu_update.h mvfgpu_write_report
+    _fields_ = [("struct_size", C.c_uint32), ("launches", C.c_uint32), ("rows_written", C.c_uint64), ("bytes_written", C.c_uint64),
+                ("refreshed", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Predicate(C.Structure):
     """mvfgpu_predicate: one clause of mvfgpu_filter_create_where."""
     _fields_ = [("column", C.c_void_p), ("op", C.c_uint32), ("n_values", C.c_uint32), ("a", C.c_uint64), ("b", C.c_uint64),
@@ -181,6 +186,10 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_mmr_walk.restype = C.c_int
     lib.mvfgpu_selftest_mmr_stage_ms.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_mmr_stage_ms.restype = C.c_int
+    lib.mvfgpu_corpus_write_rows.argtypes = [vp, vp, u64, vp, u64, C.POINTER(WriteReport)]
+    lib.mvfgpu_corpus_write_rows.restype = C.c_int
+    lib.mvfgpu_corpus_write_rows_device.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(WriteReport)]
+    lib.mvfgpu_corpus_write_rows_device.restype = C.c_int
     lib.mvfgpu_knn_join.argtypes = [vp, vp, u8, u64, u64, u32, u32, vp, vp, vp]
     lib.mvfgpu_knn_join.restype = C.c_int
     lib.mvfgpu_knn_join_device.argtypes = [vp, vp, u8, u64, u64, u32, u32, vp, vp, vp, vp]

@@ -9,6 +9,7 @@
 #include "../../include/mvf_gpu_maxsim_route.h"
 
 #include "aux_kernels.h"
+#include "host_staging.h"
 #include "internal.h"
 #include "scan_candidates.h"
 #include "scan_filter.h"
@@ -282,6 +283,7 @@ struct mvfgpu_corpus {
     mutable hipStream_t last_stream = nullptr;
     mutable bool has_done = false;
     mutable uint32_t search_launches = 0;  // kernel launches of the newest search (mvfgpu_timing::search_launches; SearchCall counts them)
+    mutable mvf::PinnedUpload write_up;    // the positions of a device row write on their way to the device (update.hip)
 
     bool profiling = false;
     int scan_path = 0;
@@ -2369,6 +2371,43 @@ int corpus_wait_newest(const mvfgpu_corpus* c) {
     if (c->has_done) MVF_HIP_TRY(hipEventSynchronize(c->ev_done[c->done_idx]));
     return MVF_OK;
 }
+WriteTargets corpus_write_targets(const mvfgpu_corpus* c) {
+    WriteTargets t;
+    t.rows = c->d_rows;
+    t.n = c->n, t.index_base = c->index_base;
+    t.dim = c->dim, t.pitch = c->pitch, t.dtype = c->dtype;
+    if (c->xnorm_ready) {
+        float* xn = static_cast<float*>(c->xnorm.p);
+        t.norms = xn;
+        t.xx2 = xn + norm_stride(c->n);
+        t.xxmax = xn + norm_max_at(c->n);
+    }
+    if (c->shadow_state == 1) {
+        t.shadow16 = static_cast<unsigned char*>(c->shadow.p);
+        t.pitch16 = shadow_pitch(c->dim);
+        t.xscale = static_cast<float*>(c->xscale.p);
+    }
+    if (c->shadow8_state == 1 || c->shadow8_state == 2) {
+        t.shadow8 = static_cast<unsigned char*>(c->shadow8.p);
+        t.pitch8 = shadow8_pitch(c->dim);
+        t.shadow8_rows = c->shadow8_state == 1 ? c->n : c->shadow8_rows;
+        t.xscale8 = static_cast<float*>(c->xscale8.p);
+        t.qs_stats = static_cast<float*>(c->qs_stats.p);
+    }
+    if (c->shadow6_state == 1) {
+        t.shadow6 = static_cast<unsigned char*>(c->shadow6.p);
+        t.shadow6_p51 = c->shadow6_p51;
+        t.xscale6 = static_cast<float*>(c->xscale6.p);
+        t.qs6_stats = static_cast<float*>(c->qs6_stats.p);
+    }
+    return t;
+}
+void corpus_rows_written(const mvfgpu_corpus* c, uint32_t refreshed) {
+    // a written Inf / NaN row has made the maxima +inf on the device: the next search that asks reads them again
+    if (refreshed & 4u) c->shadow8_finite = -1;
+    if (refreshed & 8u) c->shadow6_finite = -1;
+}
+PinnedUpload& corpus_write_upload(const mvfgpu_corpus* c) { return c->write_up; }
 int check_search_scalars(uint8_t metric, uint32_t nq, uint32_t k, const void* queries, const void* out_scores, const void* out_indices) {
     if (const int mrc = check_metric(metric)) return mrc;
     if (nq == 0) return fail(MVF_ERR_INVALID_ARGUMENT, "nq must be > 0");
@@ -2539,6 +2578,7 @@ void mvfgpu_corpus_destroy(mvfgpu_corpus* c) {
         c->pin_vec.release();
         c->prof_ts.release();
         c->h_v.release();
+        c->write_up.release();
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
         if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
         for (auto e : c->ev_done)
@@ -2583,6 +2623,7 @@ int mvfgpu_corpus_read_rows(const mvfgpu_corpus* c, uint64_t first, uint64_t cou
     }
     if (count == 0) return MVF_OK;
     DevScope guard(c->device);
+    if (const int rc = corpus_wait_newest(c)) return rc;  // a row write may be the handle's newest work (update.hip)
     const uint64_t row_bytes = (uint64_t)c->dim * elem_size(c->dtype);
     MVF_HIP_TRY(hipMemcpy2D(out_rows, row_bytes, c->d_rows + first * c->pitch, c->pitch, row_bytes, count,
                         hipMemcpyDeviceToHost));

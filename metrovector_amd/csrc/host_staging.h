@@ -110,4 +110,43 @@ int stage_host_windows(const mvfgpu_corpus* c, hipStream_t s, uint32_t nq, const
 
 inline void stage_as_given(uint32_t, uint32_t, const void**) {}  // the `prepare` of a call whose inputs are staged as they are
 
+// A small host array of a DEVICE call (the positions of a row write) on its way to the device without a wait for it: through a
+// pinned buffer the handle keeps, so that the caller's array is free again when the call returns.  upload() waits only for the
+// previous upload to have left the buffer.  The caller holds the handle's lock (corpus_device_call) and has set the device.
+struct PinnedUpload {
+    void* pin = nullptr;
+    size_t bytes = 0;
+    hipEvent_t copied = nullptr;
+    bool busy = false;
+    // room for `need` bytes, the previous upload out of it: fill it, then send()
+    int reserve(size_t need, void** out) {
+        if (busy) {
+            MVF_HIP_TRY(hipEventSynchronize(copied));
+            busy = false;
+        }
+        if (!copied) MVF_HIP_TRY(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+        if (bytes < need) {
+            if (pin) (void)hipHostFree(pin);
+            pin = nullptr, bytes = 0;
+            const size_t want = std::max<size_t>(need, 16u << 10);
+            MVF_HIP_TRY(hipHostMalloc(&pin, want, hipHostMallocDefault));
+            poison_fill_host(pin, want);
+            bytes = want;
+        }
+        *out = pin;
+        return MVF_OK;
+    }
+    int send(void* dst, size_t n, hipStream_t s) {
+        MVF_HIP_TRY(hipMemcpyAsync(dst, pin, n, hipMemcpyHostToDevice, s));
+        MVF_HIP_TRY(hipEventRecord(copied, s));
+        busy = true;
+        return MVF_OK;
+    }
+    void release() {
+        if (pin) (void)hipHostFree(pin);
+        if (copied) (void)hipEventDestroy(copied);
+        pin = nullptr, bytes = 0, copied = nullptr, busy = false;
+    }
+};
+
 }  // namespace mvf

@@ -155,9 +155,10 @@ struct Tuning {
 };
 Tuning read_tuning();
 
-// What the radius and candidate searches (radius.hip, candidates.hip) read of a handle: the resident rows and their masks,
-// fixed for the handle's life (set_tombstones / set_vector_ids must not race with searches), and the stream of the
-// host-buffer calls.
+// What the radius and candidate searches (radius.hip, candidates.hip) read of a handle: the resident rows and their masks
+// (set_tombstones / set_vector_ids must not race with searches), and the stream of the host-buffer calls.  The row ARRAY and
+// its shape are fixed for the handle's life; the rows' bytes change only through a row write (update.hip), which is ordered
+// like a search: a call that reads the view under corpus_device_call sees every write enqueued before it and none after it.
 struct CorpusView {
     int device = 0, num_cus = 256, k1_g = 0;
     uint64_t n = 0, index_base = 0;
@@ -290,5 +291,34 @@ int partition_upload(const mvfgpu_partition* part, const void* src, size_t bytes
 void partition_find(const mvfgpu_partition* part, uint64_t key, uint64_t* offset, uint64_t* count, uint64_t* from = nullptr);
 // waits for the newest work enqueued on the handle
 int corpus_wait_newest(const mvfgpu_corpus* c);
+
+// ---- row writes (update.hip; DESIGN.md §3 "Row writes")
+// Everything a handle derives from its rows' bytes, as it is RESIDENT now: a NULL array has not been built (or does not exist
+// for the space) and stays so.  Read under corpus_device_call.
+struct WriteTargets {
+    unsigned char* rows = nullptr;
+    uint64_t n = 0, index_base = 0;
+    uint32_t dim = 0, pitch = 0;
+    uint8_t dtype = 0;
+    void* norms = nullptr;  // launch_row_norms_f32's / launch_row_norms16's `out`; xx2 and xxmax behind it as they take them
+    float *xx2 = nullptr, *xxmax = nullptr;
+    unsigned char* shadow16 = nullptr;  // the scaled-f16 shadow, its pitch and scales
+    uint32_t pitch16 = 0;
+    float* xscale = nullptr;
+    unsigned char* shadow8 = nullptr;  // the int8 shadow of the rows [0, shadow8_rows), its pitch, scales and bound maxima
+    uint32_t pitch8 = 0;
+    uint64_t shadow8_rows = 0;
+    float *xscale8 = nullptr, *qs_stats = nullptr;
+    unsigned char* shadow6 = nullptr;  // the 6-bit shadow (shadow6_p51: in the 5+1 layout), its scales and bound maxima
+    bool shadow6_p51 = false;
+    float *xscale6 = nullptr, *qs6_stats = nullptr;
+};
+WriteTargets corpus_write_targets(const mvfgpu_corpus* c);
+// A write refreshed these items (mvfgpu_write_report::refreshed): the cached read-backs of a refreshed shadow's bound maxima go
+// back to "not read".  Under corpus_device_call, behind the launches.
+void corpus_rows_written(const mvfgpu_corpus* c, uint32_t refreshed);
+// the handle's pinned buffer for the positions of a device write (host_staging.h)
+struct PinnedUpload;
+PinnedUpload& corpus_write_upload(const mvfgpu_corpus* c);
 
 }  // namespace mvf

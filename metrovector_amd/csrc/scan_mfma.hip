@@ -34,6 +34,7 @@
 #include "k1_rowscore.h"
 #include "mvf_common.h"
 #include "repair_flags.h"
+#include "row_builders.h"
 #include "scan_mfma16_key.h"
 
 #include <hip/hip_fp16.h>
@@ -356,30 +357,14 @@ __global__ void prep_queries_kernel(const float* q, uint32_t nq, uint32_t nq_pad
     }
 }
 
-// ---- K4: row norms sqrt(sum x^2), one wave per row (f32 rows) ---------------------
+// ---- K4: row norms sqrt(sum x^2), one wave per row (f32 rows; the body: row_builders.h) ---------------------
 __global__ void __launch_bounds__(256) row_norms_f32_kernel(const unsigned char* rows, uint32_t n, uint32_t pitch,
                                                              uint32_t V, float* xnorm, float* xx2, float* xxmax) {
     float mx = 0.f;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = (gridDim.x * 256u) >> 6;
-    for (uint32_t r = wave; r < n; r += nwaves) {
-        const unsigned char* rp = rows + (size_t)r * pitch;
-        float s = 0.f;
-        for (uint32_t v = lane; v < V; v += 64) {
-            const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(rp + (size_t)v * 16));
-            s = fmaf(x[0], x[0], s);
-            s = fmaf(x[1], x[1], s);
-            s = fmaf(x[2], x[2], s);
-            s = fmaf(x[3], x[3], s);
-        }
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if (lane == 0) {
-            xnorm[r] = sqrtf(s);
-            xx2[r] = s;
-            if (s > mx) mx = s;  // NaN never wins: the margin uses finite rows only
-        }
-    }
-    if (lane == 0 && mx > 0.f) atomicMax(reinterpret_cast<unsigned int*>(xxmax), __float_as_uint(mx));  // non-negative floats order as uints
+    for (uint32_t r = wave; r < n; r += nwaves) norms_f32_row(rows, pitch, V, r, lane, xnorm, xx2, mx);
+    fold_norm_max(xxmax, lane, mx);
 }
 
 // ---- candidate hand-off: per-block regions -> per-query lists ---------------------------------------------------

@@ -5,6 +5,7 @@
 #include "scan_mfma.h"
 
 #include "mvf_common.h"
+#include "row_builders.h"
 
 #include <hip/hip_fp16.h>
 
@@ -107,33 +108,14 @@ __global__ void prep_queries_u8_kernel(const uint8_t* q, uint32_t nq, uint32_t n
     }
 }
 
-// ---- K4 for the narrow types: one wave per row ----------------------------------------------
+// ---- K4 for the narrow types: one wave per row (the bodies, and the shadow row's: row_builders.h) ---------------
 __global__ void __launch_bounds__(256) row_norms_f16_kernel(const unsigned char* rows, uint32_t n, uint32_t pitch,
                                                              uint32_t V, float* xnorm, float* xx2, float* xxmax) {
     float mx = 0.f;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = (gridDim.x * 256u) >> 6;
-    for (uint32_t r = wave; r < n; r += nwaves) {
-        const unsigned char* rp = rows + (size_t)r * pitch;
-        float s = 0.f;
-        for (uint32_t v = lane; v < V; v += 64) {
-            const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rp + (size_t)v * 16));
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                const float a = __half2float(__ushort_as_half((unsigned short)(x[w] & 0xFFFFu)));
-                const float b2 = __half2float(__ushort_as_half((unsigned short)(x[w] >> 16)));
-                s = fmaf(a, a, s);
-                s = fmaf(b2, b2, s);
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if (lane == 0) {
-            xnorm[r] = sqrtf(s);
-            xx2[r] = s;
-            if (s > mx) mx = s;
-        }
-    }
-    if (lane == 0 && mx > 0.f) atomicMax(reinterpret_cast<unsigned int*>(xxmax), __float_as_uint(mx));
+    for (uint32_t r = wave; r < n; r += nwaves) norms_f16_row(rows, pitch, V, r, lane, xnorm, xx2, mx);
+    fold_norm_max(xxmax, lane, mx);
 }
 
 // Scaled-f16 SHADOW of a Float32 corpus, used for selection only (api.hip): row r is multiplied by 2^s_r with
@@ -145,58 +127,14 @@ __global__ void __launch_bounds__(256) shadow_f16_kernel(const unsigned char* ro
                                                           float* xscale) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = (gridDim.x * 256u) >> 6;
-    const uint32_t V32 = pitch32 / 16, V16 = pitch16 / 16;
-    for (uint32_t r = wave; r < n; r += nwaves) {
-        const unsigned char* rp = rows32 + (size_t)r * pitch32;
-        float mx = 0.f;
-        for (uint32_t v = lane; v < V32; v += 64) {
-            const u32x4 x = *reinterpret_cast<const u32x4*>(rp + (size_t)v * 16);
-#pragma unroll
-            for (int w = 0; w < 4; w++) mx = fmaxf(mx, fabsf(__uint_as_float(x[w])));
-        }
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        int sh = 0;
-        if (mx > 0.f && mx < 3.0e38f) {
-            int ex;
-            (void)frexpf(mx, &ex);  // mx = m * 2^ex, m in [0.5, 1)
-            sh = 15 - ex;
-        }
-        unsigned char* op = rows16 + (size_t)r * pitch16;
-        for (uint32_t v = lane; v < V16; v += 64) {  // one 16-B f16 vector = two f32 vectors
-            u32x4 o;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const uint32_t v32 = 2 * v + h;
-                u32x4 x = u32x4{0, 0, 0, 0};
-                if (v32 < V32) x = *reinterpret_cast<const u32x4*>(rp + (size_t)v32 * 16);  // f32 padding is zero
-#pragma unroll
-                for (int w = 0; w < 2; w++) {
-                    const unsigned short lo = __half_as_ushort(__float2half_rn(ldexpf(__uint_as_float(x[2 * w]), sh)));
-                    const unsigned short hi = __half_as_ushort(__float2half_rn(ldexpf(__uint_as_float(x[2 * w + 1]), sh)));
-                    o[2 * h + w] = (uint32_t)lo | ((uint32_t)hi << 16);
-                }
-            }
-            *reinterpret_cast<u32x4*>(op + (size_t)v * 16) = o;
-        }
-        if (lane == 0) xscale[r] = ldexpf(1.0f, -sh);
-    }
+    for (uint32_t r = wave; r < n; r += nwaves) shadow_f16_row(rows32, pitch32, rows16, pitch16, xscale, r, lane);
 }
 
 __global__ void __launch_bounds__(256) row_norms_i8_kernel(const unsigned char* rows, uint32_t n, uint32_t pitch,
                                                             uint32_t V, int32_t* xx) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = (gridDim.x * 256u) >> 6;
-    for (uint32_t r = wave; r < n; r += nwaves) {
-        const unsigned char* rp = rows + (size_t)r * pitch;
-        int s = 0;
-        for (uint32_t v = lane; v < V; v += 64) {
-            const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rp + (size_t)v * 16));
-#pragma unroll
-            for (int w = 0; w < 4; w++) s = __builtin_amdgcn_sdot4((int)x[w], (int)x[w], s, false);
-        }
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if (lane == 0) xx[r] = s;
-    }
+    for (uint32_t r = wave; r < n; r += nwaves) norms_i8_row(rows, pitch, V, r, lane, xx);
 }
 
 // UInt8 rows: xx[r] = sum (x-128)^2, xbias[r] = 128 * sum (x-128), over the row's REAL elements
@@ -204,30 +142,7 @@ __global__ void __launch_bounds__(256) row_norms_u8_kernel(const unsigned char* 
                                                             uint32_t V, uint32_t dim, int32_t* xx, int32_t* xbias) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = (gridDim.x * 256u) >> 6;
-    for (uint32_t r = wave; r < n; r += nwaves) {
-        const unsigned char* rp = rows + (size_t)r * pitch;
-        int s2 = 0, s1 = 0;
-        for (uint32_t v = lane; v < V; v += 64) {
-            const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rp + (size_t)v * 16));
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                // bytes past `dim` inside the last vector are zero padding: keep them 0 in the signed domain too
-                const uint32_t e0 = v * 16 + w * 4;
-                uint32_t mask = e0 + 4 <= dim ? 0xFFFFFFFFu : e0 >= dim ? 0u : (0xFFFFFFFFu >> (8 * (4 - (dim - e0))));
-                const uint32_t xs = (x[w] ^ 0x80808080u) & mask;
-                s2 = __builtin_amdgcn_sdot4((int)xs, (int)xs, s2, false);
-                s1 = __builtin_amdgcn_sdot4((int)xs, 0x01010101, s1, false);
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            s2 += __shfl_xor(s2, off, 64);
-            s1 += __shfl_xor(s1, off, 64);
-        }
-        if (lane == 0) {
-            xx[r] = s2;
-            xbias[r] = 128 * s1;
-        }
-    }
+    for (uint32_t r = wave; r < n; r += nwaves) norms_u8_row(rows, pitch, V, dim, r, lane, xx, xbias);
 }
 
 }  // namespace

@@ -27,6 +27,7 @@
 
 #include "internal.h"
 #include "mvf_common.h"
+#include "row_builders.h"
 #include "scan_mfma.h"
 #include "shadow_6b.h"
 #include "shadow_5p1.h"
@@ -34,111 +35,20 @@
 namespace mvf {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void atomic_max_nonneg6(float* dst, float v) {  // v >= 0 or +inf; NaN -> +inf
-    if (!(v == v)) v = __uint_as_float(0x7F800000u);
-    atomicMax(reinterpret_cast<unsigned int*>(dst), __float_as_uint(v));
-}
-
 // One wave per row, lane l taking element 64 u + l of unit u.  rows: Float32 at `pitch`; out: the tiled shadow (shadow_6b.h),
 // xscale6[r] = s_r, stats[0..3] = max s_r(|x6|+|ex|), max s_r|ex|, the same two over |x| -- shadow_i8_kernel's four, from the
 // measured |x6| and |ex|.  Every byte of the rows [0, n) is written (padding elements as the code of zero).
 // P51: the same codes in the 5+1 layout (shadow_5p1.h) -- a lane quantises the elements 128 U + l and 128 U + 64 + l of unit U
 // in the 6-bit kernel's order (the sums behind the bound maxima see the same operands in the same sequence: identical maxima).
+// The row's body is row_builders.h's shadow_6b_row, shared with the list-driven refresh of a row write (scan_update.hip).
 template <bool P51>
 __global__ void __launch_bounds__(256) shadow_6b_kernel(const unsigned char* rows, uint32_t n, uint32_t pitch, uint32_t dim,
                                                          unsigned char* rows6, float* xscale6, float* stats) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = (gridDim.x * 256u) >> 6;
-    const uint32_t units = s6_units(dim);
-    float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
-    for (uint32_t r = wave; r < n; r += nwaves) {
-        const float* rp = reinterpret_cast<const float*>(rows + (size_t)r * pitch);
-        float mx = 0.f, ss = 0.f;
-        bool bad = false;
-        for (uint32_t c = lane; c < dim; c += 64) {
-            const float v = rp[c];
-            bad |= !(fabsf(v) < 3.0e38f);
-            mx = fmaxf(mx, fabsf(v));
-            ss = fmaf(v, v, ss);
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-            ss += __shfl_xor(ss, off, 64);
-        }
-        bad = __builtin_amdgcn_ballot_w64(bad) != 0 || !(ss < 3.0e38f);
-        const float sr = bad ? 0.f : mx / (float)kS6Max;
-        float x2 = 0.f, e2 = 0.f;
-        // the code of element c (padding: the code of zero); x2 / e2 take its terms
-        auto quantise = [&](uint32_t c) __attribute__((always_inline)) -> uint32_t {
-            const float x = c < dim ? rp[c] : 0.f;
-            float t = sr > 0.f ? x / sr : 0.f;       // IEEE division: x = sr (t / (1 + eps)), |eps| <= 2^-24
-            float q = rintf(t);
-            q = fminf(fmaxf(q, -(float)kS6Max), (float)kS6Max);  // |t| <= 31 (1 + 2^-23): the clamp never bites beyond rounding
-            const float e = t - q;
-            x2 = fmaf(q, q, x2);
-            e2 = fmaf(e, e, e2);
-            return (uint32_t)((int)q + kS6Bias);
-        };
-        auto word_of = [&](uint32_t byte) __attribute__((always_inline)) -> uint32_t {  // the bytes of lanes l .. l + 3
-            return byte | ((uint32_t)__shfl_down((int)byte, 1, 64) << 8) | ((uint32_t)__shfl_down((int)byte, 2, 64) << 16) |
-                   ((uint32_t)__shfl_down((int)byte, 3, 64) << 24);
-        };
-        if constexpr (P51) {
-            for (uint32_t u = 0; u < s51_units(dim); u++) {
-                const uint32_t y0 = quantise(u * 128 + lane), y1 = quantise(u * 128 + 64 + lane);
-                const uint32_t hi0 = y0 >> 1, hi1 = y1 >> 1, b = lane & 15u, pl = lane >> 4;
-                // the 15 spare bits of byte b of the five planes: hi of the elements 80 + b, 96 + b, 112 + b (lanes 16 + b, 32 + b, 48 + b)
-                const uint32_t sp = (uint32_t)__shfl((int)hi1, 16 + (int)b, 64) | ((uint32_t)__shfl((int)hi1, 32 + (int)b, 64) << 5) |
-                                    ((uint32_t)__shfl((int)hi1, 48 + (int)b, 64) << 10);
-                const uint32_t w = word_of(hi0 | (((sp >> (3u * pl)) & 7u) << 5));     // planes 0..3: element 16 pl + b
-                const uint32_t w4 = word_of(hi1 | (((sp >> 12) & 7u) << 5));            // plane 4 (lanes 0..15): element 64 + b
-                if ((lane & 3u) == 0) *reinterpret_cast<uint32_t*>(rows6 + s51_hi_offset(r, dim, u, pl) + b) = w;
-                if (lane < 16 && (lane & 3u) == 0) *reinterpret_cast<uint32_t*>(rows6 + s51_hi_offset(r, dim, u, 4) + b) = w4;
-                const unsigned long long l0 = __builtin_amdgcn_ballot_w64((y0 & 1u) != 0), l1 = __builtin_amdgcn_ballot_w64((y1 & 1u) != 0);
-#pragma unroll
-                for (uint32_t ph = 0; ph < 2; ph++) {  // lane l makes bit 64 ph + l of the lo plane
-                    const uint32_t B = 64u * ph + lane, d = B >> 5, beta = B & 31u, i = 32u * d + 4u * (beta & 7u) + (beta >> 3);
-                    const unsigned long long bits = __builtin_amdgcn_ballot_w64((((i < 64 ? l0 : l1) >> (i & 63u)) & 1ull) != 0);
-                    if (lane == 0) *reinterpret_cast<unsigned long long*>(rows6 + s51_lo_offset(r, dim, u) + 8u * ph) = bits;
-                }
-            }
-        } else
-        for (uint32_t u = 0; u < units; u++) {
-            const uint32_t y = quantise(u * 64 + lane);
-            // lanes 0..47 hold the low six bits of byte (lane & 15) of plane lane / 16; its top two come from lane 48 + (lane & 15)
-            const uint32_t yd = (uint32_t)__shfl((int)y, 48 + (int)(lane & 15u), 64);
-            const uint32_t w = word_of(y | (((yd >> (2u * (lane >> 4))) & 3u) << 6));
-            if (lane < 48 && (lane & 3u) == 0)
-                *reinterpret_cast<uint32_t*>(rows6 + s6_offset(r, dim, u, lane >> 4) + (lane & 15u)) = w;
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            x2 += __shfl_xor(x2, off, 64);
-            e2 += __shfl_xor(e2, off, 64);
-        }
-        if (lane == 0) {
-            xscale6[r] = sr;
-            const float inf = __uint_as_float(0x7F800000u);
-            // measured norms, inflated for the f32 sums above and the (1 + eps) of the division
-            const float ex = sqrtf(e2) * 1.0005f + 1e-3f, xa = sqrtf(x2) * 1.0005f + ex;
-            const float a = bad ? inf : sr * xa, b = bad ? inf : sr * ex;
-            const float xn = sqrtf(ss);
-            m0 = fmaxf(m0, a);
-            m1 = fmaxf(m1, b);
-            if (bad) m2 = m3 = inf;
-            else if (xn > 0.f) {
-                m2 = fmaxf(m2, a / xn * 1.000001f);
-                m3 = fmaxf(m3, b / xn * 1.000001f);
-            }
-        }
-    }
-    if (lane == 0) {
-        atomic_max_nonneg6(stats + 0, m0);
-        atomic_max_nonneg6(stats + 1, m1);
-        atomic_max_nonneg6(stats + 2, m2);
-        atomic_max_nonneg6(stats + 3, m3);
-    }
+    ShadowMaxima m;
+    for (uint32_t r = wave; r < n; r += nwaves) shadow_6b_row<P51>(rows, pitch, dim, rows6, xscale6, r, lane, m);
+    fold_shadow_maxima(stats, lane, m);
 }
 
 }  // namespace

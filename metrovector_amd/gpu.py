@@ -499,6 +499,10 @@ def _pack_clauses(clauses) -> tuple[C.Array, list]:
     return arr, keep
 
 
+def _write_report(rep: "_lib.WriteReport") -> dict:
+    return {"launches": rep.launches, "rows_written": rep.rows_written, "bytes_written": rep.bytes_written, "refreshed": rep.refreshed}
+
+
 class GpuCorpus:
     """One shard of a vector space, resident in HBM on one MI355X."""
 
@@ -616,6 +620,40 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_corpus_gather_rows(self._h, idx.ctypes.data_as(C.c_void_p), idx.size,
                                                             out.ctypes.data_as(C.c_void_p)))
         return out
+
+    # ---- row writes (include/mvf_gpu_update.h) ---------------------------------------
+    def write_rows(self, indices, rows: np.ndarray) -> dict:
+        """New bytes into row positions (`mvfgpu_corpus_write_rows`; DESIGN.md §3 "Row writes"): `rows` [m, dimension] of the
+        stored dtype go to `indices` [m] -- global positions, or vector ids where ids are attached --, every derived array
+        that is resident (norms, shadows) is refreshed for exactly those rows, and the call returns when the write is
+        complete.  A row named twice is refused.  Returns the report: launches, rows_written, bytes_written, refreshed
+        (bit 0 norms, 1 f16 shadow, 2 int8 shadow, 3 6-bit shadow)."""
+        _, dim, dt = self._fixed()
+        rows = np.asarray(rows)
+        if rows.dtype != _NP_OF[dt]:
+            raise InvalidArgument(f"rows must have the space's stored dtype {np.dtype(_NP_OF[dt]).name}, got {rows.dtype.name}")
+        idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), np.uint64)
+        if rows.ndim != 2 or rows.shape != (idx.size, dim):
+            raise InvalidArgument(f"rows must be [{idx.size}, {dim}] (one row per index), got shape {rows.shape}")
+        if rows.shape[0] and rows.strides[1] != rows.itemsize:
+            rows = np.ascontiguousarray(rows)
+        stride = rows.strides[0] if rows.shape[0] > 1 else dim * rows.itemsize
+        if stride < dim * rows.itemsize:  # a broadcast or reversed view
+            rows = np.ascontiguousarray(rows)
+            stride = dim * rows.itemsize
+        rep = _lib.WriteReport()
+        _lib.gpu_check(_lib.gpu().mvfgpu_corpus_write_rows(self._h, idx.ctypes.data_as(C.c_void_p) if idx.size else None, idx.size,
+                                                           rows.ctypes.data_as(C.c_void_p) if idx.size else None, stride, C.byref(rep)))
+        return _write_report(rep)
+
+    def write_rows_device(self, positions, d_rows: int, stride_bytes: int, stream: int = 0) -> dict:
+        """Device-pointer row write (`mvfgpu_corpus_write_rows_device`), asynchronous on `stream`: `positions` [m] are GLOBAL
+        positions in host memory (never ids), `d_rows` m rows of the stored dtype in device memory, `stride_bytes` apart."""
+        pos = np.ascontiguousarray(np.asarray(positions).reshape(-1), np.uint64)
+        rep = _lib.WriteReport()
+        _lib.gpu_check(_lib.gpu().mvfgpu_corpus_write_rows_device(self._h, pos.ctypes.data_as(C.c_void_p) if pos.size else None, pos.size,
+                                                                  C.c_void_p(d_rows), stride_bytes, C.c_void_p(stream), C.byref(rep)))
+        return _write_report(rep)
 
     # ---- search ----------------------------------------------------------------
     def search(self, queries: np.ndarray, k: int, metric: int = L2) -> SearchResult:

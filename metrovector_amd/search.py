@@ -187,6 +187,16 @@ def rerank_top_k(space: VectorSpace, queries, candidates, k: int, metric: int | 
     return out
 
 
+def write_rows(corpus: GpuCorpus, indices, rows) -> dict:
+    """Replace resident rows (`mvfgpu_corpus_write_rows`; DESIGN.md §3 "Row writes"): `rows` [m, dimension] go to `indices` [m]
+    of a corpus `upload_space` made -- global positions, or vector ids where the space has them -- and every later search of the
+    corpus answers as one uploaded from the changed rows would.  `rows` must hold the space's stored dtype (nothing is
+    converted: a Float16 space takes float16).  Together with tombstones this is the fixed-capacity upsert: upload with spare
+    rows kept deleted, write a new vector into a free slot, then clear its bit with `GpuCorpus.set_tombstones`.  The file
+    behind the space is not changed.  Returns the write's report (`GpuCorpus.write_rows`)."""
+    return corpus.write_rows(indices, rows)
+
+
 def diversify_top_k(space: VectorSpace, queries, candidates, k: int, lambda_mult: float = 0.5, metric: int | None = None,
                     corpus: GpuCorpus | None = None, device: int = 0, with_vectors: bool = False) -> list[list[ScoredVector]]:
     """Diversified re-ranking by maximal marginal relevance (`mvfgpu_search_mmr`; DESIGN.md §3 "Diversified re-ranking"): of

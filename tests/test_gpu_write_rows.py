@@ -1,0 +1,560 @@
+"""Row writes on the device (include/mvf_gpu_update.h; DESIGN.md §3 "Row writes"): after mvfgpu_corpus_write_rows a handle
+answers every entry point as its TWIN does -- a second handle created from the changed row array with the same tombstones,
+ids, scan path, tuning and attached objects.
+
+Every case holds n = 4133 rows (64 whole 6-bit tiles and a last tile of 37), k <= 20.  The written positions include 0, 63, 64,
+4095, 4096 and 4132; the writes of a world come in three calls of 1, 37 and 700 rows.  So that a stale shadow or norm SHOWS,
+the written rows hold, for each query, an exact copy of the query, a copy scaled by 1e3 (integer spaces: saturated) and the
+negation of the row that was rank 1 before the write; `world` asserts on the CPU, with the oracle over the changed rows, that a
+written row is in every query's top-k under every metric.
+
+Bits are compared where the library promises bits -- Int8 / UInt8 spaces on every route, ONE Float32 query on the routes 0, 1,
+6 and 7 --, tests/_util.py's tolerance criterion against the oracle over the changed rows elsewhere, for the handle and for its
+twin."""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+import pytest
+
+from _util import assert_exact, assert_float_topk
+from metrovector_amd import _lib
+from metrovector_amd import errors as E
+from metrovector_amd import gpu as G
+
+pytestmark = pytest.mark.gpu
+
+N, K, NQ = 4133, 10, 64
+FIXED = (0, 63, 64, 4095, 4096, 4132)
+COUNTS = (1, 37, 700)
+SEED = 0x57524954
+L2, IP, COS = G.L2, G.INNER_PRODUCT, G.COSINE
+METRICS = (L2, IP, COS)
+F32, F16, I8, U8 = G.FLOAT32, G.FLOAT16, G.INT8, G.UINT8
+NP = {F32: np.float32, F16: np.float16, I8: np.int8, U8: np.uint8}
+DIMS = (50, 192, 256)  # a pitch with pad bytes; the 6-bit layout under MVF_STREAM_5P1=1; the 5+1 layout there
+NORMS, S_F16, S_I8, S_6B = 1, 2, 4, 8  # mvfgpu_write_report::refreshed
+
+
+# ---- the worlds: rows, queries, the changed rows and the three writes that change them --------------------------------------
+def _scaled(q, dt):
+    if dt in (F32, F16):
+        return (q.astype(np.float32) * np.float32(1e3)).astype(NP[dt])
+    lo, hi = (-128, 127) if dt == I8 else (0, 255)
+    return np.clip(q.astype(np.int64) * 1000, lo, hi).astype(NP[dt])
+
+
+def _negated(x, dt):
+    if dt in (F32, F16):
+        return -x
+    if dt == I8:
+        return np.clip(-x.astype(np.int64), -128, 127).astype(np.int8)
+    return (255 - x.astype(np.int64)).astype(np.uint8)
+
+
+@dataclasses.dataclass
+class World:
+    dt: int
+    dim: int
+    rows0: np.ndarray    # before the writes
+    rows1: np.ndarray    # behind them
+    q: np.ndarray        # [NQ, dim], the query dtype
+    writes: list         # [(positions u64, rows)] of 1, 37 and 700 rows
+    written: np.ndarray  # every written position
+
+
+_WORLDS, _SCORES = {}, {}
+
+
+def world(oracle, dt, dim):
+    key = (dt, dim)
+    if key in _WORLDS:
+        return _WORLDS[key]
+    rows0 = np.ascontiguousarray(oracle.synth_rows(SEED + 16 * dim + dt, 0, N, dim, dt))
+    q = np.ascontiguousarray(oracle.synth_queries(SEED + 16 * dim + dt + 7, NQ, dim, dt))
+    fresh = oracle.synth_rows(SEED + 16 * dim + dt + 11, 0, sum(COUNTS), dim, dt)
+    rank1 = oracle.search(rows0, dt, IP, q, 1)[1][:, 0].astype(np.int64)
+    rng = np.random.default_rng(SEED + dim + dt)
+    spare = [int(p) for p in rng.permutation(N) if int(p) not in FIXED and int(p) not in set(rank1.tolist())]
+    new = {}  # position -> row
+
+    def put(row, pos=None):
+        pos = spare.pop() if pos is None else pos
+        assert pos not in new
+        new[pos] = row
+        return pos
+
+    for i, p in enumerate(FIXED):  # the fixed positions hold the first queries' copies
+        put(q[i].astype(NP[dt]), p)
+    first = list(FIXED)  # the positions of the writes of 1 and 37 rows: the fixed ones, and what the first three queries need
+    for i in range(NQ):
+        if i >= len(FIXED):
+            put(q[i].astype(NP[dt]))
+        s = put(_scaled(q[i], dt))
+        r = int(rank1[i])
+        if r not in new:  # (a rank-1 row that is a fixed position, or another query's too, is overwritten already)
+            new[r] = _negated(rows0[r], dt)
+        first += [s, r] if i < 3 else []
+    first = list(dict.fromkeys(first))
+    while len(new) < sum(COUNTS):
+        put(fresh[len(new)])
+    while len(first) < COUNTS[0] + COUNTS[1]:
+        p = next(p for p in new if p not in first)
+        first.append(p)
+    rest = [p for p in new if p not in first]
+    assert first[0] == 0 and len(rest) == COUNTS[2]
+    rows1 = rows0.copy()
+    for p, row in new.items():
+        rows1[p] = row
+    writes = []
+    for pos in (first[:1], first[1:], rest):
+        pos = np.array(pos, np.uint64)
+        writes.append((pos, np.ascontiguousarray(rows1[pos.astype(np.int64)])))
+    assert [len(w[0]) for w in writes] == list(COUNTS)
+    w = World(dt, dim, rows0, rows1, q, writes, np.array(sorted(new), np.int64))
+    assert set(FIXED) <= set(w.written.tolist())
+    # a property of the reference alone: a write that forgets a shadow or a norm cannot go unseen
+    for metric in METRICS:
+        top = oracle.search(rows1, dt, metric, q, K)[1].astype(np.int64)
+        hit = np.isin(top, w.written).any(axis=1)
+        assert hit.all(), f"dtype {dt} dim {dim} metric {metric}: no written row in the top-{K} of queries {np.nonzero(~hit)[0][:5]}"
+    _WORLDS[key] = w
+    return w
+
+
+def all_scores(oracle, w, metric, qi):
+    """the oracle's score of every changed row for query qi (float spaces), computed once"""
+    key = (w.dt, w.dim, metric, qi)
+    if key not in _SCORES:
+        _SCORES[key] = oracle.scores(w.rows1, w.dt, metric, w.q[qi])[0]
+    return _SCORES[key]
+
+
+_F32ROWS = {}
+
+
+def rows_f32(w):
+    key = (w.dt, w.dim)
+    if key not in _F32ROWS:
+        _F32ROWS[key] = w.rows1.astype(np.float32)
+    return _F32ROWS[key]
+
+
+def write_all(c, w):
+    return [c.write_rows(pos, rows) for pos, rows in w.writes]
+
+
+def same(a, b, what):
+    """every array of two results, byte for byte (NaN scores included)"""
+    assert type(a) is type(b)
+    for f in dataclasses.fields(a):
+        x, y = getattr(a, f.name), getattr(b, f.name)
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), f"{what}: {f.name} differs from the twin's"
+
+
+def expect_refreshed(shadows):
+    """mvfgpu_corpus_info::shadows -> the bits of mvfgpu_write_report::refreshed those shadows need"""
+    return (S_I8 if shadows & 5 else 0) | (S_F16 if shadows & 2 else 0) | (S_6B if shadows & 8 else 0)
+
+
+def check_against_oracle(oracle, w, metric, nq, res, what):
+    if w.dt in (I8, U8) and metric != COS:
+        assert_exact(res, *oracle.search(w.rows1, w.dt, metric, w.q[:nq], K))
+        return
+    for qi in range(nq):
+        assert_float_topk(metric, res.scores[qi], res.indices[qi], all_scores(oracle, w, metric, qi), rows_f32(w),
+                          w.q[qi].astype(np.float32), K)
+
+
+def bits_promised(dt, path, nq):
+    return dt in (I8, U8) or (dt == F32 and nq == 1 and path in (0, 1, 6, 7))
+
+
+ROUTES = ([(F32, p, None) for p in (1, 2, 3, 5, 6)] + [(F32, 7, "0"), (F32, 7, "1")] + [(F16, p, None) for p in (1, 2, 5, 6)] +
+          [(I8, 1, None), (I8, 2, None), (U8, 1, None), (U8, 2, None)])
+ROUTE_IDS = [f"dt{dt}-path{p}" + (f"-5p1={e}" if e else "") for dt, p, e in ROUTES]
+
+
+def _handle(rows, path, **kw):
+    c = G.GpuCorpus.from_array(rows, **kw)
+    c.set_scan_path(path)
+    return c
+
+
+def _searches(c, w):
+    return {(metric, nq): c.search(w.q[:nq], K, metric) for metric in METRICS for nq in (1, 3, NQ)}
+
+
+def _route_case(oracle, monkeypatch, dt, path, env, search_first):
+    if env is not None:
+        monkeypatch.setenv("MVF_STREAM_5P1", env)  # read when a handle is created
+    for dim in DIMS:
+        w = world(oracle, dt, dim)
+        with _handle(w.rows0, path) as c, _handle(w.rows1, path) as twin:
+            if search_first:
+                _searches(c, w)  # so that the derived state exists
+                shadows = c.info().shadows
+            reports = write_all(c, w)
+            for rep, count in zip(reports, COUNTS):
+                assert rep["rows_written"] == count
+                if not search_first:
+                    assert rep["refreshed"] == 0 and rep["launches"] == 1, "nothing was resident: nothing to refresh"
+                    continue
+                want = expect_refreshed(shadows)
+                assert rep["refreshed"] & want == want, f"dim {dim}: shadows {shadows:#x} were resident, refreshed {rep['refreshed']:#x}"
+                if path != 1:  # every other route built the norms (the batched selection, the shadow streams' bound)
+                    assert rep["refreshed"] & NORMS, f"dim {dim}: the norms were resident"
+                if dt == F32 and path == 3:
+                    assert shadows & 2 and rep["refreshed"] & S_F16
+                if dt in (F32, F16) and path in (5, 6, 7):
+                    assert shadows & 1 and rep["refreshed"] & S_I8
+                if dt == F32 and path == 7:
+                    assert shadows & 8 and rep["refreshed"] & S_6B
+                assert rep["launches"] == 1 + bin(rep["refreshed"]).count("1")
+            got, want = _searches(c, w), _searches(twin, w)
+            for (metric, nq), res in got.items():
+                what = f"dtype {dt} path {path} dim {dim} metric {metric} nq {nq}"
+                if bits_promised(dt, path, nq):
+                    same(res, want[(metric, nq)], what)
+                else:
+                    check_against_oracle(oracle, w, metric, nq, want[(metric, nq)], what + " (twin)")
+                check_against_oracle(oracle, w, metric, nq, res, what)
+            assert c.read_rows(0, N).tobytes() == w.rows1.tobytes()
+
+
+# ---- 1 ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt, path, env", ROUTES, ids=ROUTE_IDS)
+def test_every_route_equals_the_twin(oracle, monkeypatch, dt, path, env):
+    _route_case(oracle, monkeypatch, dt, path, env, search_first=True)
+
+
+# ---- 2 ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt, path, env", ROUTES, ids=ROUTE_IDS)
+def test_write_before_any_search(oracle, monkeypatch, dt, path, env):
+    _route_case(oracle, monkeypatch, dt, path, env, search_first=False)
+
+
+# ---- 3 ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", [F32, F16])
+@pytest.mark.parametrize("dim", [50, 256])
+def test_partial_int8_shadow(oracle, monkeypatch, dt, dim):
+    monkeypatch.setenv("MVF_I8_SHADOW_ROWS", "2048")
+    w = world(oracle, dt, dim)
+    assert (w.written < 2048).any() and (w.written >= 2048).any()
+    with _handle(w.rows0, 0) as c, _handle(w.rows1, 0) as twin:  # (a forced path 5 insists on the whole shadow)
+        for metric in METRICS:
+            c.search(w.q, K, metric)
+        inf = c.info()
+        assert inf.shadows & 4, "the shadow of a prefix of the rows"
+        pitch8 = (dim + 15) // 16 * 16
+        for rep, (pos, _) in zip(write_all(c, w), w.writes):
+            assert rep["refreshed"] & S_I8 and rep["refreshed"] & NORMS and not rep["refreshed"] & S_6B
+            assert bool(rep["refreshed"] & S_F16) == bool(inf.shadows & 2)  # (Float32: the rows behind the prefix select on the f16 shadow)
+            covered = int((pos < 2048).sum())
+            per_row = inf.pitch_bytes + 8 + (((2 * dim + 15) // 16 * 16 + 4) if rep["refreshed"] & S_F16 else 0)
+            assert rep["bytes_written"] == len(pos) * per_row + covered * (pitch8 + 4)
+        for metric in METRICS:
+            res, ref = c.search(w.q, K, metric), twin.search(w.q, K, metric)
+            check_against_oracle(oracle, w, metric, NQ, res, f"dtype {dt} dim {dim} metric {metric}")
+            check_against_oracle(oracle, w, metric, NQ, ref, f"dtype {dt} dim {dim} metric {metric} (twin)")
+
+
+# ---- 4 ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("path", [6, 7])
+@pytest.mark.parametrize("dim", [50, 256])
+def test_a_non_finite_row_behind_a_cached_finite_state(oracle, path, dim):
+    w = world(oracle, F32, dim)
+    q = w.q[:1]
+    rows = w.rows0.copy()
+    at = np.array([64, 4100], np.uint64)
+
+    def equal_to_a_twin(c, what):
+        """-> the kernel the twin's last search scanned with"""
+        with _handle(rows, path) as twin:
+            twin.set_profiling(True)
+            for metric in METRICS:
+                same(c.search(q, K, metric), twin.search(q, K, metric), f"path {path} dim {dim} metric {metric}: {what}")
+            return twin.last_timing().scan_kernel
+
+    with _handle(rows, path) as c:
+        c.set_profiling(True)
+        for metric in METRICS:  # the finite state is read back and cached
+            c.search(q, K, metric)
+        assert c.last_timing().scan_kernel == 7 and c.info().shadows & (1 if path == 6 else 8)  # K1 over the selection shadow
+        bad = w.rows0[at.astype(np.int64)].copy()
+        bad[0, 3], bad[1, dim - 1] = np.inf, np.nan
+        rows[at.astype(np.int64)] = bad
+        rep = c.write_rows(at, bad)
+        assert rep["refreshed"] & (S_I8 if path == 6 else S_6B)
+        kernel = equal_to_a_twin(c, "a +Inf and a NaN row written")
+        assert c.last_timing().scan_kernel == kernel, "the routes go where the twin's go"
+        if path == 7:
+            assert kernel == 1, "a 6-bit shadow with a non-finite row is left to the stored rows"
+        good = np.stack([q[0], -q[0]]).astype(np.float32)
+        rows[at.astype(np.int64)] = good
+        c.write_rows(at, good)
+        equal_to_a_twin(c, "both rows finite again")
+        assert c.read_rows(0, N).tobytes() == rows.tobytes()
+
+
+# ---- 5 ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", [F32, F16, I8, U8])
+def test_payload_and_pad_bytes(oracle, dt):
+    dim = 50
+    w = world(oracle, dt, dim)
+    row_bytes = dim * np.dtype(NP[dt]).itemsize
+    stride = row_bytes + 24
+    with _handle(w.rows0, 1) as c, _handle(w.rows1, 1) as twin:
+        for pos, new in w.writes:
+            buf = np.full(len(pos) * stride + 1, 0xFF, np.uint8)  # the gaps between the rows, and a source at an odd address
+            src = buf[1:]
+            for i in range(len(pos)):
+                src[i * stride:i * stride + row_bytes] = new[i].view(np.uint8)
+            rep = _lib.WriteReport()
+            _lib.gpu_check(_lib.gpu().mvfgpu_corpus_write_rows(c._h, pos.ctypes.data_as(C.c_void_p), len(pos), C.c_void_p(src.ctypes.data),
+                                                              stride, C.byref(rep)))
+            assert rep.rows_written == len(pos) and rep.struct_size == C.sizeof(rep)
+        assert c.read_rows(0, N).tobytes() == twin.read_rows(0, N).tobytes() == w.rows1.tobytes()
+        some = np.concatenate([w.written[:50], np.arange(0, N, 97)]).astype(np.uint64)
+        assert c.gather_rows(some).tobytes() == twin.gather_rows(some).tobytes()
+        for metric in (COS, L2):  # K1's 16-byte loads read the pad bytes behind element 49: they are zero, as after an upload
+            for nq in (1, 3):
+                (res, vec), (ref, rvec) = c.search_fetch(w.q[:nq], K, metric), twin.search_fetch(w.q[:nq], K, metric)
+                same(res, ref, f"dtype {dt} metric {metric} nq {nq}")
+                assert vec.tobytes() == rvec.tobytes()
+                assert np.isin(res.indices[0].astype(np.int64), w.written).any()
+
+
+def test_device_sources_aligned_and_not(oracle):
+    """W0's 16-byte path and its byte path, from device memory at the caller's stride"""
+    import torch
+    w = world(oracle, F32, 50)
+    pos, new = w.writes[1]
+    row_bytes, expect = 200, w.rows0.copy()
+    expect[pos.astype(np.int64)] = new
+    for stride, offset in ((208, 0), (224, 0), (224, 4), (203, 1)):
+        host = np.full(offset + len(pos) * stride, 0xFF, np.uint8)
+        for i in range(len(pos)):
+            host[offset + i * stride:offset + i * stride + row_bytes] = new[i].view(np.uint8)
+        dev = torch.from_numpy(host).cuda()
+        with _handle(w.rows0, 1) as c:
+            rep = c.write_rows_device(pos, dev.data_ptr() + offset, stride, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            assert rep["rows_written"] == len(pos) and rep["launches"] == 1
+            assert c.read_rows(0, N).tobytes() == expect.tobytes(), f"stride {stride} offset {offset}"
+            with _handle(expect, 1) as twin:
+                same(c.search(w.q[:3], K, COS), twin.search(w.q[:3], K, COS), f"stride {stride} offset {offset}")
+
+
+# ---- 6 ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("route", ["1", "2"])
+def test_attached_objects_survive(oracle, monkeypatch, route):
+    monkeypatch.setenv("MVF_FILTER_ROUTE", route)
+    w = world(oracle, I8, 50)
+    rng = np.random.default_rng(5)
+    mask = rng.random(N) < 0.5
+    mask[w.written[::2]] = True
+    values = (np.arange(N) % 37).astype(np.uint32)
+    q = w.q[:3]
+    cand = np.stack([np.concatenate([w.written[i::7][:40], rng.integers(0, N, 24)]) for i in range(3)]).astype(np.uint64)
+    sets = np.ascontiguousarray(w.q[:12].reshape(3, 4, 50))
+
+    def objects(c):
+        col = c.attach_column(values)
+        return dict(bitmap=c.make_filter(mask), col=col, where=c.make_filter_where([(col, "<", 20)]), part=c.make_partition(col))
+
+    def answers(c, o, radius):
+        out = {}
+        for metric in (L2, IP):
+            out["bitmap", metric] = c.search_filtered(q, K, metric, o["bitmap"])
+            out["where", metric] = c.search_filtered(q, K, metric, o["where"])
+            out["partitioned", metric] = c.search_partitioned(q, [3, 4, 36], K, metric, o["part"])
+            out["grouped", metric] = c.search_grouped(q, K, 2, metric, o["part"])
+            out["maxsim", metric] = c.search_maxsim(sets, K, metric, o["part"])
+            out["maxsim_candidates", metric] = c.search_maxsim_candidates(sets, np.arange(0, 30, 2), K, metric, o["part"])
+            out["candidates", metric] = c.search_candidates(q, cand, K, metric)
+            out["mmr", metric] = c.search_mmr(q, cand, K, 0.5, metric)
+            out["radius", metric] = c.search_radius(q, radius[metric], 20, metric)
+            out["join", metric] = c.knn_join(K, metric, 0, 128)
+        return out
+
+    with _handle(w.rows0, 0) as c, _handle(w.rows1, 0) as twin:
+        o = objects(c)  # before the write
+        write_all(c, w)
+        ot = objects(twin)
+        plain = twin.search(q, 15, L2), twin.search(q, 15, IP)
+        radius = {L2: plain[0].scores[:, -1].copy(), IP: plain[1].scores[:, -1].copy()}  # about fifteen matches per query
+        got, want = answers(c, o, radius), answers(twin, ot, radius)  # (a stale object would be refused here)
+        for key in got:
+            same(got[key], want[key], f"{key} under MVF_FILTER_ROUTE={route}")
+        assert (got["radius", L2].counts >= 15).all()
+        for x in list(o.values()) + list(ot.values()):
+            x.close()
+
+
+# ---- 7 ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("path", [1, 6])
+def test_free_slot_insert(oracle, path):
+    w = world(oracle, F32, 50)
+    q = w.q[9:10]
+    dead = np.zeros(N, bool)
+    dead[64] = True
+    rows = w.rows0.copy()
+    rows[64] = q[0]
+    with _handle(w.rows0, path) as c, _handle(rows, path) as twin:
+        for h in (c, twin):
+            h.set_tombstones(np.packbits(dead, bitorder="little"))
+        c.search(q, K, L2)
+        c.write_rows([64], q)
+        res = c.search(q, K, L2)
+        assert 64 not in res.indices[0].tolist(), "a deleted row stays deleted"
+        same(res, twin.search(q, K, L2), "the slot still deleted")
+        for h in (c, twin):
+            h.set_tombstones(np.zeros((N + 7) // 8, np.uint8))
+        res = c.search(q, K, L2)
+        assert res.indices[0, 0] == 64 and res.scores[0, 0] == 0.0
+        same(res, twin.search(q, K, L2), "the slot live")
+
+
+# ---- 8 ------------------------------------------------------------------------------------------------------------------------
+def test_rows_are_addressed_by_id_where_ids_are_attached(oracle):
+    w = world(oracle, I8, 50)
+    ids = (1000 + 3 * np.arange(N)).astype(np.uint64)
+    with _handle(w.rows0, 0) as c, _handle(w.rows1, 0) as twin:
+        for h in (c, twin):
+            h.set_vector_ids(ids)
+        c.search(w.q[:3], K, IP)
+        for pos, new in w.writes:
+            c.write_rows(ids[pos.astype(np.int64)], new)
+        for metric in METRICS:
+            res = c.search(w.q[:3], K, metric)
+            same(res, twin.search(w.q[:3], K, metric), f"metric {metric}")
+            assert np.isin(res.indices, ids).all() and np.isin(res.indices, ids[w.written]).any(axis=1).all()
+        for unknown in (5, 1001, 1000 + 3 * N, 0xFFFFFFFFFFFFFFFF):
+            with pytest.raises(E.IndexOutOfBounds):
+                c.write_rows(np.array([1000, unknown], np.uint64), w.rows0[:2])
+        assert c.read_rows(0, N).tobytes() == w.rows1.tobytes()
+
+
+# ---- 9 ------------------------------------------------------------------------------------------------------------------------
+def test_refusals_in_their_order_leave_the_handle_untouched(oracle):
+    w = world(oracle, F32, 50)
+    INV, OOB, base = 12, 5, 1000
+    lib = _lib.gpu()
+    new = np.ascontiguousarray(w.rows1[:4])
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    u64 = lambda *v: np.array(v, np.uint64)       # noqa: E731
+
+    with G.GpuCorpus.from_array(w.rows0, index_base=base) as c:
+        def call(idx, count, rows, stride, device=False):
+            rep = _lib.WriteReport()
+            if device:
+                rc = lib.mvfgpu_corpus_write_rows_device(c._h, None if idx is None else ptr(idx), count, rows, stride, None, C.byref(rep))
+            else:
+                rc = lib.mvfgpu_corpus_write_rows(c._h, None if idx is None else ptr(idx), count, rows, stride, C.byref(rep))
+            return rc, lib.mvfgpu_last_error_message().decode()
+
+        both = u64(base + 7, base + 7)
+        cases = [  # each breaks its own rule AND every later one: the order shows
+            (None, 2, None, 8, INV, "NULL"),                                  # 2. NULL indices and rows
+            (both, 2, None, 8, INV, "NULL"),                                  #    NULL rows
+            (u64(base + N, base + N), 2, ptr(new), 199, INV, "stride_bytes"),   # 3. before the out-of-bounds index
+            (u64(base + N, base + N), 2, ptr(new), 200, OOB, "out of bounds"),  # 4. before the repeated row
+            (u64(base, base - 1), 2, ptr(new), 200, OOB, "out of bounds"),
+            (u64(base, 0xFFFFFFFFFFFFFFFF), 2, ptr(new), 200, OOB, "out of bounds"),
+            (u64(base + 1, base + 7, base + 2, base + 7), 4, ptr(new), 200, INV, f"row position {base + 7} is named twice"),  # 5.
+        ]
+        for device in (False, True):
+            for idx, count, rows, stride, want, text in cases:
+                rc, msg = call(idx, count, rows, stride, device)
+                assert rc == want and text in msg, (device, rc, msg)
+                assert c.read_rows(0, N).tobytes() == w.rows0.tobytes(), f"refused and yet written: {msg}"
+            rc, _ = call(None, 0, None, 0, device)
+            assert rc == 0, "count == 0 does nothing"
+        rc = lib.mvfgpu_corpus_write_rows(c._h, ptr(u64(base)), 1, ptr(new), 200, None)  # the report is optional
+        assert rc == 0 and c.read_rows(0, 1).tobytes() == new[:1].tobytes()
+        with pytest.raises(E.InvalidArgument):
+            c.write_rows([base, base + 1, base], new[:3])
+
+
+# ---- 10 -----------------------------------------------------------------------------------------------------------------------
+def test_a_write_is_ordered_like_a_search(oracle):
+    """search on stream A, write on stream B, search on stream A, ONE synchronisation: the first search sees none of the write,
+    the second all of it"""
+    import torch
+    w = world(oracle, F32, 50)
+    pos, new = w.writes[2]
+    rows1 = w.rows0.copy()
+    rows1[pos.astype(np.int64)] = new
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    nq = 3
+    dq = torch.from_numpy(w.q[:nq]).cuda()
+    dnew = torch.from_numpy(new).cuda()
+    outs = [(torch.empty((nq, K), dtype=torch.float32, device="cuda"), torch.empty((nq, K), dtype=torch.int64, device="cuda"),
+             torch.empty((nq, K), dtype=torch.int32, device="cuda")) for _ in range(2)]
+    with _handle(w.rows0, 1) as c, _handle(w.rows0, 1) as old, _handle(rows1, 1) as twin:
+        c.search(w.q[:nq], K, COS)
+        torch.cuda.synchronize()
+        c.search_device(dq.data_ptr(), F32, 50, nq, K, COS, outs[0][0].data_ptr(), outs[0][1].data_ptr(), outs[0][2].data_ptr(), a.cuda_stream)
+        c.write_rows_device(pos, dnew.data_ptr(), 200, b.cuda_stream)
+        c.search_device(dq.data_ptr(), F32, 50, nq, K, COS, outs[1][0].data_ptr(), outs[1][1].data_ptr(), outs[1][2].data_ptr(), a.cuda_stream)
+        torch.cuda.synchronize()
+        for (s, i, r), ref, what in ((outs[0], old, "the search before the write"), (outs[1], twin, "the search behind the write")):
+            got = G.SearchResult(s.cpu().numpy(), i.cpu().numpy().view(np.uint64), r.cpu().numpy())
+            same(got, ref.search(w.q[:nq], K, COS), what)
+        assert c.read_rows(0, N).tobytes() == rows1.tobytes()
+
+
+# ---- 11 -----------------------------------------------------------------------------------------------------------------------
+def test_a_shard_of_a_set_is_written_through_its_own_handle(oracle):
+    w = world(oracle, F32, 50)
+    cut = 2066
+    pos, new = w.writes[2]
+    sel = pos >= cut  # global positions into the second handle
+    rows1 = w.rows0.copy()
+    rows1[pos[sel].astype(np.int64)] = new[sel]
+
+    def shards(rows):
+        return [G.GpuCorpus.from_array(np.ascontiguousarray(rows[:cut])), G.GpuCorpus.from_array(np.ascontiguousarray(rows[cut:]), index_base=cut)]
+
+    mine, twins = shards(w.rows0), shards(rows1)
+    try:
+        assert mine[1].rows == 2067
+        with G.ShardSet(mine) as ss, G.ShardSet(twins) as st:
+            ss.search(w.q, K, IP)
+            rep = mine[1].write_rows(pos[sel], new[sel])
+            assert rep["rows_written"] == int(sel.sum())
+            for metric in METRICS:
+                for nq in (1, NQ):
+                    same(ss.search(w.q[:nq], K, metric), st.search(w.q[:nq], K, metric), f"metric {metric} nq {nq}")
+            with pytest.raises(E.IndexOutOfBounds):
+                mine[1].write_rows(pos[~sel][:1], new[~sel][:1])
+    finally:
+        for h in mine + twins:
+            h.close()
+
+
+# ---- 12 -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt, path, dim", [(F32, 7, 256), (F32, 7, 192), (F32, 3, 50), (F16, 5, 50), (I8, 2, 50), (U8, 2, 50)])
+def test_cost_shape(oracle, monkeypatch, dt, path, dim):
+    monkeypatch.setenv("MVF_STREAM_5P1", "1")
+    w = world(oracle, dt, dim)
+    with _handle(w.rows0, path) as c:
+        for nq in (1, NQ):
+            for metric in (IP, COS):  # (the integer spaces' norms serve Cosine)
+                c.search(w.q[:nq], K, metric)
+        inf = c.info()
+        reps = write_all(c, w)
+        assert reps[0]["launches"] == reps[1]["launches"] == reps[2]["launches"], "the launches do not depend on the count"
+        assert reps[0]["refreshed"] == reps[2]["refreshed"]
+        r = reps[0]["refreshed"]
+        per_row = inf.pitch_bytes
+        per_row += (4 if dt == I8 else 8) if r & NORMS else 0
+        per_row += ((2 * dim + 15) // 16 * 16 + 4) if r & S_F16 else 0
+        per_row += ((dim + 15) // 16 * 16 + 4) if r & S_I8 else 0
+        if r & S_6B:
+            p51 = dim % 128 == 0 or dim % 128 > 64
+            per_row += (96 * ((dim + 127) // 128) if p51 else 48 * ((dim + 63) // 64)) + 4
+        for rep, count in zip(reps, COUNTS):
+            assert rep["bytes_written"] == count * per_row, (rep, per_row)
+        assert r == (expect_refreshed(inf.shadows) | NORMS)
