@@ -1,6 +1,7 @@
 """Row writes, CPU tier (include/mvf_gpu_update.h; DESIGN.md §3 "Row writes"): the symbols are exported, the header compiles
 as C99 and as C++17 and declares the struct the bindings mirror, the refusal that needs no handle works without a device, and
-GpuCorpus.write_rows checks dtype and shape before any native call."""
+GpuCorpus.write_rows checks dtype and shape before any native call; and the worlds of the GPU tests (tests/_write_rows.py) have, under
+the oracle alone, the properties that make a skipped row show."""
 import ctypes as C
 import os
 import re
@@ -120,3 +121,64 @@ def test_python_layer_checks_dtype_and_shape_before_any_native_call():
     # what passes the checks reaches the library, which refuses the NULL handle
     with pytest.raises(E.InvalidArgument, match="corpus is NULL"):
         c.write_rows([0], np.zeros((1, 4), np.int8))
+
+
+# ---- the worlds of tests/test_gpu_write_rows_edges.py, held with the oracle alone (tests/_write_rows.py) ---------------------------
+def _world_cases():
+    import _write_rows as W
+    return ([("large", dt, dim) for dt, dims in W.LARGE_DIMS.items() for dim in dims] +
+            [("wide", dt, dim) for dt, dims in W.WIDE_DIMS.items() for dim in dims])
+
+
+@pytest.mark.parametrize("kind, dt, dim", _world_cases())
+def test_a_skipped_list_entry_of_the_large_and_wide_worlds_would_show(oracle, kind, dt, dim):
+    """every segment of the list -- the entries a wave serves first, second and third -- holds rows that are in their queries'
+    top-k over the changed rows and not over the old ones"""
+    import _write_rows as W
+    w = (W.large_world if kind == "large" else W.wide_world)(oracle, dt, dim)
+    (pos, rows), = w.writes
+    lst = pos.astype(np.int64)
+    es = np.dtype(W.NP[dt]).itemsize
+    if kind == "large":
+        assert w.rows0.shape == (16421, dim) and len(lst) == 16389 == 2 * 8192 + 5 and 16421 == 256 * 64 + 37
+        assert set((0, 63, 64, 16383, 16384, 16420)) <= set(lst.tolist())
+        assert w.segments == ((0, 8192), (8192, 16384), (16384, 16389))
+        assert (rows[-5:] == w.q[:5].astype(W.NP[dt])).all(), "the last five entries hold the exact copies of the queries 0..4"
+        assert dt != G.FLOAT32 or 16389 * (4 + (dim * es + 15) // 16 * 16) > 3 << 20, "the host call's blob is pageable"
+    else:
+        assert w.rows0.shape == (4133, dim) and len(lst) == 700
+        assert (dim * es + 15) // 16 > 64, "more than 64 16-byte vectors to the row"
+    assert len(set(lst.tolist())) == len(lst) and not (np.sort(lst) == lst).all(), "distinct positions, not in ascending order"
+    assert (w.rows1[lst] == rows).all() and (np.sort(lst) == w.written).all()
+    untouched = np.setdiff1d(np.arange(len(w.rows0)), lst)
+    assert (w.rows1[untouched] == w.rows0[untouched]).all()
+    for s, (a, b) in enumerate(w.segments):
+        assert len(w.planted[s]) >= 5
+        for i, mine in w.planted[s]:
+            assert all(a <= int(np.nonzero(lst == p)[0][0]) < b for p in mine)
+    W.planted_rows_show(oracle, w)
+
+
+def test_the_outlier_rows_are_what_they_are_meant_to_be():
+    """in numpy f32: the huge rows' sums of squares are finite, the overflowing row's elements are finite and their squares' sum is
+    +inf, the non-finite rows hold one +Inf and one NaN"""
+    import _write_rows as W
+    like = np.ones((2, 256), np.float32)
+    for dim in (50, 256):
+        for dt in (G.FLOAT32, G.FLOAT16):
+            huge = W.outlier_rows(dt, dim, "huge", like[:, :dim]).astype(np.float32)
+            assert np.isfinite(huge).all() and (huge == (1e18 if dt == G.FLOAT32 else 60000.0)).all()
+            s = np.float32(0)
+            for x in huge[0]:
+                s = np.float32(s + x * x)
+            assert np.isfinite(s) and s < np.float32(3.0e38), "below the builders' own finiteness limit"
+            bad = W.outlier_rows(dt, dim, "non-finite", like[:, :dim])
+            assert np.isposinf(bad[0]).sum() == 1 and np.isnan(bad[1]).sum() == 1 and np.isfinite(bad).sum() == 2 * dim - 2
+        over = W.outlier_rows(G.FLOAT32, dim, "overflowing", None)
+        assert over.dtype == np.float32 and np.isfinite(over).all()
+        with np.errstate(over="ignore"):
+            assert np.isposinf(np.sum(over[0] * over[0], dtype=np.float32)) and np.isposinf(over[0, 0] * over[0, 0] * np.float32(dim))
+    assert set(W.OUTLIER_KINDS) == {G.FLOAT32, G.FLOAT16} and "overflowing" not in W.OUTLIER_KINDS[G.FLOAT16]
+    q = W.extreme_queries(G.FLOAT32, 50, np.arange(1, 51, dtype=np.float32))
+    assert not q["zero"].any() and 0.5e-20 < np.linalg.norm(q["tiny"].astype(np.float64)) < 2e-20
+    assert 0.5e15 < np.linalg.norm(q["big"].astype(np.float64)) < 2e15
