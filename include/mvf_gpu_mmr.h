@@ -63,6 +63,17 @@ int mvfgpu_search_mmr_device(const mvfgpu_corpus* corpus, uint8_t metric, const 
 int mvfgpu_selftest_mmr_walk(const float* rel_scores, const float* sim_scores, uint32_t m, uint8_t metric, float lambda, uint32_t k,
                              uint32_t* out_order, float* out_objective);
 /*
+ * Self-test of the walk kernel's form (no GPU, no handle): which instantiation of D0 ("D0") walks rows of
+ * `dimension` elements of `data_type` -- the decision the launch itself takes.  forced_g = 0: the library's own lane-group rule;
+ * 1, 4, 8, 16, 32 or 64: the width MVF_K1_G forces on a handle.  *out_g = lanes per row, *out_j = 16-byte steps per lane,
+ * *out_qlds = 1 where the picked row is staged as a query in LDS (Int8 / UInt8 always; float rows whose padded f32 copy, g x j
+ * vectors, takes at most 40 KiB), 0 where it goes to the query's f32 scratch row and is read back through the cache.  Refused with
+ * MVF_ERR_INVALID_ARGUMENT: a NULL output, an unknown data type, dimension 0, an Int8 / UInt8 dimension above MVFGPU_MAX_INT_DIM,
+ * a row above 1 GiB, any other forced_g.
+ */
+int mvfgpu_selftest_mmr_form(uint8_t data_type, uint32_t dimension, uint32_t forced_g, uint32_t* out_g, uint32_t* out_j,
+                             uint32_t* out_qlds);
+/*
  * Stage timer (scripts/probe_mmr.py): mvfgpu_search_mmr_device with events between its stages; waits for the stream.
  * out_ms[0..1] = C0 with the relevance scores, D0 (the walk); each summed over the call's windows.  Refused beside the search's
  * own refusals: a NULL out_ms.

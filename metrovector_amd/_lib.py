@@ -184,6 +184,8 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_search_mmr_device.restype = C.c_int
     lib.mvfgpu_selftest_mmr_walk.argtypes = [vp, vp, u32, u8, C.c_float, u32, vp, vp]
     lib.mvfgpu_selftest_mmr_walk.restype = C.c_int
+    lib.mvfgpu_selftest_mmr_form.argtypes = [u8, u32, u32, vp, vp, vp]
+    lib.mvfgpu_selftest_mmr_form.restype = C.c_int
     lib.mvfgpu_selftest_mmr_stage_ms.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_mmr_stage_ms.restype = C.c_int
     lib.mvfgpu_corpus_write_rows.argtypes = [vp, vp, u64, vp, u64, C.POINTER(WriteReport)]

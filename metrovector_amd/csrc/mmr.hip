@@ -68,7 +68,7 @@ int mmr_core(const CorpusView& v, uint8_t metric, const void* d_queries, uint32_
         return MVF_OK;
     }
     const OneQueryGroup g1 = one_query_group(v);
-    const bool qscratch = !is_int_dtype(v.dtype) && g1.qbytes > kCandQueryLdsMax;
+    const bool qscratch = !mmr_form(v.dtype, g1.G, g1.J).qlds;
     const size_t qrow = query_row_bytes(v);
     const size_t per_q = (size_t)m * 12 + 4 + (qscratch ? (size_t)v.dim * 4 : 0);
     const uint32_t W = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)nq, (size_t)kWindow, kScratchBytes / per_q}));
@@ -219,6 +219,26 @@ int mvfgpu_selftest_mmr_walk(const float* rel_scores, const float* sim_scores, u
         if (out_objective) out_objective[j] = pad_score(metric);
     }
     return (int)npick;
+}
+
+int mvfgpu_selftest_mmr_form(uint8_t data_type, uint32_t dimension, uint32_t forced_g, uint32_t* out_g, uint32_t* out_j,
+                             uint32_t* out_qlds) {
+    if (!out_g || !out_j || !out_qlds) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (elem_size(data_type) == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "unsupported vector data type code " + std::to_string(data_type));
+    if (dimension == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "dimension must be > 0");
+    if (is_int_dtype(data_type) && dimension > MVFGPU_MAX_INT_DIM)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "Int8/UInt8 dimension exceeds the exact-i32 bound (33025)");
+    if ((uint64_t)dimension * elem_size(data_type) > (1ull << 30)) return set_fail(MVF_ERR_INVALID_ARGUMENT, "a row holds at most 1 GiB");
+    if (forced_g != 0 && forced_g != 1 && forced_g != 4 && forced_g != 8 && forced_g != 16 && forced_g != 32 && forced_g != 64)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "forced_g must be 0, 1, 4, 8, 16, 32 or 64, got " + std::to_string(forced_g));
+    const uint32_t V = (uint32_t)(((uint64_t)dimension * elem_size(data_type) + 15u) / 16u);  // alloc_rows' pitch / 16
+    int G = 0;
+    uint32_t J = 0;
+    k1_group(V, 1, (int)forced_g, &G, &J);  // one_query_group's
+    *out_g = (uint32_t)G;
+    *out_j = J;
+    *out_qlds = mmr_form(data_type, G, J).qlds ? 1u : 0u;
+    return MVF_OK;
 }
 
 int mvfgpu_selftest_mmr_stage_ms(const mvfgpu_corpus* c, uint8_t metric, const void* d_queries, uint8_t query_dtype, uint32_t query_dim,

@@ -28,6 +28,21 @@ struct MmrWalkParams {
     float* out_objective;    // nullable
 };
 
+// The form of D0 that walks rows of J steps per lane of a G-lane group, a pure function: the bytes of the picked row padded as
+// a query (cand_query_bytes); qlds: that copy is staged in LDS -- Int8 / UInt8 always, float rows up to kCandQueryLdsMax bytes,
+// beyond that it goes to the query's f32 scratch row and is read back through the cache.  mmr_walk_launch picks its
+// instantiation from it, mmr_core sizes the scratch row by it and mvfgpu_selftest_mmr_form reports it.
+struct MmrForm {
+    uint32_t qbytes;
+    bool qlds;
+};
+inline MmrForm mmr_form(uint8_t dtype, int G, uint32_t J) {
+    MmrForm f;
+    f.qbytes = cand_query_bytes(dtype, G, J);
+    f.qlds = is_int_dtype(dtype) || f.qbytes <= kCandQueryLdsMax;
+    return f;
+}
+
 // G: the lane group of one_query_group (K1's one-query shape)
 hipError_t mmr_walk_launch(uint8_t dtype, int metric, int G, const MmrWalkParams& p, hipStream_t s);
 

@@ -200,8 +200,9 @@ const void* pick_kernel(int metric, int G, bool qlds) {
 hipError_t mmr_walk_launch(uint8_t dtype, int metric, int G, const MmrWalkParams& p, hipStream_t s) {
     if (p.nq == 0 || p.m == 0) return hipSuccess;
     if (p.m > kMmrMaxCandidates) return hipErrorInvalidValue;
-    const uint32_t qbytes = cand_query_bytes(dtype, G, p.J);
-    const bool qlds = is_int_dtype(dtype) || qbytes <= kCandQueryLdsMax;
+    const MmrForm form = mmr_form(dtype, G, p.J);
+    const uint32_t qbytes = form.qbytes;
+    const bool qlds = form.qlds;
     if (!qlds && !p.qscratch) return hipErrorInvalidValue;
     const void* fn = nullptr;
     switch (dtype) {

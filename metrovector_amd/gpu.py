@@ -118,6 +118,20 @@ def mmr_walk(rel_scores, sim_scores, metric: int, lambda_mult: float, k: int) ->
     return order[:k], obj[:k], int(n)
 
 
+class MmrForm(NamedTuple):
+    G: int      # lanes per row
+    J: int      # 16-byte steps per lane
+    qlds: bool  # the picked row is staged as a query in LDS; False: through the query's f32 scratch row and the cache
+
+
+def mmr_form(dtype: int, dim: int, forced_g: int = 0) -> MmrForm:
+    """The instantiation of the diversified re-ranking's walk kernel for rows of `dim` elements of `dtype` (a data type code),
+    under the library's lane-group rule or the width `MVF_K1_G` = `forced_g` forces: `mvfgpu_selftest_mmr_form`; no GPU needed."""
+    out = [C.c_uint32(0) for _ in range(3)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_mmr_form(dtype, dim, forced_g, *[C.byref(o) for o in out]))
+    return MmrForm(out[0].value, out[1].value, bool(out[2].value))
+
+
 def radius_bound(data_type: int, metric: int, radius: float) -> tuple[int, int]:
     """(largest matching order key, exact i32 bound of Int8/UInt8 L2/InnerProduct spaces) of a radius --
     `mvfgpu_selftest_radius_bound`; no GPU needed."""

@@ -280,3 +280,13 @@ def test_the_route_of_a_search_is_a_function_of_its_shape():
     assert lib.mvfgpu_selftest_route(10, 4, 0, 7, 1, 1, C.byref(out)) != 0          # unknown metric
     assert lib.mvfgpu_selftest_route(10, 4, 0, 0, 1, 0, C.byref(out)) != 0          # k = 0
     assert lib.mvfgpu_selftest_route(10, 4, 0, 0, 1, 1, None) != 0
+
+
+def test_gpu_library_exports_the_mmr_header_s_symbols():
+    """include/mvf_gpu_mmr.h continues mvf_gpu.h: the two searches, the host walk, the form self-test and the stage timer"""
+    lib = _lib.gpu()
+    names = _declared("mvf_gpu_mmr.h", "mvfgpu_")
+    assert names == ["mvfgpu_search_mmr", "mvfgpu_search_mmr_device", "mvfgpu_selftest_mmr_form", "mvfgpu_selftest_mmr_stage_ms",
+                     "mvfgpu_selftest_mmr_walk"]
+    for n in names:
+        assert hasattr(lib, n), f"libmvf_gpu.so does not export {n}"

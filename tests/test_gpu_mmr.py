@@ -277,8 +277,10 @@ def test_edge_values(oracle):
 @pytest.mark.parametrize("dtype", [G.FLOAT32, G.FLOAT16])
 def test_a_query_larger_than_lds(oracle, dtype):
     """dimension 20000 (tests/test_gpu_candidates.py test_a_query_larger_than_lds): the padded picked row takes 80 KiB, beyond the
-    40 KiB the kernels keep in LDS -- D0 reads it back from the query's scratch row"""
-    n, dim, m, k = 64, 20000, 8, 4
+    40 KiB the kernels keep in LDS -- D0 reads it back from the query's scratch row.  70 candidates are 70 lane groups of 64
+    lanes: every wave scores, in two passes of its loop, and 12 picks rewrite the scratch row eleven times while other waves have
+    read it (tests/test_gpu_mmr_forms.py holds both sides of the switch itself)"""
+    n, dim, m, k = 300, 20000, 70, 12
     rows = oracle.synth_rows(2801, 0, n, dim, dtype)
     qs = oracle.synth_queries(2802, 2, dim, dtype)
     lists = np.stack([np.random.default_rng(28 + j).permutation(n)[:m] for j in range(2)]).astype(np.uint64)

@@ -227,3 +227,181 @@ def test_every_function_of_the_header_has_a_class():
         assert hasattr(lib, name), name
     assert int(re.search(r"#define MVFGPU_MMR_MAX_CANDIDATES (\d+)u", text).group(1)) == G.MMR_MAX_CANDIDATES
     assert '#include "mvf_gpu.h"' in text
+
+
+# ---- the walk kernel's forms: mvfgpu_selftest_mmr_form, the case table and the references of tests/test_gpu_mmr_forms.py
+def test_the_form_table_is_the_rule_and_the_selftest():
+    """tests/_mmr.py's FORM_CELLS / FORCED_CELLS, written out by hand, against choose_group's rule restated in Python
+    (MM.form_rule) and against the host code the launch itself calls; the rule against the self-test over every dimension up to
+    2100 and around the LDS switch; the table holds all six widths of every type, both sides of the switch and the widest
+    integer rows"""
+    for (dt, dim), cell in MM.FORM_CELLS.items():
+        assert MM.form_rule(dt, dim) == cell == tuple(G.mmr_form(MM.DTYPE[dt], dim)), (dt, dim)
+    for (dt, dim, width), cell in MM.FORCED_CELLS.items():
+        assert MM.form_rule(dt, dim, width) == cell == tuple(G.mmr_form(MM.DTYPE[dt], dim, width)), (dt, dim, width)
+        assert MM.form_rule(dt, dim)[0] != width, "a width only MVF_K1_G reaches"
+    for dt in MM.DTYPE:
+        assert {cell[0] for (t, _), cell in MM.FORM_CELLS.items() if t == dt} == {1, 4, 8, 16, 32, 64}, dt
+        for dim in list(range(1, 2101)) + [10239, 10240, 10241, 10248, 20000, 33025]:
+            for width in (0, 16):
+                assert MM.form_rule(dt, dim, width) == tuple(G.mmr_form(MM.DTYPE[dt], dim, width)), (dt, dim, width)
+    for dt, near, far in MM.FORM_SWITCH:
+        assert MM.FORM_CELLS[dt, near][2] and not MM.FORM_CELLS[dt, far][2] and far == near + 1
+    for dt in ("i8", "u8"):
+        assert MM.FORM_CELLS[dt, 33025] == (64, 33, True) and 64 * 33 * 16 == 33792   # the dynamic LDS of the widest rows
+    assert [cell for (dt, dim, w), cell in MM.FORCED_CELLS.items() if not cell[2]] == [(16, 161, False), (16, 81, False)]
+    # every call of a through-the-cache case keeps all four waves busy over several rewrites of the scratch row
+    cases = [(dt, dim, 0) for dt, dim in MM.FORM_CASES] + MM.FORCED_CASES
+    for ci, (dt, dim, width) in enumerate(cases):
+        qlds = MM.form_rule(dt, dim, width)[2]
+        for mi in range(3):
+            calls = MM.form_calls(ci, mi, dim, qlds)
+            assert all(m <= MM.form_rows(dim) and m in MM.form_ms(dim) for m, _, _, _ in calls)
+            assert {k for _, k, _, _ in calls} >= {MM.F64_K} and calls[0][1] == calls[0][0] and {nq for *_, nq in calls} == {1, 3}
+            assert qlds or all(m >= 65 and k >= 8 for m, k, _, _ in calls)
+    ms = {(dim >= 10240, m) for ci, (dt, dim, width) in enumerate(cases) for mi in range(3) for m, *_ in MM.form_calls(ci, mi, dim, True)}
+    assert ms == {(False, 65), (False, 257), (False, 1000), (False, 1024), (True, 65), (True, 257)}
+
+
+def test_the_form_selftest_refuses_bad_arguments():
+    lib = _lib.gpu()
+    outs = [C.c_uint32(0) for _ in range(3)]
+    ok = [C.byref(o) for o in outs]
+    msg = lambda: lib.mvfgpu_last_error_message().decode()  # noqa: E731
+    assert lib.mvfgpu_selftest_mmr_form(0, 100, 0, *ok) == 0 and [o.value for o in outs] == [32, 1, 1]
+    for i in range(3):
+        assert lib.mvfgpu_selftest_mmr_form(0, 100, 0, *[None if j == i else p for j, p in enumerate(ok)]) == INV and msg() == "NULL buffer"
+    assert lib.mvfgpu_selftest_mmr_form(9, 100, 0, *ok) == INV and "data type" in msg()
+    assert lib.mvfgpu_selftest_mmr_form(0, 0, 0, *ok) == INV and msg() == "dimension must be > 0"
+    for dtype in (2, 3):
+        assert lib.mvfgpu_selftest_mmr_form(dtype, 33025, 0, *ok) == 0
+        assert lib.mvfgpu_selftest_mmr_form(dtype, 33026, 0, *ok) == INV and "33025" in msg()
+    assert lib.mvfgpu_selftest_mmr_form(0, 33026, 0, *ok) == 0
+    assert lib.mvfgpu_selftest_mmr_form(0, (1 << 28) + 1, 0, *ok) == INV and "1 GiB" in msg()
+    for forced in (2, 3, 48, 128):
+        assert lib.mvfgpu_selftest_mmr_form(0, 100, forced, *ok) == INV and "forced_g" in msg()
+    with pytest.raises(E.InvalidArgument):
+        G.mmr_form(2, 40000)
+
+
+FLOAT_FORMS = [(ci, c) for ci, c in enumerate([(dt, dim, 0) for dt, dim in MM.FORM_CASES] + MM.FORCED_CASES) if not MM.is_int(c[0])]
+
+
+@pytest.mark.parametrize("ci,case", FLOAT_FORMS, ids=[f"{dt}d{dim}g{w}" for _, (dt, dim, w) in FLOAT_FORMS])
+def test_the_float64_walk_s_own_path_is_clear(ci, case):
+    """the condition that keeps the band from hiding a failure, from the reference alone: along the float64 walk's own path at
+    most 4 of the 32 steps have a second candidate within the band, for every metric and lambda the GPU file uses"""
+    from _util import TOL
+    dt, dim, _ = case
+    rows, qs = MM.form_world(dt, dim)
+    sel = np.sort(MM.f64_list(dt, dim, rows.shape[0], MM.f64_m(ci, dim)).astype(np.int64))
+    terms = MM.f64_terms(rows[sel], qs[0], TOL)
+    for mi, metric in enumerate(METRICS):
+        unclear, _ = MM.f64_walk(metric, MM.f64_lambda(ci, mi), terms[metric], MM.F64_K)
+        assert unclear <= MM.F64_OWN_UNCLEAR_MAX, f"metric {metric}: {unclear} unclear steps of {MM.F64_K}"
+
+
+def _f32_scores(x, queries, metric):
+    """a kernel's scores as numpy float32 (pairwise sums): [nq, c]"""
+    import _wide as W
+    return np.stack([W.pairwise_f32_scores(x, q, metric) for q in queries])
+
+
+@pytest.fixture(scope="module")
+def teeth_world():
+    """257 Float32 rows of dimension 100 with ten exact copies of row 5 further up the list, their float64 terms and their
+    scores in numpy float32"""
+    from _util import TOL
+    rows, qs = MM.form_world("f32", 100)
+    x = rows[:257].copy()
+    x[100:110] = x[5]
+    return x, qs[0], MM.f64_terms(x, qs[0], TOL), {m: (_f32_scores(x, qs[:1], m)[0], _f32_scores(x, x, m)) for m in METRICS}
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_the_float64_check_has_teeth(teeth_world, metric):
+    """the contract's walk in numpy float32 passes the float64 check; a walk that ignores red, one that sums the sims, one that
+    takes the sim's sign wrongly under L2 and one that breaks ties by descending position do not"""
+    x, q, terms, f32 = teeth_world
+    rel, sim = f32[metric]
+    for lam in (0.3, 0.5):
+        order, obj = MM.numpy_walk(metric, rel, sim, lam, MM.F64_K)
+        unclear, frac = MM.f64_walk(metric, lam, terms[metric], MM.F64_K, order, obj, rel[order])
+        assert frac < 1.0 and unclear <= MM.F64_DEVICE_UNCLEAR_MAX
+        models = ["top_k", "sum"] + (["l2_sign"] if metric == G.L2 else [])
+        for model in models:
+            worder, wobj = MM.wrong_walk(metric, rel, sim, lam, MM.F64_K, model)
+            assert worder != order, model
+            with pytest.raises(AssertionError):
+                MM.f64_walk(metric, lam, terms[metric], MM.F64_K, worder, wobj, rel[worder])
+        # ties: the copies of row 5 hold equal objectives until one is picked, which all 257 picks bring about
+        order, obj = MM.numpy_walk(metric, rel, sim, lam, 257)
+        MM.f64_walk(metric, lam, terms[metric], 257, order, obj, rel[order])
+        worder, wobj = MM.wrong_walk(metric, rel, sim, lam, 257, "descending")
+        with pytest.raises(AssertionError, match="copy"):
+            MM.f64_walk(metric, lam, terms[metric], 257, worder, wobj, rel[worder])
+        order, obj = order[:MM.F64_K], obj[:MM.F64_K]
+        # the right picks with an objective or a score off by three tolerances
+        for name in ("objective", "score"):
+            o2, s2 = obj.copy(), rel[order].copy()
+            (o2 if name == "objective" else s2)[7] += np.float32(3e-5 * max(1.0, float(np.abs(rel).max()) * float(np.abs(sim).max())))
+            with pytest.raises(AssertionError, match=name):
+                MM.f64_walk(metric, lam, terms[metric], MM.F64_K, order, o2, s2)
+
+
+def test_the_ascending_copies_property_has_teeth(teeth_world):
+    x, q, terms, f32 = teeth_world
+    groups = np.arange(257)
+    groups[100:110] = 5
+    for metric in METRICS:
+        rel, sim = f32[metric]
+        assert MM.first_descending_copy(MM.numpy_walk(metric, rel, sim, 0.3, 257)[0], groups) is None
+        bad = MM.first_descending_copy(MM.wrong_walk(metric, rel, sim, 0.3, 257, "descending")[0], groups)
+        assert bad is not None and bad[0] < bad[1]
+    assert MM.first_descending_copy([3, 9, 4, 10], np.array([0] * 5 + [1] * 6)) is None
+    assert MM.first_descending_copy([3, 9, 10, 2], np.array([0] * 5 + [1] * 6)) == (0, 3)
+    # the ownership edges of D0's block: position i is folded by thread i % 256 of wave (i % 256) / 64
+    g = np.arange(1024)
+    assert MM.tie_edges(g) == (False, False, False)
+    for a, b, want in ((0, 64, (True, False, False)), (0, 1, (False, False, False)), (3, 260, (False, True, False)),
+                       (3, 256 + 67, (True, True, False)), (3, 515, (False, True, True))):
+        g2 = g.copy()
+        g2[b] = g2[a]
+        assert MM.tie_edges(g2) == want, (a, b)
+    import _dups as D
+    for dtype in (0, 1):
+        cp = D.corpus_b(MM.DUP_SEED + dtype, MM.DUP_N, MM.DUP_DIM, dtype)
+        assert MM.tie_edges(cp.group_of[MM.dup_list().astype(np.int64)]) == (True, True, True)
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_a_walk_that_flushes_float16_subnormals_is_rejected(oracle, metric):
+    """tests/_edges.py's flush-to-zero model as D0's row_element: the picked row reaches the scoring flushed, the rows scored
+    against it and the relevance do not.  On S (every metric) and on R (L2 and Cosine) the model's walk differs from the contract's
+    (the recipe check), and from what the twin identities expect -- R's picks from H's under Cosine, S's from H's under L2"""
+    import _edges as ED
+    case = ED.get_case(oracle, MM.EDGE_SHAPE, ED.F16)
+    sel = np.sort(np.unique(MM.edge_lists(case)[0]))
+    sel = sel[sel < case.n].astype(np.int64)
+    k, lam = MM.EDGE_K, MM.EDGE_LAMBDA
+
+    def walks(kind):
+        x16 = case.rows(kind)[sel]
+        x = x16.astype(np.float32)
+        q = case.queries_for(kind, metric, case.pool[:1])
+        rel = _f32_scores(x, q, metric)[0]
+        right = MM.numpy_walk(metric, rel, _f32_scores(x, x, metric), lam, k)
+        model = MM.numpy_walk(metric, rel, _f32_scores(x, ED.flushed(x16).astype(np.float32), metric), lam, k)
+        return right, model
+
+    (h_order, h_obj), (h_model, h_mobj) = walks("H")
+    assert h_model == h_order and h_mobj.tobytes() == h_obj.tobytes(), "H holds no subnormal: the model is the contract there"
+    for kind in ("S", "R"):
+        (order, obj), (model, mobj) = walks(kind)
+        if (kind, metric) != ("R", G.INNER_PRODUCT):   # there a subnormal row's sims are too small to move any maximum: S decides
+            assert model != order or mobj.tobytes() != obj.tobytes(), f"{kind}: the recipe check tells the model from the contract"
+        if (kind, metric) == ("R", G.COSINE):
+            assert order == h_order and obj.tobytes() == h_obj.tobytes() and model != h_order
+        if (kind, metric) == ("S", G.L2):
+            assert order == h_order and obj.tobytes() == np.ldexp(h_obj, ED.SHIFT["S"]).astype(np.float32).tobytes()
+            assert model != h_order
