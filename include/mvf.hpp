@@ -36,6 +36,7 @@
 
 #include "mvf_file.h"
 #include "mvf_gpu.h"
+#include "mvf_gpu_maxsim_align.h"
 #include "mvf_gpu_maxsim_route.h"
 #include "mvf_gpu_mmr.h"
 #include "mvf_gpu_update.h"
@@ -657,6 +658,47 @@ public:
         mvfgpu_column_destroy(col);
         detail::check_gpu(rc);
         for (uint32_t i = 0; i < count; i++) out.emplace_back(keys[i], scores[i]);
+        return out;
+    }
+    // Which vector of every listed document scored best for every query vector (mvfgpu_maxsim_align; DESIGN.md section 3,
+    // "Alignments").  `keys` holds values of `column` -- usually the documents find_top_k_documents or rerank_top_k_documents
+    // just returned; alignments are not part of those searches: the recipe is the search, then this call on its keys.
+    // -> [keys.size()][n_tokens] (vector index, score) in list order: the document's best vector for the token and its score; a
+    // document's scores summed in token order are its rerank_top_k_documents score.  A value no live vector carries gets
+    // (UINT64_MAX, +inf under L2 / -inf otherwise) for every token.  The column and the index live for this call.
+    std::vector<std::vector<std::pair<uint64_t, float>>> align_documents(const std::vector<float>& query_vectors,
+                                                                         const std::vector<uint64_t>& keys,
+                                                                         const MetadataColumn& column) const {
+        if (dt_ != DataType::Float32 && dt_ != DataType::Float16)
+            throw MvfError(MVF_ERR_BUILD, "align_documents takes f32 queries: Float32 / Float16 spaces");
+        if (dim_ == 0 || query_vectors.empty() || query_vectors.size() % (size_t)dim_)
+            throw MvfError(MVF_ERR_DIMENSION_MISMATCH, "align_documents takes whole query vectors of the space's dimension");
+        if (keys.size() > UINT32_MAX) throw MvfError(MVF_ERR_INVALID_ARGUMENT, "more than 2^32 - 1 keys");
+        const size_t n_tokens = query_vectors.size() / (size_t)dim_;
+        std::vector<std::vector<std::pair<uint64_t, float>>> out(keys.size());
+        if (keys.empty()) return out;
+        mvfgpu_corpus_info inf;
+        MVFGPU_INIT(inf);
+        detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+        const uint64_t es = column.data_type == MVF_DTYPE_UINT32 ? 4 : column.data_type == MVF_DTYPE_UINT64 ? 8 : 0;
+        if (!es || column.size / es < inf.rows)
+            throw MvfError(MVF_ERR_BUILD, es ? "metadata column '" + column.name + "' holds fewer values than the space has vectors"
+                                             : "Unsupported metadata column data type");
+        mvfgpu_column* col = nullptr;
+        mvfgpu_partition* part = nullptr;
+        std::vector<float> scores(keys.size() * n_tokens);
+        std::vector<uint64_t> rows(keys.size() * n_tokens);
+        int rc = mvfgpu_column_create(c_, column.data, column.data_type, 0, column.size / es, &col);
+        if (rc == MVF_OK) rc = mvfgpu_partition_create(c_, col, &part);
+        if (rc == MVF_OK)
+            rc = mvfgpu_maxsim_align(c_, part, (uint8_t)metric_, query_vectors.data(), MVF_DTYPE_FLOAT32, dim_, 1,
+                                     (uint32_t)std::min<size_t>(n_tokens, UINT32_MAX), keys.data(), (uint32_t)keys.size(), scores.data(),
+                                     rows.data(), nullptr);
+        mvfgpu_partition_destroy(part);
+        mvfgpu_column_destroy(col);
+        detail::check_gpu(rc);
+        for (size_t i = 0; i < keys.size(); i++)
+            for (size_t t = 0; t < n_tokens; t++) out[i].emplace_back(rows[i * n_tokens + t], scores[i * n_tokens + t]);
         return out;
     }
     // The k-NN graph (mvfgpu_knn_join; DESIGN.md section 3, "Join"): for each of the rows [first, first + count) -- count

@@ -715,7 +715,8 @@ int mvfgpu_selftest_grouped_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_p
  * gives this call's score bits, keys and counts.
  * Cost (route 1; include/mvf_gpu_maxsim_route.h): the held rows leave HBM once per chunk of up to 32 tokens (fewer where the padded tokens exceed 40 KiB of LDS or the
  * scratch, chunk x n_keys x 4 + n_keys x 20 bytes per query set, would exceed its budget) and query set.
- * Not built: the arg-best rows per token; ragged token counts; per-token weights; a route over the selection shadows (the
+ * Which row was the best for which token: include/mvf_gpu_maxsim_align.h (mvfgpu_maxsim_align on this call's out_keys).
+ * Not built: ragged token counts; per-token weights; a route over the selection shadows (the
  * batched MFMA kernels: include/mvf_gpu_maxsim_route.h); shard sets; a filter on top of the partition.
  */
 #define MVFGPU_MAXSIM_MAX_TOKENS 1024u
@@ -784,8 +785,9 @@ int mvfgpu_selftest_maxsim_stage_ms(const mvfgpu_corpus* corpus, const mvfgpu_pa
  * Cost: the CANDIDATES' rows leave HBM once per chunk of tokens and query set; scratch per window of query sets is
  * mvfgpu_search_maxsim's with the window's largest distinct-candidate count in n_keys' place, plus 8 bytes per candidate row
  * (each set's rows rounded up to a multiple of 128), inside MVF_MAXSIM_SCRATCH_BYTES wherever one set's fits.
+ * Which row was the best for which token: include/mvf_gpu_maxsim_align.h (mvfgpu_maxsim_align on the same lists).
  * Not built: shard sets (a document's rows may span shards); candidate keys in device memory; ragged token counts; per-token
- * weights; the arg-best rows.
+ * weights.
  */
 int mvfgpu_search_maxsim_candidates(const mvfgpu_corpus* corpus, const mvfgpu_partition* partition, uint8_t metric,
                                     const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens,

@@ -10,12 +10,12 @@ from .errors import (BuildError, CorruptedData, DeviceError, DimensionMismatch, 
 
 from .reader import MetadataColumn, MvfReader, Vector, VectorSlice, VectorSpace  # noqa: F401,E402  (reference: src/reader.rs, src/vectors/*)
 from .builder import BuiltMvf, MvfBuilder  # noqa: F401,E402                      (reference: src/builder.rs)
-from .gpu import (CandidateResult, GpuColumn, GpuCorpus, GpuFilter, GpuPartition, MaxSimResult, MmrResult, RadiusResult, SearchResult,  # noqa: F401,E402
+from .gpu import (CandidateResult, GpuColumn, GpuCorpus, GpuFilter, GpuPartition, MaxSimAlignment, MaxSimResult, MmrResult, RadiusResult, SearchResult,  # noqa: F401,E402
                   maxsim_margin, maxsim_route, mmr_walk)
-from .search import (ScoredVector, build_knn_graph, diversify_top_k, find_top_k_diverse, find_top_k_documents, find_top_k_filtered, find_top_k_grouped, find_top_k_per_key, find_top_k_similar, find_top_k_where, find_top_k_similar_batch,  # noqa: F401,E402
-                     find_within_radius, rerank_top_k, rerank_top_k_documents, upload_space, write_rows)  # examples/similarity_search.rs:140-176; find_within_radius, rerank_top_k, build_knn_graph, find_top_k_filtered, find_top_k_where, find_top_k_per_key, find_top_k_grouped, find_top_k_documents, rerank_top_k_documents, diversify_top_k, find_top_k_diverse, write_rows: DESIGN.md §3
+from .search import (ScoredVector, align_documents, build_knn_graph, diversify_top_k, find_top_k_diverse, find_top_k_documents, find_top_k_filtered, find_top_k_grouped, find_top_k_per_key, find_top_k_similar, find_top_k_where, find_top_k_similar_batch,  # noqa: F401,E402
+                     find_within_radius, rerank_top_k, rerank_top_k_documents, upload_space, write_rows)  # examples/similarity_search.rs:140-176; find_within_radius, rerank_top_k, build_knn_graph, find_top_k_filtered, find_top_k_where, find_top_k_per_key, find_top_k_grouped, find_top_k_documents, rerank_top_k_documents, align_documents, diversify_top_k, find_top_k_diverse, write_rows: DESIGN.md §3
 
 __all__ = ["MvfError", "MvfReader", "VectorSpace", "Vector", "VectorSlice", "MvfBuilder", "BuiltMvf", "GpuCorpus",
-           "GpuFilter", "GpuColumn", "GpuPartition", "MetadataColumn", "SearchResult", "RadiusResult", "CandidateResult", "MmrResult", "MaxSimResult", "ScoredVector", "find_top_k_similar",
-           "find_top_k_similar_batch", "find_within_radius", "rerank_top_k", "build_knn_graph", "find_top_k_filtered", "find_top_k_where", "find_top_k_per_key", "find_top_k_grouped", "find_top_k_documents", "rerank_top_k_documents",
+           "GpuFilter", "GpuColumn", "GpuPartition", "MetadataColumn", "SearchResult", "RadiusResult", "CandidateResult", "MmrResult", "MaxSimResult", "MaxSimAlignment", "ScoredVector", "find_top_k_similar",
+           "find_top_k_similar_batch", "find_within_radius", "rerank_top_k", "build_knn_graph", "find_top_k_filtered", "find_top_k_where", "find_top_k_per_key", "find_top_k_grouped", "find_top_k_documents", "rerank_top_k_documents", "align_documents",
            "diversify_top_k", "find_top_k_diverse", "upload_space", "write_rows", "maxsim_route", "maxsim_margin", "mmr_walk"]

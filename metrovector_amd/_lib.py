@@ -278,6 +278,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_maxsim_candidates_plan.restype = C.c_int
     lib.mvfgpu_selftest_maxsim_candidates_stage_ms.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp]
     lib.mvfgpu_selftest_maxsim_candidates_stage_ms.restype = C.c_int
+    lib.mvfgpu_maxsim_align.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, vp, vp, vp]
+    lib.mvfgpu_maxsim_align.restype = C.c_int
+    lib.mvfgpu_maxsim_align_device.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, vp, vp, vp, vp]
+    lib.mvfgpu_maxsim_align_device.restype = C.c_int
+    lib.mvfgpu_selftest_maxsim_align_plan.argtypes = [u64, u32, u32, u64, u64, vp, vp]
+    lib.mvfgpu_selftest_maxsim_align_plan.restype = C.c_int
+    lib.mvfgpu_selftest_maxsim_align_stage_ms.argtypes = [vp, vp, u8, vp, u8, u32, u32, u32, vp, u32, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_maxsim_align_stage_ms.restype = C.c_int
     lib.mvfgpu_selftest_radius_bound.argtypes = [u8, u8, C.c_float, vp, vp]
     lib.mvfgpu_selftest_radius_bound.restype = C.c_int
     lib.mvfgpu_selftest_radius_route.argtypes = [u8, u32, C.c_int, vp]

@@ -14,6 +14,7 @@
 // and M1, the sort and the writer run per set over its candidates: the cost follows the candidates' rows.
 
 #include "../../include/mvf_gpu.h"
+#include "../../include/mvf_gpu_maxsim_align.h"
 #include "../../include/mvf_gpu_maxsim_route.h"
 
 #include "aux_kernels.h"
@@ -311,12 +312,12 @@ int maxsim_core(const mvfgpu_corpus* c, const CorpusView& v, const PartitionView
 
 int check_candidates_args(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries, uint8_t query_dtype,
                           uint32_t query_dim, uint32_t nq, uint32_t n_tokens, const uint64_t* candidate_keys, uint32_t m, uint32_t k,
-                          const void* out_scores, const void* out_keys) {
+                          const void* out_scores, const void* out_keys, const char* list_name = "candidate_keys") {
     if (const int rc = check_search_scalars(metric, nq, k, queries, out_scores, out_keys)) return rc;
     if (n_tokens == 0 || n_tokens > MVFGPU_MAXSIM_MAX_TOKENS)
         return set_fail(MVF_ERR_INVALID_ARGUMENT,
                         "n_tokens must be in 1.." + std::to_string(MVFGPU_MAXSIM_MAX_TOKENS) + ", got " + std::to_string(n_tokens));
-    if (!candidate_keys && (uint64_t)nq * m > 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer (candidate_keys)");
+    if (!candidate_keys && (uint64_t)nq * m > 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, std::string("NULL buffer (") + list_name + ")");
     if (!part) return set_fail(MVF_ERR_INVALID_ARGUMENT, "partition is NULL");
     if (const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_keys)) return rc;
     return check_partition_use(c, part);
@@ -347,9 +348,11 @@ struct CandPlan {
 
 // Windows: as many sets as maxsim_plan allows for the window's largest candidate count inside what the budget leaves beside the
 // window's concatenated list (8 bytes per position), the list itself inside the budget and below 2^32 positions; one set whatever
-// the budget.
+// the budget.  plan_of and set_bytes (the alignments): the plan function in maxsim_plan's place, and bytes that every set of a
+// window takes off the budget beside the list.
+using PlanFn = MaxsimPlan (*)(uint64_t, uint32_t, uint32_t, uint64_t, uint64_t);
 int plan_candidates(const mvfgpu_partition* part, const uint64_t* cand, uint32_t nq, uint32_t m, uint32_t n_tokens, uint64_t token_bytes,
-                    uint64_t budget, CandPlan* plan) {
+                    uint64_t budget, CandPlan* plan, PlanFn plan_of = maxsim_plan, uint64_t set_bytes = 0) {
     std::vector<std::pair<uint64_t, uint32_t>> distinct;
     plan->sets.resize(nq);
     for (uint32_t q = 0; q < nq; q++) {
@@ -383,8 +386,9 @@ int plan_candidates(const mvfgpu_partition* part, const uint64_t* cand, uint32_t
                 pos += maxsim_cand_positions(plan->sets[q].rows);
                 nk = std::max(nk, plan->sets[q].count);
             }
-            const bool list_ok = pos <= 0xFFFFFFFFull && pos * 8 <= budget;
-            const MaxsimPlan pl = maxsim_plan(nk, n_tokens, wn, token_bytes, budget > pos * 8 ? budget - pos * 8 : 0);
+            const uint64_t used = pos * 8 + wn * set_bytes;
+            const bool list_ok = pos <= 0xFFFFFFFFull && used <= budget;
+            const MaxsimPlan pl = plan_of(nk, n_tokens, wn, token_bytes, budget > used ? budget - used : 0);
             if (wn == 1 || (list_ok && pl.window >= wn)) {
                 if (pos > 0xFFFFFFFFull) return set_fail(MVF_ERR_INVALID_ARGUMENT, "a candidate list's rows take 2^32 list positions or more");
                 w = CandWindow{w0, wn, pl.chunk, nk, (uint32_t)plan->blocks.size(), (uint32_t)(pos / kMaxsimRows)};
@@ -537,6 +541,136 @@ int stage_sums(const StageMarks& marks, float* out_ms, int stages = 4) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, marks.ev[i - 1].second, marks.ev[i].second) != hipSuccess) return set_fail(MVF_ERR_DEVICE, "hipEventElapsedTime failed");
         if (marks.ev[i].first >= 0 && marks.ev[i].first < stages) out_ms[marks.ev[i].first] += ms;
+    }
+    return MVF_OK;
+}
+
+// ---- alignments: mvfgpu_maxsim_align (include/mvf_gpu_maxsim_align.h; DESIGN.md §3 "Alignments", §5 "M0-arg and the alignment
+// writer")
+
+// check_candidates_args as with k = 1, the list named `keys`; out_raw is nullable
+int check_align_args(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries, uint8_t query_dtype,
+                     uint32_t query_dim, uint32_t nq, uint32_t n_tokens, const uint64_t* keys, uint32_t m, const void* out_scores,
+                     const void* out_rows) {
+    return check_candidates_args(c, part, metric, queries, query_dtype, query_dim, nq, n_tokens, keys, m, 1, out_scores, out_rows, "keys");
+}
+
+// The device work of both alignment calls: query sets and the three outputs [nq][m][n_tokens] in device memory, the lists on the
+// host; everything on `s`.  Runs under corpus_device_call.  Per window: E0, then per chunk of tokens M0-arg and the writer;
+// every element is written by the writer, the padding of skipped entries and of windows without a candidate included.
+// marks (the stage timer only): stage 0 the plan's upload and E0, 1 M0-arg, 2 the writer.
+int maxsim_align_core(const CorpusView& v, const mvfgpu_partition* part, uint8_t metric, const void* d_queries, uint32_t nq,
+                      uint32_t n_tokens, const uint64_t* keys, uint32_t m, float* d_scores, uint64_t* d_rows, int32_t* d_raw, hipStream_t s,
+                      StageMarks* marks = nullptr) {
+    const PartitionView pv = partition_view(part);
+    if (marks) MVF_HIP_TRY(marks->mark(-1, s));
+    if (m == 0) return MVF_OK;
+    const size_t per_set = (size_t)m * n_tokens;  // elements of a set in every output
+    MaxsimAlignWriteParams wp{};
+    wp.ids = v.ids;
+    wp.index_base = v.index_base;
+    wp.m = m;
+    wp.n_tokens = n_tokens;
+    wp.metric = metric;
+    wp.dtype = v.dtype;
+    // the writer over sets [w0, w0 + wn): tokens [t0, t0 + tc) from best64 / slots, or padding throughout where best64 is NULL
+    auto write = [&](uint32_t w0, uint32_t wn, uint32_t t0, uint32_t tc, const uint64_t* best64, const uint32_t* slots, uint32_t nk) -> int {
+        MaxsimAlignWriteParams p = wp;
+        p.best64 = best64;
+        p.slots = slots;
+        p.out_scores = d_scores + (size_t)w0 * per_set;
+        p.out_rows = d_rows + (size_t)w0 * per_set;
+        p.out_raw = d_raw ? d_raw + (size_t)w0 * per_set : nullptr;
+        p.sets = wn;
+        p.n_keys = nk;
+        p.t0 = t0;
+        p.tc = tc;
+        MVF_HIP_TRY(maxsim_align_write_launch(p, s));
+        return MVF_OK;
+    };
+    auto pad = [&](uint32_t w0, uint32_t wn) { return write(w0, wn, 0, n_tokens, nullptr, nullptr, 0); };
+    if (v.n == 0 || pv.live == 0 || pv.n_keys == 0) return pad(0, nq);
+    const OneQueryGroup g1 = one_query_group(v);
+    const size_t set_bytes = query_row_bytes(v) * n_tokens;
+    CandPlan plan;
+    if (const int rc = plan_candidates(part, keys, nq, m, n_tokens, g1.qbytes, v.maxsim_scratch, &plan, maxsim_align_plan, (uint64_t)m * 4))
+        return rc;
+    if (plan.segs.empty()) return pad(0, nq);
+
+    // the slot map: an entry's key among its set's candidates (ascending key values) -- a repeat finds its first occurrence's slot
+    std::vector<uint32_t> slots((size_t)nq * m);
+    for (uint32_t q = 0; q < nq; q++) {
+        const uint64_t* held = plan.keys.data() + plan.sets[q].seg0;
+        const uint64_t* end = held + plan.sets[q].count;
+        for (uint32_t i = 0; i < m; i++) {
+            const uint64_t key = keys[(size_t)q * m + i];
+            const uint64_t* at = std::lower_bound(held, end, key);
+            slots[(size_t)q * m + i] = at != end && *at == key ? (uint32_t)(at - held) : UINT32_MAX;
+        }
+    }
+    // the plan, one upload: segments | sets | blocks (8-byte entries) | slot map
+    const size_t segs_b = plan.segs.size() * sizeof(MaxsimCandSeg), sets_b = (size_t)nq * sizeof(MaxsimCandSet),
+                 blocks_b = plan.blocks.size() * sizeof(MaxsimCandBlock), slots_b = slots.size() * 4;
+    std::vector<unsigned char> blob(segs_b + sets_b + blocks_b + slots_b);
+    std::memcpy(blob.data(), plan.segs.data(), segs_b);
+    std::memcpy(blob.data() + segs_b, plan.sets.data(), sets_b);
+    if (blocks_b) std::memcpy(blob.data() + segs_b + sets_b, plan.blocks.data(), blocks_b);
+    std::memcpy(blob.data() + segs_b + sets_b + blocks_b, slots.data(), slots_b);
+    AsyncBuf dplan;
+    MVF_HIP_TRY(dplan.alloc(blob.size(), s));
+    if (const int rc = partition_upload(part, blob.data(), blob.size(), dplan.p, s)) return rc;
+    const unsigned char* dp = static_cast<const unsigned char*>(dplan.p);
+    const MaxsimCandSeg* p_segs = reinterpret_cast<const MaxsimCandSeg*>(dp);
+    const MaxsimCandSet* p_sets = reinterpret_cast<const MaxsimCandSet*>(dp + segs_b);
+    const MaxsimCandBlock* p_blocks = reinterpret_cast<const MaxsimCandBlock*>(dp + segs_b + sets_b);
+    const uint32_t* p_slots = reinterpret_cast<const uint32_t*>(dp + segs_b + sets_b + blocks_b);
+
+    for (const CandWindow& w : plan.windows) {
+        if (w.n_keys == 0) {  // no set of the window holds a candidate
+            if (const int rc = pad(w.w0, w.wn)) return rc;
+            continue;
+        }
+        const uint32_t nk = w.n_keys, wn = w.wn;
+        const size_t npos = (size_t)w.n_blocks * kMaxsimRows;
+        AsyncBuf dlist, dbest;
+        MVF_HIP_TRY(dlist.alloc(npos * 8, s));  // rows [npos], then slot ordinals [npos]
+        MVF_HIP_TRY(dbest.alloc((size_t)wn * w.chunk * nk * 8, s));
+        // E0: the window's concatenated list
+        MaxsimExpandParams ep{};
+        ep.rows_by_key = pv.rows_by_key;
+        ep.sets = p_sets + w.w0;
+        ep.segs = p_segs;
+        ep.blocks = p_blocks + w.blk0;
+        ep.n_blocks = w.n_blocks;
+        ep.list = static_cast<uint32_t*>(dlist.p);
+        ep.ord = ep.list + npos;
+        MVF_HIP_TRY(maxsim_expand_launch(ep, s));
+        if (marks) MVF_HIP_TRY(marks->mark(0, s));
+        for (uint32_t t0 = 0; t0 < n_tokens; t0 += w.chunk) {
+            const uint32_t tc = std::min(w.chunk, n_tokens - t0);
+            MVF_HIP_TRY(hipMemsetAsync(dbest.p, 0xFF, (size_t)wn * tc * nk * 8, s));
+            MaxsimScoreParams sp{};
+            sp.rows = v.rows;
+            sp.queries = static_cast<const unsigned char*>(d_queries) + (size_t)w.w0 * set_bytes;
+            sp.list = ep.list;
+            sp.ord = ep.ord;
+            sp.best64 = static_cast<uint64_t*>(dbest.p);
+            sp.m = (uint32_t)npos;
+            sp.n_keys = nk;
+            sp.sets = wn;
+            sp.n_tokens = n_tokens;
+            sp.t0 = t0;
+            sp.tc = tc;
+            sp.dim = v.dim;
+            sp.pitch = v.pitch;
+            sp.V = v.V;
+            sp.J = g1.J;
+            sp.blocks = ep.blocks;
+            MVF_HIP_TRY(maxsim_score_arg_launch(v.dtype, metric, g1.G, sp, s));
+            if (marks) MVF_HIP_TRY(marks->mark(1, s));
+            if (const int rc = write(w.w0, wn, t0, tc, sp.best64, p_slots + (size_t)w.w0 * m, nk)) return rc;
+            if (marks) MVF_HIP_TRY(marks->mark(2, s));
+        }
     }
     return MVF_OK;
 }
@@ -825,6 +959,70 @@ int mvfgpu_selftest_maxsim_form(uint8_t data_type, uint32_t dimension, uint32_t 
     *out_token_bytes = f.token_bytes;
     *out_form = f.reg ? 0u : f.qlds ? 1u : 2u;
     *out_lds_chunk_cap = maxsim_plan(1, MVFGPU_MAXSIM_MAX_TOKENS, 1, f.token_bytes, ~0ull).chunk;
+    return MVF_OK;
+}
+
+int mvfgpu_maxsim_align_device(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,
+                               uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens, const uint64_t* keys, uint32_t m,
+                               float* d_scores, uint64_t* d_rows, int32_t* d_raw, void* hip_stream) {
+    const int rc = check_align_args(c, part, metric, d_queries, query_dtype, query_dim, nq, n_tokens, keys, m, d_scores, d_rows);
+    if (rc != MVF_OK) return rc;
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    return corpus_device_call(c, s, [&]() {
+        return maxsim_align_core(corpus_view(c), part, metric, d_queries, nq, n_tokens, keys, m, d_scores, d_rows, d_raw, s);
+    });
+}
+
+int mvfgpu_maxsim_align(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* queries, uint8_t query_dtype,
+                        uint32_t query_dim, uint32_t nq, uint32_t n_tokens, const uint64_t* keys, uint32_t m, float* out_scores,
+                        uint64_t* out_rows, int32_t* out_raw) {
+    const int rc0 = check_align_args(c, part, metric, queries, query_dtype, query_dim, nq, n_tokens, keys, m, out_scores, out_rows);
+    if (rc0 != MVF_OK) return rc0;
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    if (m == 0) return MVF_OK;  // nothing to write
+    std::lock_guard<std::mutex> host_lk(corpus_host_mutex(c));
+    const CorpusView v = corpus_view(c);
+    hipStream_t s = static_cast<hipStream_t>(v.stream);
+    const size_t per_set = (size_t)m * n_tokens;
+    const HostIn in[] = {{queries, query_row_bytes(v) * n_tokens}};
+    const HostOut out[] = {{out_rows, per_set * 8}, {out_scores, per_set * 4}, {out_raw, per_set * 4}};
+    return stage_host_windows(c, s, nq, in, out, stage_as_given, [&](uint32_t w0, uint32_t wn, void* const* d_in, void* const* d_out) {
+        return maxsim_align_core(v, part, metric, d_in[0], wn, n_tokens, keys + (size_t)w0 * m, m, static_cast<float*>(d_out[1]),
+                                 static_cast<uint64_t*>(d_out[0]), static_cast<int32_t*>(d_out[2]), s);
+    });
+}
+
+int mvfgpu_selftest_maxsim_align_stage_ms(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint8_t metric, const void* d_queries,
+                                          uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t n_tokens, const uint64_t* keys,
+                                          uint32_t m, float* d_scores, uint64_t* d_rows, int32_t* d_raw, void* hip_stream, float* out_ms) {
+    if (!out_ms) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    const int rc0 = check_align_args(c, part, metric, d_queries, query_dtype, query_dim, nq, n_tokens, keys, m, d_scores, d_rows);
+    if (rc0 != MVF_OK) return rc0;
+    DevScope guard(corpus_view(c).device);
+    if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    StageMarks marks;
+    int rc = corpus_device_call(c, s, [&]() {
+        return maxsim_align_core(corpus_view(c), part, metric, d_queries, nq, n_tokens, keys, m, d_scores, d_rows, d_raw, s, &marks);
+    });
+    if (rc == MVF_OK && hipStreamSynchronize(s) != hipSuccess) rc = set_fail(MVF_ERR_DEVICE, "hipStreamSynchronize failed");
+    for (int i = 0; i < 3; i++) out_ms[i] = 0.0f;
+    return rc == MVF_OK ? stage_sums(marks, out_ms, 3) : rc;
+}
+
+int mvfgpu_selftest_maxsim_align_plan(uint64_t n_keys, uint32_t n_tokens, uint32_t nq, uint64_t token_bytes, uint64_t budget_bytes,
+                                      uint32_t* tokens_per_chunk, uint32_t* sets_per_window) {
+    if (!tokens_per_chunk || !sets_per_window) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (n_tokens == 0 || n_tokens > MVFGPU_MAXSIM_MAX_TOKENS)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT,
+                        "n_tokens must be in 1.." + std::to_string(MVFGPU_MAXSIM_MAX_TOKENS) + ", got " + std::to_string(n_tokens));
+    if (nq == 0 || budget_bytes == 0) return set_fail(MVF_ERR_INVALID_ARGUMENT, "empty batch or budget");
+    const MaxsimPlan pl = maxsim_align_plan(n_keys, n_tokens, nq, token_bytes, budget_bytes);
+    *tokens_per_chunk = pl.chunk;
+    *sets_per_window = pl.window;
     return MVF_OK;
 }
 

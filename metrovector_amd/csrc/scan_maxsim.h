@@ -70,6 +70,7 @@ struct MaxsimScoreParams {
     uint32_t* best;
     uint32_t m, n_keys, sets, n_tokens, t0, tc, dim, pitch, V, J;
     const struct MaxsimCandBlock* blocks;  // the candidate form's block table; not read by the full search's form
+    uint64_t* best64;                      // M0-arg's minima (scan_maxsim_align.hip); not read by M0
 };
 hipError_t maxsim_score_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s);
 
@@ -139,6 +140,45 @@ struct MaxsimWriteParams {
     const MaxsimCandSet* cand;  // nullable
 };
 hipError_t maxsim_write_launch(const MaxsimWriteParams& p, hipStream_t s);
+
+// ---- alignments (mvfgpu_maxsim_align; scan_maxsim_align.hip; DESIGN.md §3 "Alignments", §5 "M0-arg and the alignment writer")
+// The plan of an alignment call: maxsim_plan's chunk rules -- at most kMaxsimChunkMax tokens, at most what kCandQueryLdsMax bytes
+// of padded tokens take, at least one token group whatever the budget -- with chunk x n_keys x 8 bytes of minima per query set of
+// a window inside budget_bytes: M0-arg keeps a u64 per (token, key) and there are no sums and no sort buffers.  The caller takes
+// the window's concatenated list (8 bytes per position) and the slot map (4 bytes per list entry) off the budget first.  One set
+// whatever the budget.
+inline MaxsimPlan maxsim_align_plan(uint64_t n_keys, uint32_t n_tokens, uint32_t nq, uint64_t token_bytes, uint64_t budget_bytes) {
+    const uint64_t in_lds = token_bytes == 0 || token_bytes > kCandQueryLdsMax ? kMaxsimChunkMax : kCandQueryLdsMax / token_bytes;
+    const uint64_t cap = std::min<uint64_t>({n_tokens, kMaxsimChunkMax, in_lds});
+    const uint64_t least = std::min<uint64_t>(cap, kMaxsimTokenGroup);
+    const uint64_t nk = n_keys ? n_keys : 1, fit = budget_bytes / nk / 8;
+    MaxsimPlan pl;
+    pl.chunk = (uint32_t)std::min(std::max(fit, least), cap);
+    pl.window = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({budget_bytes / (nk * pl.chunk * 8), nq, kMaxsimWindow}));
+    return pl;
+}
+
+// M0-arg: maxsim_score_candidates_launch with the argument kept.  p.best64[set][t][n_keys], all-ones on entry, receives the
+// smallest (order key << 32 | local row) of tokens [t0, t0 + tc) of every query set over each candidate's rows: the first row in
+// mvfgpu_search's order.  p.best is not read.  The scoring is M0's, line for line.
+hipError_t maxsim_score_arg_launch(uint8_t dtype, int metric, int G, const MaxsimScoreParams& p, hipStream_t s);
+
+// The alignment writer.  One thread per (entry i of a set's list, token t of the chunk): slot = slots[set][i], the entry's slot
+// ordinal (UINT32_MAX: skipped; a repeat carries its first occurrence's), and element (set, i, t0 + t) of the three outputs
+// [sets][m][n_tokens] is the score, the reported row (ids[row] or index_base + row) and the exact integer (out_raw nullable) of
+// best64[set][t][slot], or mvfgpu_search's padding for a skipped entry.  best64 NULL: every element is padding.
+struct MaxsimAlignWriteParams {
+    const uint64_t* best64;
+    const uint32_t* slots;  // [sets][m]
+    const uint64_t* ids;    // nullable
+    uint64_t index_base;
+    float* out_scores;
+    uint64_t* out_rows;
+    int32_t* out_raw;
+    uint32_t sets, m, n_keys, n_tokens, t0, tc;
+    uint8_t metric, dtype;
+};
+hipError_t maxsim_align_write_launch(const MaxsimAlignWriteParams& p, hipStream_t s);
 
 // ---- the MFMA selection route (scan_maxsim_mfma.hip; DESIGN.md §3 "Multi-vector search: the MFMA route", §5 "A0 / P0")
 // The route of a full multi-vector search, a pure function (mvfgpu_selftest_maxsim_route; the launch calls it): 1 = the one-pass

@@ -52,6 +52,14 @@ class MaxSimResult:
 
 
 @dataclass
+class MaxSimAlignment:
+    """Each listed key's best row per query token (`GpuCorpus.maxsim_align`), in list order; padding where a key is not held."""
+    rows: np.ndarray     # u64 [nq, m, n_tokens]: the row as every search reports it (UINT64_MAX pads)
+    scores: np.ndarray   # f32 [nq, m, n_tokens]: its score for the token; summed in token order, the key's MaxSim score
+    raw: np.ndarray      # i32 [nq, m, n_tokens] (exact integer score on Int8/UInt8 spaces)
+
+
+@dataclass
 class MaxSimSelection:
     """What the MFMA selection route held on the device for one call (`GpuCorpus.maxsim_mfma_selection`); keys in ascending value."""
     sums: np.ndarray        # f32 [nq, n_keys]: the approximate sums as the candidate rule read them
@@ -406,6 +414,15 @@ def maxsim_plan(n_keys: int, n_tokens: int, nq: int, token_bytes: int, budget_by
     `nq` sets, padded tokens of `token_bytes` and a scratch budget: `mvfgpu_selftest_maxsim_plan`; no GPU needed."""
     chunk, window = C.c_uint32(0), C.c_uint32(0)
     _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_plan(n_keys, n_tokens, nq, token_bytes, budget_bytes, C.byref(chunk), C.byref(window)))
+    return chunk.value, window.value
+
+
+def maxsim_align_plan(n_keys: int, n_tokens: int, nq: int, token_bytes: int, budget_bytes: int) -> tuple[int, int]:
+    """(tokens per chunk, query sets per window) of an alignment call (`GpuCorpus.maxsim_align`) whose windows hold up to `n_keys`
+    distinct keys per set, inside what the scratch budget leaves beside the list and the slot map:
+    `mvfgpu_selftest_maxsim_align_plan`; no GPU needed."""
+    chunk, window = C.c_uint32(0), C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_align_plan(n_keys, n_tokens, nq, token_bytes, budget_bytes, C.byref(chunk), C.byref(window)))
     return chunk.value, window.value
 
 
@@ -1103,6 +1120,58 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_candidates_stage_ms(
             self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq, n_tokens,
             cand.ctypes.data_as(C.c_void_p) if cand.size else None, cand.shape[1], k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+            _opt(stream), out))
+        return tuple(float(x) for x in out)
+
+    # ---- alignments: each listed key's best row per query token ----------------------------
+    def maxsim_align(self, query_sets: np.ndarray, keys, metric: int, part: GpuPartition) -> MaxSimAlignment:
+        """Which row of every listed key scored best for every query token (`mvfgpu_maxsim_align`): `query_sets` is
+        [nq, n_tokens, dim] (a 2-D array is one set), `keys` [m] (one list for every set) or [nq, m] -- usually the keys a
+        multi-vector search just returned: for a full search, `search_maxsim` and then this call on its keys.  Rows, scores and raw
+        are [nq, m, n_tokens] in list order; element (q, i, t) is `search_partitioned`'s single result for token t of set q with
+        key keys[q, i] and k = 1, padding where the partition does not hold the key; a key's scores summed in token order are its
+        `search_maxsim_candidates` score."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        q = np.asarray(query_sets)
+        if q.ndim == 2:
+            q = q[None, :, :]
+        if q.ndim != 3:
+            raise InvalidArgument(f"query sets must be [nq, n_tokens, dim], got shape {q.shape}")
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, n_tokens, qdim = q.shape
+        kk = _candidate_lists(keys, nq)
+        m = kk.shape[1]
+        shape = (nq, m, n_tokens)
+        sc, rows, raw = np.empty(shape, np.float32), np.empty(shape, np.uint64), np.empty(shape, np.int32)
+        # never a NULL output: the library checks the buffers before it looks at m
+        out = [(a if a.size else np.empty(1, a.dtype)).ctypes.data_as(C.c_void_p) for a in (sc, rows, raw)]
+        _lib.gpu_check(_lib.gpu().mvfgpu_maxsim_align(self._h, hpart, metric, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, n_tokens,
+                                                      kk.ctypes.data_as(C.c_void_p) if kk.size else None, m, *out))
+        return MaxSimAlignment(rows, sc, raw)
+
+    def maxsim_align_device(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int, keys,
+                            metric: int, d_scores: int, d_rows: int, d_raw: int = 0, stream: int = 0) -> None:
+        """Device-pointer alignments (`mvfgpu_maxsim_align_device`), asynchronous on `stream`: the three outputs are
+        [nq, m, n_tokens] in device memory; `keys` ([m] or [nq, m]) stays on the host and is read before the call returns."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        kk = _candidate_lists(keys, nq)
+        _lib.gpu_check(_lib.gpu().mvfgpu_maxsim_align_device(
+            self._h, hpart, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq, n_tokens,
+            kk.ctypes.data_as(C.c_void_p) if kk.size else None, kk.shape[1], C.c_void_p(d_scores), C.c_void_p(d_rows), _opt(d_raw),
+            _opt(stream)))
+
+    def maxsim_align_stage_ms(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int, keys,
+                              metric: int, d_scores: int, d_rows: int, d_raw: int = 0, stream: int = 0) -> tuple[float, float, float]:
+        """(plan upload + E0, M0-arg, writer) in ms of one alignment call, summed over its chunks and windows
+        (`mvfgpu_selftest_maxsim_align_stage_ms`); waits for the stream."""
+        out = (C.c_float * 3)()
+        kk = _candidate_lists(keys, nq)
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_align_stage_ms(
+            self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim, nq, n_tokens,
+            kk.ctypes.data_as(C.c_void_p) if kk.size else None, kk.shape[1], C.c_void_p(d_scores), C.c_void_p(d_rows), _opt(d_raw),
             _opt(stream), out))
         return tuple(float(x) for x in out)
 

@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .errors import BuildError, InvalidVectorType
-from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, MaxSimResult, SearchResult, pack_allow_mask, query_dtype_code
+from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, MaxSimAlignment, MaxSimResult, SearchResult, pack_allow_mask, query_dtype_code
 from .reader import VectorSpace
 
 _NP_OF = {0: np.float32, 1: np.float16, 2: np.int8, 3: np.uint8}
@@ -466,6 +466,40 @@ def rerank_top_k_documents(space: VectorSpace, query_vectors, candidate_keys, k:
             with corpus.make_partition(col) as part:
                 return corpus.search_maxsim_candidates(np.asarray(query_vectors, dtype=_NP_OF[query_dtype_code(dt)]), candidate_keys, k,
                                                        metric, part)
+    finally:
+        if own:
+            corpus.close()
+
+
+def align_documents(space: VectorSpace, query_vectors, keys, column: str, metric: int | None = None,
+                    corpus: GpuCorpus | None = None, device: int = 0) -> MaxSimAlignment:
+    """Which vector of every listed document scored best for every query vector (`mvfgpu_maxsim_align`; DESIGN.md §3
+    "Alignments"): the tokens or passages behind a late-interaction score.  `keys` holds values of the column, [m] for every
+    query or [nq, m] -- usually the keys `find_top_k_documents` or `rerank_top_k_documents` just returned; alignments are not part
+    of those searches: the recipe is the search, then this call on its keys.  Returns rows, scores and raw [nq, m, n_tokens] in list
+    order, padding (row UINT64_MAX) for values no live vector carries; a document's scores summed in token order are its
+    `rerank_top_k_documents` score.  The column is read as `find_top_k_per_key` reads it, with the same refusals; it and the
+    index live for this call (`GpuCorpus.maxsim_align` for many batches)."""
+    if metric is None:
+        metric = int(space.distance_metric())
+    if metric not in (L2, INNER_PRODUCT, COSINE):
+        raise BuildError(f"Unsupported distance metric {metric}")
+    total = space.total_vectors()
+    mc = space._reader.metadata_column(column)  # everything about the file's column is refused before anything is uploaded
+    es = {4: 4, 5: 8}.get(int(mc.data_type))
+    if es is None:
+        raise BuildError("Unsupported metadata column data type")
+    if mc.size // es < total:
+        raise BuildError(f"metadata column '{column}' holds {mc.size // es} values, the space has {total} vectors")
+    dt = int(space.data_type())
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        base = int(corpus.info().index_base)
+        with corpus.attach_column_pointer(mc.as_ptr(), int(mc.data_type), base, mc.size // es) as col:
+            with corpus.make_partition(col) as part:
+                return corpus.maxsim_align(np.asarray(query_vectors, dtype=_NP_OF[query_dtype_code(dt)]), keys, metric, part)
     finally:
         if own:
             corpus.close()
