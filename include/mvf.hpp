@@ -36,6 +36,7 @@
 
 #include "mvf_file.h"
 #include "mvf_gpu.h"
+#include "mvf_gpu_hamming.h"
 #include "mvf_gpu_maxsim_align.h"
 #include "mvf_gpu_maxsim_route.h"
 #include "mvf_gpu_mmr.h"
@@ -412,6 +413,21 @@ public:
                                                    (uint32_t)k, scores.data(), idx.data(), nullptr, &count));
         std::vector<ScoredVector> out;
         for (size_t i = 0; i < k && i < count; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
+    // Hamming search (mvfgpu_search_hamming, mvf_gpu_hamming.h; DESIGN.md section 3, "Hamming search"): the k rows of a UInt8
+    // space of bit-packed rows nearest to `query` -- the space's dimension() packed bytes -- by the number of differing bits;
+    // a hit's score is that distance, ties go by ascending position, k reaches MVFGPU_K_PER_PASS.  The usual first stage in
+    // front of rerank_top_k on the float space of the same file.
+    std::vector<ScoredVector> find_top_k_hamming(const std::vector<uint8_t>& query, size_t k) const {
+        if (dt_ != DataType::UInt8) throw MvfError(MVF_ERR_BUILD, "find_top_k_hamming takes a UInt8 space of bit-packed rows");
+        if (k == 0) return {};
+        std::vector<float> scores(k);
+        std::vector<uint64_t> idx(k);
+        detail::check_gpu(mvfgpu_search_hamming(c_, query.data(), MVF_DTYPE_UINT8, (uint32_t)query.size(), 1, (uint32_t)k, scores.data(),
+                                                idx.data(), nullptr));
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
         return out;
     }
     // Diversified re-ranking by maximal marginal relevance (mvfgpu_search_mmr, mvf_gpu_mmr.h): of the rows

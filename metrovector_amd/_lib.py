@@ -188,6 +188,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_mmr_form.restype = C.c_int
     lib.mvfgpu_selftest_mmr_stage_ms.argtypes = [vp, u8, vp, u8, u32, u32, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_mmr_stage_ms.restype = C.c_int
+    lib.mvfgpu_search_hamming.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp]
+    lib.mvfgpu_search_hamming.restype = C.c_int
+    lib.mvfgpu_search_hamming_device.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_search_hamming_device.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_form.argtypes = [u32, u32, u32, u64, u32, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_form.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_stage_ms.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_stage_ms.restype = C.c_int
     lib.mvfgpu_corpus_write_rows.argtypes = [vp, vp, u64, vp, u64, C.POINTER(WriteReport)]
     lib.mvfgpu_corpus_write_rows.restype = C.c_int
     lib.mvfgpu_corpus_write_rows_device.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(WriteReport)]

@@ -140,6 +140,30 @@ def mmr_form(dtype: int, dim: int, forced_g: int = 0) -> MmrForm:
     return MmrForm(out[0].value, out[1].value, bool(out[2].value))
 
 
+class HammingForm(NamedTuple):
+    form: int           # 0: register form (a lane keeps its 16-byte step of the row in registers), 1: streaming form
+    lanes_per_row: int  # lanes of a row's group
+    query_tile: int     # queries a scan block holds in LDS
+    row_slices: int     # row ranges the scan is split into
+    lds_bytes: int      # LDS of a scan block
+    merge_entries: int  # list entries H1 merges per query at most: row_slices * next_pow2(k) stays inside it
+
+
+def hamming_form(dim: int, nq: int, k: int, rows: int, num_cus: int = 0) -> HammingForm:
+    """The shape of a Hamming search over `rows` rows of `dim` packed bytes with `nq` queries in a window and list length k, on
+    a part of `num_cus` compute units (0: 256) -- the decision the launch itself takes (`mvfgpu_selftest_hamming_form`,
+    include/mvf_gpu_hamming.h; no GPU needed)."""
+    out = [C.c_uint32(0) for _ in range(6)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_form(dim, nq, k, rows, num_cus, *[C.byref(o) for o in out]))
+    return HammingForm(*[o.value for o in out])
+
+
+def pack_sign_bits(x) -> np.ndarray:
+    """Float embeddings [..., d] -> the rows or queries of a Hamming search, uint8 [..., ceil(d / 8)]: bit i of a row is
+    x[..., i] > 0, the first dimension in bit 0 of byte 0, the last byte zero-filled."""
+    return np.packbits(np.asarray(x) > 0, axis=-1, bitorder="little")
+
+
 def radius_bound(data_type: int, metric: int, radius: float) -> tuple[int, int]:
     """(largest matching order key, exact i32 bound of Int8/UInt8 L2/InnerProduct spaces) of a radius --
     `mvfgpu_selftest_radius_bound`; no GPU needed."""
@@ -754,6 +778,31 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_search_candidates_device(self._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                   nq, _opt(d_candidates), m, k, C.c_void_p(d_scores),
                                                                   C.c_void_p(d_indices), _opt(d_raw), _opt(d_counts), _opt(stream)))
+
+    def search_hamming(self, queries: np.ndarray, k: int) -> SearchResult:
+        """The k rows of smallest Hamming distance per query (`mvfgpu_search_hamming`, include/mvf_gpu_hamming.h) on a UInt8
+        corpus of bit-packed rows (`pack_sign_bits`): uint8 queries [nq, dimension]; raw = the distance, scores = float(raw),
+        ties by ascending position, at most 1024 results per query."""
+        q, qcode, nq, qdim = _query_args(queries)
+        sc, idx, raw = _result_arrays(nq, k)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_hamming(self._h, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
+                                                        sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                        raw.ctypes.data_as(C.c_void_p)))
+        return SearchResult(sc, idx, raw)
+
+    def search_hamming_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, d_scores: int,
+                              d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
+        """Device-pointer Hamming search (`mvfgpu_search_hamming_device`), asynchronous on `stream`."""
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_hamming_device(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
+                                                               C.c_void_p(d_scores), C.c_void_p(d_indices), _opt(d_raw), _opt(stream)))
+
+    def hamming_stage_ms(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, d_scores: int, d_indices: int,
+                         stream: int = 0) -> tuple[float, float]:
+        """(H0, H1) milliseconds of one device call (`mvfgpu_selftest_hamming_stage_ms`); waits for the stream."""
+        ms = (C.c_float * 2)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_stage_ms(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
+                                                                   C.c_void_p(d_scores), C.c_void_p(d_indices), None, _opt(stream), ms))
+        return float(ms[0]), float(ms[1])
 
     def search_mmr(self, queries: np.ndarray, candidates: np.ndarray, k: int, lambda_mult: float = 0.5, metric: int = L2) -> MmrResult:
         """Diversified re-ranking (`mvfgpu_search_mmr`, include/mvf_gpu_mmr.h): of each query's candidate rows -- `candidates`

@@ -107,6 +107,29 @@ def find_top_k_similar(space: VectorSpace, query, k: int, metric: int | None = N
     return out
 
 
+def find_top_k_hamming(space: VectorSpace, query, k: int, corpus: GpuCorpus | None = None, device: int = 0,
+                       with_vectors: bool = False) -> list[ScoredVector]:
+    """The k rows of a UInt8 space of bit-packed rows nearest to `query` by Hamming distance (`mvfgpu_search_hamming`;
+    DESIGN.md §3 "Hamming search"), following `find_top_k_similar`: `query` holds the space's `dimension()` packed bytes
+    (`pack_sign_bits` makes them from a float embedding), a hit's score is the distance, ties go by ascending position and
+    k reaches 1024.  The usual first stage in front of `rerank_top_k` on the float space of the same file; the row payloads
+    are fetched only when `with_vectors` is set."""
+    if int(space.data_type()) != 3:
+        raise BuildError("Hamming search takes a UInt8 space of bit-packed rows")
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        res = corpus.search_hamming(np.asarray(query, dtype=np.uint8), k)
+        valid = res.indices[0] != np.uint64(0xFFFFFFFFFFFFFFFF)  # fewer than k live rows: fewer items
+        rows = corpus.gather_rows(res.indices[0][valid]) if with_vectors and valid.any() else None
+    finally:
+        if own:
+            corpus.close()
+    return [ScoredVector(int(idx), float(score), rows[j].copy() if rows is not None else None)
+            for j, (idx, score) in enumerate(zip(res.indices[0][valid], res.scores[0][valid]))]
+
+
 def find_top_k_similar_batch(space: VectorSpace, queries, k: int, metric: int | None = None,
                              corpus: GpuCorpus | None = None, device: int = 0,
                              with_vectors: bool = False) -> list[list[ScoredVector]]:
