@@ -46,7 +46,8 @@ def test_against_numpy(dim, rows, nq, k):
 
 
 def test_rows_put_there_by_write_rows():
-    """the pitch padding of written rows holds whatever the write left there: the answer must not depend on it"""
+    """searches see written rows: a corpus created as all ones and overwritten row by row answers as the written rows do
+    (the write, like the upload, leaves zeros in the pitch padding behind `dimension`: DESIGN.md §5 "W0")"""
     x, q = _data(17, 3001, 5)
     with G.GpuCorpus.from_array(np.full_like(x, 0xFF), device=0) as c:
         c.write_rows(np.arange(3001, dtype=np.uint64), x)
