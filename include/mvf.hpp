@@ -37,6 +37,7 @@
 #include "mvf_file.h"
 #include "mvf_gpu.h"
 #include "mvf_gpu_hamming.h"
+#include "mvf_gpu_hamming_route.h"
 #include "mvf_gpu_maxsim_align.h"
 #include "mvf_gpu_maxsim_route.h"
 #include "mvf_gpu_mmr.h"
@@ -430,6 +431,10 @@ public:
         for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
         return out;
     }
+    // The route of find_top_k_hamming and of batched Hamming searches on the handle (mvfgpu_set_hamming_route,
+    // mvf_gpu_hamming_route.h): 0 the library's rule, 1 always xor and popcount, 2 the MFMA route where it is eligible (rows of
+    // up to 512 packed bytes).  The answers are the same bytes.
+    void set_hamming_route(int route) { detail::check_gpu(mvfgpu_set_hamming_route(c_, route)); }
     // Diversified re-ranking by maximal marginal relevance (mvfgpu_search_mmr, mvf_gpu_mmr.h): of the rows
     // `candidates` names (as rerank_top_k takes them, at most MVFGPU_MMR_MAX_CANDIDATES) k that are relevant and not near-copies
     // of each other, in pick order; lambda in [0, 1] -- 1 ranks by relevance alone.  Each hit's score is the query's score of

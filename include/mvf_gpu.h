@@ -1011,7 +1011,7 @@ int mvfgpu_set_scan_path(mvfgpu_corpus* corpus, int path);
 
 /*
  * The tuning switches of the environment (MVF_K1_G, MVF_K2_*, MVF_I8_SHADOW, MVF_F16_SHADOW, MVF_QS_REFINE,
- * MVF_STREAM_I8, MVF_STREAM_6B, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_FILTER_ROUTE, MVF_MAXSIM_ROUTE, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
+ * MVF_STREAM_I8, MVF_STREAM_6B, MVF_REPAIR_WINDOW, MVF_UPLOAD_THREADS, MVF_HOST_ZC_*, MVF_HOST_FLAG_WAIT, MVF_LARGE_K, MVF_FILTER_ROUTE, MVF_MAXSIM_ROUTE, MVF_HAMMING_ROUTE, MVF_DEBUG_REPAIR; INTEGRATION.md lists them) are read ONCE per
  * handle, when it is created: a search never calls getenv.  An A/B script that changes the environment of a live handle
  * calls this to have it read again.  A development aid: it waits for the handle's host-buffer searches, but
  * mvfgpu_search_device reads the switches unlocked -- do not call it beside device-pointer searches of the same handle.

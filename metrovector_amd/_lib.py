@@ -196,6 +196,12 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_hamming_form.restype = C.c_int
     lib.mvfgpu_selftest_hamming_stage_ms.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_hamming_stage_ms.restype = C.c_int
+    lib.mvfgpu_set_hamming_route.argtypes = [vp, i32]
+    lib.mvfgpu_set_hamming_route.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_route.argtypes = [u32, u32, u32, u64, i32, vp]
+    lib.mvfgpu_selftest_hamming_route.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_mfma_form.argtypes = [u32, u32, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_mfma_form.restype = C.c_int
     lib.mvfgpu_corpus_write_rows.argtypes = [vp, vp, u64, vp, u64, C.POINTER(WriteReport)]
     lib.mvfgpu_corpus_write_rows.restype = C.c_int
     lib.mvfgpu_corpus_write_rows_device.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(WriteReport)]

@@ -3,15 +3,19 @@
 //
 // Per window of up to 1024 queries, on one stream: H0 scans the rows once per query tile and leaves each row slice's sorted
 // best k per query, H1 merges a query's lists and writes its results (scan_hamming.hip).  The scratch is the lists alone.
+// Where hamming_route says so (include/mvf_gpu_hamming_route.h), HQ and H2 stand in H0's place: the same lists from the matrix
+// unit, with the prepared queries and the candidate buffers as further scratch (scan_hamming_mfma.hip; §5 "HQ / H2").
 // The host call runs the same device work per host window (host_staging.h); both calls keep mvfgpu_search_device's stream
 // discipline (corpus_device_call).  Nothing here reads norms, shadows or the repair feedback.
 
 #include "../../include/mvf_gpu_hamming.h"
+#include "../../include/mvf_gpu_hamming_route.h"
 
 #include "host_staging.h"
 #include "internal.h"
 #include "mvf_common.h"
 #include "scan_hamming.h"
+#include "scan_hamming_mfma.h"
 
 #include <algorithm>
 #include <string>
@@ -35,7 +39,7 @@ int check_hamming_args(const mvfgpu_corpus* c, const void* queries, uint8_t quer
 }
 
 // The device work of both calls: queries and results in device memory, everything on `s`, no host wait.
-// ms (the stage timer only): the windows' H0 and H1 times are added to ms[0..1]; waits for each window.
+// ms (the stage timer only): the windows' times before H1 (H0, or HQ + H2) and of H1 are added to ms[0..1]; waits for each window.
 int hamming_core(const CorpusView& v, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores, uint64_t* d_indices,
                  int32_t* d_raw, hipStream_t s, float* ms = nullptr) {
     hipEvent_t marks[3] = {nullptr, nullptr, nullptr};
@@ -45,10 +49,16 @@ int hamming_core(const CorpusView& v, const void* d_queries, uint32_t nq, uint32
             if (rc == MVF_OK && hipEventCreate(&e) != hipSuccess) rc = set_fail(MVF_ERR_DEVICE, "hipEventCreate failed");
     for (uint32_t w0 = 0; w0 < nq && rc == MVF_OK; w0 += kWindow) {
         const uint32_t wn = std::min(kWindow, nq - w0);
+        const bool mfma = hamming_route(v.dim, wn, k, v.n, v.hamming_route) == 2u;
         const HammingForm f = hamming_form(v.dim, wn, k, v.n, (uint32_t)v.num_cus);
-        AsyncBuf dlists;
-        if (const hipError_t e = dlists.alloc((size_t)wn * f.row_slices * f.kcap * 8, s)) {  // (the timer's events are destroyed below)
-            rc = set_fail(MVF_ERR_DEVICE, std::string("the slices' lists: ") + hipGetErrorString(e));
+        const HammingMfmaForm mf = mfma ? hamming_mfma_form(v.dim, wn, k, v.n, (uint32_t)v.num_cus) : HammingMfmaForm{};
+        const uint32_t row_slices = mfma ? mf.row_slices : f.row_slices, kcap = f.kcap;
+        AsyncBuf dlists, dprepared, dcand;
+        hipError_t ea = dlists.alloc((size_t)wn * row_slices * kcap * 8, s);
+        if (ea == hipSuccess && mfma) ea = dprepared.alloc((size_t)mf.prepared_bytes, s);
+        if (ea == hipSuccess && mfma) ea = dcand.alloc((size_t)mf.scratch_bytes, s);
+        if (ea != hipSuccess) {  // (the timer's events are destroyed below)
+            rc = set_fail(MVF_ERR_DEVICE, std::string("the slices' lists: ") + hipGetErrorString(ea));
             break;
         }
         HammingParams p{};
@@ -56,7 +66,7 @@ int hamming_core(const CorpusView& v, const void* d_queries, uint32_t nq, uint32
         p.queries = static_cast<const unsigned char*>(d_queries) + (size_t)w0 * v.dim;
         p.tomb = v.tomb;
         p.n = v.n;
-        p.slice_rows = f.slice_rows;
+        p.slice_rows = mfma ? mf.slice_rows : f.slice_rows;
         p.dim = v.dim;
         p.pitch = v.pitch;
         p.V = v.V;
@@ -64,15 +74,28 @@ int hamming_core(const CorpusView& v, const void* d_queries, uint32_t nq, uint32
         p.k = k;
         p.kcap = f.kcap;
         p.buf = f.buf;
-        p.query_tile = f.query_tile;
-        p.row_slices = f.row_slices;
+        p.query_tile = mfma ? mf.query_tile : f.query_tile;
+        p.row_slices = row_slices;
         p.lists = static_cast<uint64_t*>(dlists.p);
         p.index_base = v.index_base;
         p.ids = v.ids;
         p.out_scores = d_scores + (size_t)w0 * k;
         p.out_indices = d_indices + (size_t)w0 * k;
         p.out_raw = d_raw ? d_raw + (size_t)w0 * k : nullptr;
-        if (const hipError_t e = hamming_launch(f, p, s, ms ? marks : nullptr)) {
+        hipError_t e;
+        if (mfma) {
+            HammingMfmaParams a{};
+            a.p = p;
+            a.chunks = mf.chunks;
+            a.tiles = mf.tiles;
+            a.prepared = static_cast<unsigned char*>(dprepared.p);
+            a.starts = reinterpret_cast<float*>(a.prepared + (size_t)mf.tiles * mf.query_tile * ham_mfma_query_bytes(mf.chunks));
+            a.cand = static_cast<uint64_t*>(dcand.p);
+            e = hamming_mfma_launch(mf, a, s, ms ? marks : nullptr);
+        } else {
+            e = hamming_launch(f, p, s, ms ? marks : nullptr);
+        }
+        if (e != hipSuccess) {
             rc = set_fail(MVF_ERR_DEVICE, std::string("hamming_launch: ") + hipGetErrorString(e));
             break;
         }
@@ -150,6 +173,32 @@ int mvfgpu_selftest_hamming_stage_ms(const mvfgpu_corpus* c, const void* d_queri
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     out_ms[0] = out_ms[1] = 0.0f;
     return corpus_device_call(c, s, [&]() { return hamming_core(corpus_view(c), d_queries, nq, k, d_scores, d_indices, d_raw, s, out_ms); });
+}
+
+int mvfgpu_selftest_hamming_route(uint32_t dimension, uint32_t nq_in_window, uint32_t k, uint64_t rows, int forced, uint32_t* out_route) {
+    if (!out_route) return set_fail(MVF_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (forced < 0 || forced > 2) return set_fail(MVF_ERR_INVALID_ARGUMENT, "route must be 0, 1 or 2");
+    if (const int rc = mvfgpu_selftest_hamming_form(dimension, nq_in_window, k, rows, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    *out_route = hamming_route(dimension, std::min(nq_in_window, kWindow), k, rows, forced);
+    return MVF_OK;
+}
+
+int mvfgpu_selftest_hamming_mfma_form(uint32_t dimension, uint32_t nq, uint32_t k, uint64_t rows, uint32_t num_cus, uint32_t* out_query_tile,
+                                      uint32_t* out_rows_per_wave, uint32_t* out_threads, uint32_t* out_row_slices, uint64_t* out_slice_rows,
+                                      uint32_t* out_lds_bytes, uint64_t* out_prepared_bytes, uint64_t* out_scratch_bytes) {
+    if (const int rc = mvfgpu_selftest_hamming_form(dimension, nq, k, rows, num_cus, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (hamming_route(dimension, 1, k, rows, 2) != 2u)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT, "rows of more than 512 packed bytes are not eligible for the MFMA route, got " + std::to_string(dimension));
+    const HammingMfmaForm f = hamming_mfma_form(dimension, std::min(nq, kWindow), k, rows, num_cus);
+    if (out_query_tile) *out_query_tile = f.query_tile;
+    if (out_rows_per_wave) *out_rows_per_wave = f.wave_rows;
+    if (out_threads) *out_threads = f.threads;
+    if (out_row_slices) *out_row_slices = f.row_slices;
+    if (out_slice_rows) *out_slice_rows = f.slice_rows;
+    if (out_lds_bytes) *out_lds_bytes = f.lds_bytes;
+    if (out_prepared_bytes) *out_prepared_bytes = f.prepared_bytes;
+    if (out_scratch_bytes) *out_scratch_bytes = f.scratch_bytes;
+    return MVF_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,67 @@
+// hamming_select.h — what the Hamming scans share on the device (scan_hamming.hip: H0; scan_hamming_mfma.hip: HQ / H2): the
+// kernel attribute, a row's 16-byte step and its mask, the sort that cuts a query's buffer to k, and the slices' lists.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bitonic.h"
+#include "scan_hamming.h"
+
+namespace mvf {
+
+// A guard, not a tuning: the kernels are integer work whose answers are compared byte for byte, and they are compiled with the
+// packed-f32 VALU forms (v_pk_*_f32) switched off so that no compiler version lowers H1's one float conversion or a 64-bit
+// move to them.  Effect with the current compiler: none on the arithmetic -- the ISA holds no v_pk_* instruction with or
+// without the attribute -- but a callee without the attribute is not inlined into a kernel with it, so __syncthreads is a call here (a few dozen cycles beside each barrier) and the
+// helpers below use builtins and a plain word struct instead of the HIP vector types.  It can be removed without changing a result.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HAM_KERNEL __global__ __attribute__((target("no-packed-fp32-ops")))
+#else
+#define HAM_KERNEL __global__
+#endif
+
+// a 16-byte step as four words (a plain aggregate: loads and LDS reads of it are one 128-bit access)
+struct alignas(16) u32x4 {
+    uint32_t x, y, z, w;
+};
+
+// the u32 words of 16-byte step `step` that lie inside `dim` bytes: all ones, the tail's low bytes, or zero
+__device__ __forceinline__ u32x4 step_mask(uint32_t step, uint32_t dim) {
+    uint32_t m[4];
+#pragma unroll
+    for (uint32_t w = 0; w < 4; w++) {
+        const uint32_t at = step * 16u + w * 4u;
+        const uint32_t have = at >= dim ? 0u : (dim - at >= 4u ? 4u : dim - at);
+        m[w] = have == 4u ? 0xFFFFFFFFu : ((1u << (8u * have)) - 1u);
+    }
+    return u32x4{m[0], m[1], m[2], m[3]};
+}
+
+// One query's buffer settled by the whole block: buf[0 .. c) in any order -> its entries ascending in LDS, kPadComposite behind
+// them up to a power of two.  Returns what the query keeps, min(c, k); the caller's thread 0 stores it and the new threshold,
+// buf[k - 1] where the buffer held k.
+// REG (H2; NT = 256): the network runs in registers where 8 entries a thread hold the buffer -- a step inside a wave is a lane
+// exchange, and 512 entries take 6 barrier steps instead of 45.
+template <int NT, bool REG = false>
+__device__ __forceinline__ uint32_t sort_cut(uint64_t* buf, uint32_t c, uint32_t k, int tid) {
+    const uint32_t P = c < 2u ? 2u : next_pow2(c);
+    for (uint32_t i = c + (uint32_t)tid; i < P; i += NT) buf[i] = kPadComposite;
+    __syncthreads();
+    if (REG && P <= 2u * NT) bitonic_sort_u64_reg<NT, 2>(buf, P, tid);
+    else if (REG && P <= 8u * NT) bitonic_sort_u64_reg<NT, 8>(buf, P, tid);
+    else bitonic_sort_u64<NT>(buf, P, tid);
+    return c < k ? c : k;
+}
+
+// a tile's sorted lists -- query q's cnt[q] entries at bufs + q * p.buf -- to lists[q][slice][kcap]
+template <int NT>
+__device__ __forceinline__ void store_lists(const uint64_t* bufs, const uint32_t* cnt, const HammingParams& p, uint32_t q0, uint32_t qn,
+                                            uint32_t slice) {
+    for (uint32_t i = threadIdx.x; i < qn * p.kcap; i += NT) {
+        const uint32_t q = i / p.kcap, e = i % p.kcap;
+        p.lists[((size_t)(q0 + q) * p.row_slices + slice) * p.kcap + e] = e < cnt[q] ? bufs[(size_t)q * p.buf + e] : kPadComposite;
+    }
+}
+
+}  // namespace mvf

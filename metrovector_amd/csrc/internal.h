@@ -151,6 +151,7 @@ struct Tuning {
     int filter_route = 0;       // MVF_FILTER_ROUTE=1|2: a filtered search always by the mask route (1) / always by the list route (2; the list is then built whatever the count); 0: the rule (filter_route_rule)
     size_t maxsim_scratch = 512ull << 20;  // MVF_MAXSIM_SCRATCH_BYTES: the multi-vector search's scratch per window (tests: several token chunks and windows at a small shape)
     int maxsim_route = 0;       // MVF_MAXSIM_ROUTE=1|2: a multi-vector search always by the one-pass route (1) / by the MFMA selection route where it is eligible (2); 0: the rule (maxsim_route, scan_maxsim.h)
+    int hamming_route = 0;      // MVF_HAMMING_ROUTE=1|2: a Hamming search always by H0 (1) / by the MFMA route where it is eligible (2); 0: the rule (hamming_route, scan_hamming_mfma.h)
     int large_k = 0;            // MVF_LARGE_K=1|2: k beyond one pass always by passes (1; k <= 16384) / always by the whole-shard sort (2); 0: the cheaper one
 };
 Tuning read_tuning();
@@ -173,6 +174,7 @@ struct CorpusView {
     int filter_route = 0;            // Tuning::filter_route
     size_t maxsim_scratch = 0;       // Tuning::maxsim_scratch
     int maxsim_route = 0;            // mvfgpu_set_maxsim_route, else Tuning::maxsim_route
+    int hamming_route = 0;           // mvfgpu_set_hamming_route, else Tuning::hamming_route
 };
 CorpusView corpus_view(const mvfgpu_corpus* c);
 // bytes of one query of the handle's space: Float32, or the space's own type for Int8 / UInt8

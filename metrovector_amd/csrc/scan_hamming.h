@@ -93,5 +93,7 @@ struct HammingParams {
 // H0 over the grid (row slices x query tiles), then H1 with one block per query: two launches on `s`, no host wait.
 // marks (the stage timer only): three events, recorded in front of H0, between the two and behind H1.
 hipError_t hamming_launch(const HammingForm& f, const HammingParams& p, hipStream_t s, hipEvent_t* marks = nullptr);
+// H1 alone, over the lists[nq][p.row_slices][p.kcap] a scan left (hamming_launch's second launch; scan_hamming_mfma.hip's third)
+hipError_t hamming_merge_launch(const HammingParams& p, hipStream_t s);
 
 }  // namespace mvf

@@ -17,22 +17,12 @@
 #include "scan_hamming.h"
 
 #include "bitonic.h"
+#include "hamming_select.h"
 
 namespace mvf {
 namespace {
 
 constexpr int NT = (int)kHamThreads;
-
-// A guard, not a tuning: the kernels are integer work whose answers are compared byte for byte, and they are compiled with the
-// packed-f32 VALU forms (v_pk_*_f32) switched off so that no compiler version lowers H1's one float conversion or a 64-bit
-// move to them.  Effect with the current compiler: none on the arithmetic -- the ISA holds no v_pk_* instruction with or
-// without the attribute -- but a callee without the attribute is not inlined into a kernel with it, so __syncthreads is a call here (a few dozen cycles beside each barrier) and the
-// helpers below use builtins and a plain word struct instead of the HIP vector types.  It can be removed without changing a result.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define HAM_KERNEL __global__ __attribute__((target("no-packed-fp32-ops")))
-#else
-#define HAM_KERNEL __global__
-#endif
 
 template <int S>
 __device__ __forceinline__ uint32_t lane_xor(uint32_t v) {
@@ -61,28 +51,11 @@ __device__ __forceinline__ void butterfly_step(uint32_t (&acc)[QB], uint32_t sub
     }
 }
 
-// a 16-byte step as four words (a plain aggregate: loads and LDS reads of it are one 128-bit access)
-struct alignas(16) u32x4 {
-    uint32_t x, y, z, w;
-};
-
 __device__ __forceinline__ uint32_t xor_bits(const u32x4& a, const u32x4& b, uint32_t acc) {
     acc = __builtin_popcount(a.x ^ b.x) + acc;
     acc = __builtin_popcount(a.y ^ b.y) + acc;
     acc = __builtin_popcount(a.z ^ b.z) + acc;
     return __builtin_popcount(a.w ^ b.w) + acc;
-}
-
-// the u32 words of 16-byte step `step` that lie inside `dim` bytes: all ones, the tail's low bytes, or zero
-__device__ __forceinline__ u32x4 step_mask(uint32_t step, uint32_t dim) {
-    uint32_t m[4];
-#pragma unroll
-    for (uint32_t w = 0; w < 4; w++) {
-        const uint32_t at = step * 16u + w * 4u;
-        const uint32_t have = at >= dim ? 0u : (dim - at >= 4u ? 4u : dim - at);
-        m[w] = have == 4u ? 0xFFFFFFFFu : ((1u << (8u * have)) - 1u);
-    }
-    return u32x4{m[0], m[1], m[2], m[3]};
 }
 
 // A block's LDS: the queries' buffers, thresholds, words, counts and the flag "a buffer is nearly full".
@@ -147,26 +120,14 @@ __device__ __forceinline__ void settle(const TileLds& t, const HammingParams& p,
         if (!last && c + STEP <= p.buf) continue;
         c = c < p.buf ? c : p.buf;
         uint64_t* buf = t.bufs + (size_t)q * p.buf;
-        const uint32_t P = c < 2u ? 2u : next_pow2(c);
-        for (uint32_t i = c + (uint32_t)tid; i < P; i += NT) buf[i] = kPadComposite;
-        __syncthreads();
-        bitonic_sort_u64<NT>(buf, P, tid);
+        const uint32_t keep = sort_cut<NT>(buf, c, p.k, tid);
         if (tid == 0) {
-            const uint32_t keep = c < p.k ? c : p.k;
             t.cnt[q] = keep;
             t.thr[q] = keep >= p.k ? buf[p.k - 1u] : kPadComposite;
         }
     }
     if (tid == 0) t.flag[0] = 0;
     __syncthreads();
-}
-
-// the tile's sorted lists to lists[q][slice][kcap]
-__device__ __forceinline__ void store_lists(const TileLds& t, const HammingParams& p, uint32_t q0, uint32_t qn, uint32_t slice) {
-    for (uint32_t i = threadIdx.x; i < qn * p.kcap; i += NT) {
-        const uint32_t q = i / p.kcap, e = i % p.kcap;
-        p.lists[((size_t)(q0 + q) * p.row_slices + slice) * p.kcap + e] = e < t.cnt[q] ? t.bufs[(size_t)q * p.buf + e] : kPadComposite;
-    }
 }
 
 extern __shared__ __align__(16) unsigned char ham_smem[];
@@ -215,7 +176,7 @@ HAM_KERNEL __launch_bounds__(NT) void hamming_reg_kernel(const HammingParams p) 
         settle<STEP>(t, p, qn, false);
     }
     settle<STEP>(t, p, qn, true);
-    store_lists(t, p, q0, qn, slice);
+    store_lists<NT>(t.bufs, t.cnt, p, q0, qn, slice);
 }
 
 template <int G, int QT>
@@ -259,7 +220,7 @@ HAM_KERNEL __launch_bounds__(NT) void hamming_stream_kernel(const HammingParams 
         settle<STEP>(t, p, qn, false);
     }
     settle<STEP>(t, p, qn, true);
-    store_lists(t, p, q0, qn, slice);
+    store_lists<NT>(t.bufs, t.cnt, p, q0, qn, slice);
 }
 
 // H1
@@ -389,7 +350,14 @@ hipError_t hamming_launch(const HammingForm& f, const HammingParams& p, hipStrea
         if (e != hipSuccess) return e;
     }
     if (const hipError_t e = mark(1)) return e;
-    const uint32_t total = f.row_slices * f.kcap;  // H1
+    if (const hipError_t e = hamming_merge_launch(arg, s)) return e;
+    return mark(2);
+}
+
+hipError_t hamming_merge_launch(const HammingParams& p, hipStream_t s) {
+    HammingParams arg = p;
+    void* args[] = {&arg};
+    const uint32_t total = p.row_slices * p.kcap;
     const uint32_t held = total < kHamMergeLds ? (total < 2u ? 2u : next_pow2(total)) : kHamMergeLds;
     const size_t lds = (size_t)held * 8u;
     const void* mfn = reinterpret_cast<const void*>(&hamming_merge_kernel);
@@ -397,8 +365,7 @@ hipError_t hamming_launch(const HammingForm& f, const HammingParams& p, hipStrea
         const hipError_t e = hipFuncSetAttribute(mfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    if (const hipError_t e = hipLaunchKernel(mfn, dim3(p.nq), dim3(1024), args, lds, s)) return e;
-    return mark(2);
+    return hipLaunchKernel(mfn, dim3(p.nq), dim3(1024), args, lds, s);
 }
 
 }  // namespace mvf

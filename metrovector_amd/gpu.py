@@ -158,6 +158,34 @@ def hamming_form(dim: int, nq: int, k: int, rows: int, num_cus: int = 0) -> Hamm
     return HammingForm(*[o.value for o in out])
 
 
+class HammingMfmaForm(NamedTuple):
+    query_tile: int      # queries whose prepared bits a scan block holds in LDS
+    rows_per_wave: int   # rows a wave owns per iteration
+    threads: int         # threads of a scan block
+    row_slices: int      # row ranges the scan is split into
+    slice_rows: int      # rows of a slice
+    lds_bytes: int       # LDS of a scan block
+    prepared_bytes: int  # scratch: the prepared queries and their starts
+    scratch_bytes: int   # scratch: the candidate buffers
+
+
+def hamming_route(dim: int, nq: int, k: int, rows: int, forced: int = 0) -> int:
+    """The route one window of `nq` queries of a Hamming search takes over `rows` rows of `dim` packed bytes: 1 = xor and
+    popcount, 2 = the MFMA route; `forced` = 0 (the library's rule), 1 or 2 (`GpuCorpus.set_hamming_route`, `MVF_HAMMING_ROUTE`):
+    `mvfgpu_selftest_hamming_route`, include/mvf_gpu_hamming_route.h; no GPU needed."""
+    out = C.c_uint32(0)
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_route(dim, nq, k, rows, forced, C.byref(out)))
+    return out.value
+
+
+def hamming_mfma_form(dim: int, nq: int, k: int, rows: int, num_cus: int = 0) -> HammingMfmaForm:
+    """The shape of a window of a Hamming search on the MFMA route -- the decision the launch itself takes
+    (`mvfgpu_selftest_hamming_mfma_form`, include/mvf_gpu_hamming_route.h; no GPU needed)."""
+    out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_mfma_form(dim, nq, k, rows, num_cus, *[C.byref(o) for o in out]))
+    return HammingMfmaForm(*[o.value for o in out])
+
+
 def pack_sign_bits(x) -> np.ndarray:
     """Float embeddings [..., d] -> the rows or queries of a Hamming search, uint8 [..., ceil(d / 8)]: bit i of a row is
     x[..., i] > 0, the first dimension in bit 0 of byte 0, the last byte zero-filled."""
@@ -779,6 +807,11 @@ class GpuCorpus:
                                                                   nq, _opt(d_candidates), m, k, C.c_void_p(d_scores),
                                                                   C.c_void_p(d_indices), _opt(d_raw), _opt(d_counts), _opt(stream)))
 
+    def set_hamming_route(self, route: int) -> None:
+        """The route of `search_hamming` / `search_hamming_device`: 0 the library's rule, 1 always xor and popcount, 2 the MFMA
+        route where it is eligible (rows of up to 512 packed bytes); the answers are the same bytes (`mvfgpu_set_hamming_route`)."""
+        _lib.gpu_check(_lib.gpu().mvfgpu_set_hamming_route(self._h, route))
+
     def search_hamming(self, queries: np.ndarray, k: int) -> SearchResult:
         """The k rows of smallest Hamming distance per query (`mvfgpu_search_hamming`, include/mvf_gpu_hamming.h) on a UInt8
         corpus of bit-packed rows (`pack_sign_bits`): uint8 queries [nq, dimension]; raw = the distance, scores = float(raw),
@@ -798,7 +831,8 @@ class GpuCorpus:
 
     def hamming_stage_ms(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, d_scores: int, d_indices: int,
                          stream: int = 0) -> tuple[float, float]:
-        """(H0, H1) milliseconds of one device call (`mvfgpu_selftest_hamming_stage_ms`); waits for the stream."""
+        """(H0 -- or HQ + H2 on the MFMA route --, H1) milliseconds of one device call (`mvfgpu_selftest_hamming_stage_ms`);
+        waits for the stream."""
         ms = (C.c_float * 2)()
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_stage_ms(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
                                                                    C.c_void_p(d_scores), C.c_void_p(d_indices), None, _opt(stream), ms))

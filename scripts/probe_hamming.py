@@ -12,6 +12,11 @@ both paths, and says so.  Every figure is the median of the timed repetitions wi
 of every form.
 
     python scripts/probe_hamming.py [--out profiles/r24_hamming.txt] [--small]
+    python scripts/probe_hamming.py --routes [--out profiles/r25_hamming_mfma.txt] [--small]
+        (route 1, H0 + H1, against route 2, HQ + H2 + H1 -- mvfgpu_set_hamming_route -- on one handle in one process, alternating,
+        with the stage timer: 10M rows of 128 bytes at k = 100 over the window sizes 16 .. 1024, 10M rows of 32 .. 512 bytes at 1024
+        queries, k = 1024 once; H2's multiply-accumulates, nq x rows x bits, over the time in front of H1 against the datasheet's
+        dense FP4 and int8 matrix peaks; the answers of both routes compared on every timed shape; the unpacked L2 search once)
     rocprofv3 --pmc <counters> --output-format csv -d <dir> -- python scripts/probe_hamming.py --kernels-only
         (hardware counters of H0 / H1 in a run of their own: 10M rows, one and 1024 queries, two calls each, nothing timed)
 """
@@ -46,17 +51,87 @@ def event_ms(fn, stream, reps):
     return ts
 
 
+FP4_PEAK, I8_PEAK = 10.1e15 / 2, 5.0e15 / 2  # multiply-accumulates per second: the datasheet's dense MXFP4 and INT8 rates
+
+
+def routes_table(say, small):
+    """route 1 against route 2 per shape: the stage timer's (before H1, H1) of both, alternating, on one handle"""
+    n = 200_000 if small else 10_000_000
+    rng = np.random.default_rng(0x48414D)
+    st = torch.cuda.Stream()
+    say(f"Hamming search, routes 1 (H0 + H1) and 2 (HQ + H2 + H1) on one handle, MI355X, {n / 1e6:g}M random rows; stage timer, median "
+        f"[min .. max] of {REPS} repetitions alternating between the routes after a warm-up of both; scan = everything in front of H1")
+    shapes = [(DIM, nq, K) for nq in (16, 64, 128, 256, 1024)] + [(DIM, 1024, 1024)] + [(d, 1024, K) for d in (32, 64, 256, 512)]
+    wins = []
+    for dim in dict.fromkeys(d for d, _, _ in shapes):
+        x = rng.integers(0, 256, (n, dim), dtype=np.uint8)
+        with G.GpuCorpus.from_array(x, device=0) as c:
+            for _, nq, k in [sh for sh in shapes if sh[0] == dim]:
+                dq = torch.from_numpy(rng.integers(0, 256, (nq, dim), dtype=np.uint8)).cuda()
+                out = {r: (torch.empty((nq, k), dtype=torch.float32, device="cuda"), torch.empty((nq, k), dtype=torch.int64, device="cuda"))
+                       for r in (1, 2)}
+                torch.cuda.synchronize()
+
+                def stages(r):
+                    c.set_hamming_route(r)
+                    return c.hamming_stage_ms(dq.data_ptr(), G.UINT8, dim, nq, k, out[r][0].data_ptr(), out[r][1].data_ptr(), st.cuda_stream)
+
+                stages(1), stages(2)
+                same = torch.equal(out[1][0], out[2][0]) and torch.equal(out[1][1], out[2][1])
+                ms = {1: [], 2: []}
+                for _ in range(REPS):
+                    for r in (1, 2):
+                        ms[r].append(stages(r))
+                t = {r: np.array(ms[r]) for r in ms}
+                tot = {r: float(np.median(t[r].sum(1))) for r in t}
+                macs = float(nq) * n * dim * 8
+                rate = macs / (float(np.median(t[2][:, 0])) * 1e-3)
+                f = G.hamming_mfma_form(dim, nq, k, n)
+                say(f"{dim:4d} bytes nq {nq:4d} k {k:4d}: route 1 scan {spread(t[1][:, 0])} H1 {spread(t[1][:, 1])} | route 2 ({f.row_slices} slices, "
+                    f"tile {f.query_tile}) scan {spread(t[2][:, 0])} H1 {spread(t[2][:, 1])} | route 1 / route 2 {tot[1] / tot[2]:5.2f}x | H2 "
+                    f"{rate / 1e12:7.1f} T MAC/s = {100 * rate / FP4_PEAK:4.1f} % of the FP4 peak, {100 * rate / I8_PEAK:4.1f} % of the int8 peak | "
+                    f"same bytes: {'yes' if same else 'NO'}")
+                wins.append(((dim, nq, k), tot[1] / tot[2]))
+            c.set_hamming_route(0)
+            if dim == DIM:  # the recipe the packed search replaces, on the same box: the rows unpacked to 0/1 bytes under L2
+                try:
+                    with G.GpuCorpus.from_array(np.unpackbits(x, axis=1), device=0) as c8:
+                        dq8 = torch.from_numpy(rng.integers(0, 2, (1024, DIM * 8), dtype=np.uint8)).cuda()
+                        o8 = (torch.empty((1024, K), dtype=torch.float32, device="cuda"), torch.empty((1024, K), dtype=torch.int64, device="cuda"))
+                        torch.cuda.synchronize()
+
+                        def base():
+                            c8.search_device(dq8.data_ptr(), G.UINT8, DIM * 8, 1024, K, G.L2, o8[0].data_ptr(), o8[1].data_ptr(), 0, st.cuda_stream)
+
+                        for _ in range(3):
+                            base()
+                        st.synchronize()
+                        say(f"{DIM:4d} bytes nq 1024 k {K:4d}: the unpacked L2 search ({DIM * 8} UInt8 elements a row), device call {spread(event_ms(base, st, REPS))}")
+                except Exception as e:  # noqa: BLE001 - a refusal of the 8 x larger copy is reported
+                    say(f"the unpacked copy could not be held ({type(e).__name__}: {e}): the L2 search is not measured")
+        del x
+    say("route 1 / route 2 above 1.07 (the spread between boxes): " + ", ".join(f"{s} {w:.2f}x" for s, w in wins if w > 1.07))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--small", action="store_true", help="a rehearsal: 200k and 100k rows, 1 and 64 queries")
     ap.add_argument("--kernels-only", action="store_true", help="two device calls per shape and nothing else: for a counter run")
+    ap.add_argument("--routes", action="store_true", help="route 1 against route 2 (the MFMA route) over window sizes, row lengths and k")
     a = ap.parse_args()
     lines = []
 
     def say(s):
         print(s, flush=True)
         lines.append(s)
+
+    if a.routes:
+        routes_table(say, a.small)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
 
     n_big, n_cmp, nqs = (200_000, 100_000, [1, 64]) if a.small else (10_000_000, 2_000_000, [1, 1024])
     rng = np.random.default_rng(0x48414D)
