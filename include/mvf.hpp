@@ -41,6 +41,7 @@
 #include "mvf_gpu_maxsim_align.h"
 #include "mvf_gpu_maxsim_route.h"
 #include "mvf_gpu_mmr.h"
+#include "mvf_gpu_signbits.h"
 #include "mvf_gpu_update.h"
 #include "mvf_status.h"
 
@@ -427,6 +428,21 @@ public:
         std::vector<uint64_t> idx(k);
         detail::check_gpu(mvfgpu_search_hamming(c_, query.data(), MVF_DTYPE_UINT8, (uint32_t)query.size(), 1, (uint32_t)k, scores.data(),
                                                 idx.data(), nullptr));
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
+    // Sign-bit search (mvfgpu_search_signbits, mvf_gpu_signbits.h; DESIGN.md section 3, "Sign-bit search"): the k rows of a UInt8
+    // space of bit-packed rows of up to 512 bytes that score highest against an Int8 `query` of 8 x dimension() elements,
+    // sum over e of query[e] * (bit e of the row ? +1 : -1); a hit's score is that exact sum, ties go by ascending position,
+    // k reaches MVFGPU_K_PER_PASS.  The asymmetric first stage in front of rerank_top_k on the float space of the same file.
+    std::vector<ScoredVector> find_top_k_signbits(const std::vector<int8_t>& query, size_t k) const {
+        if (dt_ != DataType::UInt8) throw MvfError(MVF_ERR_BUILD, "find_top_k_signbits takes a UInt8 space of bit-packed rows");
+        if (k == 0) return {};
+        std::vector<float> scores(k);
+        std::vector<uint64_t> idx(k);
+        detail::check_gpu(mvfgpu_search_signbits(c_, query.data(), MVF_DTYPE_INT8, (uint32_t)query.size(), 1, (uint32_t)k, scores.data(),
+                                                 idx.data(), nullptr));
         std::vector<ScoredVector> out;
         for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
         return out;

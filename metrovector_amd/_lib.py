@@ -202,6 +202,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_hamming_route.restype = C.c_int
     lib.mvfgpu_selftest_hamming_mfma_form.argtypes = [u32, u32, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_hamming_mfma_form.restype = C.c_int
+    lib.mvfgpu_search_signbits.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp]
+    lib.mvfgpu_search_signbits.restype = C.c_int
+    lib.mvfgpu_search_signbits_device.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_search_signbits_device.restype = C.c_int
+    lib.mvfgpu_selftest_signbits_form.argtypes = [u32, u32, u32, u64, u32, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_signbits_form.restype = C.c_int
+    lib.mvfgpu_selftest_signbits_stage_ms.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_signbits_stage_ms.restype = C.c_int
     lib.mvfgpu_corpus_write_rows.argtypes = [vp, vp, u64, vp, u64, C.POINTER(WriteReport)]
     lib.mvfgpu_corpus_write_rows.restype = C.c_int
     lib.mvfgpu_corpus_write_rows_device.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(WriteReport)]

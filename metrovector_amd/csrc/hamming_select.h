@@ -1,5 +1,6 @@
 // hamming_select.h — what the Hamming scans share on the device (scan_hamming.hip: H0; scan_hamming_mfma.hip: HQ / H2): the
-// kernel attribute, a row's 16-byte step and its mask, the sort that cuts a query's buffer to k, and the slices' lists.
+// kernel attribute, a row's 16-byte step and its mask, the sort that cuts a query's buffer to k, and the slices' lists; and what
+// H2 shares with the sign-bit scan (scan_signbits.hip: S2): a row chunk's load and the candidate buffers in the global scratch.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -61,6 +62,69 @@ __device__ __forceinline__ void store_lists(const uint64_t* bufs, const uint32_t
     for (uint32_t i = threadIdx.x; i < qn * p.kcap; i += NT) {
         const uint32_t q = i / p.kcap, e = i % p.kcap;
         p.lists[((size_t)(q0 + q) * p.row_slices + slice) * p.kcap + e] = e < cnt[q] ? bufs[(size_t)q * p.buf + e] : kPadComposite;
+    }
+}
+
+// ---- what the matrix-unit scans share (scan_hamming_mfma.hip: H2; scan_signbits.hip: S2) ----
+
+// The selection part of such a block's LDS: the sort area, the queries' thresholds and counts, the flag "a buffer is nearly full".
+struct SelectLds {
+    uint64_t *sort, *thr;
+    uint32_t *cnt, *flag;
+};
+
+// A live row whose composite (key << 32 | row, smaller is better) beats the query's threshold joins the query's buffer in the
+// global scratch cand[query][buf] of the block (H0's rule and H0's bookkeeping: between two checks a buffer receives each row
+// once at most, so it cannot run over).
+__device__ __forceinline__ void offer(const SelectLds& t, const HammingParams& p, uint64_t* cand, uint32_t q, uint32_t key, uint32_t r) {
+    const uint64_t comp = ((uint64_t)key << 32) | r;
+    if (comp < t.thr[q] && !(p.tomb && ((p.tomb[r >> 5] >> (r & 31u)) & 1u))) {
+        const uint32_t slot = __hip_atomic_fetch_add(&t.cnt[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (slot < p.buf) cand[(size_t)q * p.buf + slot] = comp;
+        if (slot + 1u + kHamStepRows > p.buf) t.flag[0] = 1u;
+    }
+}
+
+// Behind an iteration: every buffer that could not take kHamStepRows more entries (all of them at the end of the slice) goes
+// through the sort area: sorted, cut to k, written back, its threshold lowered to its k-th composite.
+template <int NT>
+__device__ __forceinline__ void settle(const SelectLds& t, const HammingParams& p, uint64_t* cand, uint32_t qn, bool last) {
+    const int tid = (int)threadIdx.x;
+    __syncthreads();
+    const uint32_t full = t.flag[0];
+    __syncthreads();
+    if (!full && !last) return;
+    for (uint32_t q = 0; q < qn; q++) {
+        uint32_t c = t.cnt[q];
+        if (!last && c + kHamStepRows <= p.buf) continue;
+        c = c < p.buf ? c : p.buf;
+        uint64_t* own = cand + (size_t)q * p.buf;
+        for (uint32_t i = (uint32_t)tid; i < c; i += NT) t.sort[i] = own[i];
+        const uint32_t keep = sort_cut<NT, true>(t.sort, c, p.k, tid);
+        for (uint32_t i = (uint32_t)tid; i < keep; i += NT) own[i] = t.sort[i];
+        if (tid == 0) {
+            t.cnt[q] = keep;
+            t.thr[q] = keep >= p.k ? t.sort[p.k - 1u] : kPadComposite;
+        }
+        __syncthreads();  // the sort area is the next query's
+    }
+    if (tid == 0) t.flag[0] = 0;
+    __syncthreads();
+}
+
+// the lane's 16 bytes of chunk t of its F rows (row0, row0 + 16, ...; g the lane's k-group): zeros behind the slice's end and
+// behind the pitch, the row's last step masked to `dim` (the pitch padding is never relied on)
+template <int F>
+__device__ __forceinline__ void load_chunk(uint32_t (&w)[F][4], const HammingParams& p, uint64_t row0, uint64_t hi, uint32_t t, uint32_t g,
+                                           const u32x4& tail) {
+    const uint32_t step = t * 4u + g;
+#pragma unroll
+    for (int f = 0; f < F; f++) {
+        const uint64_t r = row0 + (uint64_t)(f * 16);
+        u32x4 v{0, 0, 0, 0};
+        if (r < hi && step < p.V) v = *(reinterpret_cast<const u32x4*>(p.rows + r * p.pitch) + step);
+        if (step == p.V - 1u) v.x &= tail.x, v.y &= tail.y, v.z &= tail.z, v.w &= tail.w;
+        w[f][0] = v.x, w[f][1] = v.y, w[f][2] = v.z, w[f][3] = v.w;
     }
 }
 

@@ -88,6 +88,8 @@ struct HammingParams {
     float* out_scores;             // [nq][k]
     uint64_t* out_indices;
     int32_t* out_raw;              // nullable
+    int32_t score_bias;            // 0: a key is a distance, written as it is (+inf padding).  Otherwise (scan_signbits.hip) a key is
+                                   // score_bias - s for a score s where larger is better: H1 writes s (-inf padding)
 };
 
 // H0 over the grid (row slices x query tiles), then H1 with one block per query: two launches on `s`, no host wait.

@@ -279,15 +279,16 @@ HAM_KERNEL __launch_bounds__(1024) void hamming_merge_kernel(const HammingParams
     for (uint32_t i = tid; i < p.k; i += 1024u) {
         const uint64_t comp = i < have ? buf[i] : kPadComposite;
         const size_t o = (size_t)q * p.k + i;
-        if (comp == kPadComposite) {  // mvfgpu_search's padding under L2
-            p.out_scores[o] = pad_score(MVF_METRIC_L2);
+        if (comp == kPadComposite) {  // mvfgpu_search's padding under L2; under InnerProduct for a biased key
+            p.out_scores[o] = pad_score(p.score_bias ? MVF_METRIC_INNER_PRODUCT : MVF_METRIC_L2);
             p.out_indices[o] = ~0ull;
             if (p.out_raw) p.out_raw[o] = 0;
         } else {
-            const uint32_t d = (uint32_t)(comp >> 32), r = (uint32_t)comp;
-            p.out_scores[o] = (float)d;  // exact: d < 2^24
+            const uint32_t r = (uint32_t)comp;
+            const int32_t d = p.score_bias ? p.score_bias - (int32_t)(comp >> 32) : (int32_t)(comp >> 32);
+            p.out_scores[o] = (float)d;  // exact: |d| < 2^24
             p.out_indices[o] = p.ids ? p.ids[r] : p.index_base + r;
-            if (p.out_raw) p.out_raw[o] = (int32_t)d;
+            if (p.out_raw) p.out_raw[o] = d;
         }
     }
 }

@@ -74,65 +74,11 @@ HAM_KERNEL __launch_bounds__(256) void hamming_prepare_kernel(const HammingMfmaP
 
 extern __shared__ __align__(16) unsigned char ham_mfma_smem[];
 
-// A block's LDS: the staged queries, the sort area, thresholds, starts, counts and the flag "a buffer is nearly full".
-struct MfmaLds {
+// A block's LDS: the staged queries and the starts beside the selection's part (hamming_select.h: offer, settle, load_chunk).
+struct MfmaLds : SelectLds {
     const u32x4* qs;
-    uint64_t *sort, *thr;
     float* start;
-    uint32_t *cnt, *flag;
 };
-
-// A live row whose composite beats the query's threshold joins the query's buffer in the scratch (H0's rule and H0's
-// bookkeeping: between two checks a buffer receives each row once at most, so it cannot run over).
-__device__ __forceinline__ void offer(const MfmaLds& t, const HammingParams& p, uint64_t* cand, uint32_t q, uint32_t d, uint32_t r) {
-    const uint64_t comp = ((uint64_t)d << 32) | r;
-    if (comp < t.thr[q] && !(p.tomb && ((p.tomb[r >> 5] >> (r & 31u)) & 1u))) {
-        const uint32_t slot = __hip_atomic_fetch_add(&t.cnt[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (slot < p.buf) cand[(size_t)q * p.buf + slot] = comp;
-        if (slot + 1u + kHamStepRows > p.buf) t.flag[0] = 1u;
-    }
-}
-
-// Behind an iteration: every buffer that could not take kHamStepRows more entries (all of them at the end of the slice) goes
-// through the sort area: sorted, cut to k, written back, its threshold lowered to its k-th composite.
-__device__ __forceinline__ void settle(const MfmaLds& t, const HammingParams& p, uint64_t* cand, uint32_t qn, bool last) {
-    const int tid = (int)threadIdx.x;
-    __syncthreads();
-    const uint32_t full = t.flag[0];
-    __syncthreads();
-    if (!full && !last) return;
-    for (uint32_t q = 0; q < qn; q++) {
-        uint32_t c = t.cnt[q];
-        if (!last && c + kHamStepRows <= p.buf) continue;
-        c = c < p.buf ? c : p.buf;
-        uint64_t* own = cand + (size_t)q * p.buf;
-        for (uint32_t i = (uint32_t)tid; i < c; i += NT) t.sort[i] = own[i];
-        const uint32_t keep = sort_cut<NT, true>(t.sort, c, p.k, tid);
-        for (uint32_t i = (uint32_t)tid; i < keep; i += NT) own[i] = t.sort[i];
-        if (tid == 0) {
-            t.cnt[q] = keep;
-            t.thr[q] = keep >= p.k ? t.sort[p.k - 1u] : kPadComposite;
-        }
-        __syncthreads();  // the sort area is the next query's
-    }
-    if (tid == 0) t.flag[0] = 0;
-    __syncthreads();
-}
-
-// the lane's 16 bytes of chunk t of its F rows: zeros behind the slice's end and behind the pitch, the row's last step masked
-// to `dim` (the pitch padding is never relied on)
-__device__ __forceinline__ void load_chunk(uint32_t (&w)[F][4], const HammingParams& p, uint64_t row0, uint64_t hi, uint32_t t, uint32_t g,
-                                           const u32x4& tail) {
-    const uint32_t step = t * 4u + g;
-#pragma unroll
-    for (int f = 0; f < F; f++) {
-        const uint64_t r = row0 + (uint64_t)(f * 16);
-        u32x4 v{0, 0, 0, 0};
-        if (r < hi && step < p.V) v = *(reinterpret_cast<const u32x4*>(p.rows + r * p.pitch) + step);
-        if (step == p.V - 1u) v.x &= tail.x, v.y &= tail.y, v.z &= tail.z, v.w &= tail.w;
-        w[f][0] = v.x, w[f][1] = v.y, w[f][2] = v.z, w[f][3] = v.w;
-    }
-}
 
 template <int NC>
 HAM_KERNEL __launch_bounds__(NT) void hamming_mfma_kernel(const HammingMfmaParams a) {
@@ -230,9 +176,9 @@ HAM_KERNEL __launch_bounds__(NT) void hamming_mfma_kernel(const HammingMfmaParam
                 }
             }
         }
-        settle(t, p, cand, qn, false);
+        settle<NT>(t, p, cand, qn, false);
     }
-    settle(t, p, cand, qn, true);
+    settle<NT>(t, p, cand, qn, true);
     store_lists<NT>(cand, t.cnt, p, q0, qn, slice);
 }
 

@@ -192,6 +192,33 @@ def pack_sign_bits(x) -> np.ndarray:
     return np.packbits(np.asarray(x) > 0, axis=-1, bitorder="little")
 
 
+class SignbitsForm(NamedTuple):
+    query_tile: int     # queries whose prepared elements a scan block holds in LDS: 16, 32, 64 or 128
+    row_slices: int     # row ranges the scan is split into
+    chunks: int         # 64-byte chunks of a row
+    lds_bytes: int      # LDS of a scan block
+    scratch_bytes: int  # scratch: the candidate buffers
+
+
+def signbits_form(dim: int, nq: int, k: int, rows: int, num_cus: int = 0) -> SignbitsForm:
+    """The shape of a window of a sign-bit search over `rows` rows of `dim` packed bytes with `nq` queries and list length k, on
+    a part of `num_cus` compute units (0: 256) -- the decision the launch itself takes (`mvfgpu_selftest_signbits_form`,
+    include/mvf_gpu_signbits.h; no GPU needed)."""
+    out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_signbits_form(dim, nq, k, rows, num_cus, *[C.byref(o) for o in out]))
+    return SignbitsForm(*[o.value for o in out])
+
+
+def quantize_queries_int8(x) -> np.ndarray:
+    """Float embeddings [..., d] -> the queries of a sign-bit search, int8 [..., 8 * ceil(d / 8)]: each query scaled by
+    127 / max|x| of its own, rounded to nearest (np.rint) and padded with zero elements, which score 0 whatever the bit; an
+    all-zero query stays zero.  The scale changes no ranking: a query's scores are all multiplied by it."""
+    x = np.asarray(x, dtype=np.float64)
+    top = np.max(np.abs(x), axis=-1, keepdims=True) if x.shape[-1] else np.zeros(x.shape[:-1] + (1,))
+    q = np.rint(x * (127.0 / np.where(top > 0, top, 1.0))).astype(np.int8)
+    return np.pad(q, [(0, 0)] * (q.ndim - 1) + [(0, -x.shape[-1] % 8)])
+
+
 def radius_bound(data_type: int, metric: int, radius: float) -> tuple[int, int]:
     """(largest matching order key, exact i32 bound of Int8/UInt8 L2/InnerProduct spaces) of a radius --
     `mvfgpu_selftest_radius_bound`; no GPU needed."""
@@ -837,6 +864,32 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_stage_ms(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
                                                                    C.c_void_p(d_scores), C.c_void_p(d_indices), None, _opt(stream), ms))
         return float(ms[0]), float(ms[1])
+
+    def search_signbits(self, queries: np.ndarray, k: int) -> SearchResult:
+        """The k rows of largest sign-bit score per query (`mvfgpu_search_signbits`, include/mvf_gpu_signbits.h) on a UInt8
+        corpus of bit-packed rows of up to 512 bytes (`pack_sign_bits`): int8 queries [nq, 8 * dimension]
+        (`quantize_queries_int8`); raw = sum_e q[e] * (bit e ? +1 : -1), scores = float(raw), ties by ascending position, at
+        most 1024 results per query."""
+        q, qcode, nq, qdim = _query_args(queries)
+        sc, idx, raw = _result_arrays(nq, k)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_signbits(self._h, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
+                                                         sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                         raw.ctypes.data_as(C.c_void_p)))
+        return SearchResult(sc, idx, raw)
+
+    def search_signbits_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, d_scores: int,
+                               d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
+        """Device-pointer sign-bit search (`mvfgpu_search_signbits_device`), asynchronous on `stream`."""
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_signbits_device(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
+                                                                C.c_void_p(d_scores), C.c_void_p(d_indices), _opt(d_raw), _opt(stream)))
+
+    def signbits_stage_ms(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, d_scores: int, d_indices: int,
+                          stream: int = 0) -> tuple[float, float, float]:
+        """(prepare, scan, merge) milliseconds of one device call (`mvfgpu_selftest_signbits_stage_ms`); waits for the stream."""
+        ms = (C.c_float * 3)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_signbits_stage_ms(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
+                                                                    C.c_void_p(d_scores), C.c_void_p(d_indices), None, _opt(stream), ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def search_mmr(self, queries: np.ndarray, candidates: np.ndarray, k: int, lambda_mult: float = 0.5, metric: int = L2) -> MmrResult:
         """Diversified re-ranking (`mvfgpu_search_mmr`, include/mvf_gpu_mmr.h): of each query's candidate rows -- `candidates`

@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .errors import BuildError, InvalidVectorType
-from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, MaxSimAlignment, MaxSimResult, SearchResult, pack_allow_mask, query_dtype_code
+from .gpu import COSINE, INNER_PRODUCT, L2, GpuCorpus, MaxSimAlignment, MaxSimResult, SearchResult, pack_allow_mask, quantize_queries_int8, query_dtype_code
 from .reader import VectorSpace
 
 _NP_OF = {0: np.float32, 1: np.float16, 2: np.int8, 3: np.uint8}
@@ -121,6 +121,33 @@ def find_top_k_hamming(space: VectorSpace, query, k: int, corpus: GpuCorpus | No
         corpus = upload_space(space, device)
     try:
         res = corpus.search_hamming(np.asarray(query, dtype=np.uint8), k)
+        valid = res.indices[0] != np.uint64(0xFFFFFFFFFFFFFFFF)  # fewer than k live rows: fewer items
+        rows = corpus.gather_rows(res.indices[0][valid]) if with_vectors and valid.any() else None
+    finally:
+        if own:
+            corpus.close()
+    return [ScoredVector(int(idx), float(score), rows[j].copy() if rows is not None else None)
+            for j, (idx, score) in enumerate(zip(res.indices[0][valid], res.scores[0][valid]))]
+
+
+def find_top_k_signbits(space: VectorSpace, query, k: int, corpus: GpuCorpus | None = None, device: int = 0,
+                        with_vectors: bool = False) -> list[ScoredVector]:
+    """The k rows of a UInt8 space of bit-packed rows (up to 512 bytes each) that score highest against a query that keeps its
+    magnitudes: sum_e q[e] * (bit e of the row ? +1 : -1) (`mvfgpu_search_signbits`; DESIGN.md §3 "Sign-bit search"),
+    following `find_top_k_hamming`.  A float `query` of up to 8 * `dimension()` elements is quantised with
+    `quantize_queries_int8`, an int8 one is taken as it is; a hit's score is the exact integer sum, ties go by ascending
+    position and k reaches 1024.  A first stage in front of `rerank_top_k` on the float space of the same file; the row
+    payloads are fetched only when `with_vectors` is set."""
+    if int(space.data_type()) != 3:
+        raise BuildError("sign-bit search takes a UInt8 space of bit-packed rows")
+    q = np.asarray(query)
+    if q.dtype != np.int8:
+        q = quantize_queries_int8(q)
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        res = corpus.search_signbits(q, k)
         valid = res.indices[0] != np.uint64(0xFFFFFFFFFFFFFFFF)  # fewer than k live rows: fewer items
         rows = corpus.gather_rows(res.indices[0][valid]) if with_vectors and valid.any() else None
     finally:
