@@ -41,6 +41,7 @@
 #include "mvf_gpu_maxsim_align.h"
 #include "mvf_gpu_maxsim_route.h"
 #include "mvf_gpu_mmr.h"
+#include "mvf_gpu_hamming_radius.h"
 #include "mvf_gpu_signbits.h"
 #include "mvf_gpu_update.h"
 #include "mvf_status.h"
@@ -430,6 +431,23 @@ public:
                                                 idx.data(), nullptr));
         std::vector<ScoredVector> out;
         for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
+    // Hamming radius search (mvfgpu_search_hamming_radius, mvf_gpu_hamming_radius.h; DESIGN.md section 3, "Hamming radius
+    // search"): every row of a UInt8 space of bit-packed rows of up to 512 bytes within `radius` bits of `query`, inclusive --
+    // near-duplicate and perceptual-hash lookups.  Returns the best max_results matches (0 .. MVFGPU_K_PER_PASS) as
+    // find_top_k_hamming returns hits; *count (nullable) receives the exact number of matches, also beyond max_results.
+    std::vector<ScoredVector> find_within_hamming(const std::vector<uint8_t>& query, uint32_t radius, size_t max_results,
+                                                  uint64_t* count = nullptr) const {
+        if (dt_ != DataType::UInt8) throw MvfError(MVF_ERR_BUILD, "find_within_hamming takes a UInt8 space of bit-packed rows");
+        uint64_t n = 0;
+        std::vector<float> scores(max_results);
+        std::vector<uint64_t> idx(max_results);
+        detail::check_gpu(mvfgpu_search_hamming_radius(c_, query.data(), MVF_DTYPE_UINT8, (uint32_t)query.size(), 1, &radius, max_results, &n,
+                                                       max_results ? scores.data() : nullptr, max_results ? idx.data() : nullptr, nullptr));
+        if (count) *count = n;
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < max_results && i < n; i++) out.push_back({idx[i], scores[i], {}});
         return out;
     }
     // Sign-bit search (mvfgpu_search_signbits, mvf_gpu_signbits.h; DESIGN.md section 3, "Sign-bit search"): the k rows of a UInt8

@@ -1,6 +1,7 @@
 // hamming_select.h — what the Hamming scans share on the device (scan_hamming.hip: H0; scan_hamming_mfma.hip: HQ / H2): the
 // kernel attribute, a row's 16-byte step and its mask, the sort that cuts a query's buffer to k, and the slices' lists; and what
-// H2 shares with the sign-bit scan (scan_signbits.hip: S2): a row chunk's load and the candidate buffers in the global scratch.
+// H2 shares with the sign-bit scan (scan_signbits.hip: S2): a row chunk's load and the candidate buffers in the global scratch;
+// and what H2 shares with the radius scan (scan_hamming_radius.hip: HR2): a row word's FP4 operand.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -126,6 +127,17 @@ __device__ __forceinline__ void load_chunk(uint32_t (&w)[F][4], const HammingPar
         if (step == p.V - 1u) v.x &= tail.x, v.y &= tail.y, v.z &= tail.z, v.w &= tail.w;
         w[f][0] = v.x, w[f][1] = v.y, w[f][2] = v.z, w[f][3] = v.w;
     }
+}
+
+// ---- what the FP4 scans share (scan_hamming_mfma.hip: H2; scan_hamming_radius.hip: HR2) ----
+
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+// A row's word w as the A operand of one v_mfma_scale_f32_16x16x128_f8f6f4 step (scan_hamming_mfma.hip, "Operands"): VGPR j holds
+// bit 4 n + j of w in nibble n as FP4 0x2 = 1.0 where the bit is set, 0 elsewhere; an FP4 operand fills four of the eight VGPRs.
+__device__ __forceinline__ v8i fp4_row_operand(uint32_t w) {
+    return v8i{(int)((w << 1) & 0x22222222u), (int)(w & 0x22222222u), (int)((w >> 1) & 0x22222222u), (int)((w >> 2) & 0x22222222u), 0, 0, 0, 0};
 }
 
 }  // namespace mvf

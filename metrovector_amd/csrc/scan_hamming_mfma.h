@@ -92,6 +92,10 @@ struct HammingMfmaParams {
     uint64_t* cand;           // [slice][tile][QT][buf] composites
 };
 
+// HQ alone: a.p.queries [a.p.nq][a.p.dim] -> a.prepared and a.starts for a.tiles tiles of a.p.query_tile = 16 x {1, 2, 4, 8}
+// queries (H2 takes 128 or 64; scan_hamming_radius.hip's HR2 every one of them).  One launch on `s`.
+hipError_t hamming_prepare_launch(const HammingMfmaParams& a, hipStream_t s);
+
 // HQ, H2 over the grid (row slices x query tiles), then H1: three launches on `s`, no host wait.
 // marks (the stage timer only): three events, recorded in front of HQ, between H2 and H1 and behind H1.
 hipError_t hamming_mfma_launch(const HammingMfmaForm& f, const HammingMfmaParams& a, hipStream_t s, hipEvent_t* marks = nullptr);

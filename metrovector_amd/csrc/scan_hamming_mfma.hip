@@ -36,9 +36,6 @@ namespace {
 constexpr int NT = (int)kHamMfmaThreads;
 constexpr int F = (int)kHamMfmaWaveRows / 16;  // A fragments of a wave
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 // HQ: one thread per 16-byte item of the prepared queries; the first item of a query also counts its bits.  Queries behind
 // the window's last fill their tile as all-zero queries: nothing H2 stages is unwritten.
 HAM_KERNEL __launch_bounds__(256) void hamming_prepare_kernel(const HammingMfmaParams a) {
@@ -134,11 +131,7 @@ HAM_KERNEL __launch_bounds__(NT) void hamming_mfma_kernel(const HammingMfmaParam
                 for (int m = 0; m < 4; m++) {
                     v8i av[F];
 #pragma unroll
-                    for (int f = 0; f < F; f++) {
-                        const uint32_t w = cur[f][m];
-                        av[f] = v8i{(int)((w << 1) & 0x22222222u), (int)(w & 0x22222222u), (int)((w >> 1) & 0x22222222u),
-                                    (int)((w >> 2) & 0x22222222u), 0, 0, 0, 0};
-                    }
+                    for (int f = 0; f < F; f++) av[f] = fp4_row_operand(cur[f][m]);
 #pragma unroll
                     for (int c = 0; c < NC; c++) {
                         const u32x4 b = bq[(m * NC + c) * 64];
@@ -184,6 +177,14 @@ HAM_KERNEL __launch_bounds__(NT) void hamming_mfma_kernel(const HammingMfmaParam
 
 }  // namespace
 
+hipError_t hamming_prepare_launch(const HammingMfmaParams& a, hipStream_t s) {
+    HammingMfmaParams arg = a;
+    void* args[] = {&arg};
+    const uint32_t items = a.tiles * a.p.query_tile * a.chunks * 16u;
+    if (items == 0) return hipSuccess;
+    return hipLaunchKernel(reinterpret_cast<const void*>(&hamming_prepare_kernel), dim3((items + 255u) / 256u), dim3(256), args, 0, s);
+}
+
 hipError_t hamming_mfma_launch(const HammingMfmaForm& f, const HammingMfmaParams& a, hipStream_t s, hipEvent_t* marks) {
     if (a.p.nq == 0) return hipSuccess;
     HammingMfmaParams arg = a;
@@ -195,10 +196,7 @@ hipError_t hamming_mfma_launch(const HammingMfmaForm& f, const HammingMfmaParams
                        : f.query_tile == 64u ? reinterpret_cast<const void*>(&hamming_mfma_kernel<4>) : nullptr;
         if (!fn || f.lds_bytes > 160u * 1024u || (uint64_t)f.row_slices * f.kcap > kHamMergeMax || f.scratch_bytes > kHamMfmaScratch)
             return hipErrorInvalidValue;
-        // HQ
-        const uint32_t items = f.tiles * f.query_tile * f.chunks * 16u;
-        const void* qfn = reinterpret_cast<const void*>(&hamming_prepare_kernel);
-        if (const hipError_t e = hipLaunchKernel(qfn, dim3((items + 255u) / 256u), dim3(256), args, 0, s)) return e;
+        if (const hipError_t e = hamming_prepare_launch(a, s)) return e;  // HQ
         // H2
         if (f.lds_bytes > 48u * 1024u) {
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes);

@@ -209,6 +209,24 @@ def signbits_form(dim: int, nq: int, k: int, rows: int, num_cus: int = 0) -> Sig
     return SignbitsForm(*[o.value for o in out])
 
 
+class HammingRadiusForm(NamedTuple):
+    query_tile: int     # queries whose prepared bits a scan block holds in LDS: 16, 32, 64 or 128
+    row_slices: int     # row ranges the scan is split into
+    blocks_per_cu: int  # blocks the slice rule gives a compute unit: what the tile's LDS admits, 8 at most
+    chunks: int         # 64-byte chunks of a row
+    lds_bytes: int      # LDS of a scan block
+    scratch_bytes: int  # a window's device scratch where entries are asked for
+
+
+def hamming_radius_form(dim: int, nq: int, rows: int, num_cus: int = 0) -> HammingRadiusForm:
+    """The shape of a window of a Hamming radius search over `rows` rows of `dim` packed bytes with `nq` queries, on a part of
+    `num_cus` compute units (0: 256) -- the decision the launch itself takes (`mvfgpu_selftest_hamming_radius_form`,
+    include/mvf_gpu_hamming_radius.h; no GPU needed)."""
+    out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_radius_form(dim, nq, rows, num_cus, *[C.byref(o) for o in out]))
+    return HammingRadiusForm(*[o.value for o in out])
+
+
 def quantize_queries_int8(x) -> np.ndarray:
     """Float embeddings [..., d] -> the queries of a sign-bit search, int8 [..., 8 * ceil(d / 8)]: each query scaled by
     127 / max|x| of its own, rounded to nearest (np.rint) and padded with zero elements, which score 0 whatever the bit; an
@@ -864,6 +882,34 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_stage_ms(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
                                                                    C.c_void_p(d_scores), C.c_void_p(d_indices), None, _opt(stream), ms))
         return float(ms[0]), float(ms[1])
+
+    def search_hamming_radius(self, queries: np.ndarray, radii, max_per_query: int) -> RadiusResult:
+        """Every row within `radii` bits of each query (`mvfgpu_search_hamming_radius`, include/mvf_gpu_hamming_radius.h) on a
+        UInt8 corpus of bit-packed rows of up to 512 bytes: uint8 queries [nq, dimension]; `radii` is a scalar or one value per
+        query, inclusive; counts are exact, the entries are the best min(count, max_per_query) matches as `search_hamming`
+        writes them; `max_per_query` = 0 .. 1024, 0 asks for counts only."""
+        q, qcode, nq, qdim = _query_args(queries)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, np.uint32), (nq,)), np.uint32)
+        m = int(max_per_query)
+        if m < 0:
+            raise InvalidArgument("max_per_query must be >= 0")
+        counts = np.zeros(nq, np.uint64)
+        sc, idx, raw = _result_arrays(nq, m)
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if m else (lambda a: None)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_hamming_radius(self._h, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq,
+                                                               r.ctypes.data_as(C.c_void_p), m, counts.ctypes.data_as(C.c_void_p),
+                                                               ptr(sc), ptr(idx), ptr(raw)))
+        return RadiusResult(counts, sc, idx, raw)
+
+    def hamming_radius_stage_ms(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, d_radii: int, max_per_query: int,
+                                d_counts: int, d_scores: int, d_indices: int, stream: int = 0) -> tuple[float, float, float]:
+        """(prepare, scan, pack) milliseconds of the radius search's device work on resident buffers
+        (`mvfgpu_selftest_hamming_radius_stage_ms`); waits for the stream."""
+        ms = (C.c_float * 3)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_radius_stage_ms(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq,
+                                                                          C.c_void_p(d_radii), max_per_query, C.c_void_p(d_counts),
+                                                                          _opt(d_scores), _opt(d_indices), None, _opt(stream), ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def search_signbits(self, queries: np.ndarray, k: int) -> SearchResult:
         """The k rows of largest sign-bit score per query (`mvfgpu_search_signbits`, include/mvf_gpu_signbits.h) on a UInt8

@@ -130,6 +130,28 @@ def find_top_k_hamming(space: VectorSpace, query, k: int, corpus: GpuCorpus | No
             for j, (idx, score) in enumerate(zip(res.indices[0][valid], res.scores[0][valid]))]
 
 
+def find_within_hamming(space: VectorSpace, query, radius: int, max_results: int = 1024, corpus: GpuCorpus | None = None,
+                        device: int = 0, with_vectors: bool = False) -> tuple[int, list[ScoredVector]]:
+    """Every row of a UInt8 space of bit-packed rows (up to 512 bytes each) within `radius` bits of `query`, inclusive
+    (`mvfgpu_search_hamming_radius`; DESIGN.md §3 "Hamming radius search"): the exact number of matches, and the best
+    `max_results` of them (0 .. 1024) as `find_top_k_hamming` returns hits -- ascending distance, ties by ascending position.
+    Near-duplicate and perceptual-hash lookups; the row payloads are fetched only when `with_vectors` is set."""
+    if int(space.data_type()) != 3:
+        raise BuildError("Hamming radius search takes a UInt8 space of bit-packed rows")
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        res = corpus.search_hamming_radius(np.asarray(query, dtype=np.uint8), radius, max_results)
+        n = min(int(res.counts[0]), res.indices.shape[1])
+        rows = corpus.gather_rows(res.indices[0][:n]) if with_vectors and n else None
+    finally:
+        if own:
+            corpus.close()
+    return int(res.counts[0]), [ScoredVector(int(res.indices[0][j]), float(res.scores[0][j]), rows[j].copy() if rows is not None else None)
+                                for j in range(n)]
+
+
 def find_top_k_signbits(space: VectorSpace, query, k: int, corpus: GpuCorpus | None = None, device: int = 0,
                         with_vectors: bool = False) -> list[ScoredVector]:
     """The k rows of a UInt8 space of bit-packed rows (up to 512 bytes each) that score highest against a query that keeps its
