@@ -43,6 +43,7 @@
 #include "mvf_gpu_mmr.h"
 #include "mvf_gpu_hamming_radius.h"
 #include "mvf_gpu_signbits.h"
+#include "mvf_gpu_tanimoto.h"
 #include "mvf_gpu_update.h"
 #include "mvf_status.h"
 
@@ -461,6 +462,21 @@ public:
         std::vector<uint64_t> idx(k);
         detail::check_gpu(mvfgpu_search_signbits(c_, query.data(), MVF_DTYPE_INT8, (uint32_t)query.size(), 1, (uint32_t)k, scores.data(),
                                                  idx.data(), nullptr));
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
+    // Tanimoto search (mvfgpu_search_tanimoto, mvf_gpu_tanimoto.h; DESIGN.md section 3, "Tanimoto search"): the k rows of a UInt8
+    // space of bit-packed rows of up to 512 bytes of largest Jaccard / Tanimoto similarity to `query` (dimension() bytes),
+    // popcount(q & x) / popcount(q | x) -- fingerprints, MinHash bitmaps, set-valued features.  A hit's score is the correctly
+    // rounded f32 quotient (0 where both are empty), ties go by ascending position, k reaches MVFGPU_K_PER_PASS.
+    std::vector<ScoredVector> find_top_k_tanimoto(const std::vector<uint8_t>& query, size_t k) const {
+        if (dt_ != DataType::UInt8) throw MvfError(MVF_ERR_BUILD, "find_top_k_tanimoto takes a UInt8 space of bit-packed rows");
+        if (k == 0) return {};
+        std::vector<float> scores(k);
+        std::vector<uint64_t> idx(k);
+        detail::check_gpu(mvfgpu_search_tanimoto(c_, query.data(), MVF_DTYPE_UINT8, (uint32_t)query.size(), 1, (uint32_t)k, scores.data(),
+                                                 idx.data()));
         std::vector<ScoredVector> out;
         for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
         return out;

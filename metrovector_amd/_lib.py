@@ -210,6 +210,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_signbits_form.restype = C.c_int
     lib.mvfgpu_selftest_signbits_stage_ms.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_signbits_stage_ms.restype = C.c_int
+    lib.mvfgpu_search_tanimoto.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp]
+    lib.mvfgpu_search_tanimoto.restype = C.c_int
+    lib.mvfgpu_search_tanimoto_device.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp]
+    lib.mvfgpu_search_tanimoto_device.restype = C.c_int
+    lib.mvfgpu_selftest_tanimoto_form.argtypes = [u32, u32, u32, u64, u32, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_tanimoto_form.restype = C.c_int
+    lib.mvfgpu_selftest_tanimoto_stage_ms.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_tanimoto_stage_ms.restype = C.c_int
     lib.mvfgpu_search_hamming_radius.argtypes = [vp, vp, u8, u32, u32, vp, u64, vp, vp, vp, vp]
     lib.mvfgpu_search_hamming_radius.restype = C.c_int
     lib.mvfgpu_selftest_hamming_radius_form.argtypes = [u32, u32, u64, u32, vp, vp, vp, vp, vp, vp]

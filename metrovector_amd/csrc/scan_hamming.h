@@ -90,6 +90,8 @@ struct HammingParams {
     int32_t* out_raw;              // nullable
     int32_t score_bias;            // 0: a key is a distance, written as it is (+inf padding).  Otherwise (scan_signbits.hip) a key is
                                    // score_bias - s for a score s where larger is better: H1 writes s (-inf padding)
+    uint32_t float_key;            // set (scan_tanimoto.hip): a key is score_bias - the bits of a non-negative f32 score: H1 writes
+                                   // uint_as_float(score_bias - key) to out_scores (-inf padding); there is no out_raw
 };
 
 // H0 over the grid (row slices x query tiles), then H1 with one block per query: two launches on `s`, no host wait.

@@ -283,6 +283,9 @@ HAM_KERNEL __launch_bounds__(1024) void hamming_merge_kernel(const HammingParams
             p.out_scores[o] = pad_score(p.score_bias ? MVF_METRIC_INNER_PRODUCT : MVF_METRIC_L2);
             p.out_indices[o] = ~0ull;
             if (p.out_raw) p.out_raw[o] = 0;
+        } else if (p.float_key) {  // (out_raw is NULL)
+            p.out_scores[o] = __uint_as_float((uint32_t)p.score_bias - (uint32_t)(comp >> 32));
+            p.out_indices[o] = p.ids ? p.ids[(uint32_t)comp] : p.index_base + (uint32_t)comp;
         } else {
             const uint32_t r = (uint32_t)comp;
             const int32_t d = p.score_bias ? p.score_bias - (int32_t)(comp >> 32) : (int32_t)(comp >> 32);

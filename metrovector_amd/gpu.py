@@ -41,7 +41,7 @@ def device_count() -> int:
 class SearchResult:
     scores: np.ndarray   # f32 [nq, k]
     indices: np.ndarray  # u64 [nq, k]
-    raw: np.ndarray      # i32 [nq, k] (exact integer score on Int8/UInt8 spaces)
+    raw: np.ndarray      # i32 [nq, k] (exact integer score on Int8/UInt8 spaces); None from search_tanimoto, whose score is a quotient
 
 
 @dataclass
@@ -225,6 +225,24 @@ def hamming_radius_form(dim: int, nq: int, rows: int, num_cus: int = 0) -> Hammi
     out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)]
     _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_radius_form(dim, nq, rows, num_cus, *[C.byref(o) for o in out]))
     return HammingRadiusForm(*[o.value for o in out])
+
+
+class TanimotoForm(NamedTuple):
+    query_tile: int     # queries whose prepared bits a scan block holds in LDS: 16, 32, 64 or 128
+    chunks: int         # 64-byte chunks of a row
+    row_slices: int     # row ranges the scan is split into
+    slice_rows: int     # rows of a range
+    lds_bytes: int      # LDS of a scan block
+    scratch_bytes: int  # scratch: the candidate buffers
+
+
+def tanimoto_form(dim: int, nq: int, k: int, rows: int, num_cus: int = 0) -> TanimotoForm:
+    """The shape of a window of a Tanimoto search over `rows` rows of `dim` packed bytes with `nq` queries and list length k, on
+    a part of `num_cus` compute units (0: 256) -- the decision the launch itself takes (`mvfgpu_selftest_tanimoto_form`,
+    include/mvf_gpu_tanimoto.h; no GPU needed)."""
+    out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_tanimoto_form(dim, nq, k, rows, num_cus, *[C.byref(o) for o in out]))
+    return TanimotoForm(*[o.value for o in out])
 
 
 def quantize_queries_int8(x) -> np.ndarray:
@@ -935,6 +953,31 @@ class GpuCorpus:
         ms = (C.c_float * 3)()
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_signbits_stage_ms(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
                                                                     C.c_void_p(d_scores), C.c_void_p(d_indices), None, _opt(stream), ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def search_tanimoto(self, queries: np.ndarray, k: int) -> SearchResult:
+        """The k rows of largest Tanimoto (Jaccard) similarity per query (`mvfgpu_search_tanimoto`,
+        include/mvf_gpu_tanimoto.h) on a UInt8 corpus of bit-packed rows of up to 512 bytes: uint8 queries [nq, dimension];
+        scores = popcount(q & x) / popcount(q | x) as the correctly rounded f32 quotient (0 where both are empty), ties by
+        ascending position, at most 1024 results per query, -inf padding; `raw` is None."""
+        q, qcode, nq, qdim = _query_args(queries)
+        sc, idx, _ = _result_arrays(nq, k)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_tanimoto(self._h, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
+                                                         sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p)))
+        return SearchResult(sc, idx, None)
+
+    def search_tanimoto_device(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, d_scores: int,
+                               d_indices: int, stream: int = 0) -> None:
+        """Device-pointer Tanimoto search (`mvfgpu_search_tanimoto_device`), asynchronous on `stream`."""
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_tanimoto_device(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
+                                                                C.c_void_p(d_scores), C.c_void_p(d_indices), _opt(stream)))
+
+    def tanimoto_stage_ms(self, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int, d_scores: int, d_indices: int,
+                          stream: int = 0) -> tuple[float, float, float]:
+        """(prepare, scan, merge) milliseconds of one device call (`mvfgpu_selftest_tanimoto_stage_ms`); waits for the stream."""
+        ms = (C.c_float * 3)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_tanimoto_stage_ms(self._h, C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
+                                                                    C.c_void_p(d_scores), C.c_void_p(d_indices), _opt(stream), ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
 
     def search_mmr(self, queries: np.ndarray, candidates: np.ndarray, k: int, lambda_mult: float = 0.5, metric: int = L2) -> MmrResult:

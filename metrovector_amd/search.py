@@ -179,6 +179,29 @@ def find_top_k_signbits(space: VectorSpace, query, k: int, corpus: GpuCorpus | N
             for j, (idx, score) in enumerate(zip(res.indices[0][valid], res.scores[0][valid]))]
 
 
+def find_top_k_tanimoto(space: VectorSpace, query, k: int, corpus: GpuCorpus | None = None, device: int = 0,
+                        with_vectors: bool = False) -> list[ScoredVector]:
+    """The k rows of a UInt8 space of bit-packed rows (up to 512 bytes each) of largest Tanimoto / Jaccard similarity to the
+    uint8 `query` of `dimension()` bytes, popcount(q & x) / popcount(q | x) (`mvfgpu_search_tanimoto`; DESIGN.md §3 "Tanimoto
+    search"), following `find_top_k_hamming`: molecular fingerprints, MinHash bitmaps, set-valued features.  A hit's score is
+    the correctly rounded f32 quotient (0 where query and row are both empty), ties go by ascending position and k reaches
+    1024; the row payloads are fetched only when `with_vectors` is set."""
+    if int(space.data_type()) != 3:
+        raise BuildError("Tanimoto search takes a UInt8 space of bit-packed rows")
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        res = corpus.search_tanimoto(np.asarray(query, dtype=np.uint8), k)
+        valid = res.indices[0] != np.uint64(0xFFFFFFFFFFFFFFFF)  # fewer than k live rows: fewer items
+        rows = corpus.gather_rows(res.indices[0][valid]) if with_vectors and valid.any() else None
+    finally:
+        if own:
+            corpus.close()
+    return [ScoredVector(int(idx), float(score), rows[j].copy() if rows is not None else None)
+            for j, (idx, score) in enumerate(zip(res.indices[0][valid], res.scores[0][valid]))]
+
+
 def find_top_k_similar_batch(space: VectorSpace, queries, k: int, metric: int | None = None,
                              corpus: GpuCorpus | None = None, device: int = 0,
                              with_vectors: bool = False) -> list[list[ScoredVector]]:
