@@ -38,6 +38,7 @@
 #include "mvf_gpu.h"
 #include "mvf_gpu_hamming.h"
 #include "mvf_gpu_hamming_route.h"
+#include "mvf_gpu_hamming_maxsim.h"
 #include "mvf_gpu_maxsim_align.h"
 #include "mvf_gpu_maxsim_route.h"
 #include "mvf_gpu_mmr.h"
@@ -686,6 +687,42 @@ public:
         if (rc == MVF_OK)
             rc = mvfgpu_search_maxsim(c_, part, (uint8_t)metric_, query_vectors.data(), MVF_DTYPE_FLOAT32, dim_, 1,
                                       (uint32_t)std::min<size_t>(n_tokens, UINT32_MAX), (uint32_t)k, scores.data(), keys.data(), &count);
+        mvfgpu_partition_destroy(part);
+        mvfgpu_column_destroy(col);
+        detail::check_gpu(rc);
+        for (uint32_t i = 0; i < count; i++) out.emplace_back(keys[i], scores[i]);
+        return out;
+    }
+    // find_top_k_documents over BINARISED token embeddings (mvfgpu_search_hamming_maxsim, mvf_gpu_hamming_maxsim.h; DESIGN.md
+    // section 3, "Binary MaxSim"): a UInt8 space of bit-packed tokens of up to 512 bytes, a document's score the sum over the
+    // query's tokens of that token's smallest Hamming distance among the document's rows.  query_tokens holds n_tokens x
+    // dimension bytes; the column as in find_top_k_per_key.  -> (column value, the exact integer sum), SMALLEST first, ties by
+    // ascending value.  The column and the index live for this call.
+    std::vector<std::pair<uint64_t, float>> find_top_k_documents_hamming(const std::vector<uint8_t>& query_tokens, size_t k,
+                                                                         const MetadataColumn& column) const {
+        if (dt_ != DataType::UInt8) throw MvfError(MVF_ERR_BUILD, "find_top_k_documents_hamming takes a UInt8 space of bit-packed rows");
+        if (dim_ == 0 || query_tokens.empty() || query_tokens.size() % (size_t)dim_)
+            throw MvfError(MVF_ERR_DIMENSION_MISMATCH, "find_top_k_documents_hamming takes whole query tokens of the space's dimension");
+        const size_t n_tokens = query_tokens.size() / (size_t)dim_;
+        std::vector<std::pair<uint64_t, float>> out;
+        if (k == 0) return out;
+        mvfgpu_corpus_info inf;
+        MVFGPU_INIT(inf);
+        detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+        const uint64_t es = column.data_type == MVF_DTYPE_UINT32 ? 4 : column.data_type == MVF_DTYPE_UINT64 ? 8 : 0;
+        if (!es || column.size / es < inf.rows)
+            throw MvfError(MVF_ERR_BUILD, es ? "metadata column '" + column.name + "' holds fewer values than the space has vectors"
+                                             : "Unsupported metadata column data type");
+        mvfgpu_column* col = nullptr;
+        mvfgpu_partition* part = nullptr;
+        std::vector<float> scores(k);
+        std::vector<uint64_t> keys(k);
+        uint32_t count = 0;
+        int rc = mvfgpu_column_create(c_, column.data, column.data_type, 0, column.size / es, &col);
+        if (rc == MVF_OK) rc = mvfgpu_partition_create(c_, col, &part);
+        if (rc == MVF_OK)
+            rc = mvfgpu_search_hamming_maxsim(c_, part, query_tokens.data(), MVF_DTYPE_UINT8, dim_, 1,
+                                              (uint32_t)std::min<size_t>(n_tokens, UINT32_MAX), (uint32_t)k, scores.data(), keys.data(), &count);
         mvfgpu_partition_destroy(part);
         mvfgpu_column_destroy(col);
         detail::check_gpu(rc);

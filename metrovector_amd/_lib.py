@@ -218,6 +218,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_tanimoto_form.restype = C.c_int
     lib.mvfgpu_selftest_tanimoto_stage_ms.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp]
     lib.mvfgpu_selftest_tanimoto_stage_ms.restype = C.c_int
+    lib.mvfgpu_search_hamming_maxsim.argtypes = [vp, vp, vp, u8, u32, u32, u32, u32, vp, vp, vp]
+    lib.mvfgpu_search_hamming_maxsim.restype = C.c_int
+    lib.mvfgpu_search_hamming_maxsim_device.argtypes = [vp, vp, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_search_hamming_maxsim_device.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_maxsim_form.argtypes = [u32, u32, u32, u64, u64, u64, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_maxsim_form.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_maxsim_stage_ms.argtypes = [vp, vp, vp, u8, u32, u32, u32, u32, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_maxsim_stage_ms.restype = C.c_int
     lib.mvfgpu_search_hamming_radius.argtypes = [vp, vp, u8, u32, u32, vp, u64, vp, vp, vp, vp]
     lib.mvfgpu_search_hamming_radius.restype = C.c_int
     lib.mvfgpu_selftest_hamming_radius_form.argtypes = [u32, u32, u64, u32, vp, vp, vp, vp, vp, vp]

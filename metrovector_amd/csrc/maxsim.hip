@@ -24,6 +24,7 @@
 #include "scan_gather.h"
 #include "scan_maxsim.h"
 #include "scan_mfma.h"
+#include "stage_marks.h"
 
 #include <algorithm>
 #include <cstring>
@@ -45,21 +46,6 @@ int check_maxsim_args(const mvfgpu_corpus* c, const mvfgpu_partition* part, uint
     if (const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_keys)) return rc;
     return check_partition_use(c, part);
 }
-
-// the stage timer's events: one behind every stage of every chunk and window, with the stage it closes
-struct StageMarks {
-    std::vector<std::pair<int, hipEvent_t>> ev;
-    hipError_t mark(int stage, hipStream_t s) {
-        hipEvent_t e = nullptr;
-        hipError_t rc = hipEventCreate(&e);
-        if (rc != hipSuccess) return rc;
-        ev.emplace_back(stage, e);
-        return hipEventRecord(e, s);
-    }
-    ~StageMarks() {
-        for (auto& m : ev) (void)hipEventDestroy(m.second);
-    }
-};
 
 // what the stage timer of route 2 asks for beside the marks: per set of the CALL the candidate keys and the blocks re-scored
 struct MfmaStats {
@@ -530,17 +516,6 @@ int maxsim_candidates_core(const CorpusView& v, const mvfgpu_partition* part, ui
         wp.cand = ep.sets;
         MVF_HIP_TRY(maxsim_write_launch(wp, s));
         if (marks) MVF_HIP_TRY(marks->mark(3, s));
-    }
-    return MVF_OK;
-}
-
-// the stage timer's sums: every stage's time from the event in front of it
-int stage_sums(const StageMarks& marks, float* out_ms, int stages = 4) {
-    for (int i = 0; i < stages; i++) out_ms[i] = 0.0f;
-    for (size_t i = 1; i < marks.ev.size(); i++) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, marks.ev[i - 1].second, marks.ev[i].second) != hipSuccess) return set_fail(MVF_ERR_DEVICE, "hipEventElapsedTime failed");
-        if (marks.ev[i].first >= 0 && marks.ev[i].first < stages) out_ms[marks.ev[i].first] += ms;
     }
     return MVF_OK;
 }

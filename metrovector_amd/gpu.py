@@ -245,6 +245,27 @@ def tanimoto_form(dim: int, nq: int, k: int, rows: int, num_cus: int = 0) -> Tan
     return TanimotoForm(*[o.value for o in out])
 
 
+class HammingMaxsimForm(NamedTuple):
+    query_tile: int         # query rows one pass of the scan scores against a block's rows
+    chunks: int             # 64-byte chunks of a row
+    rows_in_registers: int  # 1: a lane's words of its rows stay in registers over a launch (pitch <= 64), 0: loaded again per pass
+    chunk_tokens: int       # tokens per chunk
+    window_sets: int        # query sets per window
+    lds_bytes: int          # LDS of a scan block
+    scratch_bytes: int      # what the budget holds: minima, sums, sort buffers and prepared tokens of a window
+
+
+def hamming_maxsim_form(dim: int, nq: int, n_tokens: int, n_keys: int, held_rows: int, budget_bytes: int = 512 << 20,
+                        num_cus: int = 0) -> HammingMaxsimForm:
+    """The shape of a binary MaxSim call over `held_rows` rows of `dim` packed bytes under `n_keys` keys, with `nq` query sets of
+    `n_tokens` tokens and a scratch budget of `budget_bytes` (`MVF_MAXSIM_SCRATCH_BYTES`) -- the decisions the launch itself takes
+    (`mvfgpu_selftest_hamming_maxsim_form`, include/mvf_gpu_hamming_maxsim.h; no GPU needed)."""
+    out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_maxsim_form(dim, nq, n_tokens, n_keys, held_rows, budget_bytes, num_cus,
+                                                                  *[C.byref(o) for o in out]))
+    return HammingMaxsimForm(*[o.value for o in out])
+
+
 def quantize_queries_int8(x) -> np.ndarray:
     """Float embeddings [..., d] -> the queries of a sign-bit search, int8 [..., 8 * ceil(d / 8)]: each query scaled by
     127 / max|x| of its own, rounded to nearest (np.rint) and padded with zero elements, which score 0 whatever the bit; an
@@ -1264,6 +1285,47 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_selftest_maxsim_stage_ms(self._h, part._h, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                   nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
                                                                   _opt(stream), out))
+        return tuple(float(x) for x in out)
+
+    # ---- binary MaxSim: top-k keys by summed per-token best Hamming distance ----------------
+    def search_hamming_maxsim(self, query_sets: np.ndarray, k: int, part: GpuPartition) -> MaxSimResult:
+        """The k keys of `part` of smallest summed per-token best Hamming distance for every SET of bit-packed query tokens
+        (`mvfgpu_search_hamming_maxsim`, include/mvf_gpu_hamming_maxsim.h) on a UInt8 corpus of bit-packed rows of up to 512
+        bytes: `query_sets` is uint8 [nq, n_tokens, dimension] (a 2-D array is one set); scores are the exact integer sums as
+        float32, ties by ascending key, +inf and UINT64_MAX pad."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        q = np.asarray(query_sets)
+        if q.ndim == 2:
+            q = q[None, :, :]
+        if q.ndim != 3:
+            raise InvalidArgument(f"query sets must be [nq, n_tokens, dim], got shape {q.shape}")
+        qcode = _CODE_OF.get(q.dtype)
+        if qcode is None:
+            raise BuildError(f"unsupported query dtype {q.dtype}")
+        q = np.ascontiguousarray(q)
+        nq, n_tokens, qdim = q.shape
+        sc, keys, cnt = np.empty((nq, k), np.float32), np.empty((nq, k), np.uint64), np.zeros(nq, np.uint32)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_hamming_maxsim(self._h, hpart, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, n_tokens, k,
+                                                               sc.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p),
+                                                               cnt.ctypes.data_as(C.c_void_p)))
+        return MaxSimResult(sc, keys, cnt)
+
+    def search_hamming_maxsim_device(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int,
+                                     k: int, d_scores: int, d_keys: int, d_counts: int = 0, stream: int = 0) -> None:
+        """Device-pointer binary MaxSim (`mvfgpu_search_hamming_maxsim_device`), asynchronous on `stream`."""
+        hpart = _open_handle(part, GpuPartition, "part")
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_hamming_maxsim_device(self._h, hpart, C.c_void_p(d_queries), query_dtype, query_dim, nq,
+                                                                      n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+                                                                      _opt(d_counts), _opt(stream)))
+
+    def hamming_maxsim_stage_ms(self, part: GpuPartition, d_queries: int, query_dtype: int, query_dim: int, nq: int, n_tokens: int, k: int,
+                                d_scores: int, d_keys: int, stream: int = 0) -> tuple[float, float, float, float]:
+        """(prepare, scan, sum, tail) in ms of one binary MaxSim call, summed over its chunks and windows
+        (`mvfgpu_selftest_hamming_maxsim_stage_ms`); waits for the stream."""
+        out = (C.c_float * 4)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_maxsim_stage_ms(self._h, part._h, C.c_void_p(d_queries), query_dtype, query_dim,
+                                                                          nq, n_tokens, k, C.c_void_p(d_scores), C.c_void_p(d_keys),
+                                                                          None, _opt(stream), out))
         return tuple(float(x) for x in out)
 
     def set_maxsim_route(self, route: int) -> None:

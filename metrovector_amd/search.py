@@ -533,6 +533,33 @@ def find_top_k_documents(space: VectorSpace, query_vectors, k: int, column: str,
             corpus.close()
 
 
+def find_top_k_documents_hamming(space: VectorSpace, query_tokens, k: int, column: str, corpus: GpuCorpus | None = None,
+                                 device: int = 0) -> MaxSimResult:
+    """`find_top_k_documents` over BINARISED token embeddings (`mvfgpu_search_hamming_maxsim`; DESIGN.md §3 "Binary MaxSim"): a
+    UInt8 space whose rows are bit-packed tokens of `dimension()` bytes, a document's score the sum over the query's tokens of
+    that token's smallest Hamming distance among the document's rows, the k documents of SMALLEST sum first.  `query_tokens` is
+    uint8 [n_tokens, dimension] for one query or [nq, n_tokens, dimension].  The column is read as `find_top_k_per_key` reads it,
+    with the same refusals.  Returns scores [nq, k] (the exact integer sums), keys [nq, k] (UINT64_MAX pads) and counts [nq]."""
+    total = space.total_vectors()
+    mc = space._reader.metadata_column(column)  # everything about the file's column is refused before anything is uploaded
+    es = {4: 4, 5: 8}.get(int(mc.data_type))
+    if es is None:
+        raise BuildError("Unsupported metadata column data type")
+    if mc.size // es < total:
+        raise BuildError(f"metadata column '{column}' holds {mc.size // es} values, the space has {total} vectors")
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        base = int(corpus.info().index_base)
+        with corpus.attach_column_pointer(mc.as_ptr(), int(mc.data_type), base, mc.size // es) as col:
+            with corpus.make_partition(col) as part:
+                return corpus.search_hamming_maxsim(np.asarray(query_tokens, dtype=np.uint8), k, part)
+    finally:
+        if own:
+            corpus.close()
+
+
 def rerank_top_k_documents(space: VectorSpace, query_vectors, candidate_keys, k: int, column: str, metric: int | None = None,
                            corpus: GpuCorpus | None = None, device: int = 0) -> MaxSimResult:
     """`find_top_k_documents` among CANDIDATE documents (`mvfgpu_search_maxsim_candidates`; DESIGN.md §3 "Candidate keys"): the
