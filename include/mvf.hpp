@@ -37,6 +37,7 @@
 #include "mvf_file.h"
 #include "mvf_gpu.h"
 #include "mvf_gpu_hamming.h"
+#include "mvf_gpu_hamming_filtered.h"
 #include "mvf_gpu_hamming_route.h"
 #include "mvf_gpu_hamming_maxsim.h"
 #include "mvf_gpu_maxsim_align.h"
@@ -431,6 +432,25 @@ public:
         std::vector<uint64_t> idx(k);
         detail::check_gpu(mvfgpu_search_hamming(c_, query.data(), MVF_DTYPE_UINT8, (uint32_t)query.size(), 1, (uint32_t)k, scores.data(),
                                                 idx.data(), nullptr));
+        std::vector<ScoredVector> out;
+        for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
+        return out;
+    }
+    // find_top_k_hamming among the rows a predicate admits (mvfgpu_search_hamming_filtered, mvf_gpu_hamming_filtered.h; DESIGN.md
+    // section 3, "Filtered Hamming search"): bit r of allow_bits (byte r >> 3, bit r & 7; at least one bit per row) admits row r.
+    // Deleted rows are never returned; fewer than k admitted rows give fewer hits.  The filter lives for this call.
+    std::vector<ScoredVector> find_top_k_hamming_filtered(const std::vector<uint8_t>& query, size_t k,
+                                                          const std::vector<uint8_t>& allow_bits) const {
+        if (dt_ != DataType::UInt8) throw MvfError(MVF_ERR_BUILD, "find_top_k_hamming_filtered takes a UInt8 space of bit-packed rows");
+        if (k == 0) return {};
+        mvfgpu_filter* f = nullptr;
+        detail::check_gpu(mvfgpu_filter_create(c_, allow_bits.data(), 0, (uint64_t)allow_bits.size() * 8, &f));
+        std::vector<float> scores(k);
+        std::vector<uint64_t> idx(k);
+        const int rc = mvfgpu_search_hamming_filtered(c_, f, query.data(), MVF_DTYPE_UINT8, (uint32_t)query.size(), 1, (uint32_t)k,
+                                                      scores.data(), idx.data(), nullptr);
+        mvfgpu_filter_destroy(f);
+        detail::check_gpu(rc);
         std::vector<ScoredVector> out;
         for (size_t i = 0; i < k && idx[i] != UINT64_MAX; i++) out.push_back({idx[i], scores[i], {}});
         return out;

@@ -34,8 +34,9 @@ extern "C" {
  * discipline.  Neither builds norms or shadows, reads or posts the repair feedback, or changes what a later call on the handle
  * does.  Two launches per 1024 queries, whatever k.
  *
- * Not built: k above 1024; shard sets; filters, partitions and candidate lists taking this metric; Int8 handles; a binary
- * shadow for the float routes.  (Radius search under Hamming: mvf_gpu_hamming_radius.h; Jaccard / Tanimoto: mvf_gpu_tanimoto.h.)
+ * Not built: k above 1024; shard sets; partitions and candidate lists taking this metric; Int8 handles; a binary
+ * shadow for the float routes.  (Filters: mvf_gpu_hamming_filtered.h; radius search under Hamming: mvf_gpu_hamming_radius.h;
+ * Jaccard / Tanimoto: mvf_gpu_tanimoto.h.)
  */
 int mvfgpu_search_hamming(const mvfgpu_corpus* corpus, const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq,
                           uint32_t k, float* out_scores, uint64_t* out_indices, int32_t* out_raw);

@@ -202,6 +202,14 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_hamming_route.restype = C.c_int
     lib.mvfgpu_selftest_hamming_mfma_form.argtypes = [u32, u32, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_hamming_mfma_form.restype = C.c_int
+    lib.mvfgpu_search_hamming_filtered.argtypes = [vp, vp, vp, u8, u32, u32, u32, vp, vp, vp]
+    lib.mvfgpu_search_hamming_filtered.restype = C.c_int
+    lib.mvfgpu_search_hamming_filtered_device.argtypes = [vp, vp, vp, u8, u32, u32, u32, vp, vp, vp, vp]
+    lib.mvfgpu_search_hamming_filtered_device.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_filtered_form.argtypes = [u32, u32, u32, u64, u64, u32, i32, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_filtered_form.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_filtered_stage_ms.argtypes = [vp, vp, vp, u8, u32, u32, u32, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_filtered_stage_ms.restype = C.c_int
     lib.mvfgpu_search_signbits.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp]
     lib.mvfgpu_search_signbits.restype = C.c_int
     lib.mvfgpu_search_signbits_device.argtypes = [vp, vp, u8, u32, u32, u32, vp, vp, vp, vp]

@@ -107,14 +107,7 @@ int check_filtered_args(const mvfgpu_corpus* c, const mvfgpu_filter* f, uint8_t 
     if (!f) return set_fail(MVF_ERR_INVALID_ARGUMENT, "filter is NULL");
     const int rc = check_search_args(c, metric, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
     if (rc != MVF_OK) return rc;
-    if (f->owner != c) return set_fail(MVF_ERR_INVALID_ARGUMENT, "the filter was created for another corpus handle");
-    const CorpusView v = corpus_view(c);
-    if (f->tomb_gen != v.tomb_gen)
-        return set_fail(MVF_ERR_INVALID_ARGUMENT,
-                        "stale filter: mvfgpu_corpus_set_tombstones changed the handle's tombstones after the filter was created");
-    use->deny = f->deny;
-    use->list = f->list;
-    use->admitted = f->admitted;
+    if (const int rcu = filter_check_use(c, f, use)) return rcu;
     const uint32_t route = f->forced_route ? (uint32_t)f->forced_route : filter_route_rule(f->rows, f->dim, f->dtype, nq, k, f->admitted);
     use->by_list = route == 2u && f->list != nullptr;
     return MVF_OK;
@@ -123,6 +116,20 @@ int check_filtered_args(const mvfgpu_corpus* c, const mvfgpu_filter* f, uint8_t 
 }  // namespace
 
 namespace mvf {
+
+int filter_check_use(const mvfgpu_corpus* c, const mvfgpu_filter* f, FilterUse* use) {
+    if (f->owner != c) return set_fail(MVF_ERR_INVALID_ARGUMENT, "the filter was created for another corpus handle");
+    const CorpusView v = corpus_view(c);
+    if (f->tomb_gen != v.tomb_gen)
+        return set_fail(MVF_ERR_INVALID_ARGUMENT,
+                        "stale filter: mvfgpu_corpus_set_tombstones changed the handle's tombstones after the filter was created");
+    use->deny = f->deny;
+    use->list = f->list;
+    use->admitted = f->admitted;
+    use->forced_route = f->forced_route;
+    use->by_list = false;
+    return MVF_OK;
+}
 
 int filter_list_search(const CorpusView& v, const FilterUse& flt, uint8_t metric, const void* d_queries, uint32_t nq, uint32_t k,
                        float* d_scores, uint64_t* d_indices, int32_t* d_raw, hipStream_t s) {

@@ -38,10 +38,15 @@ int check_hamming_args(const mvfgpu_corpus* c, const void* queries, uint8_t quer
     return check_search_args(c, MVF_METRIC_L2, queries, query_dtype, query_dim, nq, k, out_scores, out_indices);
 }
 
-// The device work of both calls: queries and results in device memory, everything on `s`, no host wait.
+}  // namespace
+
+namespace mvf {
+
+// The device work of both calls (internal.h): queries and results in device memory, everything on `s`, no host wait.  tomb: the
+// mask of the rows that are never returned -- the handle's tombstones, or a filter's deny mask (hamming_filtered.hip).
 // ms (the stage timer only): the windows' times before H1 (H0, or HQ + H2) and of H1 are added to ms[0..1]; waits for each window.
-int hamming_core(const CorpusView& v, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores, uint64_t* d_indices,
-                 int32_t* d_raw, hipStream_t s, float* ms = nullptr) {
+int hamming_core(const CorpusView& v, const uint32_t* tomb, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
+                 uint64_t* d_indices, int32_t* d_raw, hipStream_t s, float* ms) {
     hipEvent_t marks[3] = {nullptr, nullptr, nullptr};
     int rc = MVF_OK;
     if (ms)
@@ -64,7 +69,7 @@ int hamming_core(const CorpusView& v, const void* d_queries, uint32_t nq, uint32
         HammingParams p{};
         p.rows = v.rows;
         p.queries = static_cast<const unsigned char*>(d_queries) + (size_t)w0 * v.dim;
-        p.tomb = v.tomb;
+        p.tomb = tomb;
         p.n = v.n;
         p.slice_rows = mfma ? mf.slice_rows : f.slice_rows;
         p.dim = v.dim;
@@ -113,7 +118,7 @@ int hamming_core(const CorpusView& v, const void* d_queries, uint32_t nq, uint32
     return rc;
 }
 
-}  // namespace
+}  // namespace mvf
 
 extern "C" {
 
@@ -124,7 +129,10 @@ int mvfgpu_search_hamming_device(const mvfgpu_corpus* c, const void* d_queries, 
     DevScope guard(corpus_view(c).device);
     if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    return corpus_device_call(c, s, [&]() { return hamming_core(corpus_view(c), d_queries, nq, k, d_scores, d_indices, d_raw, s); });
+    return corpus_device_call(c, s, [&]() {
+        const CorpusView v = corpus_view(c);
+        return hamming_core(v, v.tomb, d_queries, nq, k, d_scores, d_indices, d_raw, s);
+    });
 }
 
 int mvfgpu_search_hamming(const mvfgpu_corpus* c, const void* queries, uint8_t query_dtype, uint32_t query_dim, uint32_t nq, uint32_t k,
@@ -139,7 +147,7 @@ int mvfgpu_search_hamming(const mvfgpu_corpus* c, const void* queries, uint8_t q
     const HostIn in[] = {{queries, (size_t)v.dim}};
     const HostOut out[] = {{out_indices, (size_t)k * 8}, {out_scores, (size_t)k * 4}, {out_raw, (size_t)k * 4}};
     return stage_host_windows(c, s, nq, in, out, stage_as_given, [&](uint32_t, uint32_t wn, void* const* d_in, void* const* d_out) {
-        return hamming_core(v, d_in[0], wn, k, static_cast<float*>(d_out[1]), static_cast<uint64_t*>(d_out[0]),
+        return hamming_core(v, v.tomb, d_in[0], wn, k, static_cast<float*>(d_out[1]), static_cast<uint64_t*>(d_out[0]),
                             static_cast<int32_t*>(d_out[2]), s);
     });
 }
@@ -172,7 +180,10 @@ int mvfgpu_selftest_hamming_stage_ms(const mvfgpu_corpus* c, const void* d_queri
     if (!guard.ok) return set_fail(MVF_ERR_DEVICE, "hipSetDevice failed");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     out_ms[0] = out_ms[1] = 0.0f;
-    return corpus_device_call(c, s, [&]() { return hamming_core(corpus_view(c), d_queries, nq, k, d_scores, d_indices, d_raw, s, out_ms); });
+    return corpus_device_call(c, s, [&]() {
+        const CorpusView v = corpus_view(c);
+        return hamming_core(v, v.tomb, d_queries, nq, k, d_scores, d_indices, d_raw, s, out_ms);
+    });
 }
 
 int mvfgpu_selftest_hamming_route(uint32_t dimension, uint32_t nq_in_window, uint32_t k, uint64_t rows, int forced, uint32_t* out_route) {

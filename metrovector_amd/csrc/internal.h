@@ -240,7 +240,12 @@ struct FilterUse {
     const uint32_t* list = nullptr;
     uint64_t admitted = 0;
     bool by_list = false;
+    int forced_route = 0;  // the owner's MVF_FILTER_ROUTE when the filter was created
 };
+// May a search of `c` use `f` (non-NULL)?  A filter created for another handle, then a stale one, are refused with
+// mvfgpu_search_filtered's messages; otherwise *use holds what the filter is, by_list left for the caller's own route rule.
+// Touches no device.
+int filter_check_use(const mvfgpu_corpus* c, const mvfgpu_filter* f, FilterUse* use);
 // mvfgpu_search / mvfgpu_search_device restricted to the filter's rows (api.hip): the mask route runs the plain search's routes
 // and kernels with flt.deny in the tombstones' place; by_list, no admitted row or an empty corpus go to filter_list_search.
 // Neither polls nor posts the repair feedback.
@@ -293,6 +298,13 @@ int partition_upload(const mvfgpu_partition* part, const void* src, size_t bytes
 void partition_find(const mvfgpu_partition* part, uint64_t key, uint64_t* offset, uint64_t* count, uint64_t* from = nullptr);
 // waits for the newest work enqueued on the handle
 int corpus_wait_newest(const mvfgpu_corpus* c);
+
+// ---- Hamming search (hamming.hip; DESIGN.md §3 "Hamming search")
+// mvfgpu_search_hamming_device's device work for a caller that already runs under corpus_device_call, with `tomb` where the
+// scan reads the handle's tombstones (hamming_filtered.hip passes a filter's deny mask): the windows, the route H0 or HQ / H2
+// and H1, everything on `s`, no host wait.  ms: the stage timer's two sums (waits for each window), or NULL.
+int hamming_core(const CorpusView& v, const uint32_t* tomb, const void* d_queries, uint32_t nq, uint32_t k, float* d_scores,
+                 uint64_t* d_indices, int32_t* d_raw, hipStream_t s, float* ms = nullptr);
 
 // ---- row writes (update.hip; DESIGN.md §3 "Row writes")
 // Everything a handle derives from its rows' bytes, as it is RESIDENT now: a NULL array has not been built (or does not exist

@@ -186,6 +186,28 @@ def hamming_mfma_form(dim: int, nq: int, k: int, rows: int, num_cus: int = 0) ->
     return HammingMfmaForm(*[o.value for o in out])
 
 
+class HammingFilteredForm(NamedTuple):
+    route: int          # 1: mask (the Hamming search's scan with the filter's deny mask), 2: list (HG over the filter's rows)
+    query_tile: int     # route 2: queries whose prepared bits a scan block holds in LDS (route 1: 0, as everything below)
+    chunks: int         # 64-byte chunks of a row
+    list_slices: int    # ranges the filter's list is split into
+    slice_entries: int  # list entries of a slice
+    lds_bytes: int      # LDS of a scan block
+    scratch_bytes: int  # scratch: the candidate buffers
+
+
+def hamming_filtered_form(dim: int, nq: int, k: int, rows: int, admitted: int, has_row_list: bool = True, forced_route: int = 0,
+                          num_cus: int = 0) -> HammingFilteredForm:
+    """The route one window of `nq` queries of a filtered Hamming search takes over `rows` rows of `dim` packed bytes under a
+    filter that admits `admitted` of them, and the list route's shape -- the decisions the launch itself takes
+    (`mvfgpu_selftest_hamming_filtered_form`, include/mvf_gpu_hamming_filtered.h; no GPU needed).  `forced_route`: the
+    filter's (`MVF_FILTER_ROUTE`), 0 = the library's rule."""
+    out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_filtered_form(dim, nq, k, rows, admitted, int(has_row_list), forced_route, num_cus,
+                                                                    *[C.byref(o) for o in out]))
+    return HammingFilteredForm(*[o.value for o in out])
+
+
 def pack_sign_bits(x) -> np.ndarray:
     """Float embeddings [..., d] -> the rows or queries of a Hamming search, uint8 [..., ceil(d / 8)]: bit i of a row is
     x[..., i] > 0, the first dimension in bit 0 of byte 0, the last byte zero-filled."""
@@ -1181,6 +1203,36 @@ class GpuCorpus:
         _lib.gpu_check(_lib.gpu().mvfgpu_search_filtered_device(self._h, hflt, metric, C.c_void_p(d_queries), query_dtype, query_dim,
                                                                 nq, k, C.c_void_p(d_scores), C.c_void_p(d_indices),
                                                                 _opt(d_raw), _opt(stream)))
+
+    def search_hamming_filtered(self, queries: np.ndarray, k: int, flt: GpuFilter) -> SearchResult:
+        """`search_hamming` among the rows `flt` admits (`mvfgpu_search_hamming_filtered`, include/mvf_gpu_hamming_filtered.h):
+        the same results in every respect -- raw = the distance, ties by ascending position, at most 1024 per query."""
+        hflt = _open_handle(flt, GpuFilter, "flt")
+        q, qcode, nq, qdim = _query_args(queries)
+        sc, idx, raw = _result_arrays(nq, k)
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_hamming_filtered(self._h, hflt, q.ctypes.data_as(C.c_void_p), qcode, qdim, nq, k,
+                                                                 sc.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                                                 raw.ctypes.data_as(C.c_void_p)))
+        return SearchResult(sc, idx, raw)
+
+    def search_hamming_filtered_device(self, flt: GpuFilter, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int,
+                                       d_scores: int, d_indices: int, d_raw: int = 0, stream: int = 0) -> None:
+        """Device-pointer filtered Hamming search (`mvfgpu_search_hamming_filtered_device`), asynchronous on `stream`."""
+        hflt = _open_handle(flt, GpuFilter, "flt")
+        _lib.gpu_check(_lib.gpu().mvfgpu_search_hamming_filtered_device(self._h, hflt, C.c_void_p(d_queries), query_dtype, query_dim,
+                                                                        nq, k, C.c_void_p(d_scores), C.c_void_p(d_indices),
+                                                                        _opt(d_raw), _opt(stream)))
+
+    def hamming_filtered_stage_ms(self, flt: GpuFilter, d_queries: int, query_dtype: int, query_dim: int, nq: int, k: int,
+                                  d_scores: int, d_indices: int, stream: int = 0) -> tuple[float, float, float]:
+        """(prepare, scan, merge) milliseconds of one device call (`mvfgpu_selftest_hamming_filtered_stage_ms`); waits for the
+        stream."""
+        ms = (C.c_float * 3)()
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_filtered_stage_ms(self._h, _open_handle(flt, GpuFilter, "flt"),
+                                                                            C.c_void_p(d_queries), query_dtype, query_dim, nq, k,
+                                                                            C.c_void_p(d_scores), C.c_void_p(d_indices), None,
+                                                                            _opt(stream), ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # ---- partitioned search: one key per query -------------------------------------------
     def make_partition(self, column: GpuColumn) -> GpuPartition:

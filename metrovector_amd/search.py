@@ -130,6 +130,30 @@ def find_top_k_hamming(space: VectorSpace, query, k: int, corpus: GpuCorpus | No
             for j, (idx, score) in enumerate(zip(res.indices[0][valid], res.scores[0][valid]))]
 
 
+def find_top_k_hamming_filtered(space: VectorSpace, query, k: int, allow, corpus: GpuCorpus | None = None, device: int = 0,
+                                with_vectors: bool = False) -> list[ScoredVector]:
+    """`find_top_k_hamming` among the rows a predicate admits (`mvfgpu_search_hamming_filtered`; DESIGN.md §3 "Filtered Hamming
+    search"): `allow` covers the WHOLE space as `find_top_k_filtered` takes it.  Deleted rows are never returned; fewer than k
+    admitted rows give fewer items.  The filter lives for this call: a caller with many queries per predicate makes one with
+    `GpuCorpus.make_filter` or `make_filter_where` and calls `GpuCorpus.search_hamming_filtered`."""
+    if int(space.data_type()) != 3:
+        raise BuildError("Hamming search takes a UInt8 space of bit-packed rows")
+    bits = pack_allow_mask(allow, space.total_vectors())  # malformed masks are refused before anything is uploaded
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        with corpus.make_filter(bits, first_bit=int(corpus.info().index_base)) as flt:
+            res = corpus.search_hamming_filtered(np.asarray(query, dtype=np.uint8), k, flt)
+        valid = res.indices[0] != np.uint64(0xFFFFFFFFFFFFFFFF)
+        rows = corpus.gather_rows(res.indices[0][valid]) if with_vectors and valid.any() else None
+    finally:
+        if own:
+            corpus.close()
+    return [ScoredVector(int(idx), float(score), rows[j].copy() if rows is not None else None)
+            for j, (idx, score) in enumerate(zip(res.indices[0][valid], res.scores[0][valid]))]
+
+
 def find_within_hamming(space: VectorSpace, query, radius: int, max_results: int = 1024, corpus: GpuCorpus | None = None,
                         device: int = 0, with_vectors: bool = False) -> tuple[int, list[ScoredVector]]:
     """Every row of a UInt8 space of bit-packed rows (up to 512 bytes each) within `radius` bits of `query`, inclusive
