@@ -43,6 +43,7 @@
 #include "mvf_gpu_maxsim_align.h"
 #include "mvf_gpu_maxsim_route.h"
 #include "mvf_gpu_mmr.h"
+#include "mvf_gpu_hamming_pairs.h"
 #include "mvf_gpu_hamming_radius.h"
 #include "mvf_gpu_signbits.h"
 #include "mvf_gpu_tanimoto.h"
@@ -471,6 +472,37 @@ public:
         std::vector<ScoredVector> out;
         for (size_t i = 0; i < max_results && i < n; i++) out.push_back({idx[i], scores[i], {}});
         return out;
+    }
+    // Hamming pair join (mvfgpu_hamming_pairs, mvf_gpu_hamming_pairs.h; DESIGN.md section 3, "Hamming pair join"): every two rows
+    // of a UInt8 space of bit-packed rows of up to 512 bytes within `radius` bits of each other, inclusive -- the deduplication of
+    // SimHash / MinHash codes in one call.  Returns the exact number of pairs; where it is at most max_pairs (up to
+    // MVFGPU_HAMMING_PAIRS_MAX) *pairs receives them as (first, second, distance) in ascending position order, otherwise it is
+    // left empty and the caller calls again with room.  degrees (nullable) receives each row's number of partners, by position.
+    struct DuplicatePair {
+        uint64_t first, second;
+        int32_t distance;
+    };
+    uint64_t find_duplicate_pairs(uint32_t radius, size_t max_pairs, std::vector<DuplicatePair>* pairs,
+                                  std::vector<uint32_t>* degrees = nullptr) const {
+        if (dt_ != DataType::UInt8) throw MvfError(MVF_ERR_BUILD, "find_duplicate_pairs takes a UInt8 space of bit-packed rows");
+        if (!pairs) max_pairs = 0;
+        uint64_t total = 0, listed = 0;
+        std::vector<uint64_t> first(max_pairs), second(max_pairs);
+        std::vector<int32_t> raw(max_pairs);
+        if (degrees) {
+            mvfgpu_corpus_info inf;
+            MVFGPU_INIT(inf);
+            detail::check_gpu(mvfgpu_corpus_get_info(c_, &inf));
+            degrees->assign((size_t)inf.rows, 0);
+        }
+        detail::check_gpu(mvfgpu_hamming_pairs(c_, radius, max_pairs, &total, degrees ? degrees->data() : nullptr,
+                                               max_pairs ? first.data() : nullptr, max_pairs ? second.data() : nullptr,
+                                               max_pairs ? raw.data() : nullptr, &listed));
+        if (pairs) {
+            pairs->clear();
+            for (size_t i = 0; i < listed; i++) pairs->push_back({first[i], second[i], raw[i]});
+        }
+        return total;
     }
     // Sign-bit search (mvfgpu_search_signbits, mvf_gpu_signbits.h; DESIGN.md section 3, "Sign-bit search"): the k rows of a UInt8
     // space of bit-packed rows of up to 512 bytes that score highest against an Int8 `query` of 8 x dimension() elements,

@@ -44,7 +44,7 @@ extern "C" {
  * entries is completed with one mvfgpu_search_hamming over all such queries (its entries are its top-max_per_query).
  *
  * Not built: a device-resident asynchronous call; rows above 512 packed bytes; max_per_query above 1024; shard sets; filters
- * and partitions; a self-join ("all duplicate pairs"); a VALU form.
+ * and partitions; a VALU form.  The self-join ("all duplicate pairs") is mvfgpu_hamming_pairs (mvf_gpu_hamming_pairs.h).
  */
 int mvfgpu_search_hamming_radius(const mvfgpu_corpus* corpus, const void* queries, uint8_t query_dtype, uint32_t query_dim,
                                  uint32_t nq, const uint32_t* radii, uint64_t max_per_query, uint64_t* out_counts,

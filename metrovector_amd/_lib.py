@@ -240,6 +240,12 @@ def gpu() -> C.CDLL:
     lib.mvfgpu_selftest_hamming_radius_form.restype = C.c_int
     lib.mvfgpu_selftest_hamming_radius_stage_ms.argtypes = [vp, vp, u8, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp]
     lib.mvfgpu_selftest_hamming_radius_stage_ms.restype = C.c_int
+    lib.mvfgpu_hamming_pairs.argtypes = [vp, u32, u64, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_hamming_pairs.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_pairs_form.argtypes = [u32, u64, u32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_pairs_form.restype = C.c_int
+    lib.mvfgpu_selftest_hamming_pairs_stage_ms.argtypes = [vp, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mvfgpu_selftest_hamming_pairs_stage_ms.restype = C.c_int
     lib.mvfgpu_corpus_write_rows.argtypes = [vp, vp, u64, vp, u64, C.POINTER(WriteReport)]
     lib.mvfgpu_corpus_write_rows.restype = C.c_int
     lib.mvfgpu_corpus_write_rows_device.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(WriteReport)]

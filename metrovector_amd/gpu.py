@@ -85,6 +85,17 @@ class RadiusResult:
         return self.counts > RADIUS_LIST_CAP if self.scores.shape[1] > 0 else np.zeros(self.counts.shape, bool)
 
 
+@dataclass
+class HammingPairs:
+    total: int                  # the exact number of pairs, whatever max_pairs was
+    listed: bool                # the three arrays hold every pair (total <= max_pairs); otherwise they are empty
+    first: np.ndarray           # u64 [total]: the pair's row at the lower position, as every search reports a row
+    second: np.ndarray          # u64 [total]: its row at the higher position; the list ascends by (i, j) position
+    raw: np.ndarray             # i32 [total]: the pair's Hamming distance
+    degrees: np.ndarray | None  # u32 [rows] by position: the other live rows within the radius (0 for a deleted row)
+
+
+HAMMING_PAIRS_MAX = 1 << 24  # include/mvf_gpu_hamming_pairs.h MVFGPU_HAMMING_PAIRS_MAX
 RADIUS_LIST_CAP = 8192  # include/mvf_gpu.h MVFGPU_RADIUS_LIST_CAP
 JOIN_WINDOW = 1024      # include/mvf_gpu.h MVFGPU_JOIN_WINDOW
 JOIN_EXCLUDE_SELF = 1   # include/mvf_gpu.h MVFGPU_JOIN_EXCLUDE_SELF
@@ -247,6 +258,29 @@ def hamming_radius_form(dim: int, nq: int, rows: int, num_cus: int = 0) -> Hammi
     out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)]
     _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_radius_form(dim, nq, rows, num_cus, *[C.byref(o) for o in out]))
     return HammingRadiusForm(*[o.value for o in out])
+
+
+class HammingPairsForm(NamedTuple):
+    query_tile: int     # rows of a column tile, which a scan block expands into LDS: 16, 32, 64 or 128
+    chunks: int         # 64-byte chunks of a row
+    span_rows: int      # rows of a span, which a block streams against its tile: a multiple of 256, 1024 .. 8192
+    tiles: int          # column tiles
+    spans: int          # spans
+    blocks: int         # launched (tile, span) pairs: those whose span holds a row position above the tile's first
+    lds_bytes: int      # LDS of a scan block
+    scratch_bytes: int  # the call's device scratch where `max_pairs` pairs are asked for and found
+    block: tuple | None  # (tile, span) of block `block_index` of the 1-D grid, where one was asked for
+
+
+def hamming_pairs_form(dim: int, rows: int, num_cus: int = 0, max_pairs: int = 0, block_index: int | None = None) -> HammingPairsForm:
+    """The shape of a Hamming pair join over `rows` rows of `dim` packed bytes on a part of `num_cus` compute units (0: 256) --
+    the decisions the launch itself takes, and the place of one block of its triangular grid through the function the kernel
+    decodes its own index with (`mvfgpu_selftest_hamming_pairs_form`, include/mvf_gpu_hamming_pairs.h; no GPU needed)."""
+    out = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)]
+    at = [C.c_uint64(0), C.c_uint64(0)]
+    _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_pairs_form(dim, rows, num_cus, max_pairs, block_index or 0, *[C.byref(o) for o in out],
+                                                                 *[C.byref(o) if block_index is not None else None for o in at]))
+    return HammingPairsForm(*[o.value for o in out], (at[0].value, at[1].value) if block_index is not None else None)
 
 
 class TanimotoForm(NamedTuple):
@@ -971,6 +1005,34 @@ class GpuCorpus:
                                                                           C.c_void_p(d_radii), max_per_query, C.c_void_p(d_counts),
                                                                           _opt(d_scores), _opt(d_indices), None, _opt(stream), ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def hamming_pairs(self, radius: int, max_pairs: int = 1 << 20, degrees: bool = True) -> HammingPairs:
+        """Every two live rows of this UInt8 corpus of bit-packed rows (up to 512 bytes each) within `radius` bits of each other,
+        inclusive (`mvfgpu_hamming_pairs`, include/mvf_gpu_hamming_pairs.h): the exact total, each row's degree, and -- where the
+        total is at most `max_pairs` (0 .. 2^24; 0 asks for total and degrees only) -- the pairs in ascending (i, j) position,
+        each row reported as the searches report it.  `listed` False: call again with max_pairs >= total."""
+        m = int(max_pairs)
+        if m < 0:
+            raise InvalidArgument("max_pairs must be >= 0")
+        room = min(m, HAMMING_PAIRS_MAX)  # (a larger max_pairs is refused by the library before it writes)
+        first, second, raw = np.empty(room, np.uint64), np.empty(room, np.uint64), np.empty(room, np.int32)
+        deg = np.empty(self.rows, np.uint32) if degrees else None
+        total, listed = C.c_uint64(0), C.c_uint64(0)
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if m else (lambda a: None)
+        _lib.gpu_check(_lib.gpu().mvfgpu_hamming_pairs(self._h, radius, m, C.byref(total), deg.ctypes.data_as(C.c_void_p) if degrees else None,
+                                                       ptr(first), ptr(second), ptr(raw), C.byref(listed)))
+        n = int(listed.value)
+        return HammingPairs(int(total.value), m > 0 and total.value <= m, first[:n], second[:n], raw[:n], deg)
+
+    def hamming_pairs_stage_ms(self, radius: int, max_pairs: int, d_degrees: int, d_first: int, d_second: int, d_raw: int = 0,
+                               stream: int = 0) -> tuple[int, int, float, float]:
+        """(total, listed, scan ms, order ms) of the pair join with its degrees and its list written to device buffers
+        (`mvfgpu_selftest_hamming_pairs_stage_ms`); waits for the stream."""
+        ms = (C.c_float * 2)()
+        total, listed = C.c_uint64(0), C.c_uint64(0)
+        _lib.gpu_check(_lib.gpu().mvfgpu_selftest_hamming_pairs_stage_ms(self._h, radius, max_pairs, C.byref(total), _opt(d_degrees), _opt(d_first),
+                                                                         _opt(d_second), _opt(d_raw), C.byref(listed), _opt(stream), ms))
+        return int(total.value), int(listed.value), float(ms[0]), float(ms[1])
 
     def search_signbits(self, queries: np.ndarray, k: int) -> SearchResult:
         """The k rows of largest sign-bit score per query (`mvfgpu_search_signbits`, include/mvf_gpu_signbits.h) on a UInt8

@@ -176,6 +176,28 @@ def find_within_hamming(space: VectorSpace, query, radius: int, max_results: int
                                 for j in range(n)]
 
 
+def find_duplicate_pairs(space: VectorSpace, radius: int, max_pairs: int = 1 << 20, corpus: GpuCorpus | None = None,
+                         device: int = 0) -> tuple[int, list[tuple[int, int, int]] | None]:
+    """Every two rows of a UInt8 space of bit-packed rows (up to 512 bytes each) within `radius` bits of each other, inclusive
+    (`mvfgpu_hamming_pairs`; DESIGN.md §3 "Hamming pair join"): the deduplication of SimHash / MinHash / perceptual-hash codes in
+    one call.  Returns the exact number of pairs and, where it is at most `max_pairs` (up to 2^24), the pairs as
+    (first, second, distance) in ascending position order; None where they did not fit -- call again with room.  Deleted rows
+    pair with nothing; a row's degree and the raw arrays come from `GpuCorpus.hamming_pairs`."""
+    if int(space.data_type()) != 3:
+        raise BuildError("the Hamming pair join takes a UInt8 space of bit-packed rows")
+    own = corpus is None
+    if own:
+        corpus = upload_space(space, device)
+    try:
+        res = corpus.hamming_pairs(radius, max_pairs, degrees=False)
+    finally:
+        if own:
+            corpus.close()
+    if not res.listed:
+        return res.total, None
+    return res.total, list(zip(res.first.tolist(), res.second.tolist(), res.raw.tolist()))
+
+
 def find_top_k_signbits(space: VectorSpace, query, k: int, corpus: GpuCorpus | None = None, device: int = 0,
                         with_vectors: bool = False) -> list[ScoredVector]:
     """The k rows of a UInt8 space of bit-packed rows (up to 512 bytes each) that score highest against a query that keeps its
